@@ -18,11 +18,15 @@ after and reported as config.no_temporal_value.
   5  configs[4]: one 3840x2160 stream per GPU, ORB 4000 kp, 16 pairs per step
 
 `--gpus N` starts N ranks itself (one process per GPU, torch.distributed over RCCL) unless it is already running
-under a launcher (WORLD_SIZE set, which must then equal N).  Prints ONE JSON line on rank 0 (driver contract) with
+under a launcher (WORLD_SIZE set, which must then equal N).  Prints ONE JSON line on rank 0 (driver contract).  A plain
+run sets up, warms up, times `--steps` steps and prints the headline; `--dump-outputs DIR` also writes what the last
+timed step computed (H, status, and for the stream configs the carried state) as DIR/<name>.npy.  `--full` adds
+  no_temporal_value, canonical_order_value, fast_solver_value -- the same loop in the other modes (pair configs)
   roofline     -- the dominant kernel group (by device time) against the HBM roofline: algorithmic bytes per launch /
                   average launch duration measured with hipEvents on the kernels' own stream.
   cpu_baseline -- the CPU oracle (C++ restatement, oracle/) timed on a bounded sample of the same frames on this
                   host's cores (N=1, rank 0 only).  A reported baseline, not the target.
+A plain run reports these as null.
 """
 import argparse
 import json
@@ -91,6 +95,10 @@ def parse_args():
     ap.add_argument("--sync-solve", action="store_true",
                     help="diagnostic: RANSAC on the detect stream (no overlap with the next step), for clean per-stage times")
     ap.add_argument("--contexts", type=int, default=1, help="independent contexts/streams the steps alternate over (pair configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the other modes, per-stage times + roofline and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 / float32)")
     args = ap.parse_args()
     cfg = {1: dict(kind="pairs", w=1280, h=720, nfeat=500, pairs=1024, steps=10),
            2: dict(kind="pairs", w=1280, h=720, nfeat=500, pairs=256, steps=40),
@@ -103,7 +111,27 @@ def parse_args():
     args.nfeatures = args.nfeatures or cfg["nfeat"]
     args.pairs = args.pairs or cfg["pairs"]
     args.steps = args.steps if args.steps is not None else cfg["steps"]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, per_pair, whole):
+    """Writes per_pair (arrays indexed by pair along axis 0) and whole (small arrays) as out_dir/<name>.npy.  Beyond
+    DUMP_LIMIT_BYTES the per-pair arrays are cut to a fixed, seeded sample of pairs, whose indices go to pair_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(per_pair.values())))
+    row_bytes = sum(a[:1].nbytes for a in per_pair.values())
+    keep = max(1, (DUMP_LIMIT_BYTES - sum(a.nbytes for a in whole.values()) - 8 * n) // max(row_bytes, 1))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        per_pair = {k: a[idx] for k, a in per_pair.items()}
+        whole = dict(whole, pair_index=idx.astype(np.float64))
+    for k, a in {**per_pair, **whole}.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def spawn_ranks(n):
@@ -338,16 +366,18 @@ def main():
         os.dup2(saved_stdout, 1)
         os.close(saved_stdout)
         saved_stdout = None
-    for c_ in ctxs:
-        c_.profile_read()         # drop warm-up spans
-        c_.profile_enable(True)
+    if args.full:                 # per-stage hipEvent brackets for the roofline
+        for c_ in ctxs:
+            c_.profile_read()         # drop warm-up spans
+            c_.profile_enable(True)
     elapsed = timed(args.steps)
     stages = {}
-    for c_ in ctxs:
-        c_.profile_enable(False)
-        for name, (cnt_, ms_) in c_.profile_read().items():
-            a_, b_ = stages.get(name, (0, 0.0))
-            stages[name] = (a_ + cnt_, b_ + ms_)
+    if args.full:
+        for c_ in ctxs:
+            c_.profile_enable(False)
+            for name, (cnt_, ms_) in c_.profile_read().items():
+                a_, b_ = stages.get(name, (0, 0.0))
+                stages[name] = (a_ + cnt_, b_ + ms_)
     for c_ in ctxs:
         c_.synchronize()
     if args.kind == "pairs":
@@ -356,13 +386,16 @@ def main():
     else:
         H, status = Hs[0].clone(), sts[0].clone()
     st = status.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        whole = {"state": state.cpu().numpy()} if args.kind != "pairs" else {}      # stream configs: the carried superposition
+        dump_outputs(args.dump_outputs, {"H": H.cpu().numpy().reshape(-1, 3, 3), "status": st.astype(np.float32)}, whole)
     ok_frac = float((st == 0).mean())
     value = pairs_per_step * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
     # the same loop without the two content-dependent (exact) FAST shortcuts, reported next to the headline
     no_temporal_value = None
-    if not args.no_temporal and args.kind == "pairs" and not args.skip_no_temporal:
+    if args.full and not args.no_temporal and args.kind == "pairs" and not args.skip_no_temporal:
         set_temporal(False)
         for _ in range(2):
             step()
@@ -373,7 +406,7 @@ def main():
     # the same loop in the canonical key-point order (rounds 1-3: all ties, (level, y, x) order; FAST threshold lifting applies):
     # faster, but H then agrees with the reference's OpenCV run only where RANSAC's consensus does not depend on the draw
     canonical_order_value = None
-    if args.order == "reference" and args.kind == "pairs" and not args.skip_no_temporal:
+    if args.full and args.order == "reference" and args.kind == "pairs" and not args.skip_no_temporal:
         for c_ in ctxs:
             c_.set_keypoint_order(0)
         for _ in range(2):
@@ -386,7 +419,7 @@ def main():
     # the same loop with the tolerance-mode solver (LDL^T for LM's 8x8 systems): what a caller who accepts frame corners within
     # ~1e-3 px of the operator's own arithmetic gets; reported next to the headline, which stays on the exact solver
     fast_solver_value = None
-    if args.solver == "exact" and not args.skip_no_temporal:
+    if args.full and args.solver == "exact" and not args.skip_no_temporal:
         for c_ in ctxs:
             c_.set_solver_mode(1)
         for _ in range(2):
@@ -397,118 +430,120 @@ def main():
             c_.set_solver_mode(0)
 
     # ---- roofline of the dominant kernel group --------------------------------------------------------------------
-    per_frame, per_pair = algorithmic_bytes(w, h, nfeat, args.channels)
-    stage_ms = {k: (v[1] / max(v[0], 1)) for k, v in stages.items() if v[0] > 0}      # average duration of one launch group
-    dom = max(stage_ms, key=lambda k: stage_ms[k])
-    frames_per_launch = 2 * B if args.kind == "pairs" else B + 1
-    pairs_per_launch = world * B if (args.kind == "twophase" and dom == "ransac_final") else B
-    by = per_frame[dom] * frames_per_launch if dom in per_frame else per_pair.get(dom, 0) * pairs_per_launch
-    achieved = by / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                "algorithmic_bytes_per_launch": int(by), "avg_launch_ms": round(stage_ms[dom], 4),
-                "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()}}
-    # A stream config's dominant kernel is the sequential scan (one wave per SIMD, ~80 bytes per pair): an HBM fraction says
-    # nothing about it.  What bounds it is a chain of dependent f64 operations; the kernel can account its own cycles by phase
-    # (EVH_RANSAC_PROF), so one more step of the same workload is run in a child process with the accounting on and its
-    # per-pair cycle model is attached as roofline.scan_cycles (clock 2.4 GHz: cycles / 2.4e6 = ms per pair).
-    if dom == "ransac_final" and args.kind != "pairs" and rank == 0 and not args.skip_no_temporal and not os.environ.get("EVH_RANSAC_PROF"):
-        try:
-            import re
-            env = dict(os.environ, EVH_RANSAC_PROF="1")
-            for k_ in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "EVH_BENCH_FORCE_DIST"):
-                env.pop(k_, None)
-            argv = [sys.executable, os.path.abspath(__file__), "--config", str(args.config), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                    "--cpu-pairs", "0", "--skip-no-temporal", "--gen-procs", "1", "--solver", args.solver, "--order", args.order]
-            if args.force_max_iters:
-                argv.append("--force-max-iters")
-            pr = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=600)
-            lines = [l for l in pr.stderr.splitlines() if l.startswith("[evh ransac_final prof]")]
-            if lines:
-                t = lines[-1]
-                def num(pat):
-                    m = re.search(pat, t)
-                    return float(m.group(1)) if m else None
-                roofline["scan_cycles"] = {
-                    "per_pair_total": num(r"total (\d+)"), "hypotheses": num(r"hyp (\d+)"), "compact": num(r"compact (\d+)"),
-                    "refit": num(r"refit (\d+)"), "lm": num(r" lm (\d+)"), "lm_iterations": num(r"iters ([\d.]+)"),
-                    "lm_solves": num(r"solve8 (\d+)"), "lm_evaluations": num(r"eval (\d+)"),
-                    "jacobi_rotations_9x9": num(r"9x9 ([\d.]+)"), "jacobi_rotations_8x8": num(r"8x8 ([\d.]+)"),
-                    "source": "EVH_RANSAC_PROF=1 on one more step of this workload in a child process (in-kernel s_memtime accounting, thread 0 of each scan)"}
-                tot = roofline["scan_cycles"]["per_pair_total"]
-                if tot:
-                    roofline["scan_cycles"]["ms_per_pair_at_2.4GHz"] = round(tot / 2.4e6, 4)
-        except Exception as e:      # the model is informational
-            roofline["scan_cycles"] = {"error": str(e)[:200]}
-    # HBM bytes (PMC) and VALU instruction counts are NOT measured in this run: they come from the committed rocprofv3
-    # --pmc passes of exactly this workload (profiles/traffic.json, profiles/valu.json, keyed by kernel group and
-    # geometry) and are labelled as replayed; a workload without a committed pass reports null.
-    key = "%s@%dx%dx%d_n%d_c%d" % (dom, w, h, B, nfeat, args.channels)
-    for fname, field in (("traffic.json", "traffic"), ("valu.json", "valu_issue")):
-        path = os.path.join(ROOT, "profiles", fname)
-        try:
-            entry = json.load(open(path)).get(key) if (args.kind in ("pairs", "stream") and os.path.exists(path)) else None
-        except Exception:
-            entry = None
-        if entry is None:
-            continue
-        if field == "traffic":
-            if isinstance(entry, dict):
-                roofline["traffic"] = entry["hbm_bytes"]
-                roofline["traffic_correction"] = {
-                    "fetch_factor": entry["fetch_correction"], "fetch_counter_bytes": entry["fetch_counter_bytes"],
-                    "write_bytes": entry["write_bytes"],
-                    "why": ("FETCH_SIZE tallies 128-byte lines at 64 bytes on gfx950; calibrated on this kernel's own staging "
-                            "pattern: profiles/r03_fetch_calibration.txt") if dom == "fast" else
-                           ("FETCH_SIZE tallies 128-byte lines at 64 bytes on gfx950 (factor calibrated on the FAST kernel's line-sized "
-                            "reads, profiles/r03_fetch_calibration.txt; an upper bound for this kernel's shorter reads)")}
-            else:                     # a round-2 record: raw counter sum
-                roofline["traffic"] = entry
-            roofline["traffic_over_algorithmic"] = round(roofline["traffic"] / max(by, 1), 3)
-            roofline["traffic_source"] = "replayed: profiles/%s[%s] (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, not this run)" % (fname, key)
-        elif stage_ms[dom] > 0:
-            props = torch.cuda.get_device_properties(dev)
-            per = entry["valu_wave_insts_per_launch"] / (stage_ms[dom] * 1e-3) / (props.multi_processor_count * 2.4e9)
-            roofline["valu_issue"] = {"wave_insts_per_launch": entry["valu_wave_insts_per_launch"],
-                                      "per_clk_per_cu_at_2.4GHz": round(per, 3), "ceiling": [0.96, 1.75],
-                                      "valu_source": "replayed: profiles/%s[%s] (%s); duration measured in this run" % (fname, key, entry.get("source", ""))}
-    if dom == "fast":
-        # the FAST tile grid covers only the pixels ORB can emit (31-px border rule) plus one ring: the kernel reads this
-        # fraction of the P*A bytes the SURVEY 8d model charges it with (`achieved` keeps the model's bytes)
-        lvs = level_sizes(w, h)
-        roofline["fast_tiled_fraction"] = round(sum(max(1, -(-(a - 55) // 128)) * 128 * max(1, -(-(b - 62) // 28)) * 28 for a, b in lvs)
-                                                / float(sum(a * b for a, b in lvs)), 4)
-    # whole-pipeline view: independent pair = 2*B_frame + B_match + B_out; a stream pair = 1 frame
-    pipe_bytes = (2 if args.kind == "pairs" else 1) * sum(per_frame.values()) + sum(per_pair.values())
-    roofline["pipeline_bytes_per_pair"] = int(pipe_bytes)
-    roofline["pipeline_frac"] = round(pipe_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5)
-    # the same with SURVEY 8d's own byte model: B_frame = A*(1 + (P-1) + P) + min(P*A, 1369*N) + 48*N with the gray frame
-    # resident (+ 3*A when the BGR entry is timed), B_match = 72*N, B_out = 80 -- source read once, levels 1..7 written
-    # once, every level read once; no re-read by the unfused pyramid, no write of level 0
-    A8 = areas_sum = None
-    lv8 = level_sizes(w, h)
-    A8 = lv8[0][0] * lv8[0][1]; areas_sum = sum(a * b for a, b in lv8)
-    b_frame = A8 + (areas_sum - A8) + areas_sum + min(areas_sum, 1369 * nfeat) + 48 * nfeat + (3 * A8 if args.channels == 3 else 0)
-    pipe8d = (2 if args.kind == "pairs" else 1) * b_frame + 72 * nfeat + 80
-    roofline["pipeline_bytes_per_pair_survey8d"] = int(pipe8d)
-    roofline["pipeline_frac_survey8d"] = round(pipe8d * value / world / 1e9 / HBM_PEAK_GBS, 5)
+    roofline = None
+    if args.full:
+        per_frame, per_pair = algorithmic_bytes(w, h, nfeat, args.channels)
+        stage_ms = {k: (v[1] / max(v[0], 1)) for k, v in stages.items() if v[0] > 0}      # average duration of one launch group
+        dom = max(stage_ms, key=lambda k: stage_ms[k])
+        frames_per_launch = 2 * B if args.kind == "pairs" else B + 1
+        pairs_per_launch = world * B if (args.kind == "twophase" and dom == "ransac_final") else B
+        by = per_frame[dom] * frames_per_launch if dom in per_frame else per_pair.get(dom, 0) * pairs_per_launch
+        achieved = by / (stage_ms[dom] * 1e-3) / 1e9 if stage_ms[dom] > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                    "algorithmic_bytes_per_launch": int(by), "avg_launch_ms": round(stage_ms[dom], 4),
+                    "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()}}
+        # A stream config's dominant kernel is the sequential scan (one wave per SIMD, ~80 bytes per pair): an HBM fraction says
+        # nothing about it.  What bounds it is a chain of dependent f64 operations; the kernel can account its own cycles by phase
+        # (EVH_RANSAC_PROF), so one more step of the same workload is run in a child process with the accounting on and its
+        # per-pair cycle model is attached as roofline.scan_cycles (clock 2.4 GHz: cycles / 2.4e6 = ms per pair).
+        if dom == "ransac_final" and args.kind != "pairs" and rank == 0 and not args.skip_no_temporal and not os.environ.get("EVH_RANSAC_PROF"):
+            try:
+                import re
+                env = dict(os.environ, EVH_RANSAC_PROF="1")
+                for k_ in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "EVH_BENCH_FORCE_DIST"):
+                    env.pop(k_, None)
+                argv = [sys.executable, os.path.abspath(__file__), "--config", str(args.config), "--gpus", "1", "--steps", "1", "--warmup", "1",
+                        "--cpu-pairs", "0", "--skip-no-temporal", "--gen-procs", "1", "--solver", args.solver, "--order", args.order]
+                if args.force_max_iters:
+                    argv.append("--force-max-iters")
+                pr = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=600)
+                lines = [l for l in pr.stderr.splitlines() if l.startswith("[evh ransac_final prof]")]
+                if lines:
+                    t = lines[-1]
+                    def num(pat):
+                        m = re.search(pat, t)
+                        return float(m.group(1)) if m else None
+                    roofline["scan_cycles"] = {
+                        "per_pair_total": num(r"total (\d+)"), "hypotheses": num(r"hyp (\d+)"), "compact": num(r"compact (\d+)"),
+                        "refit": num(r"refit (\d+)"), "lm": num(r" lm (\d+)"), "lm_iterations": num(r"iters ([\d.]+)"),
+                        "lm_solves": num(r"solve8 (\d+)"), "lm_evaluations": num(r"eval (\d+)"),
+                        "jacobi_rotations_9x9": num(r"9x9 ([\d.]+)"), "jacobi_rotations_8x8": num(r"8x8 ([\d.]+)"),
+                        "source": "EVH_RANSAC_PROF=1 on one more step of this workload in a child process (in-kernel s_memtime accounting, thread 0 of each scan)"}
+                    tot = roofline["scan_cycles"]["per_pair_total"]
+                    if tot:
+                        roofline["scan_cycles"]["ms_per_pair_at_2.4GHz"] = round(tot / 2.4e6, 4)
+            except Exception as e:      # the model is informational
+                roofline["scan_cycles"] = {"error": str(e)[:200]}
+        # HBM bytes (PMC) and VALU instruction counts are NOT measured in this run: they come from the committed rocprofv3
+        # --pmc passes of exactly this workload (profiles/traffic.json, profiles/valu.json, keyed by kernel group and
+        # geometry) and are labelled as replayed; a workload without a committed pass reports null.
+        key = "%s@%dx%dx%d_n%d_c%d" % (dom, w, h, B, nfeat, args.channels)
+        for fname, field in (("traffic.json", "traffic"), ("valu.json", "valu_issue")):
+            path = os.path.join(ROOT, "profiles", fname)
+            try:
+                entry = json.load(open(path)).get(key) if (args.kind in ("pairs", "stream") and os.path.exists(path)) else None
+            except Exception:
+                entry = None
+            if entry is None:
+                continue
+            if field == "traffic":
+                if isinstance(entry, dict):
+                    roofline["traffic"] = entry["hbm_bytes"]
+                    roofline["traffic_correction"] = {
+                        "fetch_factor": entry["fetch_correction"], "fetch_counter_bytes": entry["fetch_counter_bytes"],
+                        "write_bytes": entry["write_bytes"],
+                        "why": ("FETCH_SIZE tallies 128-byte lines at 64 bytes on gfx950; calibrated on this kernel's own staging "
+                                "pattern: profiles/r03_fetch_calibration.txt") if dom == "fast" else
+                               ("FETCH_SIZE tallies 128-byte lines at 64 bytes on gfx950 (factor calibrated on the FAST kernel's line-sized "
+                                "reads, profiles/r03_fetch_calibration.txt; an upper bound for this kernel's shorter reads)")}
+                else:                     # a round-2 record: raw counter sum
+                    roofline["traffic"] = entry
+                roofline["traffic_over_algorithmic"] = round(roofline["traffic"] / max(by, 1), 3)
+                roofline["traffic_source"] = "replayed: profiles/%s[%s] (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, not this run)" % (fname, key)
+            elif stage_ms[dom] > 0:
+                props = torch.cuda.get_device_properties(dev)
+                per = entry["valu_wave_insts_per_launch"] / (stage_ms[dom] * 1e-3) / (props.multi_processor_count * 2.4e9)
+                roofline["valu_issue"] = {"wave_insts_per_launch": entry["valu_wave_insts_per_launch"],
+                                          "per_clk_per_cu_at_2.4GHz": round(per, 3), "ceiling": [0.96, 1.75],
+                                          "valu_source": "replayed: profiles/%s[%s] (%s); duration measured in this run" % (fname, key, entry.get("source", ""))}
+        if dom == "fast":
+            # the FAST tile grid covers only the pixels ORB can emit (31-px border rule) plus one ring: the kernel reads this
+            # fraction of the P*A bytes the SURVEY 8d model charges it with (`achieved` keeps the model's bytes)
+            lvs = level_sizes(w, h)
+            roofline["fast_tiled_fraction"] = round(sum(max(1, -(-(a - 55) // 128)) * 128 * max(1, -(-(b - 62) // 28)) * 28 for a, b in lvs)
+                                                    / float(sum(a * b for a, b in lvs)), 4)
+        # whole-pipeline view: independent pair = 2*B_frame + B_match + B_out; a stream pair = 1 frame
+        pipe_bytes = (2 if args.kind == "pairs" else 1) * sum(per_frame.values()) + sum(per_pair.values())
+        roofline["pipeline_bytes_per_pair"] = int(pipe_bytes)
+        roofline["pipeline_frac"] = round(pipe_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5)
+        # the same with SURVEY 8d's own byte model: B_frame = A*(1 + (P-1) + P) + min(P*A, 1369*N) + 48*N with the gray frame
+        # resident (+ 3*A when the BGR entry is timed), B_match = 72*N, B_out = 80 -- source read once, levels 1..7 written
+        # once, every level read once; no re-read by the unfused pyramid, no write of level 0
+        A8 = areas_sum = None
+        lv8 = level_sizes(w, h)
+        A8 = lv8[0][0] * lv8[0][1]; areas_sum = sum(a * b for a, b in lv8)
+        b_frame = A8 + (areas_sum - A8) + areas_sum + min(areas_sum, 1369 * nfeat) + 48 * nfeat + (3 * A8 if args.channels == 3 else 0)
+        pipe8d = (2 if args.kind == "pairs" else 1) * b_frame + 72 * nfeat + 80
+        roofline["pipeline_bytes_per_pair_survey8d"] = int(pipe8d)
+        roofline["pipeline_frac_survey8d"] = round(pipe8d * value / world / 1e9 / HBM_PEAK_GBS, 5)
 
-    # rocprof-measured HBM bytes of a whole step (corrected FETCH_SIZE + WRITE_SIZE over every kernel, committed PMC passes of
-    # this workload) against this run's step time: what "rocprof HBM GB/s against the chip's peak" reads for the path
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-        ent = tj.get("step@%dx%dx%d_n%d_c%d" % (w, h, B, nfeat, args.channels)) if args.kind in ("pairs", "stream") else None
-    except Exception:
-        ent = None
-    if ent:
-        gbs = ent["hbm_bytes_per_step"] / (ms_per_step * 1e-3) / 1e9
-        roofline["hbm_traffic"] = {"bytes_per_step": ent["hbm_bytes_per_step"], "GBps": round(gbs, 1),
-                                   "frac_of_peak": round(gbs / HBM_PEAK_GBS, 4),
-                                   "source": "replayed: " + ent["source"] + "; step time of this run"}
+        # rocprof-measured HBM bytes of a whole step (corrected FETCH_SIZE + WRITE_SIZE over every kernel, committed PMC passes of
+        # this workload) against this run's step time: what "rocprof HBM GB/s against the chip's peak" reads for the path
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+            ent = tj.get("step@%dx%dx%d_n%d_c%d" % (w, h, B, nfeat, args.channels)) if args.kind in ("pairs", "stream") else None
+        except Exception:
+            ent = None
+        if ent:
+            gbs = ent["hbm_bytes_per_step"] / (ms_per_step * 1e-3) / 1e9
+            roofline["hbm_traffic"] = {"bytes_per_step": ent["hbm_bytes_per_step"], "GBps": round(gbs, 1),
+                                       "frac_of_peak": round(gbs / HBM_PEAK_GBS, 4),
+                                       "source": "replayed: " + ent["source"] + "; step time of this run"}
 
     # ---- CPU baseline (oracle) on a bounded sample, rank 0 at N=1 only --------------------------------------------------
     cpu_baseline = None
-    if rank == 0 and world == 1 and args.cpu_pairs != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_pairs != 0:
         from oracle import oracle as O
         cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         cores = min(cores, 16)   # the GPU box's CPU share for one GPU

@@ -188,16 +188,13 @@ def test_driver_loop_matches_reference(goldens, monkeypatch, chunk):
     assert frame_processing.DEFAULT_FEATURES == ["SURF", "SIFT", "ORB"]                      # frame_processing.py:40
 
 
-def test_install_as_evenvizion_keeps_the_real_package_reachable(tmp_path, monkeypatch):
+def test_install_as_evenvizion_keeps_the_real_package_reachable(tmp_path):
     """evenvizion_amd.install_as_evenvizion(): the five imports of evenvizion/examples/evenvizion_component.py:30-35
     work afterwards -- the processing modules resolve to this implementation, `evenvizion.visualization.*` (out of scope
     here) still resolves to the real package's own files, found through its search path WITHOUT running its __init__
-    (which would import every example script).  The stand-in package below has the reference's layout; when
-    /root/reference is present (build container only) the same is done against the real files with cv2 / imutils
-    replaced by inert stubs."""
+    (which would import every example script).  The stand-in package below has the reference's layout."""
     import importlib
     import sys
-    import types
     import evenvizion_amd
 
     def run(package_parent):
@@ -239,11 +236,6 @@ def test_install_as_evenvizion_keeps_the_real_package_reachable(tmp_path, monkey
         "def heatmap_video_processing(*a, **k):\n    return HEATMAP_CONSTANT\n"
         "def comparison_original_with_fixed_coordinate_video_processing(*a, **k):\n    return None\n")
     run(root)
-    if os.path.isdir("/root/reference/evenvizion"):
-        for name in ("cv2", "imutils"):
-            if name not in sys.modules:
-                monkeypatch.setitem(sys.modules, name, types.ModuleType(name))
-        run("/root/reference")
     importlib.invalidate_caches()
 
 

@@ -29,9 +29,9 @@ rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_AC
 (rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum -d $O/rdreq -o rdreq --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --cpu-pairs 0 --gen-procs 1 --unique 64 --skip-no-temporal > $O/rdreq.log 2>&1 || true)
 # the stream workload (BASELINE configs[2]): kernel stats only
 rocprofv3 --kernel-trace --stats -d $O/stats3 -o stats3 --output-format csv -- python3 $R/bench.py --config 3 --steps 4 --warmup 1 --cpu-pairs 0 --gen-procs 1 > $O/stats3.log 2>&1
-cd $R && python bench.py > $O/bench.json 2> $O/bench.err
-for c in 2 3 4 5; do python bench.py --config $c > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || true; done
-python bench.py --config 3 --force-max-iters > $O/bench_cfg3_forced.json 2> $O/bench_cfg3_forced.err || true
+cd $R && python bench.py --full > $O/bench.json 2> $O/bench.err
+for c in 2 3 4 5; do python bench.py --full --config $c > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || true; done
+python bench.py --full --config 3 --force-max-iters > $O/bench_cfg3_forced.json 2> $O/bench_cfg3_forced.err || true
 # probes: stream cases (adaptive / forced), several streams per call, host frames in / dict out, the three detector types
 python tools/stream_probe.py > $O/stream_probe.json 2> $O/stream_probe.err || true
 python tools/stream_probe.py 3840x2160:4000:0 3840x2160:4000:1 > $O/stream_probe_4k.json 2>> $O/stream_probe.err || true

@@ -238,6 +238,10 @@ class Context:
         """Hsup f64[n,3,3] -> f64[n]: max fixed-plane coordinate over the w x h grid of each matrix."""
         Hs = np.ascontiguousarray(Hsup, np.float64).reshape(-1, 9)
         out = np.zeros(len(Hs), np.float64)
+        import torch
+        if field is not None and not (field.is_cuda and field.dtype == torch.float64 and field.is_contiguous()
+                                      and field.numel() == len(Hs) * int(h) * int(w) * 2):
+            raise ValueError("fixed_plane_max: field must be a contiguous CUDA float64 tensor of n*h*w*2 elements")
         self._check(self.lib.evh_fixed_plane_field(self.h, _hp(Hs), len(Hs), int(w), int(h),
                                                    field.data_ptr() if field is not None else None, _hp(out)))
         return out

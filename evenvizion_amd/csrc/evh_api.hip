@@ -2,6 +2,7 @@
 #include "evh_internal.h"
 #include "evh_match.h"
 #include "evh_ransac.h"
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -628,6 +629,7 @@ int evh_resize_area_u8c3(evh_ctx* c, const uint8_t* d_src, int sw, int sh, uint8
 int evh_fixed_plane_field(evh_ctx* c, const double* h_Hsup, int n, int w, int h, double* d_field, double* h_max) {
   if (!c || !h_Hsup || !h_max || n < 1 || w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, "evh_fixed_plane_field: bad argument");
   if (n > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "evh_fixed_plane_field: at most 65535 matrices per call");
+  if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, "evh_fixed_plane_field: w * h above INT_MAX");
   { int sr = ensure_scratch(c, (sizeof(double) * 9 + sizeof(unsigned long long)) * (size_t)n); if (sr) return sr; }
   double* d_H = reinterpret_cast<double*>(c->d_scratch);
   unsigned long long* d_max = reinterpret_cast<unsigned long long*>(c->d_scratch + sizeof(double) * 9 * (size_t)n);

@@ -4,6 +4,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// np.dot(H, (x, y, 1)) in the summation order pinned by the reference-glue fixtures ("hv" in glue_goldens.json, the
+// fields of plane_goldens.json): fma(h0, x, h1*y) + h2.  Every consumer of homography_transformation's arithmetic
+// (static filter, pre-transform, point transform, heat-map field) goes through this one helper.
+__device__ __forceinline__ void hdot(const double* H, double x, double y, double* tx, double* ty, double* tw) {
+  *tx = fma(H[0], x, H[1] * y) + H[2];
+  *ty = fma(H[3], x, H[4] * y) + H[5];
+  *tw = fma(H[6], x, H[7] * y) + H[8];
+}
+
 // cv::fastAtan2 (degrees): the 7th-order polynomial of core/mathfuncs
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
   const float p1 = 0.9997878412794807f * (float)(180 / 3.14159265358979323846);

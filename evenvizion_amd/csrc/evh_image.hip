@@ -4,6 +4,7 @@
 // equal sizes are a plain copy.  Weights are float32 tables built on the host
 // exactly as the operator builds them; each output value is accumulated in float32 in table order
 // (inner sum over source columns, outer sum over source rows), then rounded half-to-even and saturated.
+#include "evh_devmath.h"
 #include "evh_internal.h"
 #include <cmath>
 #include <cstring>
@@ -180,30 +181,46 @@ __global__ __launch_bounds__(256) void k_resize_linear_area(const uint8_t* __res
 }
 
 // N3: fixed-plane coordinate field of processing_visualization.py:407-408 -- every pixel (x, y) of
-// the resized frame mapped through the frame's superposed H -- and its maximum coordinate (the value
-// heatmap_video_processing returns and evenvizion_component.py writes to metrics_file.txt).
+// the resized frame mapped through the frame's superposed H (np.apply_along_axis(homography_transformation): hdot,
+// then one division per coordinate) -- and np.max of it (the value heatmap_video_processing returns and
+// evenvizion_component.py writes to metrics_file.txt).  np.max semantics: a NaN anywhere gives NaN, an all -inf
+// field gives -inf (out_max is seeded with the key of -inf by k_seed_fixed_plane_max).  w * h <= INT_MAX (the entry
+// checks), so the unsigned index plus one grid stride cannot wrap.
+
+// order-preserving key of a double, so that an integer atomicMax gives the floating-point maximum; every NaN is
+// keyed as the positive quiet NaN, above +inf
+__device__ __forceinline__ unsigned long long max_key(double m) {
+  if (m != m) return 0xFFF8000000000000ull;
+  const unsigned long long b = (unsigned long long)__double_as_longlong(m);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// np.max's pairwise rule: a NaN wins and stays (fmax would drop it); +0 outranks -0, as in the key order
+__device__ __forceinline__ double nan_max(double m, double v) {
+  if (m != m) return m;
+  return (v != v || v > m || (v == m && signbit(m))) ? v : m;
+}
+
+__global__ __launch_bounds__(256) void k_seed_fixed_plane_max(unsigned long long* __restrict__ out_max, int n) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < n) out_max[f] = max_key(-INFINITY);
+}
+
 __global__ __launch_bounds__(256) void k_fixed_plane(const double* __restrict__ Hs, int w, int h,
                                                      double* __restrict__ field, unsigned long long* __restrict__ out_max) {
   const int f = blockIdx.y;
   const double* H = Hs + 9 * f;
-  const double h0 = H[0], h1 = H[1], h2 = H[2], h3 = H[3], h4 = H[4], h5 = H[5], h6 = H[6], h7 = H[7], h8 = H[8];
+  const unsigned wh = (unsigned)w * (unsigned)h;
   double m = -INFINITY;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < w * h; i += gridDim.x * blockDim.x) {
-    const int y = i / w, x = i - y * w;
-    const double dx = (double)x, dy = (double)y;
-    const double d = (h6 * dx + h7 * dy) + h8;
-    const double u = ((h0 * dx + h1 * dy) + h2) / d;
-    const double v = ((h3 * dx + h4 * dy) + h5) / d;
-    if (field) { field[((int64_t)f * w * h + i) * 2] = u; field[((int64_t)f * w * h + i) * 2 + 1] = v; }
-    m = fmax(m, fmax(u, v));
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < wh; i += gridDim.x * blockDim.x) {
+    const unsigned y = i / (unsigned)w, x = i - y * (unsigned)w;
+    double tx, ty, tw;
+    hdot(H, (double)x, (double)y, &tx, &ty, &tw);
+    const double u = tx / tw, v = ty / tw;
+    if (field) { field[((int64_t)f * wh + i) * 2] = u; field[((int64_t)f * wh + i) * 2 + 1] = v; }
+    m = nan_max(m, nan_max(u, v));
   }
-  for (int s = 32; s > 0; s >>= 1) m = fmax(m, __shfl_xor(m, s));
-  if ((threadIdx.x & 63) == 0 && m > -INFINITY) {
-    // order-preserving key of a double so that an integer atomicMax gives the floating-point maximum
-    unsigned long long b = (unsigned long long)__double_as_longlong(m);
-    b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    atomicMax(&out_max[f], b);
-  }
+  for (int s = 32; s > 0; s >>= 1) m = nan_max(m, __shfl_xor(m, s));
+  if ((threadIdx.x & 63) == 0 && m != -INFINITY) atomicMax(&out_max[f], max_key(m));
 }
 
 // N1: utils.superposition_dict (utils.py:184-211) as one sequential scan: out[0] = H[0] (matrix_H_first),
@@ -239,9 +256,8 @@ __global__ __launch_bounds__(256) void k_transform_points(const double* __restri
   if (i >= n) return;
   const double* H = M + 9 * (int64_t)idx[i];
   const double x = kx * pts[2 * i], y = ky * pts[2 * i + 1];
-  const double tx = fma(H[0], x, H[1] * y) + H[2];
-  const double ty = fma(H[3], x, H[4] * y) + H[5];
-  const double tw = fma(H[6], x, H[7] * y) + H[8];
+  double tx, ty, tw;
+  hdot(H, x, y, &tx, &ty, &tw);
   double u = tx / tw, v = ty / tw;
   if (decimals >= 0) {
     double sc = 1.0;
@@ -404,8 +420,9 @@ int evh_launch_transform_points(evh_ctx* c, const double* d_M, const int* d_idx,
 }
 
 int evh_launch_fixed_plane(evh_ctx* c, const double* d_H, int n, int w, int h, double* d_field, unsigned long long* d_max) {
-  EVH_HIP(c, hipMemsetAsync(d_max, 0, sizeof(unsigned long long) * (size_t)n, c->stream));
-  const int blocks = std::min((w * h + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_seed_fixed_plane_max, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_max, n);
+  EVH_HIP(c, hipGetLastError());
+  const int blocks = (int)std::min(((int64_t)w * h + 255) / 256, (int64_t)1024);
   hipLaunchKernelGGL(k_fixed_plane, dim3(blocks, n), dim3(256), 0, c->stream, d_H, w, h, d_field, d_max);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;

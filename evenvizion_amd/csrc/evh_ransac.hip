@@ -28,6 +28,7 @@
 //   lane per output entry adds the tile's terms in point order.
 // All floating-point sums keep a fixed order (-ffp-contract=off); f64 throughout the solves, f32 for the
 // reprojection error, as the operator being replaced.
+#include "evh_devmath.h"
 #include "evh_internal.h"
 #include "evh_ransac.h"
 #include <float.h>
@@ -1995,13 +1996,6 @@ __device__ __forceinline__ bool find_homography_block(BlockLds<NW, LANES>& B, co
   __syncthreads();
   pf_add(prof, PF_TOTAL, pf_now_if(prof) - pf0);
   return true;
-}
-
-// np.dot(H, (x, y, 1)) in the summation order pinned by the reference-glue fixtures: fma(h0, x, h1*y) + h2
-__device__ __forceinline__ void hdot(const double* H, double x, double y, double* tx, double* ty, double* tw) {
-  *tx = fma(H[0], x, H[1] * y) + H[2];
-  *ty = fma(H[3], x, H[4] * y) + H[5];
-  *tw = fma(H[6], x, H[7] * y) + H[8];
 }
 
 // find_point_displacement + get_largest_group_points; rbin = int scratch [n] (global); returns kept count (uniform).

@@ -98,10 +98,12 @@ int evh_resize_area_u8(evh_ctx* ctx, const uint8_t* d_src, int nimg, int sw, int
 int evh_resize_area_u8c3(evh_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh);
 
 /* ---- N3: fixed-plane coordinate field of the heat-map (processing_visualization.py:407-408,419) ------- */
-/* For each of n superposed matrices h_Hsup f64[n,9]: (u,v) = H.(x,y,1) for every pixel of a w x h grid (what
- * np.apply_along_axis(homography_transformation, 2, template, H) computes) and max over the grid of max(u,v) --
- * the per-frame value whose maximum over the video is written to metrics_file.txt.  d_field (device,
- * f64[n,h,w,2], may be NULL) receives the field; h_max f64[n] the maxima.  Synchronises.                     */
+/* For each of n superposed matrices h_Hsup f64[n,9]: (u,v) = H.(x,y,1) for every pixel of a w x h grid, in the
+ * arithmetic of np.apply_along_axis(homography_transformation, 2, template, H) (tx = fma(h0, x, h1*y) + h2, then
+ * u = tx / tw), and np.max over the grid of (u,v) -- the per-frame value whose maximum over the video is written to
+ * metrics_file.txt.  np.max semantics: a NaN anywhere gives NaN (the positive quiet NaN), an all -inf grid gives
+ * -inf.  d_field (device, f64[n,h,w,2], may be NULL) receives the field; h_max f64[n] the maxima.  n <= 65535 and
+ * w * h <= INT_MAX, else EVH_ERR_CAPACITY.  Synchronises.                                                     */
 int evh_fixed_plane_field(evh_ctx* ctx, const double* h_Hsup, int n, int w, int h, double* d_field, double* h_max);
 
 /* ---- N1: the consumers of dict_with_homography_matrix.json ------------------------------------------------ */

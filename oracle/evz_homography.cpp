@@ -10,6 +10,8 @@
  *   evenvizion/processing/utils.py:258-325      find_point_displacement / get_largest_group_points
  *   evenvizion/processing/utils.py:328-363      compute_homography
  *   evenvizion/processing/utils.py:118-145      matrix_superposition
+ *   evenvizion/visualization/processing_visualization.py:401-419  the heat-map field and its np.max
+ *   evenvizion/processing/fixed_coordinate_system.py:56-69,109-122  np.around(homography_transformation(...))
  *   evenvizion/processing/video_processing.py:58-107  the stream loop
  * findHomography's arithmetic (calib3d ptsetreg/fundam/levmarq, core Jacobi) is restated from the published
  * OpenCV 3.4 algorithm; pinned jointly with the other operators, since round 4, by the reference's own video and recorded result (tests/test_capture_golden.py: all 120 matrices of dict_with_homography_matrix.json reproduced to the last digit) -- see evz_oracle.h.  The Python-glue functions are pinned by the
@@ -594,6 +596,63 @@ extern "C" void evo_matrix_superposition(const double* H, const double* Hsup, in
     for (int c = 0; c < 3; c++)  // np.dot(3x3, 3x3): forward FMA chain (pinned by glue_goldens.json "sup_false")
       P[3 * r + c] = std::fma(H[3 * r + 2], Hsup[6 + c], std::fma(H[3 * r + 1], Hsup[3 + c], H[3 * r] * Hsup[c]));
   for (int i = 0; i < 9; i++) out[i] = P[i] / P[8];
+}
+
+/* np.max's pairwise rule on the heat-map field: a NaN wins and stays; +0 outranks -0 (the device's integer key order) */
+static inline double np_max2(double m, double v) {
+  if (std::isnan(m)) return m;
+  if (std::isnan(v) || v > m || (v == m && std::signbit(m) && !std::signbit(v))) return v;
+  return m;
+}
+
+/* np.max(np.apply_along_axis(homography_transformation, 2, make_template((h, w, 3)), H)) per matrix
+ * (processing_visualization.py:401-419): field [n][h][w][2] (NULL: maxima only), max[n].  All -inf gives -inf;
+ * a NaN anywhere gives NaN.  Rows are shared out over `threads` workers.                                          */
+extern "C" void evo_fixed_plane_field(const double* Hs, int n, int w, int h, double* field, double* mx, int threads) {
+  const int64_t rows = (int64_t)n * h;
+  std::vector<double> rmax(rows);
+  auto work = [&](int t, int nt) {
+    for (int64_t r = t; r < rows; r += nt) {
+      const int f = (int)(r / h), y = (int)(r % h);
+      const double* H = Hs + 9 * (int64_t)f;
+      double m = -INFINITY;
+      for (int x = 0; x < w; x++) {
+        double tx, ty, tw;
+        hdot(H, (double)x, (double)y, &tx, &ty, &tw);
+        const double u = tx / tw, v = ty / tw;
+        if (field) { double* o = field + ((int64_t)f * w * h + (int64_t)y * w + x) * 2; o[0] = u; o[1] = v; }
+        m = np_max2(np_max2(m, u), v);
+      }
+      rmax[r] = m;
+    }
+  };
+  if (threads <= 1) work(0, 1);
+  else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) th.emplace_back(work, t, threads);
+    for (auto& x : th) x.join();
+  }
+  for (int f = 0; f < n; f++) {
+    double m = -INFINITY;
+    for (int y = 0; y < h; y++) m = np_max2(m, rmax[(int64_t)f * h + y]);
+    mx[f] = std::isnan(m) ? std::fabs(NAN) : m;
+  }
+}
+
+/* from_original_to_fix / from_fix_to_original's point arithmetic (fixed_coordinate_system.py:56-69, 109-122),
+ * batched as evh_transform_points: out[i] = np.around(np.dot(M[idx[i]], (kx*x, ky*y, 1))[:2] / [2], decimals);
+ * np.around = rint(v * 10^d) / 10^d with 10^d built by repeated multiplication (exact to 10^22); decimals < 0: none. */
+extern "C" void evo_transform_points(const double* M, const int32_t* idx, const double* pts, int n, double kx, double ky,
+                                     int decimals, double* out) {
+  double sc = 1.0;
+  for (int d = 0; d < decimals; d++) sc *= 10.0;
+  for (int i = 0; i < n; i++) {
+    double tx, ty, tw;
+    hdot(M + 9 * (int64_t)idx[i], kx * pts[2 * i], ky * pts[2 * i + 1], &tx, &ty, &tw);
+    double u = tx / tw, v = ty / tw;
+    if (decimals >= 0) { u = std::rint(u * sc) / sc; v = std::rint(v * sc) / sc; }
+    out[2 * i] = u; out[2 * i + 1] = v;
+  }
 }
 
 /* KeyPoints.match_static_kps (matching.py:131-163); a = self (current frame), b = acceding (previous) */

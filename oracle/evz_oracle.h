@@ -132,6 +132,11 @@ int evo_compute_homography(const float* a, const float* b, int n, const double* 
 int evo_compute_homography_ex(const float* a, const float* b, int n, const double* Hsup, int force_max, double* H);
 /* matrix_superposition (utils.py:118-145) */
 void evo_matrix_superposition(const double* H, const double* Hsup, int first, double* out);
+/* heat-map field + np.max per matrix (processing_visualization.py:401-419); field [n][h][w][2] or NULL */
+void evo_fixed_plane_field(const double* Hs, int n, int w, int h, double* field, double* mx, int threads);
+/* np.around(homography_transformation((kx*x, ky*y), M[idx[i]]), decimals) per point (fixed_coordinate_system.py) */
+void evo_transform_points(const double* M, const int32_t* idx, const double* pts, int n, double kx, double ky,
+                          int decimals, double* out);
 
 /* ---- whole path ---- */
 /* KeyPoints.match_static_kps from two keypoint sets; returns status, static points in oa/ob (cap = nq) */

@@ -256,6 +256,46 @@ def matrix_superposition(H, Hsup, first=False):
     return out.reshape(3, 3)
 
 
+def superposition_chain(Hs):
+    """utils.superposition_dict's running product over per-frame H in frame order (each 3x3 or None) -> list of
+    f64[3,3]: the first H passes through, a None H repeats the previous superposition.  A leading None is refused
+    (the reference crashes on it)."""
+    out, sup = [], None
+    for H in Hs:
+        if H is None:
+            if sup is None:
+                raise TypeError("superposition_chain: the first H is None")
+        else:
+            sup = matrix_superposition(H, sup, sup is None)
+        out.append(sup)
+    return out
+
+
+def fixed_plane_field(Hs, w, h, want_field=True, threads=None):
+    """Hs f64[n,3,3] -> (field f64[n,h,w,2] or None, max f64[n]): the heat-map field of every matrix over the
+    w x h grid and its np.max (NaN propagates, all -inf gives -inf)."""
+    Hs = np.ascontiguousarray(Hs, np.float64).reshape(-1, 9)
+    n = len(Hs)
+    field = np.empty((n, h, w, 2), np.float64) if want_field else None
+    mx = np.zeros(n, np.float64)
+    if threads is None:
+        threads = min(16, os.cpu_count() or 1)
+    lib().evo_fixed_plane_field(_p(Hs), n, int(w), int(h), None if field is None else _p(field), _p(mx), int(threads))
+    return field, mx
+
+
+def transform_points(mats, idx, pts, kx=1.0, ky=1.0, decimals=-1):
+    """pts f64[n,2], idx i32[n] (row of mats f64[m,3,3] per point) -> f64[n,2]: np.around(homography_transformation(
+    (kx*x, ky*y), mats[idx]), decimals); decimals < 0: no rounding."""
+    mats = np.ascontiguousarray(mats, np.float64).reshape(-1, 9)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    assert len(idx) == len(pts) and (len(idx) == 0 or (idx.min() >= 0 and idx.max() < len(mats)))
+    out = np.zeros_like(pts)
+    lib().evo_transform_points(_p(mats), _p(idx), _p(pts), len(pts), C.c_double(kx), C.c_double(ky), int(decimals), _p(out))
+    return out
+
+
 def match_static(xy_a, desc_a, xy_b, desc_b):
     """KeyPoints(a).match_static_kps(KeyPoints(b)) -> (status, pts_a, pts_b)"""
     xy_a = _f32(xy_a).reshape(-1, 2); xy_b = _f32(xy_b).reshape(-1, 2)

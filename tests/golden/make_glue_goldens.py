@@ -10,6 +10,7 @@ image and are replaced by inert stub modules here, so only the reference's glue 
     utils.compute_homography's pre-transform                    (utils.py:351-358)
     utils.matrix_superposition / superposition_dict             (utils.py:118-145,184-211)
     utils.homography_transformation                             (utils.py:71-92)
+    np.max(np.apply_along_axis(homography_transformation, ...))  (processing_visualization.py:401-419)
     video_processing.get_homography_dict's loop                 (video_processing.py:58-107)
 plus the reference's one known-answer artefact (metrics_file.txt).
 Fixtures are data (inputs + expected outputs); no reference source text is stored.
@@ -226,15 +227,12 @@ def main():
     hd, resize_info = utils.read_homography_dict(gpath)
     sup = utils.superposition_dict(hd)
     h, w = resize_info["h"], resize_info["w"]
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    # per-frame maxima through the reference's own functions (processing_visualization.py:401-419), not a vectorised
+    # restatement: np.dot's summation order is part of what is pinned
+    import evenvizion.visualization.processing_visualization as pv
+    template = pv.make_template((h, w, 3))
     keys = list(sup.keys())
-    maxima = []
-    for k in keys:
-        Hk = np.asarray(sup[k], np.float64)
-        d = Hk[2, 0] * xs + Hk[2, 1] * ys + Hk[2, 2]
-        u = (Hk[0, 0] * xs + Hk[0, 1] * ys + Hk[0, 2]) / d
-        v = (Hk[1, 0] * xs + Hk[1, 1] * ys + Hk[1, 2]) / d
-        maxima.append(float(max(u.max(), v.max())))
+    maxima = [float(np.max(np.apply_along_axis(utils.homography_transformation, 2, template, sup[k]))) for k in keys]
     metric_txt = open(os.path.join(REF, "evenvizion/examples/test_video_processing/test_video/metrics_file.txt")).read()
     out["kat_f12"] = dict(metrics_file=metric_txt.strip(), n_matrices=len(hd), resize_info=resize_info,
                           max_excluding_last=float(np.max(maxima[:-1])), max_including_last=float(np.max(maxima)),

@@ -901,9 +901,11 @@ def test_python_api_mirror_vs_oracle():
     runtime.reset()
 
 
-def test_heatmap_extent_reproduces_reference_metrics_file():
+def test_heatmap_field_in_reference_order_reproduces_metrics_file():
     """N3: the GPU coordinate field reproduces the reference's committed metrics_file.txt bit for bit
-    (Maximum movement during the entire video: 863.0428982580879) from the committed H JSON."""
+    (Maximum movement during the entire video: 863.0428982580879) from the committed H JSON, and its field is the
+    reference's own np.apply_along_axis(homography_transformation) (fma(h0, x, h1*y) + h2), not an unfused
+    ((h0*x + h1*y) + h2) restatement, which differs at ~10^4 coordinates of a frame."""
     import os
     from evenvizion_amd import heatmap, runtime
     from evenvizion_amd.processing import utils
@@ -915,17 +917,22 @@ def test_heatmap_extent_reproduces_reference_metrics_file():
     assert heatmap.max_movement(sup, ri) == want == 863.0428982580879
     keys, m = heatmap.frame_maxima(sup, ri)
     assert keys[0] == 1 and m[0] == 399.0          # frame 1 = identity: max(x) over the 400 x 224 grid
-    ys, xs = np.mgrid[0:ri["h"], 0:ri["w"]].astype(np.float64)
+    # frame 61 against the reference's own np.apply_along_axis(homography_transformation) (tests/golden/plane_goldens.json)
+    # and the oracle's restatement of its arithmetic order, fma(h0, x, h1*y) + h2
+    import hashlib
+    import json
+    rec = json.load(open(os.path.join(gold, "plane_goldens.json")))["video"]["frames"][60]
     Hk = np.asarray(sup[keys[60]], np.float64)
-    d = Hk[2, 0] * xs + Hk[2, 1] * ys + Hk[2, 2]
-    u = (Hk[0, 0] * xs + Hk[0, 1] * ys + Hk[0, 2]) / d; v = (Hk[1, 0] * xs + Hk[1, 1] * ys + Hk[1, 2]) / d
-    assert m[60] == max(u.max(), v.max())
+    assert rec["frame"] == keys[60] and Hk.ravel().tolist() == rec["H"]
+    assert m[60] == rec["max"]
     import torch
     field = torch.zeros(1, ri["h"], ri["w"], 2, dtype=torch.float64, device="cuda")
     ctx = runtime.get_context(400, 224)
     ctx.fixed_plane_max(Hk[None], ri["w"], ri["h"], field=field)
     got = field.cpu().numpy()[0]
-    assert np.array_equal(got[..., 0], u) and np.array_equal(got[..., 1], v)
+    want, want_max = O.fixed_plane_field(Hk, ri["w"], ri["h"])
+    assert np.array_equal(got, want[0]) and want_max[0] == rec["max"]
+    assert hashlib.sha256(got.tobytes()).hexdigest() == rec["field_sha256"]
     runtime.reset()
 
 

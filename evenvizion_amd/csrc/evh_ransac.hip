@@ -797,7 +797,7 @@ __device__ __forceinline__ double wave_sum_f64_(double v) {
   for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
   return v;
 }
-__device__ void fast_solve8(int lane, const double* A, const double* b, double* x, int* ok);
+__device__ void fast_solve8(int lane, const double* A, const double* b, double* x, int* ok, double min_rel_pivot = 0.0);
 struct SolveLds;
 __device__ __forceinline__ bool dlt_rows_fast(SolveLds& S, RowMat& M, int lane, const float* rows, int count, double* Hout /* LDS */,
                                               unsigned long long* prof) {
@@ -843,7 +843,11 @@ __device__ __forceinline__ bool dlt_rows_fast(SolveLds& S, RowMat& M, int lane, 
   WSYNC();
   // The refit only seeds the LM refinement, so in this mode the smallest eigenvector of L^T L (117 Jacobi rotations) gives way
   // to the inhomogeneous least-squares solution with h33 = 1 in the normalised frame: one 8x8 LDL^T.  A pivot that is not
-  // positive, or a solution that is not finite, falls back to the eigen-solve.
+  // positive, or a solution that is not finite, falls back to the eigen-solve.  So does a pivot at or below 1e-10 of its
+  // diagonal entry: when the horizon of H passes through the source centroid, h33 = 0 in the normalised frame, the 8x8
+  // block is singular and its last pivot is rounding noise of either sign -- a positive one used to go through with a
+  // solution of ordinary size that is noise over noise, a seed LM could not repair (tests/solver_families.py, f6_horizon).
+  // A pivot ratio of 1e-10 means |h33| below ~1e-5 of the null vector in the normalised frame.
   if (lane == 0) {
     for (int i = 0; i < 8; i++) {
       for (int j = 0; j < 8; j++) S.Ap[i * 8 + j] = M.A[i * MS + j];
@@ -851,7 +855,7 @@ __device__ __forceinline__ bool dlt_rows_fast(SolveLds& S, RowMat& M, int lane, 
     }
   }
   WSYNC();
-  fast_solve8(lane, S.Ap, S.tmpd, S.d, &S.ib[2]);
+  fast_solve8(lane, S.Ap, S.tmpd, S.d, &S.ib[2], 1e-10);
   WSYNC();
   bool direct = S.ib[2] != 0;
   if (direct) {
@@ -1256,15 +1260,16 @@ __device__ __forceinline__ double dot8(const double* a, const double* b) {
 // truncation threshold), so along the weakest direction the two solvers differ in the leading digits of the step and, LM being
 // cut after 10 iterations, H ends up to ~6e-4 px (corners) away from OpenCV's -- an opt-in mode (include/evhip.h); the RANSAC
 // draw, the inlier masks and the refit are untouched.  Returns false when a pivot is not positive (the
-// caller then takes the exact path), so nothing is ever solved with a factorisation that does not exist.
-__device__ bool ldl8_factor(const double* A /*LDS, symmetric 8x8*/, double (&Lm)[28], double (&Dinv)[8]) {
+// caller then takes the exact path), so nothing is ever solved with a factorisation that does not exist; min_rel_pivot > 0
+// also refuses pivots at or below that fraction of their diagonal entry (numerically singular: the refit's h33 = 1 system).
+__device__ bool ldl8_factor(const double* A /*LDS, symmetric 8x8*/, double (&Lm)[28], double (&Dinv)[8], double min_rel_pivot) {
   double Dd[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     double dj = A[j * 8 + j];
 #pragma unroll
     for (int k = 0; k < j; k++) { const double l = Lm[(j * (j - 1)) / 2 + k]; dj -= l * l * Dd[k]; }
-    if (!(dj > 0)) return false;
+    if (!(dj > 0) || dj <= min_rel_pivot * A[j * 8 + j]) return false;
     Dd[j] = dj;
     Dinv[j] = 1.0 / dj;
 #pragma unroll
@@ -1295,10 +1300,10 @@ __device__ void ldl8_solve(const double (&Lm)[28], const double (&Dinv)[8], cons
   }
 }
 // lane 0: x = A^-1 b (b != null) or x[0] = max_i |(A^-1)_ii| (b == null); flag in ok (LDS int)
-__device__ void fast_solve8(int lane, const double* A, const double* b, double* x, int* ok) {
+__device__ void fast_solve8(int lane, const double* A, const double* b, double* x, int* ok, double min_rel_pivot) {
   if (lane == 0) {
     double Lm[28], Dinv[8];
-    bool good = ldl8_factor(A, Lm, Dinv);
+    bool good = ldl8_factor(A, Lm, Dinv, min_rel_pivot);
     if (good) {
       if (b) {
         double bb[8], xx[8];

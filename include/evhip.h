@@ -147,7 +147,8 @@ enum { EVH_ORDER_CANONICAL = 0, EVH_ORDER_OPENCV = 1 };
  * EVH_SOLVER_FAST ("tolerance mode"): after RANSAC -- whose random draw, hypotheses and inlier masks stay exact, so statuses are
  *   identical -- (1) LM's 8x8 systems by LDL^T (a non-positive pivot falls back to the exact path), (2) the sums of the refit and
  *   of the LM evaluations by per-lane partial sums and a tree instead of the operator's point order, (3) the refit itself by the
- *   inhomogeneous least-squares solution with h33 = 1 in the normalised frame (one 8x8 LDL^T; eigen-solve as the fall-back) --
+ *   inhomogeneous least-squares solution with h33 = 1 in the normalised frame (one 8x8 LDL^T; the eigen-solve when a
+ *   pivot is not above 1e-10 of its diagonal entry -- h33 ~ 0 there, e.g. a horizon through the centroid -- or |h| >= 1e12) --
  *   it only seeds LM.  A stream pair costs 2.5-3x less (bench.py --config 3: 2.0 k -> 5.8 k pairs/s; the reference's default
  *   detector list at 400x224: 0.85 k -> 1.8 k), but H is no longer OpenCV's to the digit: the systems are graded over 14 orders
  *   of magnitude (raw pixel coordinates), the loop is cut after 10 iterations, and where the data do not determine H the end

@@ -276,7 +276,8 @@ bool check_subset(const float* ms1, const float* ms2, int count) {
   return true;
 }
 
-bool get_subset(const float* m1, const float* m2, int count, float* ms1, float* ms2, Rng& rng, int maxAttempts) {
+bool get_subset(const float* m1, const float* m2, int count, float* ms1, float* ms2, Rng& rng, int maxAttempts,
+                int* rejected) {
   int idx[4], i = 0, j, iters = 0;
   for (; iters < maxAttempts; iters++) {
     for (i = 0; i < 4 && iters < maxAttempts;) {
@@ -290,7 +291,7 @@ bool get_subset(const float* m1, const float* m2, int count, float* ms1, float* 
       ms2[2 * i] = m2[2 * idx_i]; ms2[2 * i + 1] = m2[2 * idx_i + 1];
       i++;
     }
-    if (i == 4 && !check_subset(ms1, ms2, i)) continue;
+    if (i == 4 && !check_subset(ms1, ms2, i)) { if (rejected) ++*rejected; continue; }
     break;
   }
   return i == 4 && iters < maxAttempts;
@@ -465,10 +466,13 @@ int lm_refine(const float* M, const float* m, int count, double* H) {
 }  // namespace
 
 /* force_max != 0: the iteration bound is never lowered (RANSACUpdateNumIters is not called), i.e. exactly
- * max(maxItersArg, 1) accepted samples are evaluated -- the fixed-iteration workload of BASELINE configs[2]. */
-extern "C" int evo_find_homography_ex(const float* a, const float* b, int n, double thr, int maxItersArg, double conf,
-                                      int force_max, double* H, uint8_t* mask, int* info) {
+ * max(maxItersArg, 1) accepted samples are evaluated -- the fixed-iteration workload of BASELINE configs[2].
+ * stats (may be null): [0] 4-subsets drawn and rejected by check_subset, [1] 1 if a draw ran out of its 10000 attempts,
+ * [2] accepted subsets whose DLT failed (hypotheses skipped). */
+static int find_homography_impl(const float* a, const float* b, int n, double thr, int maxItersArg, double conf, int force_max,
+                                double* H, uint8_t* mask, int* info, int* stats) {
   int it_run = 0, best = 0, lm_it = 0;
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
   bool result = false;
   if (info) info[0] = info[1] = info[2] = 0;
   for (int i = 0; i < n; i++) mask[i] = 0;
@@ -488,10 +492,14 @@ extern "C" int evo_find_homography_ex(const float* a, const float* b, int n, dou
     double model[9], bestModel[9];
     float ms1[8], ms2[8];
     for (int iter = 0; iter < niters; iter++) {
-      bool found = get_subset(a, b, n, ms1, ms2, rng, 10000);
-      if (!found) { if (iter == 0) return 0; break; }
+      bool found = get_subset(a, b, n, ms1, ms2, rng, 10000, stats ? &stats[0] : nullptr);
+      if (!found) {
+        if (stats) stats[1] = 1;
+        if (iter == 0) return 0;
+        break;
+      }
       it_run = iter + 1;
-      if (evo_dlt(ms1, ms2, 4, model) <= 0) continue;
+      if (evo_dlt(ms1, ms2, 4, model) <= 0) { if (stats) stats[2]++; continue; }
       int good = find_inliers(a, b, n, model, t, cur.data());
       if (good > std::max(maxGood, 3)) {
         memcpy(mask, cur.data(), n);
@@ -516,6 +524,18 @@ extern "C" int evo_find_homography_ex(const float* a, const float* b, int n, dou
   }
   if (info) info[2] = lm_it;
   return 1;
+}
+
+extern "C" int evo_find_homography_ex(const float* a, const float* b, int n, double thr, int maxItersArg, double conf,
+                                      int force_max, double* H, uint8_t* mask, int* info) {
+  return find_homography_impl(a, b, n, thr, maxItersArg, conf, force_max, H, mask, info, nullptr);
+}
+
+/* evo_find_homography_ex plus the draw's accounting (stats[3], see find_homography_impl): lets the tests show that a point
+ * set really drives get_subset's attempt loop */
+extern "C" int evo_find_homography_stats(const float* a, const float* b, int n, double thr, int maxItersArg, double conf,
+                                         int force_max, double* H, uint8_t* mask, int* info, int* stats) {
+  return find_homography_impl(a, b, n, thr, maxItersArg, conf, force_max, H, mask, info, stats);
 }
 
 extern "C" int evo_find_homography(const float* a, const float* b, int n, double thr, int maxItersArg, double conf,

@@ -120,6 +120,10 @@ int evo_find_homography(const float* a, const float* b, int n, double thr, int m
  * evaluated (the fixed-iteration RANSAC of BASELINE configs[2]; not a reference mode, a stress variant of it) */
 int evo_find_homography_ex(const float* a, const float* b, int n, double thr, int max_iters, double conf,
                            int force_max, double* H, uint8_t* mask, int* info);
+/* the same plus the draw's accounting: stats[0] = 4-subsets rejected by checkSubset (collinear triple or mixed orientation),
+ * stats[1] = 1 when a draw ran out of getSubset's 10000 attempts, stats[2] = accepted subsets whose DLT failed */
+int evo_find_homography_stats(const float* a, const float* b, int n, double thr, int max_iters, double conf,
+                              int force_max, double* H, uint8_t* mask, int* info, int* stats);
 /* building blocks exposed for tests */
 int evo_dlt(const float* src, const float* dst, int n, double* H);
 void evo_jacobi(double* A, int n, double* W, double* V);

@@ -215,6 +215,21 @@ def find_homography(a, b, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=F
     return (H.reshape(3, 3) if ok else None), mask[:n].copy(), info
 
 
+def find_homography_stats(a, b, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False):
+    """find_homography plus the draw's accounting -> (H or None, mask, info, stats i32[3]): stats[0] 4-subsets rejected by
+    checkSubset, stats[1] 1 when a draw ran out of getSubset's 10000 attempts, stats[2] accepted subsets whose DLT failed."""
+    a = _f32(a).reshape(-1, 2); b = _f32(b).reshape(-1, 2)
+    n = len(a)
+    H = np.zeros(9, np.float64); mask = np.zeros(max(n, 1), np.uint8); info = np.zeros(3, np.int32)
+    stats = np.zeros(3, np.int32)
+    f = lib().evo_find_homography_stats
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]
+    ok = f(_p(a), _p(b), n, float(thr), int(max_iters), float(conf), int(bool(force_max_iters)), _p(H), _p(mask), _p(info),
+           _p(stats))
+    return (H.reshape(3, 3) if ok else None), mask[:n].copy(), info, stats
+
+
 def dlt(src, dst):
     src = _f32(src).reshape(-1, 2); dst = _f32(dst).reshape(-1, 2)
     H = np.zeros(9, np.float64)

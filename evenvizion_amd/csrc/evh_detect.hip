@@ -386,132 +386,6 @@ __global__ __launch_bounds__(256) void k_gray_pyr1(const uint8_t* __restrict__ s
   }
 }
 
-// K2, two levels per launch (round 3): a workgroup owns one 128 x 32 tile of level l+1.  It stages the
-// level l-1 footprint of the level-l pixels that tile needs, produces those level-l pixels into LDS, stores the ones it
-// OWNS (the partition of k_gray_pyr1: columns [xofs[x0] & ~3, xofs[x0 + 128] & ~3), rows [yofs[y0], yofs[y0 + 32]) of the
-// level l+1 tap tables) and then produces its level l+1 tile from LDS: level l is written once and never read back
-// (levels 2..7 in three launches; HBM bytes per frame 3.15 -> 2.39 MB at 720p).  Same arithmetic as k_pyr_down.
-#define P2_SW 240    // staged level l-1 row bytes (>= 1.21*176 + 2 + 15, multiple of 16)
-#define P2_SH 57     // staged level l-1 rows      (>= 1.21*44 + 3)
-struct Pyr2Level { int64_t off; int stride, w, h; const int *xofs, *xc1, *yofs, *yc1; };
-__global__ __launch_bounds__(256) void k_pyr_two(uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes, int64_t s_off,
-                                                 int s_stride, Pyr2Level M, Pyr2Level D, int tiles_x, int tiles_y,
-                                                 int tx_magic, int nframes) {
-  __shared__ uint32_t tileS[P2_SH * P2_SW / 4];
-  __shared__ uint32_t tileM[GP_SH * GP_SW / 4];
-  __shared__ int x1o[GP_SW]; __shared__ int x1c[GP_SW]; __shared__ int y1o[GP_SH]; __shared__ int y1c[GP_SH];
-  __shared__ int xo_s[PD_W]; __shared__ int xc_s[PD_W]; __shared__ int yo_s[PD_H]; __shared__ int yc_s[PD_H];
-  int f, bt;
-  xcd_order(bt, f);
-  if (bt >= tiles_x * tiles_y || f >= nframes) return;  // grid padding (workgroup-uniform)
-  const int ty = div_magic20(bt, tx_magic), tx = bt - ty * tiles_x;
-  const int x0 = tx * PD_W, y0 = ty * PD_H;
-  const int x1 = min(x0 + PD_W, D.w) - 1, y1 = min(y0 + PD_H, D.h) - 1;
-  // level-l region of this workgroup: what it owns and what its level l+1 tile reads
-  const int rx0 = D.xofs[x0] & ~3, ry0 = D.yofs[y0];
-  const int own_x1 = (tx == tiles_x - 1) ? ((M.w + 3) & ~3) : (D.xofs[x0 + PD_W] & ~3);
-  const int own_y1 = (ty == tiles_y - 1) ? M.h : D.yofs[y0 + PD_H];
-  const int rx1 = max(own_x1, min(D.xofs[x1] + 2, M.w)), ry1 = max(own_y1, min(D.yofs[y1] + 2, M.h));   // exclusive
-  const int nqx = (rx1 - rx0 + 3) >> 2, nr = ry1 - ry0;                                                 // <= 44, <= 44
-  // level l-1 footprint of that region (a right / bottom edge tap is (size - 2, weight 256): ofs + 1 stays inside)
-  const int cx1 = min(rx1, M.w) - 1;
-  const int sx0 = M.xofs[rx0] & ~15, sy0 = M.yofs[ry0];
-  const int ex = M.xofs[cx1] + 1, ey = M.yofs[ry1 - 1] + 1;
-  const int ncol16 = (ex - sx0) / 16 + 1, nrow = ey - sy0 + 1;     // <= P2_SW/16 = 15, <= P2_SH
-  uint8_t* base = pyr + (int64_t)f * pyr_frame_bytes;
-  {
-    // 16 threads per staged row (<= 15 move a 16-byte cell); a thread's four cells (rows 16 apart) are all requested
-    // before the first is stored: clamped addresses, the stores carry the bounds
-    const int c16 = threadIdx.x & 15, r0 = threadIdx.x >> 4;
-    const uint4* colc = reinterpret_cast<const uint4*>(base + s_off + sx0) + min(c16, ncol16 - 1);
-    const int stride16 = s_stride >> 4;
-    static_assert((P2_SH + 15) / 16 == 4, "four staged rows per thread");
-#define P2_LD(k) colc[mad24((uint32_t)(sy0 + min(r0 + 16 * (k), nrow - 1)), (uint32_t)stride16, 0u)]
-    const uint4 v0 = P2_LD(0), v1 = P2_LD(1), v2 = P2_LD(2), v3 = P2_LD(3);
-#undef P2_LD
-    // the tap tables of both levels while the loads are in flight
-    for (int t = threadIdx.x; t < GP_SW + GP_SH + PD_W + PD_H; t += 256) {
-      if (t < GP_SW) {
-        const int xi = min(rx0 + t, M.w - 1);
-        x1o[t] = M.xofs[xi] - sx0; x1c[t] = M.xc1[xi];
-      } else if (t < GP_SW + GP_SH) {
-        const int r = t - GP_SW, yi = min(ry0 + r, M.h - 1);
-        y1o[r] = M.yofs[yi] - sy0; y1c[r] = M.yc1[yi];
-      } else if (t < GP_SW + GP_SH + PD_W) {
-        const int c = t - GP_SW - GP_SH, xi = min(x0 + c, D.w - 1);
-        xo_s[c] = D.xofs[xi] - rx0; xc_s[c] = D.xc1[xi];
-      } else {
-        const int r = t - GP_SW - GP_SH - PD_W, yi = min(y0 + r, D.h - 1);
-        yo_s[r] = D.yofs[yi] - ry0; yc_s[r] = D.yc1[yi];
-      }
-    }
-    if (c16 < ncol16) {
-      uint4* d = reinterpret_cast<uint4*>(&tileS[r0 * (P2_SW / 4) + c16 * 4]);
-      if (r0 < nrow) d[0] = v0;
-      if (r0 + 16 < nrow) d[16 * (P2_SW / 16)] = v1;
-      if (r0 + 32 < nrow) d[32 * (P2_SW / 16)] = v2;
-      if (r0 + 48 < nrow) d[48 * (P2_SW / 16)] = v3;
-    }
-  }
-  __syncthreads();
-  {
-    // level l: every quad of the region from the staged level l-1 bytes; owned quads also go to HBM
-    const uint8_t* ts = reinterpret_cast<const uint8_t*>(tileS);
-    uint8_t* mimg = base + M.off;
-    const float inv = 1.0f / (float)nqx;
-    for (int q = threadIdx.x; q < nqx * nr; q += 256) {
-      const int r = (int)(((float)q + 0.5f) * inv);     // exact: q + 0.5 is at least 0.5 away from a multiple of nqx
-      const int qx = q - (int)mad24((uint32_t)r, (uint32_t)nqx, 0u);
-      const int x = rx0 + 4 * qx, y = ry0 + r;
-      if (x >= M.w) continue;                            // padding quad: never read by a tap, never stored
-      const uint8_t* r0p = ts + y1o[r] * P2_SW;
-      const uint8_t* r1p = r0p + P2_SW;
-      const uint32_t m1 = (uint32_t)y1c[r], m0 = 256u - m1;
-      uint32_t v[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int o = x1o[qx * 4 + i];
-        const uint32_t c1 = (uint32_t)x1c[qx * 4 + i], c0 = 256u - c1;
-        const uint32_t a0 = r0p[o], b0 = r0p[o + 1], a1 = r1p[o], b1 = r1p[o + 1];
-        const uint32_t h0 = mad24(a0, c0, mad24(b0, c1, 0u));
-        const uint32_t h1 = mad24(a1, c0, mad24(b1, c1, 0u));
-        v[i] = mad24(h0, m0, mad24(h1, m1, 32768u));
-      }
-      const uint32_t out = __builtin_amdgcn_perm(v[1], v[0], 0x0C0C0602u) | __builtin_amdgcn_perm(v[3], v[2], 0x06020C0Cu);
-      tileM[r * (GP_SW / 4) + qx] = out;
-      if (x < own_x1 && y < own_y1)
-        *reinterpret_cast<uint32_t*>(mimg + mad24((uint32_t)y, (uint32_t)M.stride, (uint32_t)x)) = out;
-    }
-  }
-  __syncthreads();
-  uint8_t* dimg = base + D.off;
-  const uint8_t* tile = reinterpret_cast<const uint8_t*>(tileM);
-  const int qx = threadIdx.x & 31, qy = threadIdx.x >> 5;
-  const int x = x0 + qx * 4;
-  if (x >= D.w) return;
-#pragma unroll
-  for (int rr = 0; rr < PD_H / 8; rr++) {
-    const int y = y0 + qy * (PD_H / 8) + rr;
-    if (y >= D.h) break;
-    const uint8_t* r0 = tile + yo_s[qy * (PD_H / 8) + rr] * GP_SW;
-    const uint8_t* r1 = r0 + GP_SW;
-    const int m1 = yc_s[qy * (PD_H / 8) + rr];
-    const uint32_t m0 = 256u - (uint32_t)m1;      // same arithmetic as k_pyr_down
-    uint32_t v[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int o = xo_s[qx * 4 + i];
-      const uint32_t c1 = (uint32_t)xc_s[qx * 4 + i], c0 = 256u - c1;
-      const uint32_t a0 = r0[o], b0 = r0[o + 1], a1 = r1[o], b1 = r1[o + 1];
-      const uint32_t h0 = mad24(a0, c0, mad24(b0, c1, 0u));
-      const uint32_t h1 = mad24(a1, c0, mad24(b1, c1, 0u));
-      v[i] = mad24(h0, m0, mad24(h1, (uint32_t)m1, 32768u));
-    }
-    const uint32_t out = __builtin_amdgcn_perm(v[1], v[0], 0x0C0C0602u) | __builtin_amdgcn_perm(v[3], v[2], 0x06020C0Cu);
-    reinterpret_cast<uint32_t*>(dimg)[mad24((uint32_t)y, (uint32_t)(D.stride >> 2), (uint32_t)(x >> 2))] = out;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // K3: FAST-9/16 + corner score + 3x3 NMS + 31-px border filter, all pyramid levels of all frames in one launch.
 // Workgroup = 64x32 output tile; the tile plus a 4-pixel halo is staged in LDS (coalesced dword loads), the
@@ -548,11 +422,7 @@ struct FastArgs {
 #define FR_H (FT_H + 8)          // staged raw rows: y0-4 .. y0+FT_H+3
 #define FS_DW ((FT_W + 8) / 4)   // score row: x0-4 .. x0+131, 34 quads (dwords of 4 byte scores)
 #define FS_H (FT_H + 2)          // score rows: y0-1 .. y0+FT_H
-#ifdef EVH_FAST_TWO_LEVEL
-#define FSC_CAP (FT_W * FT_H / 2) // the A/B variant parks its first-level queue (<= 1020 quad indices) in the same words
-#else
 #define FSC_CAP 512              // scored-pixel list of the lifted path
-#endif
 
 // byte B (relative to the quad's own dword M; -4..-1 = left neighbour dword, 4..7 = right neighbour dword)
 template <int B>
@@ -629,7 +499,7 @@ struct FastLds {
   // instead of 9 workgroups sit on a compute unit while some of them are down to their tail wave
   uint16_t scored[FSC_CAP];
   alignas(16) uint32_t sink[4];      // target of the second staging store of threads that have no second item
-  int lcnt, gbase, qcnt, scnt, q1cnt;
+  int lcnt, gbase, qcnt, scnt;
   int wtot[4];                       // ordered collection: survivors per wave of the current pass
   uint32_t rowcnt[8];                // ordered collection: survivors per tile row, one byte each (FT_H = 28 rows)
 };
@@ -637,7 +507,7 @@ struct FastLds {
 // stage rows y0-4 .. y0+FT_H+3, columns x0-8 .. x0+135 with 16-byte loads (data outside the image reads as 0: it
 // only feeds pixels whose centre is outside the testable range, which are never scored); clears the counters
 __device__ __forceinline__ void fast_stage(FastLds& S, const uint8_t* img, const EvhLevel& L, int x0, int y0) {
-  if (threadIdx.x == 0) { S.lcnt = 0; S.qcnt = 0; S.scnt = 0; S.q1cnt = 0; }
+  if (threadIdx.x == 0) { S.lcnt = 0; S.qcnt = 0; S.scnt = 0; }
   if (threadIdx.x >= 8 && threadIdx.x < 16) S.rowcnt[threadIdx.x - 8] = 0;
   // 16-byte items (x0 - 8 = 16 + 128 tx is 16-byte aligned, a staged row is 9 of them): item i = (row i / 9,
   // column i % 9), 324 items = 2 per thread at most; +256 items = +28 rows +4 columns.  Rows are padded to 64 bytes,
@@ -734,23 +604,6 @@ __device__ __forceinline__ uint32_t pretest_pass4(uint32_t c, uint32_t rd, uint3
   return BITOP3(Dm, Bm, H, (A | B) & C);
 }
 
-// the vertical ring pair alone (points 0 and 8): every 9-arc holds one of them, so "neither differs from the centre by
-// more than T" rejects exactly.  First level of the two-level variant (EVH_FAST_TWO_LEVEL, an A/B build: see
-// profiles/r03_fast_two_level_ab.txt); half the comparison network and no v_alignbyte.
-__device__ __forceinline__ uint32_t vert_pass4(uint32_t c, uint32_t rd, uint32_t ru, uint32_t K4) {
-  const uint32_t H = 0x80808080u, Lm = 0x7F7F7F7Fu;
-  const uint32_t t = (c | H) - K4;
-  const uint32_t cl = BITOP3(t, c, Lm, A & (B | C));
-  const uint32_t u = (c & Lm) + K4;
-  const uint32_t ch = BITOP3(u, c, H, A | (B & C));
-  const uint32_t clH = cl | H, chL = ch & Lm;
-  const uint32_t D0 = swar_ge(clH, cl, rd, rd & Lm), D8 = swar_ge(clH, cl, ru, ru & Lm);
-  const uint32_t B0 = swar_ge(rd | H, rd, ch, chL), B8 = swar_ge(ru | H, ru, ch, chL);
-  const uint32_t Dm = BITOP3(D0 | D8, c, t, A & (B | C));
-  const uint32_t Bm = BITOP3(B0 | B8, c, u, A & ~(B & C));
-  return BITOP3(Dm, Bm, H, (A | B) & C);
-}
-
 // The segment test itself, byte-parallel: bit 7 of byte j = pixel j of the quad IS a corner at threshold T (nine contiguous
 // ring pixels all darker than centre - T or all brighter than centre + T), K4 = (T + 1) * 0x01010101.  p = the quad's centre row
 // in the staged tile (p[0], p[1], p[2] = the dwords of x-4.., x.., x+4..); ring byte k of the four pixels = one dword, taken
@@ -836,69 +689,6 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
   static_assert((FS_H * FS_DW) % 4 == 0 && FS_H * FS_DW <= 1024, "one 16-byte store per thread clears the score plane");
   if (threadIdx.x < FS_H * FS_DW / 4)                           // phase B overwrites the bytes that reach T
     reinterpret_cast<uint4*>(S.score)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-#ifdef EVH_FAST_TWO_LEVEL
-  {
-    // level 1: the vertical pair on every quad; survivors (quad index) -> q1, which lives in the words of S.scored (dead
-    // until phase B)
-    uint16_t* q1 = S.scored;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int i = threadIdx.x + 256 * k;
-      P[k] = 0;
-      if (i < FS_H * FS_DW) {
-        const uint32_t* p = S.raw + mad24((uint32_t)(sr + 3), FR_DW, (uint32_t)sq);
-        P[k] = vert_pass4(p[1], p[1 + 3 * FR_DW], p[1 - 3 * FR_DW], K4);
-      }
-      sr += 7; sq += 18;
-      if (sq >= FS_DW) { sq -= FS_DW; sr++; }
-    }
-    {
-      const unsigned long long m0 = __ballot(P[0] != 0), m1 = __ballot(P[1] != 0), m2 = __ballot(P[2] != 0),
-                               m3 = __ballot(P[3] != 0);
-      const int n0 = __popcll(m0), n1 = __popcll(m1), n2 = __popcll(m2), tot = n0 + n1 + n2 + __popcll(m3);
-      if (tot) {
-        int base = 0;
-        if ((threadIdx.x & 63) == 0) base = atomicAdd(&S.q1cnt, tot);
-        base = __builtin_amdgcn_readfirstlane(base);
-#define FQ1_PUSH(k, off, m)                                                                                             \
-        if (P[k]) q1[base + (off) + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)((m) >> 32),                               \
-                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)(m), 0u))] =    \
-            (uint16_t)(threadIdx.x + 256 * (k))
-        FQ1_PUSH(0, 0, m0); FQ1_PUSH(1, n0, m1); FQ1_PUSH(2, n0 + n1, m2); FQ1_PUSH(3, n0 + n1 + n2, m3);
-#undef FQ1_PUSH
-      }
-    }
-    __syncthreads();
-    // level 2: the full four-point test on the survivors, then the quad queue of phase B as before
-    const int n1 = S.q1cnt;
-    for (int e0 = 0; e0 < n1; e0 += 256) {             // workgroup-uniform
-      const int e = e0 + (int)threadIdx.x;
-      uint32_t Pq = 0; int qi = 0;
-      if (e < n1) {
-        qi = q1[e];
-        const int sr2 = qi / FS_DW, sq2 = qi - sr2 * FS_DW;
-        uint32_t cmask = 0x80808080u;
-        if (!interior) {
-          const int y = y0 - 1 + sr2, xq = x0 - 4 + sq2 * 4;
-          const bool rowok = y >= 3 && y < L.h - 3;
-          const int lo = min(max(3 - xq, 0), 4), hi = max(min(L.w - 3 - xq, 4), 0);
-          cmask = (rowok && lo < hi) ? (0x80808080u << (8 * lo)) & (0x80808080u >> (8 * (4 - hi))) : 0u;
-        }
-        const uint32_t* p = S.raw + mad24((uint32_t)(sr2 + 3), FR_DW, (uint32_t)sq2);
-        const uint32_t Lc = p[0], Mc = p[1], Rc = p[2], Mu = p[1 - 3 * FR_DW], Md = p[1 + 3 * FR_DW];
-        Pq = pretest_pass4(Mc, Md, __builtin_amdgcn_alignbyte(Rc, Mc, 3), Mu, __builtin_amdgcn_alignbyte(Mc, Lc, 1), K4) & cmask;
-      }
-      const unsigned long long m = __ballot(Pq != 0);
-      if (m) {
-        int base = 0;
-        if ((threadIdx.x & 63) == 0) base = atomicAdd(&S.qcnt, __popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (Pq) S.lst[base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] =
-            (uint32_t)qi | (((Pq >> 7) | (Pq >> 22)) << 16);
-      }
-    }
-  }
-#else
   // two copies of the loop: the interior one (most tiles) is straight-line code, so the LDS reads of its four quads
   // can be issued together instead of each behind its own range test
   auto quads = [&](auto interior_tag) {
@@ -1003,7 +793,6 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
 #undef FQ_PUSH
     }
   }
-#endif
   __syncthreads();
   const int nq = S.qcnt;
   // four lanes per queued quad.  (A pixel-granular list -- fewer busy waves -- was measured at +1.0 ms when a few dozen pixels
@@ -1667,12 +1456,11 @@ struct SelCvArgs {
   const uint32_t* tdesc;     // [nframes][total_tiles][8] tile burst descriptors written by k_fast
   int total_tiles;
   int heap_cap;              // entries of the dynamic LDS heap (>= 2 * largest quota + 1)
-  int level0, nlev;          // this launch handles levels level0 .. level0 + nlev - 1
   int phase_limit;           // profiling aid: 1 = stop after the row-major sequence, 2 = after the first retainBest, 0 = all
 };
 
 struct CvLds {
-  int wsumL[16], wsumR[16];   // up to 16 waves per workgroup (k_select_cv runs with 256 or 1024 threads)
+  int wsumL[16], wsumR[16];   // up to 16 waves per workgroup: k_select_cv's launch bounds (it is launched with 256 threads)
   int bc[16];
 };
 
@@ -1855,15 +1643,7 @@ __device__ void cv_heap_select(EP a, int first, int middle, int last, typename s
 // a range of at most CV_SMALL elements is worked on in LDS: a round then costs LDS latencies instead of a chain of
 // dependent global accesses (pivot, cut, lists), which is what the small pyramid levels and the last rounds of the large
 // ones consist of
-#ifndef CV_SMALL
 #define CV_SMALL 2048
-#endif
-#ifndef CV_MINW
-#define CV_MINW 1
-#endif
-#ifndef CV_MAXT
-#define CV_MAXT 1024
-#endif
 struct CvSmall {
   unsigned long long a[CV_SMALL];
   uint16_t l[CV_SMALL], r[CV_SMALL];
@@ -1961,17 +1741,16 @@ __device__ __forceinline__ float f32_from_order_key(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// Launched twice: the large pyramid levels with 1024 threads per workgroup (a partition pass is a chain of steps, each a
-// load + a workgroup scan + stores: four times the threads = a quarter of the steps), the small ones with 256.
-__global__ __launch_bounds__(CV_MAXT, CV_MINW) void k_select_cv(SelCvArgs B) {
+// One workgroup of 256 threads per (level, frame).  __launch_bounds__(1024, 1) and the blockDim-driven loops are what its
+// register allocation was tuned under (85 VGPRs, occupancy 5).
+__global__ __launch_bounds__(1024, 1) void k_select_cv(SelCvArgs B) {
   const SelectArgs& A = B.s;
   __shared__ CvLds S;
   __shared__ CvSmall SM;
   extern __shared__ unsigned long long cv_heap[];   // 2 * quota(level 0) + 2 entries
   int l, f;
   xcd_order(l, f);
-  if (f >= A.nframes || l >= B.nlev) return;
-  l += B.level0;
+  if (f >= A.nframes || l >= EVH_NLEVELS) return;
   const int tid = threadIdx.x, NT = (int)blockDim.x, NW = NT >> 6;
   const EvhLevel L = A.lv[l];
   const uint32_t* cand = A.cand + (int64_t)f * A.cand_frame_entries + L.cand_off;
@@ -2295,33 +2074,14 @@ int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int
 }
 
 int evh_launch_pyramid(evh_ctx* c, int nframes) {
-  // A/B aids, read at every launch (tests switch them): the round-2 kernel (k_pyr_down, 128 x 64 tiles) and two levels per
-  // launch (k_pyr_two: 24 % fewer HBM bytes, 70 % slower -- the pyramid is bound by its LDS byte reads and multiply-adds,
-  // profiles/r03_pyramid_two_ab.txt)
-  const bool old_form = getenv("EVH_PYR_OLD") != nullptr;
-  const bool two_form = getenv("EVH_PYR_TWO") != nullptr;
-  auto shrink_ok = [](const EvhLevel& S, const EvhLevel& D) {          // <= 1.21 x per axis: what the staged footprints are sized for
-    return (int64_t)S.w * 100 <= (int64_t)D.w * 121 && (int64_t)S.h * 100 <= (int64_t)D.h * 121 && D.w >= 2 && D.h >= 2;
-  };
   for (int l = c->level1_fused ? 2 : 1; l < EVH_NLEVELS; l++) {
     const EvhLevel& S = c->g.lv[l - 1];
     const EvhLevel& D = c->g.lv[l];
     const int* t = c->d_tabs + D.tab_off;   // xofs | xc1 | yofs | yc1 (linear_exact_tab in evh_api.hip)
-    if (two_form && l + 1 < EVH_NLEVELS && shrink_ok(S, D) && shrink_ok(D, c->g.lv[l + 1])) {
-      const EvhLevel& E = c->g.lv[l + 1];
-      const int* t2 = c->d_tabs + E.tab_off;
-      const Pyr2Level PM{D.off, D.stride, D.w, D.h, t, t + D.w, t + 2 * D.w, t + 2 * D.w + D.h};
-      const Pyr2Level PD{E.off, E.stride, E.w, E.h, t2, t2 + E.w, t2 + 2 * E.w, t2 + 2 * E.w + E.h};
-      const int tiles_x = (E.w + PD_W - 1) / PD_W, tiles_y = (E.h + PD_H - 1) / PD_H;
-      hipLaunchKernelGGL(k_pyr_two, xcd_grid(tiles_x * tiles_y, nframes), dim3(256), 0, c->stream, c->d_pyr,
-                         c->g.pyr_frame_bytes, S.off, S.stride, PM, PD, tiles_x, tiles_y, magic20(tiles_x), nframes);
-      EVH_HIP(c, hipGetLastError());
-      l++;
-      continue;
-    }
-    // the row-walking kernel stages <= 1.21 x its tile: ORB's levels shrink by 1.2 (a first level built from a
-    // resized frame never comes here: level 0 -> 1 has the same ratio)
-    const bool walk = !old_form && shrink_ok(S, D);
+    // k_pyr_walk stages <= 1.21 x its tile per axis.  ORB's levels shrink by 1.2 (level 1 of a resized frame too), but
+    // the rounded sizes of a few small levels shrink by more (400 x 220: level 7, 74 -> 61 rows): those take k_pyr_down
+    const bool walk = (int64_t)S.w * 100 <= (int64_t)D.w * 121 && (int64_t)S.h * 100 <= (int64_t)D.h * 121 &&
+                      D.w >= 2 && D.h >= 2;
     if (walk) {
       const int tiles_x = (D.w + PW_W - 1) / PW_W, tiles_y = (D.h + PW_H - 1) / PW_H;
       hipLaunchKernelGGL(k_pyr_walk, xcd_grid(tiles_x * tiles_y, nframes), dim3(256), 0, c->stream, c->d_pyr,
@@ -2366,8 +2126,8 @@ int evh_launch_fast(evh_ctx* c, int nframes, int share_group) {
   // lifted there, but the exact score is still only needed where the 4-point pre-test at 20 passes
   // reference order + lifting allowed: the full 16-point segment test decides which pixels get an exact score (k_fast_main with
   // lift_base; the 4-point pre-test alone was measured and dropped here: 22.8 ms against 19.8 ms dense on the 720p texture of
-  // SURVEY 8d, where it passes most quads).  EVH_FAST_DENSE=1 or evh_set_fast_lift(0): the dense kernel.
-  if (c->order_mode == EVH_ORDER_OPENCV && c->fast_lift && !getenv("EVH_FAST_DENSE")) {
+  // SURVEY 8d, where it passes most quads).  evh_set_fast_lift(0): the dense kernel.
+  if (c->order_mode == EVH_ORDER_OPENCV && c->fast_lift) {
     A.lift_base = 1;
     hipLaunchKernelGGL(k_fast_main, grid, dim3(256), 0, c->stream, A);
     EVH_HIP(c, hipGetLastError());
@@ -2419,22 +2179,10 @@ int evh_launch_select(evh_ctx* c, int nframes) {
     B.heap_cap = 2 * q0 + 2;
     B.tdesc = c->d_cv_tdesc; B.total_tiles = c->g.total_tiles;
     { const char* e = getenv("EVH_CV_PHASE"); B.phase_limit = e ? atoi(e) : 0; }
-    // levels with many corners (>= ~8000 expected: area above 0.3 Mpx) on 1024 threads, the rest on 256
-    // (measured: 1024 threads for the large levels 10.6 ms against 6.4 ms with 256 everywhere -- a barrier over 16 waves costs
-    // more than the steps it saves; EVH_CV_SPLIT / EVH_CV_NT keep the experiment reachable)
-    int split = 0, nt_small = 256;
-    { const char* e = getenv("EVH_CV_SPLIT"); if (e) split = std::min(EVH_NLEVELS, std::max(0, atoi(e))); }
-    { const char* e = getenv("EVH_CV_NT"); if (e) nt_small = std::min(CV_MAXT, std::max(64, atoi(e) & ~63)); }
-    if (CV_MAXT < 1024) split = 0;
+    // 256 threads on every level (1024 on the large levels was measured at 10.6 ms against 6.4 ms: a barrier over 16 waves
+    // costs more than the partition steps it saves)
     const size_t heap_bytes = sizeof(unsigned long long) * (size_t)B.heap_cap;
-    if (split > 0) {
-      B.level0 = 0; B.nlev = split;
-      hipLaunchKernelGGL(k_select_cv, xcd_grid(split, nframes), dim3(1024), heap_bytes, c->stream, B);
-    }
-    if (split < EVH_NLEVELS) {
-      B.level0 = split; B.nlev = EVH_NLEVELS - split;
-      hipLaunchKernelGGL(k_select_cv, xcd_grid(EVH_NLEVELS - split, nframes), dim3(nt_small), heap_bytes, c->stream, B);
-    }
+    hipLaunchKernelGGL(k_select_cv, xcd_grid(EVH_NLEVELS, nframes), dim3(256), heap_bytes, c->stream, B);
     EVH_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(k_pack, dim3(nframes), dim3(256), 0, c->stream, A);
     EVH_HIP(c, hipGetLastError());

@@ -12,7 +12,7 @@ struct EvhKnnArgs {
   int q_slot0, q_slot_step, t_slot0, t_slot_step;
   int32_t* idx; uint32_t* d2;
   int64_t out_stride;             // rows per pair in idx / d2
-  int hamming;
+  int hamming;                    // 32-byte rows only
   int desc_bytes;                 // 32 (ORB) or 128 (SIFT descriptor values as bytes); 0 = 32
 };
 

@@ -6,7 +6,6 @@
 #include "evh_match.h"
 #include <cfloat>
 #include <climits>
-#include <cstdlib>
 
 namespace {
 
@@ -28,13 +27,11 @@ __device__ __forceinline__ bool dist_lt(uint32_t a, uint32_t b) {
 
 // one workgroup (256 threads) per (pair, chunk of 256 queries): blockIdx.y = chunk, so that a few pairs with many
 // descriptors (4K frames, N = 4000) still fill the chip; the train set is streamed through LDS by every chunk.
-// NV = uint4 per descriptor: 2 (32 bytes, ORB) or 8 (128 bytes: SIFT's descriptor values, 0..255 each -- the operator
-// holds them as float32 and its float accumulation of the squared differences is exact, every partial sum being an
-// integer below 2^24).
-template <int NV, int TILE>
+// 32-byte rows only (ORB; a distance is at most 2 080 800, so integer order is the operator's).
 __global__ __launch_bounds__(256) void k_knn2(EvhKnnArgs A) {
-  __shared__ uint4 tdesc[TILE * NV];
-  __shared__ uint32_t tnorm[TILE];
+  constexpr int NV = 2;   // uint4 per descriptor
+  __shared__ uint4 tdesc[MT_TILE * NV];
+  __shared__ uint32_t tnorm[MT_TILE];
   const int p = blockIdx.x, tid = threadIdx.x;
   const int qs = A.q_slot0 + p * A.q_slot_step, ts = A.t_slot0 + p * A.t_slot_step;
   const int nq = A.nq_arr ? A.nq_arr[qs] : A.nq_fixed;
@@ -58,8 +55,8 @@ __global__ __launch_bounds__(256) void k_knn2(EvhKnnArgs A) {
     }
     uint32_t b0 = 0xFFFFFFFFu, b1 = 0xFFFFFFFFu;
     int i0 = -1, i1 = -1;
-    for (int t0 = 0; t0 < nt; t0 += TILE) {
-      const int tn = min(TILE, nt - t0);
+    for (int t0 = 0; t0 < nt; t0 += MT_TILE) {
+      const int tn = min(MT_TILE, nt - t0);
       __syncthreads();
       for (int i = tid; i < tn * NV; i += 256) tdesc[i] = T[NV * t0 + i];
       __syncthreads();
@@ -94,13 +91,8 @@ __global__ __launch_bounds__(256) void k_knn2(EvhKnnArgs A) {
             d = qn + tnorm[j] - 2u * s;
           }
           // ascending train order, strict '<': ties keep the lowest train index
-          if (NV == 2) {
-            if (d < b0) { b1 = b0; i1 = i0; b0 = d; i0 = t0 + j; }
-            else if (d < b1) { b1 = d; i1 = t0 + j; }
-          } else {
-            if (dist_lt(d, b0)) { b1 = b0; i1 = i0; b0 = d; i0 = t0 + j; }
-            else if (dist_lt(d, b1)) { b1 = d; i1 = t0 + j; }
-          }
+          if (d < b0) { b1 = b0; i1 = i0; b0 = d; i0 = t0 + j; }
+          else if (d < b1) { b1 = d; i1 = t0 + j; }
         }
       }
     }
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(256) void k_knn2(EvhKnnArgs A) {
 // merged once at the end under (distance class, index) -- the serial strict insertion keeps exactly the first two under that
 // order.  floor(T / 2) is the C-in of the first MFMA (read from LDS straight into the accumulators), so the epilogue of a
 // tile is a 15-instruction minimum and ONE compare against ceil((best2 - C) / 2): 2 e' >= best2 - C  =>  D >= best2, reject;
-// everything that passes takes the exact path (D rebuilt with T's parity bit, dist_lt as in k_knn2).  A workgroup stages 64
+// everything that passes takes the exact path (D rebuilt with T's parity bit, dist_lt).  A workgroup stages 64
 // train rows per barrier (XOR-swizzled 16-byte slots: ds_read_b128 without bank conflicts) for 4 waves x 128 queries.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -684,11 +676,9 @@ int evh_launch_knn2(evh_ctx* c, const EvhKnnArgs& A, int npairs) {
   // chunks of 256 queries in grid.y, bounded by the largest possible query count
   const int nq_max = A.nq_arr ? A.out_stride : A.nq_fixed;
   const int chunks = std::max(1, std::min((nq_max + 255) / 256, 64));
-  static const bool dot4_form = getenv("EVH_KNN_DOT4") != nullptr;      // A/B switch: the v_dot4 kernel for 128-byte rows too
-  if (A.desc_bytes == 128 && !A.hamming && !dot4_form)
+  if (A.desc_bytes == 128)
     hipLaunchKernelGGL(k_knn2_mfma128, dim3(npairs, std::max(1, std::min((nq_max + KM_GQ - 1) / KM_GQ, 256))), dim3(256), 0, c->stream, A);
-  else if (A.desc_bytes == 128) hipLaunchKernelGGL((k_knn2<8, 128>), dim3(npairs, chunks), dim3(256), 0, c->stream, A);
-  else hipLaunchKernelGGL((k_knn2<2, MT_TILE>), dim3(npairs, chunks), dim3(256), 0, c->stream, A);
+  else hipLaunchKernelGGL(k_knn2, dim3(npairs, chunks), dim3(256), 0, c->stream, A);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;
 }

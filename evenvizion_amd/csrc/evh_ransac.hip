@@ -792,7 +792,7 @@ struct SolveLds {        // scratch of the single-problem stages (refit, LM): us
 // ---- tolerance mode (EVH_SOLVER_FAST) of the refit's sums: lane-strided partial sums + a butterfly instead of the point-order
 // chains (see lm_eval_fast).  With a = (X, Y, 1): Lx = (a, 0, -x a), Ly = (0, a, -y a), so L^T L needs sum a_i a_j, sum x a_i a_j,
 // sum y a_i a_j and sum (x^2 + y^2) a_i a_j -- 24 sums instead of 45 chains.  The eigen-solve and the de-normalisation are shared.
-__device__ __forceinline__ double wave_sum_f64_(double v) {
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
   return v;
@@ -806,13 +806,13 @@ __device__ __forceinline__ bool dlt_rows_fast(SolveLds& S, RowMat& M, int lane, 
     const float4 r = *reinterpret_cast<const float4*>(rows + 4 * i);
     c0 += r.z; c1 += r.w; c2 += r.x; c3 += r.y;
   }
-  const double cmx = wave_sum_f64_(c0) / count, cmy = wave_sum_f64_(c1) / count, cMx = wave_sum_f64_(c2) / count, cMy = wave_sum_f64_(c3) / count;
+  const double cmx = wave_sum_f64(c0) / count, cmy = wave_sum_f64(c1) / count, cMx = wave_sum_f64(c2) / count, cMy = wave_sum_f64(c3) / count;
   c0 = c1 = c2 = c3 = 0;
   for (int i = lane; i < count; i += NL) {
     const float4 r = *reinterpret_cast<const float4*>(rows + 4 * i);
     c0 += fabs(r.z - cmx); c1 += fabs(r.w - cmy); c2 += fabs(r.x - cMx); c3 += fabs(r.y - cMy);
   }
-  double smx = wave_sum_f64_(c0), smy = wave_sum_f64_(c1), sMx = wave_sum_f64_(c2), sMy = wave_sum_f64_(c3);
+  double smx = wave_sum_f64(c0), smy = wave_sum_f64(c1), sMx = wave_sum_f64(c2), sMy = wave_sum_f64(c3);
   if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return false;
   smx = count / smx; smy = count / smy; sMx = count / sMx; sMy = count / sMy;
   double aa[6] = {0, 0, 0, 0, 0, 0}, xa[6] = {0, 0, 0, 0, 0, 0}, ya[6] = {0, 0, 0, 0, 0, 0}, qa[6] = {0, 0, 0, 0, 0, 0};
@@ -826,7 +826,7 @@ __device__ __forceinline__ bool dlt_rows_fast(SolveLds& S, RowMat& M, int lane, 
     for (int k = 0; k < 6; k++) { aa[k] += p[k]; xa[k] += x * p[k]; ya[k] += y * p[k]; qa[k] += q * p[k]; }
   }
 #pragma unroll
-  for (int k = 0; k < 6; k++) { aa[k] = wave_sum_f64_(aa[k]); xa[k] = wave_sum_f64_(xa[k]); ya[k] = wave_sum_f64_(ya[k]); qa[k] = wave_sum_f64_(qa[k]); }
+  for (int k = 0; k < 6; k++) { aa[k] = wave_sum_f64(aa[k]); xa[k] = wave_sum_f64(xa[k]); ya[k] = wave_sum_f64(ya[k]); qa[k] = wave_sum_f64(qa[k]); }
   if (lane == 0) {
     for (int i = 0; i < 9; i++) for (int j = 0; j < 9; j++) M.A[i * MS + j] = 0.0;
     const int ui[6] = {0, 0, 0, 1, 1, 2}, uj[6] = {0, 1, 2, 1, 2, 2};
@@ -1176,11 +1176,6 @@ __device__ __forceinline__ void lm_eval(SolveLds& S, int lane, const float* rows
 // N / 64 independent steps and a 6-level tree.  J's rows are (t0 t1 t2 0 0 0 t4 t5) and (0 0 0 t0 t1 t2 t6 t7): 21 distinct
 // entries of J^T J (the (3..5, 3..5) block repeats the (0..2, 0..2) block), 8 of J^T r, the squared norm, max |r|.
 // Results differ from the exact form in the last digits (tests/test_gpu_parity.py::test_fast_solver_mode states the bars).
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int sft = 32; sft > 0; sft >>= 1) v += __shfl_xor(v, sft);
-  return v;
-}
 __device__ __forceinline__ void lm_eval_fast(SolveLds& S, int lane, const float* rows, int count, const double* h, bool withJ, int slotS,
                                              int slotR) {
   const double h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7];
@@ -1483,9 +1478,7 @@ struct alignas(16) BlockLds {
 #define MW_PROD (MW_PSTR * MW_NPR)       // doubles per product buffer
 #define MW_TSTR (NL + 2)                 // doubles between two terms' rows of a tile: [term][point], 528 bytes (same reason)
 typedef double mw_d2 __attribute__((ext_vector_type(2)));
-#ifndef MW_MIN_ROWS
 #define MW_MIN_ROWS 512                   // fewer inlier rows: wave 0 alone (measured break-even ~300 rows)
-#endif
 __device__ __forceinline__ int mw_jx(int k) { return k < 3 ? k : k < 6 ? 3 : k - 2; }   // term index of J's x-row, column k
 __device__ __forceinline__ int mw_jy(int k) { return k < 3 ? 3 : k < 6 ? k - 3 : k; }   // ... y-row
 // the `which`-th entry (i <= j, tri8 order) of the given kind: 1 = x only, 2 = y only (both kinds enumerated together as

@@ -75,25 +75,26 @@ def test_pyramid_and_gray(ctx, w, h):
             assert np.array_equal(got, want[l]), "level %d differs" % l
 
 
-@pytest.mark.parametrize("form", ["EVH_PYR_OLD", "EVH_PYR_TWO"])
-def test_pyramid_alternative_kernels(ctx, monkeypatch, form):
-    """The two other pyramid kernels kept for A/B runs (k_pyr_down: round 2's tiles; k_pyr_two: levels l and l+1 from one
-    staged footprint of level l-1, VERDICT r2 item 5 -- measured slower, profiles/r03_pyramid_two_ab.txt) produce the
-    same bytes as the oracle (frame_processing.py:60-61)."""
-    monkeypatch.setenv(form, "1")
-    for (w, h) in SIZES + [(1170, 658), (641, 363)]:
-        prev, cur, _ = S.make_pair(7, w, h)
-        from evenvizion_amd._lib import Context
-        c = ctx if (w, h) in SIZES else Context(device=0, max_w=w, max_h=h, max_features=500, max_frames=2)
-        try:
-            c.orb_detect_batch(dev(np.stack([prev, cur])))
-            for f, img in enumerate((prev, cur)):
-                want = O.orb_pyramid(img)
-                for l in range(8):
-                    assert np.array_equal(c.download_level(f, l), want[l]), "%s %dx%d level %d differs" % (form, w, h, l)
-        finally:
-            if c is not ctx:
-                c.close()
+# levels whose rounded size shrinks by more than 1.21 on an axis: evh_launch_pyramid builds them with k_pyr_down
+PYR_DOWN_LEVELS = {(1170, 165): [3, 5], (238, 165): [3, 5, 7], (400, 220): [7]}
+
+
+@pytest.mark.parametrize("w,h", sorted(PYR_DOWN_LEVELS))
+def test_pyramid_down_levels(ctx, w, h):
+    """k_pyr_walk stages at most 1.21 x its tile per axis; the levels ORB's rounding shrinks by more go to k_pyr_down
+    (128 x 64 tiles).  The device's geometry must select exactly the listed levels (k_pyr_walk's condition in
+    evh_launch_pyramid), and all 8 levels must be the oracle's bytes (frame_processing.py:60-61).
+    1170 x 165 level 3 (677 x 95) is 6 x 2 tiles at an odd width; 238 x 165 takes k_pyr_down on the last level."""
+    prev, cur, _ = S.make_pair(7, w, h)
+    ctx.orb_detect_batch(dev(np.stack([prev, cur])))
+    dims = [ctx.level_info(l)[:2] for l in range(8)]
+    down = [l for l in range(1, 8)
+            if not (dims[l - 1][0] * 100 <= dims[l][0] * 121 and dims[l - 1][1] * 100 <= dims[l][1] * 121)]
+    assert down == PYR_DOWN_LEVELS[(w, h)], dims
+    for f, img in enumerate((prev, cur)):
+        want = O.orb_pyramid(img)
+        for l in range(8):
+            assert np.array_equal(ctx.download_level(f, l), want[l]), "%dx%d level %d differs" % (w, h, l)
 
 
 @pytest.mark.parametrize("w,h", SIZES)

@@ -1,5 +1,5 @@
 """2-NN micro-probe: one call of evh_match_knn2_l2u8x128 on nq x nt rows of 128 bytes (clustered random data), ms per call.
-usage: python tools/knn_probe.py [nq nt]   (EVHIP_LIBRARY / EVH_KNN_DOT4 select the build / the v_dot4 kernel)"""
+usage: python tools/knn_probe.py [nq nt]   (EVHIP_LIBRARY selects the build)"""
 import os, sys, time, json
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import numpy as np, torch

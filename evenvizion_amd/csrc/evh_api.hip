@@ -137,10 +137,25 @@ int configure(evh_ctx* c, int w, int h, int nfeatures) {
   return EVH_SUCCESS;
 }
 
-template <class T>
-int dalloc(evh_ctx* c, T** p, size_t n) {
-  EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  c->bytes_allocated += n * sizeof(T);
+// one set of per-pair buffers with `cap` rows per pair (the ORB path: kcap; the multi-type path: every type's rows)
+int alloc_pair_bufs(evh_ctx* c, EvhPairBufs& B, int cap) {
+  const size_t P = (size_t)c->max_frames, K = (size_t)cap;
+  int rc;
+#define A_(call) if ((rc = (call)) != EVH_SUCCESS) return rc
+  A_(dalloc(c, &B.knn_idx, P * K * 2));
+  A_(dalloc(c, &B.knn_d2, P * K * 2));
+  A_(dalloc(c, &B.pts, P * K * 4));
+  A_(dalloc(c, &B.pts2, P * K * 4));
+  A_(dalloc(c, &B.crow, P * K * 4));
+  A_(dalloc(c, &B.npts, P));
+  A_(dalloc(c, &B.npts2, P));
+  A_(dalloc(c, &B.pstatus, P));
+  A_(dalloc(c, &B.H1, P * 9));
+  A_(dalloc(c, &B.mask, P * K));
+  A_(dalloc(c, &B.lm, P * K * 4));
+  A_(dalloc(c, &B.info, P * 8));
+#undef A_
+  B.cap = cap;
   return EVH_SUCCESS;
 }
 
@@ -151,49 +166,77 @@ int ensure_lane_scratch(evh_ctx* c) {
   return dalloc(c, &c->d_lane_v, (size_t)c->max_frames * EVH_LANE_V_DOUBLES);
 }
 
-EvhRansacArgs pair_ransac_args(evh_ctx* c, double thr, int max_iters, double conf, int force_max) {
+// the launchers report a lane scratch that could not be allocated (force_max without lane_v)
+EvhRansacArgs ransac_args(evh_ctx* c, const EvhPairBufs& B, double thr, int max_iters, double conf, int force_max) {
   EvhRansacArgs R{};
   R.fast_solver = c->solver_mode;
   if (force_max && ensure_lane_scratch(c) == EVH_SUCCESS) R.lane_v = c->d_lane_v;
-  R.pts = c->d_pts; R.pts2 = c->d_pts2; R.row_stride = c->kcap; R.npts = c->d_npts; R.npts2 = c->d_npts2;
-  R.status = c->d_pstatus; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
-  R.mask = c->d_mask; R.crow = c->d_crow; R.lm = c->d_lm; R.H1 = c->d_H1; R.info = c->d_info;
+  R.pts = B.pts; R.pts2 = B.pts2; R.row_stride = B.cap; R.npts = B.npts; R.npts2 = B.npts2;
+  R.status = B.pstatus; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
+  R.mask = B.mask; R.crow = B.crow; R.lm = B.lm; R.H1 = B.H1; R.info = B.info;
   return R;
 }
 
-// K7 + glue on resident slots for `npairs` pairs
-int match_pairs(evh_ctx* c, int npairs, int q0, int qstep, int t0, int tstep) {
-  EvhKnnArgs K{};
-  K.q = c->d_desc; K.t = c->d_desc; K.slot_bytes = (int64_t)c->kcap * 32;
-  K.nq_arr = c->d_kp_count; K.nt_arr = c->d_kp_count;
-  K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
-  K.idx = c->d_knn_idx; K.d2 = c->d_knn_d2; K.out_stride = c->kcap; K.hamming = 0;
+// stream state {H_sup, H_prev} entering (may be NULL: first pair of the stream) and leaving a batch
+void with_state(EvhRansacArgs& R, const double* d_state_in, double* d_state_out) {
+  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
+  R.state_out = d_state_out;
+}
+
+// one feature type's per-frame results, as the matching stages read them
+struct EvhFeatView {
+  const int* counts; const int* flags; const float* xy;
+  const void* desc; int desc_bytes; bool f32;    // uint8 rows of desc_bytes values, or (f32) rows of 128 floats
+  int cap;                                       // rows per frame slot
+};
+EvhFeatView feat_view(const evh_ctx* c, int type) {
+  if (type == EVH_FEATURE_SIFT) return {c->d_sift_count, c->d_sift_flags, c->d_sift_xy, c->d_sift_desc, 128, false, c->sift_cap};
+  if (type == EVH_FEATURE_SURF) return {c->d_surf_count, c->d_surf_flags, c->d_surf_xy, c->d_surf_desc, 0, true, c->surf_cap};
+  return {c->d_kp_count, c->d_frame_flags, c->d_kp_xy, c->d_desc, 32, false, c->kcap};
+}
+
+// K7 + glue on resident slots for `npairs` pairs of one feature type, into the pair buffers B.  filter_kcap selects the
+// LDS or the global-scratch form of k_filter and sizes its work arrays.  join_solve_at_filter: the filter overwrites the
+// matched-row buffers the previous batch's (asynchronous) solve may still be reading, so it waits for that solve -- as
+// late as possible, K7 of this batch overlaps it
+int match_pairs(evh_ctx* c, const EvhFeatView& V, const EvhPairBufs& B, int filter_kcap, bool join_solve_at_filter, int npairs,
+                int q0, int qstep, int t0, int tstep) {
   int rc;
-  { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2(c, K, npairs); }
+  if (V.f32) {            // real-valued float rows: the float matcher, distances carried as float bits
+    EvhKnnF32Args K{};
+    K.q = static_cast<const float*>(V.desc); K.t = K.q; K.dim = 128; K.n_arr = V.counts; K.slot_floats = (int64_t)V.cap * 128;
+    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
+    K.idx = B.knn_idx; K.dist = reinterpret_cast<float*>(B.knn_d2); K.out_stride = B.cap;
+    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2_f32(c, K, npairs); }
+  } else {
+    EvhKnnArgs K{};
+    K.q = static_cast<const uint8_t*>(V.desc); K.t = K.q; K.slot_bytes = (int64_t)V.cap * V.desc_bytes; K.desc_bytes = V.desc_bytes;
+    K.nq_arr = V.counts; K.nt_arr = V.counts;
+    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
+    K.idx = B.knn_idx; K.d2 = B.knn_d2; K.out_stride = B.cap; K.hamming = 0;
+    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2(c, K, npairs); }
+  }
   if (rc) return rc;
   EvhFilterArgs F{};
-  F.idx = c->d_knn_idx; F.d2 = c->d_knn_d2; F.knn_stride = c->kcap;
-  F.xy_q = c->d_kp_xy; F.xy_t = c->d_kp_xy; F.xy_slot_floats = (int64_t)c->kcap * 2;
-  F.nq_arr = c->d_kp_count; F.nt_arr = c->d_kp_count; F.flags_arr = c->d_frame_flags;
+  F.idx = B.knn_idx; F.d2 = B.knn_d2; F.knn_stride = B.cap; F.d2_is_dist = V.f32 ? 1 : 0;
+  F.xy_q = V.xy; F.xy_t = V.xy; F.xy_slot_floats = (int64_t)V.cap * 2;
+  F.nq_arr = V.counts; F.nt_arr = V.counts; F.flags_arr = V.flags;
   F.q_slot0 = q0; F.q_slot_step = qstep; F.t_slot0 = t0; F.t_slot_step = tstep;
   F.ratio = 0.5; F.min_matches = 4;  // constants.py:25,28 (LOWES_RATIO, MINIMUM_MATCHING_POINTS)
-  F.pts = c->d_pts; F.pts_stride = c->kcap; F.npts = c->d_npts; F.status = c->d_pstatus; F.kcap = c->kcap;
-  // the filter overwrites the matched-row buffers the previous batch's (asynchronous) solve may still be reading
-  if (c->solve_pending) EVH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_solve_done, 0));
+  F.pts = B.pts; F.pts_stride = B.cap; F.npts = B.npts; F.status = B.pstatus; F.kcap = filter_kcap;
+  if (join_solve_at_filter && c->solve_pending) EVH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_solve_done, 0));
   EvhProfScope ps(c, EVH_ST_FILTER);
   return evh_launch_filter(c, F, npairs);
+}
+int match_orb_pairs(evh_ctx* c, int npairs, int q0, int qstep, int t0, int tstep) {
+  return match_pairs(c, feat_view(c, EVH_FEATURE_ORB), c->orb, c->kcap, true, npairs, q0, qstep, t0, tstep);
 }
 
 // context-owned scratch of the host-pointer entries (evh_transform_points, evh_superposition_scan,
 // evh_fixed_plane_field): grown on demand, reused across calls (those entries synchronise before returning)
 int ensure_scratch(evh_ctx* c, size_t bytes) {
   if (bytes <= c->scratch_bytes) return EVH_SUCCESS;
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; c->scratch_bytes = 0; }
-  const size_t want = std::max(bytes, (size_t)1 << 16);
-  EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_scratch), want));
-  c->scratch_bytes = want;
-  return EVH_SUCCESS;
+  return grow(c, &c->d_scratch, &c->scratch_bytes, std::max(bytes, (size_t)1 << 16));
 }
 
 // entry points that reuse the pair buffers on the main stream first order themselves behind a pending async solve
@@ -276,75 +319,13 @@ int ensure_multitype(evh_ctx* c) {
   const int each = std::max(c->kcap, std::max(c->sift_cap, c->surf_cap)), cap = c->kcap + c->sift_cap + c->surf_cap;
   if (each > 65536)
     return evh_fail(c, EVH_ERR_CAPACITY, "multi-type pairs: at most 65536 key points per frame and type");
-  const size_t P = (size_t)c->max_frames, K = (size_t)cap;
-  int rc;
-#define M_(call) if ((rc = (call)) != EVH_SUCCESS) return rc
-  M_(dalloc(c, &c->mt.knn_idx, P * K * 2));
-  M_(dalloc(c, &c->mt.knn_d2, P * K * 2));
-  M_(dalloc(c, &c->mt.pts, P * K * 4));
-  M_(dalloc(c, &c->mt.pts2, P * K * 4));
-  M_(dalloc(c, &c->mt.crow, P * K * 4));
-  M_(dalloc(c, &c->mt.npts, P));
-  M_(dalloc(c, &c->mt.npts2, P));
-  M_(dalloc(c, &c->mt.pstatus, P));
-  M_(dalloc(c, &c->mt.H1, P * 9));
-  M_(dalloc(c, &c->mt.mask, P * K));
-  M_(dalloc(c, &c->mt.lm, P * K * 4));
-  M_(dalloc(c, &c->mt.info, P * 8));
-  M_(dalloc(c, &c->d_acc, P * K * 4));
-  M_(dalloc(c, &c->d_nacc, P));
-  M_(dalloc(c, &c->d_accstatus, P));
-#undef M_
-  c->mt.cap = cap;
-  return EVH_SUCCESS;
-}
-
-EvhRansacArgs mt_ransac_args(evh_ctx* c, double thr, int max_iters, double conf, int force_max) {
-  EvhRansacArgs R{};
-  R.fast_solver = c->solver_mode;
-  if (force_max && ensure_lane_scratch(c) == EVH_SUCCESS) R.lane_v = c->d_lane_v;
-  const EvhPairBufs& B = c->mt;
-  R.pts = B.pts; R.pts2 = B.pts2; R.row_stride = B.cap; R.npts = B.npts; R.npts2 = B.npts2;
-  R.status = B.pstatus; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
-  R.mask = B.mask; R.crow = B.crow; R.lm = B.lm; R.H1 = B.H1; R.info = B.info;
-  return R;
-}
-
-// K7 + glue of ONE feature type into the multi-type pair buffers
-int match_pairs_type(evh_ctx* c, int type, int npairs, int q0, int qstep, int t0, int tstep) {
-  const EvhPairBufs& B = c->mt;
-  const bool sift = type == EVH_FEATURE_SIFT, surf = type == EVH_FEATURE_SURF;
-  const int* counts = sift ? c->d_sift_count : surf ? c->d_surf_count : c->d_kp_count;
-  const int tcap = sift ? c->sift_cap : surf ? c->surf_cap : c->kcap;
-  int rc;
-  if (surf) {            // real-valued float rows: the float matcher, distances carried as float bits
-    EvhKnnF32Args K{};
-    K.q = c->d_surf_desc; K.t = c->d_surf_desc; K.dim = 128; K.n_arr = counts; K.slot_floats = (int64_t)tcap * 128;
-    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
-    K.idx = B.knn_idx; K.dist = reinterpret_cast<float*>(B.knn_d2); K.out_stride = B.cap;
-    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2_f32(c, K, npairs); }
-  } else {
-    EvhKnnArgs K{};
-    K.q = sift ? c->d_sift_desc : c->d_desc; K.t = K.q;
-    K.slot_bytes = sift ? (int64_t)tcap * 128 : (int64_t)tcap * 32;
-    K.desc_bytes = sift ? 128 : 32;
-    K.nq_arr = counts; K.nt_arr = counts;
-    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
-    K.idx = B.knn_idx; K.d2 = B.knn_d2; K.out_stride = B.cap; K.hamming = 0;
-    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2(c, K, npairs); }
-  }
-  if (rc) return rc;
-  EvhFilterArgs F{};
-  F.idx = B.knn_idx; F.d2 = B.knn_d2; F.knn_stride = B.cap; F.d2_is_dist = surf ? 1 : 0;
-  F.xy_q = sift ? c->d_sift_xy : surf ? c->d_surf_xy : c->d_kp_xy; F.xy_t = F.xy_q;
-  F.xy_slot_floats = (int64_t)tcap * 2;
-  F.nq_arr = counts; F.nt_arr = counts; F.flags_arr = sift ? c->d_sift_flags : surf ? c->d_surf_flags : c->d_frame_flags;
-  F.q_slot0 = q0; F.q_slot_step = qstep; F.t_slot0 = t0; F.t_slot_step = tstep;
-  F.ratio = 0.5; F.min_matches = 4;
-  F.pts = B.pts; F.pts_stride = B.cap; F.npts = B.npts; F.status = B.pstatus;
-  F.kcap = std::max(c->kcap, std::max(c->sift_cap, c->surf_cap));
-  EvhProfScope ps(c, EVH_ST_FILTER);
-  return evh_launch_filter(c, F, npairs);
+  const size_t P = (size_t)c->max_frames, K = (size_t)cap, first = c->owned.size();
+  int rc = alloc_pair_bufs(c, c->mt, cap);
+  if (!rc) rc = dalloc(c, &c->d_acc, P * K * 4);
+  if (!rc) rc = dalloc(c, &c->d_nacc, P);
+  if (!rc) rc = dalloc(c, &c->d_accstatus, P);
+  if (rc) { dfree_from(c, first); c->mt.cap = 0; }     // a partial allocation is released: a later call starts afresh
+  return rc;
 }
 
 // frames -> H with a LIST of feature types, in list order (the reference's default list is SURF, SIFT, ORB):
@@ -378,9 +359,11 @@ int pairs_types(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframe
   if (want_surf && (rc = evh_launch_surf(c, nframes, w, h, 400.f))) return rc; // SURF_create(extended=1, hessianThreshold=400)
   if (want_orb && (rc = orb_stages(c, nframes, share_group))) return rc;
   const int q0 = 1, qstep = stream_mode ? 1 : 2, t0 = 0, tstep = stream_mode ? 1 : 2;
-  EvhRansacArgs R = mt_ransac_args(c, thr, max_iters, conf, force_max);
+  EvhRansacArgs R = ransac_args(c, c->mt, thr, max_iters, conf, force_max);
+  const int each = std::max(c->kcap, std::max(c->sift_cap, c->surf_cap));   // one filter form for every type of the list
   for (int i = 0; i < ntypes; i++) {
-    if ((rc = match_pairs_type(c, types[i], npairs, q0, qstep, t0, tstep))) return rc;
+    // the solve was joined once, above: this path has no asynchronous solve of its own to overlap
+    if ((rc = match_pairs(c, feat_view(c, types[i]), c->mt, each, false, npairs, q0, qstep, t0, tstep))) return rc;
     { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, R, npairs); }
     if (rc) return rc;
     EvhAccArgs A{};
@@ -393,10 +376,99 @@ int pairs_types(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframe
   M.out = c->mt.pts2; M.nout = c->mt.npts2; M.status = c->mt.pstatus; M.out_stride = c->mt.cap;
   if ((rc = evh_launch_merge(c, M, npairs))) return rc;
   R.H = d_H; R.out_status = d_status;
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
+  with_state(R, d_state_in, d_state_out);
   EvhProfScope ps(c, EVH_ST_RANSAC_FINAL);
   return evh_launch_ransac_final(c, R, npairs, stream_mode ? 1 : 0, npairs);
+}
+
+// ORB detect of `nframes` frames (FAST thresholds shared inside groups of share_group) + match of npairs pairs
+// (frame step + 1, frame step * p): the first half of every ORB pair / stream entry
+int detect_match(evh_ctx* c, const uint8_t* d_frames, int nframes, int share_group, int npairs, int step, int sw, int sh, int w,
+                 int h, int channels, int64_t row_stride, int64_t frame_stride, int nfeatures) {
+  c->fast_share_group = share_group;
+  int rc = detect_batch(c, d_frames, nframes, sw, sh, w, h, channels, row_stride, frame_stride, nfeatures);
+  if (rc) return rc;
+  return match_orb_pairs(c, npairs, 1, step, 0, step);      // orders itself behind a pending async solve
+}
+
+// nstreams streams of frames_per_stream consecutive frames -> H per pair.  Pair slot p = (frame p + 1, frame p): a slot
+// that straddles two streams is computed and never read
+int stream_batch(evh_ctx* c, const uint8_t* d_frames, int nstreams, int frames_per_stream, int sw, int sh, int w, int h,
+                 int channels, int64_t row_stride, int64_t frame_stride, int nfeatures, double thr, int max_iters, double conf,
+                 int force_max, const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
+  const int nframes = nstreams * frames_per_stream;
+  int rc = detect_match(c, d_frames, nframes, frames_per_stream, nframes - 1, 1, sw, sh, w, h, channels, row_stride, frame_stride,
+                        nfeatures);
+  if (rc) return rc;
+  EvhRansacArgs R = ransac_args(c, c->orb, thr, max_iters, conf, force_max);
+  R.H = d_H; R.out_status = d_status;
+  with_state(R, d_state_in, d_state_out);
+  return solve_pairs(c, R, nframes - 1, nstreams, frames_per_stream - 1, frames_per_stream);
+}
+
+// final solve of pair slot 0 of the ORB buffers (its static rows are resident), optionally behind the superposition
+// h_Hsup; H and status to the host
+int final_solve_one(evh_ctx* c, const double* h_Hsup, double* h_H, int* h_status) {
+  EvhSmall* S = c->d_small;
+  EvhRansacArgs R = ransac_args(c, c->orb, 3.0, 2000, 0.995, 0);
+  R.H = S->H; R.out_status = &S->out_status;
+  if (h_Hsup) {
+    EVH_HIP(c, hipMemcpyAsync(S->Hsup, h_Hsup, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    R.Hsup0 = S->Hsup;
+  }
+  // the stream kernel with one pair applies the optional pre-transform; Hprev0 = Hsup0 only marks "not first"
+  R.Hprev0 = R.Hsup0;
+  int rc = evh_launch_ransac_final(c, R, 1, h_Hsup ? 1 : 0, 1);
+  if (rc) return rc;
+  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  EVH_HIP(c, hipMemcpy(h_H, S->H, 9 * sizeof(double), hipMemcpyDeviceToHost));
+  EVH_HIP(c, hipMemcpy(h_status, &S->out_status, sizeof(int), hipMemcpyDeviceToHost));
+  return EVH_SUCCESS;
+}
+
+// a frame slot's key-point count and flags word of one feature type, in one synchronisation
+int frame_count(evh_ctx* c, const EvhFeatView& V, int frame, int* flags) {
+  int n = 0;
+  EVH_HIP(c, hipMemcpyAsync(&n, V.counts + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(flags, V.flags + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  return n;
+}
+
+// the 8-float key-point records of SIFT and SURF: x, y, size, angle, response, octave bits, (SURF) laplacian bits
+void unpack_records(const std::vector<float>& rec, int n, float* h_xy, float* h_size, float* h_angle, float* h_response,
+                    int32_t* h_octave, int32_t* h_laplacian) {
+  for (int i = 0; i < n; i++) {
+    const float* r = &rec[(size_t)i * 8];
+    if (h_xy) { h_xy[2 * i] = r[0]; h_xy[2 * i + 1] = r[1]; }
+    if (h_size) h_size[i] = r[2];
+    if (h_angle) h_angle[i] = r[3];
+    if (h_response) h_response[i] = r[4];
+    if (h_octave) memcpy(&h_octave[i], &r[5], 4);
+    if (h_laplacian) memcpy(&h_laplacian[i], &r[6], 4);
+  }
+}
+
+// evh_ratio_unique_filter / _f32: d2 holds integer squared distances, or (is_dist) the float32 bits of distances
+int ratio_filter(evh_ctx* c, const char* who, const int32_t* d_idx, const uint32_t* d_d2, int is_dist, int nq, int nt,
+                 const float* d_xy_q, const float* d_xy_t, double ratio, int min_matches, float* d_pts, int* h_count, int* h_status) {
+  if (!c || !d_idx || !d_d2 || !d_xy_q || !d_xy_t || !d_pts || !h_count || !h_status || nq < 0 || nt < 0)
+    return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad argument");
+  const int kc = std::max(std::max(nq, nt), 1);
+  if (kc > 65535) return evh_fail(c, EVH_ERR_CAPACITY, std::string(who) + ": too many rows");
+  if (((uintptr_t)d_pts) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_pts must be 16-byte aligned");
+  int* d_cnt = c->d_small->count_status;
+  EvhFilterArgs F{};
+  F.idx = d_idx; F.d2 = d_d2; F.d2_is_dist = is_dist; F.knn_stride = nq; F.xy_q = d_xy_q; F.xy_t = d_xy_t; F.xy_slot_floats = 0;
+  F.nq_fixed = nq; F.nt_fixed = nt; F.ratio = ratio; F.min_matches = min_matches;
+  F.pts = d_pts; F.pts_stride = nq; F.npts = d_cnt; F.status = d_cnt + 1; F.kcap = kc;
+  int rc = evh_launch_filter(c, F, 1);
+  if (rc) return rc;
+  int host[2];
+  EVH_HIP(c, hipMemcpyAsync(host, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  *h_count = host[0]; *h_status = host[1];
+  return EVH_SUCCESS;
 }
 
 }  // namespace
@@ -476,19 +548,8 @@ int evh_create(int device, int max_w, int max_h, int max_features, int max_frame
     c->err = "hipMemset(d_fast_hint) failed";
     return fail(EVH_ERR_HIP);
   }
-  A_(dalloc(c, &c->d_knn_idx, F * K * 2));
-  A_(dalloc(c, &c->d_knn_d2, F * K * 2));
-  A_(dalloc(c, &c->d_pts, F * K * 4));
-  A_(dalloc(c, &c->d_pts2, F * K * 4));
-  A_(dalloc(c, &c->d_crow, F * K * 4));
-  A_(dalloc(c, &c->d_npts, F));
-  A_(dalloc(c, &c->d_npts2, F));
-  A_(dalloc(c, &c->d_pstatus, F));
-  A_(dalloc(c, &c->d_H1, F * 9));
-  A_(dalloc(c, &c->d_mask, F * K));
-  A_(dalloc(c, &c->d_lm, F * K * 4));
-  A_(dalloc(c, &c->d_info, F * 8));
-  A_(dalloc(c, &c->d_small, 64));
+  A_(alloc_pair_bufs(c, c->orb, c->kcap));
+  A_(dalloc(c, &c->d_small, 1));
 #undef A_
   e = hipMemset(c->d_kp_count, 0, F * sizeof(int));
   if (e == hipSuccess) e = hipMemset(c->d_frame_flags, 0, F * sizeof(int));
@@ -501,17 +562,7 @@ void evh_destroy(evh_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* ptrs[] = {c->d_pyr, c->d_cand, c->d_cand_count, c->d_tabs, c->d_kp_xy, c->d_kp_meta, c->d_kp_resp, c->d_kp_angle,
-                  c->d_desc, c->d_kp_count, c->d_frame_flags, c->d_tmp_meta, c->d_tmp_resp, c->d_lvl_count, c->d_fast_thr, c->d_fast_hist, c->d_fast_redo, c->d_cv_seq, c->d_cv_seq32, c->d_cv_lpos, c->d_cv_rpos, c->d_cv_mask, c->d_cv_tdesc, c->d_area_tab, c->d_lane_v, c->d_fast_hint, c->d_knn_idx, c->d_knn_d2, c->d_pts, c->d_pts2, c->d_crow,
-                  c->d_npts, c->d_npts2, c->d_pstatus, c->d_H1, c->d_mask, c->d_lm, c->d_info, c->d_small, c->d_scratch, c->d_scan_ws, c->d_filter_ws, c->d_merge_ws};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  evh_sift_free(c);
-  evh_surf_free(c);
-  {
-    void* mp[] = {c->mt.knn_idx, c->mt.knn_d2, c->mt.pts, c->mt.pts2, c->mt.crow, c->mt.npts, c->mt.npts2, c->mt.pstatus, c->mt.H1,
-                  c->mt.mask, c->mt.lm, c->mt.info, c->d_acc, c->d_nacc, c->d_accstatus};
-    for (void* p : mp) if (p) (void)hipFree(p);
-  }
+  dfree_from(c, 0);
   for (auto& s : c->prof_spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
   for (auto e : c->prof_pool) (void)hipEventDestroy(e);
   if (c->solve_stream) { (void)hipStreamSynchronize(c->solve_stream); (void)hipStreamDestroy(c->solve_stream); }
@@ -703,10 +754,9 @@ int evh_orb_capacity(const evh_ctx* c) { return c ? c->kcap : EVH_ERR_INVALID; }
 
 int evh_orb_count(evh_ctx* c, int frame) {
   if (!c || frame < 0 || frame >= c->nframes_resident) return evh_fail(c, EVH_ERR_INVALID, "bad frame slot");
-  int n = 0, fl = 0;
-  EVH_HIP(c, hipMemcpyAsync(&n, c->d_kp_count + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&fl, c->d_frame_flags + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  int fl = 0;
+  const int n = frame_count(c, feat_view(c, EVH_FEATURE_ORB), frame, &fl);
+  if (n < 0) return n;
   if (fl & 2) return evh_fail(c, EVH_ERR_CAPACITY, "key-point selection: nth_element's depth limit was reached for this frame (heap-select fall-back)");
   if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "a fixed-capacity keypoint list overflowed for this frame");
   return n;
@@ -802,23 +852,8 @@ int evh_match_knn2_hamming(evh_ctx* c, const uint8_t* d_q, int nq, const uint8_t
 
 int evh_ratio_unique_filter(evh_ctx* c, const int32_t* d_idx, const uint32_t* d_d2, int nq, int nt, const float* d_xy_q,
                             const float* d_xy_t, double ratio, int min_matches, float* d_pts, int* h_count, int* h_status) {
-  if (!c || !d_idx || !d_d2 || !d_xy_q || !d_xy_t || !d_pts || !h_count || !h_status || nq < 0 || nt < 0)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_ratio_unique_filter: bad argument");
-  const int kc = std::max(std::max(nq, nt), 1);
-  if (kc > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "evh_ratio_unique_filter: too many rows");
-  if (((uintptr_t)d_pts) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_pts must be 16-byte aligned");
-  int* d_cnt = reinterpret_cast<int*>(c->d_small);
-  EvhFilterArgs F{};
-  F.idx = d_idx; F.d2 = d_d2; F.knn_stride = nq; F.xy_q = d_xy_q; F.xy_t = d_xy_t; F.xy_slot_floats = 0;
-  F.nq_fixed = nq; F.nt_fixed = nt; F.ratio = ratio; F.min_matches = min_matches;
-  F.pts = d_pts; F.pts_stride = nq; F.npts = d_cnt; F.status = d_cnt + 1; F.kcap = kc;
-  int rc = evh_launch_filter(c, F, 1);
-  if (rc) return rc;
-  int host[2];
-  EVH_HIP(c, hipMemcpyAsync(host, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  *h_count = host[0]; *h_status = host[1];
-  return EVH_SUCCESS;
+  return ratio_filter(c, "evh_ratio_unique_filter", d_idx, d_d2, 0, nq, nt, d_xy_q, d_xy_t, ratio, min_matches, d_pts, h_count,
+                      h_status);
 }
 
 static int find_homography_entry(evh_ctx* c, const float* d_pts, int n, double thr, int max_iters, double conf, int force_max,
@@ -832,15 +867,16 @@ static int find_homography_entry(evh_ctx* c, const float* d_pts, int n, double t
   R.fast_solver = c->solver_mode;
   R.pts = const_cast<float*>(d_pts); R.n_fixed = n; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
   if (force_max) { int lr = ensure_lane_scratch(c); if (lr) return lr; R.lane_v = c->d_lane_v; }
-  R.mask = c->d_mask; R.crow = c->d_crow; R.lm = c->d_lm;
-  R.H = c->d_small; R.found = reinterpret_cast<int*>(c->d_small + 16); R.info = reinterpret_cast<int*>(c->d_small + 17);
+  EvhSmall* S = c->d_small;
+  R.mask = c->orb.mask; R.crow = c->orb.crow; R.lm = c->orb.lm;
+  R.H = S->H; R.found = &S->found; R.info = S->info;
   int rc = evh_launch_find_homography(c, R);
   if (rc) return rc;
   double Hh[9]; int found = 0, info[3] = {0, 0, 0};
-  EVH_HIP(c, hipMemcpyAsync(Hh, c->d_small, sizeof(Hh), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&found, c->d_small + 16, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(info, c->d_small + 17, sizeof(info), hipMemcpyDeviceToHost, c->stream));
-  if (h_mask && n > 0) EVH_HIP(c, hipMemcpyAsync(h_mask, c->d_mask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(Hh, S->H, sizeof(Hh), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(&found, &S->found, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(info, S->info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+  if (h_mask && n > 0) EVH_HIP(c, hipMemcpyAsync(h_mask, c->orb.mask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   EVH_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(h_H, Hh, sizeof(Hh));
   *h_found = found;
@@ -862,9 +898,10 @@ int evh_static_filter(evh_ctx* c, const double* h_H, const float* d_pts, int n, 
   if (n > c->kcap * c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "evh_static_filter: too many rows");
   if ((((uintptr_t)d_pts) | ((uintptr_t)d_out_pts)) & 15) return evh_fail(c, EVH_ERR_INVALID, "row buffers must be 16-byte aligned");
   { int jr = join_solve(c); if (jr) return jr; }
-  EVH_HIP(c, hipMemcpyAsync(c->d_small, h_H, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  int* d_cnt = reinterpret_cast<int*>(c->d_small + 16);
-  int rc = evh_launch_static_filter(c, c->d_small, d_pts, n, reinterpret_cast<int*>(c->d_lm), d_out_pts, d_cnt);
+  EvhSmall* S = c->d_small;
+  EVH_HIP(c, hipMemcpyAsync(S->H, h_H, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  int* d_cnt = &S->count;
+  int rc = evh_launch_static_filter(c, S->H, d_pts, n, reinterpret_cast<int*>(c->orb.lm), d_out_pts, d_cnt);
   if (rc) return rc;
   EVH_HIP(c, hipMemcpyAsync(h_count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   EVH_HIP(c, hipStreamSynchronize(c->stream));
@@ -878,15 +915,15 @@ int evh_pair_homography_batch(evh_ctx* c, const uint8_t* d_frames, int npairs, i
   if (mode != EVH_MODE_INDEPENDENT_PAIRS && mode != EVH_MODE_STREAM) return evh_fail(c, EVH_ERR_INVALID, "unknown mode");
   const int nframes = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 * npairs : npairs + 1;
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  c->fast_share_group = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 : nframes;   // the two frames of a pair / one stream
-  int rc = evh_orb_detect_batch(c, d_frames, nframes, w, h, channels, row_stride, frame_stride, nfeatures);
+  if (mode == EVH_MODE_STREAM)
+    return stream_batch(c, d_frames, 1, nframes, w, h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
+                        ransac_max_iters, ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
+  // FAST thresholds are shared by the two frames of a pair
+  int rc = detect_match(c, d_frames, nframes, 2, npairs, 2, w, h, w, h, channels, row_stride, frame_stride, nfeatures);
   if (rc) return rc;
-  if (mode == EVH_MODE_INDEPENDENT_PAIRS) rc = match_pairs(c, npairs, 1, 2, 0, 2);
-  else rc = match_pairs(c, npairs, 1, 1, 0, 1);
-  if (rc) return rc;
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
+  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
   R.H = d_H; R.out_status = d_status;
-  return solve_pairs(c, R, npairs, mode == EVH_MODE_STREAM ? 1 : 0, npairs, npairs);
+  return solve_pairs(c, R, npairs, 0, npairs, npairs);
 }
 
 int evh_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
@@ -895,16 +932,8 @@ int evh_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nframes
                                 double* d_state_out, double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch: bad argument");
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  const int npairs = nframes - 1;
-  c->fast_share_group = nframes;
-  int rc = evh_orb_detect_batch(c, d_frames, nframes, w, h, channels, row_stride, frame_stride, nfeatures);
-  if (rc) return rc;
-  if ((rc = match_pairs(c, npairs, 1, 1, 0, 1))) return rc;
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  R.H = d_H; R.out_status = d_status;
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
-  return solve_pairs(c, R, npairs, 1, npairs, npairs);
+  return stream_batch(c, d_frames, 1, nframes, w, h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
+                      ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
 }
 
 int evh_stream_homography_batch_resized(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
@@ -913,16 +942,8 @@ int evh_stream_homography_batch_resized(evh_ctx* c, const uint8_t* d_frames, int
                                         const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_resized: bad argument");
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  const int npairs = nframes - 1;
-  c->fast_share_group = nframes;
-  int rc = detect_batch(c, d_frames, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nfeatures);
-  if (rc) return rc;
-  if ((rc = match_pairs(c, npairs, 1, 1, 0, 1))) return rc;
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  R.H = d_H; R.out_status = d_status;
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
-  return solve_pairs(c, R, npairs, 1, npairs, npairs);
+  return stream_batch(c, d_frames, 1, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
+                      ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
 }
 
 int evh_match_static_from_slots(evh_ctx* c, int cur_slot, int prev_slot, float* h_pts, int cap, int* h_count, int* h_status) {
@@ -930,18 +951,18 @@ int evh_match_static_from_slots(evh_ctx* c, int cur_slot, int prev_slot, float* 
       prev_slot >= c->nframes_resident)
     return evh_fail(c, EVH_ERR_INVALID, "evh_match_static_from_slots: bad argument");
   { int jr = join_solve(c); if (jr) return jr; }
-  int rc = match_pairs(c, 1, cur_slot, 0, prev_slot, 0);
+  int rc = match_orb_pairs(c, 1, cur_slot, 0, prev_slot, 0);
   if (rc) return rc;
-  EvhRansacArgs R = pair_ransac_args(c, 3.0, 2000, 0.995, 0);  // constants.py:22 THRESHOLD_FOR_FIND_HOMOGRAPHY
+  EvhRansacArgs R = ransac_args(c, c->orb, 3.0, 2000, 0.995, 0);  // constants.py:22 THRESHOLD_FOR_FIND_HOMOGRAPHY
   if ((rc = evh_launch_ransac_static(c, R, 1))) return rc;
   int st = 0, n = 0;
-  EVH_HIP(c, hipMemcpyAsync(&st, c->d_pstatus, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&n, c->d_npts2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(&st, c->orb.pstatus, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(&n, c->orb.npts2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   EVH_HIP(c, hipStreamSynchronize(c->stream));
   *h_status = st; *h_count = n;
   if (st == EVH_PAIR_OK && n > 0 && h_pts) {
     if (n > cap) return evh_fail(c, EVH_ERR_CAPACITY, "h_pts too small");
-    EVH_HIP(c, hipMemcpy(h_pts, c->d_pts2, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
+    EVH_HIP(c, hipMemcpy(h_pts, c->orb.pts2, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
   }
   return EVH_SUCCESS;
 }
@@ -951,23 +972,10 @@ int evh_compute_homography(evh_ctx* c, const float* h_pts, int n, const double* 
   if (n > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "evh_compute_homography: too many rows");
   { int jr = join_solve(c); if (jr) return jr; }
   const int zero = 0;
-  EVH_HIP(c, hipMemcpyAsync(c->d_pts2, h_pts, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(c->d_npts2, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(c->d_pstatus, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  EvhRansacArgs R = pair_ransac_args(c, 3.0, 2000, 0.995, 0);
-  R.H = c->d_small; R.out_status = reinterpret_cast<int*>(c->d_small + 32);
-  if (h_Hsup) {
-    EVH_HIP(c, hipMemcpyAsync(c->d_small + 16, h_Hsup, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    R.Hsup0 = c->d_small + 16;
-  }
-  // the stream kernel with one pair applies the optional pre-transform; Hprev0 = Hsup0 only marks "not first"
-  R.Hprev0 = R.Hsup0;
-  int rc = evh_launch_ransac_final(c, R, 1, h_Hsup ? 1 : 0, 1);
-  if (rc) return rc;
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  EVH_HIP(c, hipMemcpy(h_H, c->d_small, 9 * sizeof(double), hipMemcpyDeviceToHost));
-  EVH_HIP(c, hipMemcpy(h_status, c->d_small + 32, sizeof(int), hipMemcpyDeviceToHost));
-  return EVH_SUCCESS;
+  EVH_HIP(c, hipMemcpyAsync(c->orb.pts2, h_pts, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(c->orb.npts2, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(c->orb.pstatus, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return final_solve_one(c, h_Hsup, h_H, h_status);
 }
 
 int evh_multi_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nstreams, int frames_per_stream, int w,
@@ -976,19 +984,10 @@ int evh_multi_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int n
                                       const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nstreams < 1 || frames_per_stream < 2)
     return evh_fail(c, EVH_ERR_INVALID, "evh_multi_stream_homography_batch: bad argument");
-  const int64_t nframes64 = (int64_t)nstreams * frames_per_stream;
-  if (nframes64 > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  const int nframes = (int)nframes64;
-  c->fast_share_group = frames_per_stream;
-  int rc = evh_orb_detect_batch(c, d_frames, nframes, w, h, channels, row_stride, frame_stride, nfeatures);
-  if (rc) return rc;
-  // pair slot p = (frame p + 1, frame p): the slot that straddles two streams is computed and never read
-  if ((rc = match_pairs(c, nframes - 1, 1, 1, 0, 1))) return rc;
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  R.H = d_H; R.out_status = d_status;
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
-  return solve_pairs(c, R, nframes - 1, nstreams, frames_per_stream - 1, frames_per_stream);
+  if ((int64_t)nstreams * frames_per_stream > c->max_frames)
+    return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
+  return stream_batch(c, d_frames, nstreams, frames_per_stream, w, h, w, h, channels, row_stride, frame_stride, nfeatures,
+                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
 }
 
 int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
@@ -1000,16 +999,14 @@ int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, in
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "block needs more frame slots than max_frames");
   if (row_cap != c->kcap) return evh_fail(c, EVH_ERR_INVALID, "row_cap must equal evh_orb_capacity()");
   const int npairs = nframes - 1;
-  c->fast_share_group = nframes;
-  int rc = evh_orb_detect_batch(c, d_frames, nframes, w, h, channels, row_stride, frame_stride, nfeatures);
+  int rc = detect_match(c, d_frames, nframes, nframes, npairs, 1, w, h, w, h, channels, row_stride, frame_stride, nfeatures);
   if (rc) return rc;
-  if ((rc = match_pairs(c, npairs, 1, 1, 0, 1))) return rc;      // orders itself behind a pending async solve
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
+  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
   { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, R, npairs); }
   if (rc) return rc;
-  EVH_HIP(c, hipMemcpyAsync(d_rows, c->d_pts2, sizeof(float) * 4 * (size_t)c->kcap * npairs, hipMemcpyDeviceToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(d_counts, c->d_npts2, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(d_status1, c->d_pstatus, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(d_rows, c->orb.pts2, sizeof(float) * 4 * (size_t)c->kcap * npairs, hipMemcpyDeviceToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(d_counts, c->orb.npts2, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(d_status1, c->orb.pstatus, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
   return EVH_SUCCESS;
 }
 
@@ -1021,12 +1018,11 @@ int evh_stream_scan(evh_ctx* c, const float* d_rows, int row_cap, const int32_t*
   if (row_cap < 1 || row_cap > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "row_cap larger than evh_orb_capacity()");
   if (((uintptr_t)d_rows) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_rows must be 16-byte aligned");
   { int jr = join_solve(c); if (jr) return jr; }                  // the scan uses slot 0 of the pair scratch
-  EvhRansacArgs R = pair_ransac_args(c, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
+  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
   R.pts2 = const_cast<float*>(d_rows); R.npts2 = const_cast<int*>(d_counts); R.status = const_cast<int*>(d_status1);
   R.row_stride = row_cap; R.info = nullptr;
   R.H = d_H; R.out_status = d_status;
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
+  with_state(R, d_state_in, d_state_out);
   int rc;
   { EvhProfScope ps(c, EVH_ST_RANSAC_FINAL); rc = evh_launch_ransac_final(c, R, npairs, 1, npairs); }
   return rc;
@@ -1038,19 +1034,7 @@ int evh_pair_from_slots(evh_ctx* c, int cur_slot, int prev_slot, const double* h
   int rc = evh_match_static_from_slots(c, cur_slot, prev_slot, nullptr, 0, &n, &st);
   if (rc) return rc;
   if (st != EVH_PAIR_OK) { *h_status = st; memset(h_H, 0, 9 * sizeof(double)); return EVH_SUCCESS; }
-  // static rows are already resident in d_pts2 / d_npts2 / d_pstatus
-  EvhRansacArgs R = pair_ransac_args(c, 3.0, 2000, 0.995, 0);
-  R.H = c->d_small; R.out_status = reinterpret_cast<int*>(c->d_small + 32);
-  if (h_Hsup) {
-    EVH_HIP(c, hipMemcpyAsync(c->d_small + 16, h_Hsup, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    R.Hsup0 = c->d_small + 16; R.Hprev0 = R.Hsup0;
-  }
-  rc = evh_launch_ransac_final(c, R, 1, h_Hsup ? 1 : 0, 1);
-  if (rc) return rc;
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  EVH_HIP(c, hipMemcpy(h_H, c->d_small, 9 * sizeof(double), hipMemcpyDeviceToHost));
-  EVH_HIP(c, hipMemcpy(h_status, c->d_small + 32, sizeof(int), hipMemcpyDeviceToHost));
-  return EVH_SUCCESS;
+  return final_solve_one(c, h_Hsup, h_H, h_status);   // the static rows are already resident in pair slot 0
 }
 
 
@@ -1077,10 +1061,9 @@ int evh_sift_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int 
 
 int evh_sift_count(evh_ctx* c, int frame) {
   if (!c || frame < 0 || frame >= c->sift_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "bad SIFT frame slot");
-  int n = 0, fl = 0;
-  EVH_HIP(c, hipMemcpyAsync(&n, c->d_sift_count + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&fl, c->d_sift_flags + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  int fl = 0;
+  const int n = frame_count(c, feat_view(c, EVH_FEATURE_SIFT), frame, &fl);
+  if (n < 0) return n;
   if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "more SIFT key points (or scale-space extrema) than evh_sift_enable reserved for a frame");
   return n;
 }
@@ -1098,14 +1081,7 @@ int evh_sift_download(evh_ctx* c, int frame, float* h_xy, float* h_desc, int32_t
     EVH_HIP(c, hipMemcpyAsync(d8.data(), c->d_sift_desc + o * 128, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
   }
   EVH_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) {
-    const float* r = &rec[(size_t)i * 8];
-    if (h_xy) { h_xy[2 * i] = r[0]; h_xy[2 * i + 1] = r[1]; }
-    if (h_size) h_size[i] = r[2];
-    if (h_angle) h_angle[i] = r[3];
-    if (h_response) h_response[i] = r[4];
-    if (h_octave) memcpy(&h_octave[i], &r[5], 4);
-  }
+  unpack_records(rec, n, h_xy, h_size, h_angle, h_response, h_octave, nullptr);
   if (h_desc) for (size_t i = 0; i < (size_t)n * 128; i++) h_desc[i] = (float)d8[i];
   return n;
 }
@@ -1141,24 +1117,8 @@ int evh_match_knn2_l2f32(evh_ctx* c, const float* d_q, int nq, const float* d_t,
 
 int evh_ratio_unique_filter_f32(evh_ctx* c, const int32_t* d_idx, const float* d_dist, int nq, int nt, const float* d_xy_q,
                                 const float* d_xy_t, double ratio, int min_matches, float* d_pts, int* h_count, int* h_status) {
-  if (!c || !d_idx || !d_dist || !d_xy_q || !d_xy_t || !d_pts || !h_count || !h_status || nq < 0 || nt < 0)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_ratio_unique_filter_f32: bad argument");
-  const int kc = std::max(std::max(nq, nt), 1);
-  if (kc > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "evh_ratio_unique_filter_f32: too many rows");
-  if (((uintptr_t)d_pts) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_pts must be 16-byte aligned");
-  int* d_cnt = reinterpret_cast<int*>(c->d_small);
-  EvhFilterArgs F{};
-  F.idx = d_idx; F.d2 = reinterpret_cast<const uint32_t*>(d_dist); F.d2_is_dist = 1; F.knn_stride = nq;
-  F.xy_q = d_xy_q; F.xy_t = d_xy_t; F.xy_slot_floats = 0;
-  F.nq_fixed = nq; F.nt_fixed = nt; F.ratio = ratio; F.min_matches = min_matches;
-  F.pts = d_pts; F.pts_stride = nq; F.npts = d_cnt; F.status = d_cnt + 1; F.kcap = kc;
-  int rc = evh_launch_filter(c, F, 1);
-  if (rc) return rc;
-  int host[2];
-  EVH_HIP(c, hipMemcpyAsync(host, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  *h_count = host[0]; *h_status = host[1];
-  return EVH_SUCCESS;
+  return ratio_filter(c, "evh_ratio_unique_filter_f32", d_idx, reinterpret_cast<const uint32_t*>(d_dist), 1, nq, nt, d_xy_q, d_xy_t,
+                      ratio, min_matches, d_pts, h_count, h_status);
 }
 
 int evh_pair_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int npairs, int mode, int src_w, int src_h,
@@ -1210,10 +1170,9 @@ int evh_surf_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int 
 
 int evh_surf_count(evh_ctx* c, int frame) {
   if (!c || frame < 0 || frame >= c->surf_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "bad SURF frame slot");
-  int n = 0, fl = 0;
-  EVH_HIP(c, hipMemcpyAsync(&n, c->d_surf_count + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&fl, c->d_surf_flags + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  int fl = 0;
+  const int n = frame_count(c, feat_view(c, EVH_FEATURE_SURF), frame, &fl);
+  if (n < 0) return n;
   if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "more SURF key points than evh_surf_enable reserved for a frame");
   return n;
 }
@@ -1227,15 +1186,7 @@ int evh_surf_download(evh_ctx* c, int frame, float* h_xy, float* h_desc, float* 
   EVH_HIP(c, hipMemcpyAsync(rec.data(), c->d_surf_kp + o * 8, sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream));
   if (h_desc) EVH_HIP(c, hipMemcpyAsync(h_desc, c->d_surf_desc + o * 128, sizeof(float) * 128 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   EVH_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) {
-    const float* r = &rec[(size_t)i * 8];
-    if (h_xy) { h_xy[2 * i] = r[0]; h_xy[2 * i + 1] = r[1]; }
-    if (h_size) h_size[i] = r[2];
-    if (h_angle) h_angle[i] = r[3];
-    if (h_response) h_response[i] = r[4];
-    if (h_octave) memcpy(&h_octave[i], &r[5], 4);
-    if (h_laplacian) memcpy(&h_laplacian[i], &r[6], 4);
-  }
+  unpack_records(rec, n, h_xy, h_size, h_angle, h_response, h_octave, h_laplacian);
   return n;
 }
 

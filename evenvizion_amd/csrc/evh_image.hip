@@ -362,8 +362,7 @@ static int area_tables(evh_ctx* c, int sw, int sh, int dw, int dh, double scale_
     blob.insert(blob.end(), yt.si.begin(), yt.si.end());
     for (float f : yt.al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
     EVH_HIP(c, hipStreamSynchronize(c->stream));            // the previous tables may still be in use
-    if (c->d_area_tab) { (void)hipFree(c->d_area_tab); c->d_area_tab = nullptr; }
-    EVH_HIP(c, hipMalloc(&c->d_area_tab, blob.size() * sizeof(int)));
+    if (int rc = grow(c, &c->d_area_tab, &c->area_tab_bytes, blob.size() * sizeof(int))) return rc;
     EVH_HIP(c, hipMemcpy(c->d_area_tab, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice));
     c->area_key = key; c->area_nx = (int)xt.si.size(); c->area_ny = (int)yt.si.size();
   }

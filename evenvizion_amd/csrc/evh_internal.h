@@ -2,7 +2,9 @@
 // Product code: nothing here (or in any file of this directory) includes or links oracle/.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "../../include/evhip.h"
@@ -45,14 +47,34 @@ struct EvhSiftGeom {
   int64_t frame_floats, tmp_floats;
 };
 
-// per-pair working buffers of the matching / RANSAC stages (row stride `cap` rows per pair)
+// per-pair working buffers of the matching / RANSAC stages (max_pairs = max_frames, row stride `cap` rows per pair)
 struct EvhPairBufs {
   int cap = 0;
-  int32_t* knn_idx = nullptr; uint32_t* knn_d2 = nullptr;
-  float* pts = nullptr; float* pts2 = nullptr; float* crow = nullptr;
-  int* npts = nullptr; int* npts2 = nullptr; int* pstatus = nullptr;
-  double* H1 = nullptr; uint8_t* mask = nullptr; double* lm = nullptr; int* info = nullptr;
+  int32_t* knn_idx = nullptr;     // [max_pairs][cap][2]
+  uint32_t* knn_d2 = nullptr;     // [max_pairs][cap][2]
+  float* pts = nullptr;           // [max_pairs][cap][4] matched rows
+  float* pts2 = nullptr;          // [max_pairs][cap][4] static rows
+  float* crow = nullptr;          // [max_pairs][cap][4] compacted inlier rows
+  int* npts = nullptr; int* npts2 = nullptr; int* pstatus = nullptr;   // [max_pairs]
+  double* H1 = nullptr;           // [max_pairs][9]
+  uint8_t* mask = nullptr;        // [max_pairs][cap]
+  double* lm = nullptr;           // [max_pairs][cap][4] LM per-point temporaries
+  int* info = nullptr;            // [max_pairs][8]
 };
+
+// the 64-double staging area of the single-problem entries (d_small): what each entry keeps where
+struct EvhSmall {
+  union { double H[16]; int count_status[2]; };        // +0: result matrix | ratio filter: row count, status
+  union {                                              // +16 doubles
+    double Hsup[16];                                   // superposition entering a one-pair final solve
+    struct { int found, pad_, info[3]; };              // evh_find_homography_ransac*: found flag, +17 doubles: info
+    int count;                                         // evh_static_filter: rows kept
+  };
+  union { int out_status; double tail_[32]; };         // +32 doubles: status of a one-pair final solve
+};
+static_assert(sizeof(EvhSmall) == 64 * sizeof(double) && offsetof(EvhSmall, Hsup) == 16 * sizeof(double) &&
+              offsetof(EvhSmall, info) == 17 * sizeof(double) && offsetof(EvhSmall, out_status) == 32 * sizeof(double),
+              "EvhSmall keeps the byte offsets of the 64-double staging area");
 
 struct evh_ctx {
   int device = 0;
@@ -95,7 +117,7 @@ struct evh_ctx {
   int* d_filter_ws = nullptr; size_t filter_ws_bytes = 0;   // k_filter<true>: work arrays of key-point budgets beyond the LDS form
   char* d_scan_ws = nullptr;      // fixed-iteration stream scan: state, sample table and hypothesis results (evh_ransac.hip, lazy)
   size_t scan_ws_bytes = 0;
-  int* d_area_tab = nullptr;      // INTER_AREA tables of the last ingest geometry (evh_launch_ingest_level0)
+  int* d_area_tab = nullptr; size_t area_tab_bytes = 0;     // INTER_AREA tables of the last ingest geometry (evh_launch_ingest_level0)
   int64_t area_key = -1; int area_nx = 0, area_ny = 0;
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv
@@ -112,20 +134,8 @@ struct evh_ctx {
   bool fast_share = true;         // evh_set_fast_share
   bool fast_hint = true;          // evh_set_fast_hint
   int fast_share_group = 0;       // frames per group of consecutive frames for this detect call (0: unrelated frames)
-  // pair buffers (max_pairs = max_frames)
-  int32_t* d_knn_idx = nullptr;   // [max_pairs][kcap][2]
-  uint32_t* d_knn_d2 = nullptr;   // [max_pairs][kcap][2]
-  float* d_pts = nullptr;         // [max_pairs][kcap][4] matched rows
-  float* d_pts2 = nullptr;        // [max_pairs][kcap][4] static rows
-  int* d_npts = nullptr;          // [max_pairs]
-  int* d_npts2 = nullptr;         // [max_pairs]
-  int* d_pstatus = nullptr;       // [max_pairs]
-  double* d_H1 = nullptr;         // [max_pairs][9]
-  uint8_t* d_mask = nullptr;      // [max_pairs][kcap]
-  double* d_lm = nullptr;         // [max_pairs][kcap][4] LM per-point temporaries
-  float* d_crow = nullptr;        // [max_pairs][kcap][4] compacted inlier rows
-  int* d_info = nullptr;          // [max_pairs][8]
-  double* d_small = nullptr;      // small staging area for single-problem entries (H, counts)
+  EvhPairBufs orb;                // pair buffers of the ORB path, orb.cap = kcap
+  EvhSmall* d_small = nullptr;    // small staging area for single-problem entries (H, counts)
   char* d_scratch = nullptr;      // growable scratch of the host-pointer entries (N1 / N3): no hipMalloc per call
   size_t scratch_bytes = 0;
   // ---- N4: SIFT (allocated by evh_sift_enable) ----
@@ -154,6 +164,7 @@ struct evh_ctx {
   // multi-type pairs (frame_processing.py:91-104): per-type match / static rows, their concatenation, the merged rows
   EvhPairBufs mt;                 // stride mt.cap = kcap + sift_cap + surf_cap
   float* d_acc = nullptr; int* d_nacc = nullptr; int* d_accstatus = nullptr;
+  std::vector<void**> owned;      // the pointer members above that hold a live hipMalloc (dalloc / grow): what evh_destroy frees
   size_t bytes_allocated = 0;
   std::string err;
   // per-stage timing (evh_profile_*)
@@ -180,6 +191,42 @@ int evh_fail(evh_ctx* ctx, int code, const std::string& msg);
       return evh_fail(ctx, EVH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));              \
   } while (0)
 
+// ---- device memory of a context: every allocation goes into `p`, a pointer member of *c, and is recorded there ----
+template <class T>
+int evh_dev_alloc(evh_ctx* c, T** p, size_t bytes) {
+  EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(p), bytes));
+  c->owned.push_back(reinterpret_cast<void**>(p));
+  return EVH_SUCCESS;
+}
+// fixed-size buffers (counted in bytes_allocated)
+template <class T>
+int dalloc(evh_ctx* c, T** p, size_t n) {
+  int rc = evh_dev_alloc(c, p, n * sizeof(T));
+  if (rc == EVH_SUCCESS) c->bytes_allocated += n * sizeof(T);
+  return rc;
+}
+// frees the allocations recorded at position `first` and later (all of them: evh_destroy; the tail: a failed enable)
+inline void dfree_from(evh_ctx* c, size_t first) {
+  for (size_t i = first; i < c->owned.size(); i++) { (void)hipFree(*c->owned[i]); *c->owned[i] = nullptr; }
+  c->owned.resize(std::min(first, c->owned.size()));
+}
+template <class T>
+void dfree(evh_ctx* c, T** p) {
+  auto it = std::find(c->owned.begin(), c->owned.end(), reinterpret_cast<void**>(p));
+  if (it == c->owned.end()) return;
+  (void)hipFree(*p); *p = nullptr;
+  c->owned.erase(it);
+}
+// grow-on-demand workspace: kernels already enqueued may still use the old one, so the stream drains before it is freed
+template <class T>
+int grow(evh_ctx* c, T** p, size_t* bytes, size_t need) {
+  if (need <= *bytes) return EVH_SUCCESS;
+  if (*p) { EVH_HIP(c, hipStreamSynchronize(c->stream)); dfree(c, p); *bytes = 0; }
+  int rc = evh_dev_alloc(c, p, need);
+  if (rc == EVH_SUCCESS) *bytes = need;
+  return rc;
+}
+
 // ---- kernel launchers (each enqueues on ctx->stream) ----
 int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int channels, int64_t row_stride,
                            int64_t frame_stride);
@@ -195,11 +242,9 @@ int evh_launch_transform_points(evh_ctx* c, const double* d_M, const int* d_idx,
 int evh_launch_fixed_plane(evh_ctx* c, const double* d_H, int n, int w, int h, double* d_field, unsigned long long* d_max);
 // N4: SIFT (evh_sift.hip)
 int evh_sift_allocate(evh_ctx* c, int max_sift_features);
-void evh_sift_free(evh_ctx* c);
 int evh_launch_sift(evh_ctx* c, int nframes, int w, int h);
 // N4: SURF (evh_surf.hip)
 int evh_surf_allocate(evh_ctx* c, int max_surf_features);
-void evh_surf_free(evh_ctx* c);
 int evh_launch_surf(evh_ctx* c, int nframes, int w, int h, float hessian_threshold);
 int evh_launch_resize_area(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, int sh, int cn, int64_t src_stride,
                            int64_t src_img_stride, uint8_t* d_dst, int dw, int dh, int64_t dst_stride,

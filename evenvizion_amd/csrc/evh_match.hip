@@ -705,11 +705,7 @@ int evh_launch_merge(evh_ctx* c, const EvhMergeArgs& A_, int npairs) {
   if (npairs <= 0) return EVH_SUCCESS;
   EvhMergeArgs A = A_;
   const size_t need = sizeof(int) * 2 * (size_t)A.acc_stride * (size_t)npairs;
-  if (c->merge_ws_bytes < need) {
-    if (c->d_merge_ws) { EVH_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_merge_ws); c->d_merge_ws = nullptr; c->merge_ws_bytes = 0; }
-    EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_merge_ws), need));
-    c->merge_ws_bytes = need;
-  }
+  if (int rc = grow(c, &c->d_merge_ws, &c->merge_ws_bytes, need)) return rc;
   A.work = c->d_merge_ws;
   hipLaunchKernelGGL(k_merge_dup, dim3((unsigned)((A.acc_stride + 255) / 256), npairs), dim3(256), 0, c->stream, A);
   hipLaunchKernelGGL(k_merge, dim3(npairs), dim3(256), 0, c->stream, A);
@@ -723,11 +719,7 @@ int evh_launch_filter(evh_ctx* c, const EvhFilterArgs& A_, int npairs) {
   size_t lds = sizeof(int) * 5 * (size_t)A.kcap;
   if (lds > EVH_FILTER_LDS_MAX) {          // beyond a compute unit's LDS: the work arrays in a global scratch, grown on demand
     const size_t need = (lds + 2 * sizeof(int)) * (size_t)npairs;
-    if (c->filter_ws_bytes < need) {
-      if (c->d_filter_ws) { EVH_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_filter_ws); c->d_filter_ws = nullptr; c->filter_ws_bytes = 0; }
-      EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_filter_ws), need));
-      c->filter_ws_bytes = need;
-    }
+    if (int rc = grow(c, &c->d_filter_ws, &c->filter_ws_bytes, need)) return rc;
     A.work = c->d_filter_ws;
     hipLaunchKernelGGL(k_filter<true>, dim3(npairs), dim3(256), 0, c->stream, A);
     hipLaunchKernelGGL(k_filter_dup, dim3((A.kcap + 255) / 256, npairs), dim3(256), 0, c->stream, A);

@@ -2476,11 +2476,7 @@ int scan_ws(evh_ctx* c, int nstreams, int npairs, int hmax, ScanWs* W) {
   const size_t o_state = 0, o_rng = o_state + up(sizeof(ScanState) * nstreams), o_quads = o_rng + up(8 * slots),
                o_hyp = o_quads + up(sizeof(ushort4) * slots * hmax), o_H = o_hyp + up(sizeof(int) * (size_t)nstreams * hmax),
                total = o_H + up(sizeof(double) * 9 * (size_t)nstreams * hmax);
-  if (c->scan_ws_bytes < total) {
-    if (c->d_scan_ws) { EVH_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_scan_ws); c->d_scan_ws = nullptr; c->scan_ws_bytes = 0; }
-    EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_scan_ws), total));
-    c->scan_ws_bytes = total;
-  }
+  if (int rc = grow(c, &c->d_scan_ws, &c->scan_ws_bytes, total)) return rc;
   char* b = c->d_scan_ws;
   W->state = reinterpret_cast<ScanState*>(b + o_state); W->rng_after = reinterpret_cast<unsigned long long*>(b + o_rng);
   W->quads = reinterpret_cast<ushort4*>(b + o_quads); W->hyp = reinterpret_cast<int*>(b + o_hyp);

@@ -762,13 +762,6 @@ void sift_geometry(int w, int h, EvhSiftGeom& g) {
   g.tmp_floats = (int64_t)g.os[0] * g.oh[0];
 }
 
-template <class T>
-int salloc(evh_ctx* c, T** p, size_t n) {
-  EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  c->bytes_allocated += n * sizeof(T);
-  return EVH_SUCCESS;
-}
-
 SiftArgs sift_args(evh_ctx* c) {
   SiftArgs A{};
   A.g = c->sg;
@@ -797,34 +790,27 @@ int evh_sift_allocate(evh_ctx* c, int max_sift_features) {
   const int cap = (max_sift_features + 63) & ~63;
   const size_t F = (size_t)c->max_frames;
   int rc;
-#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { evh_sift_free(c); return rc; }   /* a partial allocation is released */
-  S_(salloc(c, &c->d_sift_pyr, (size_t)group * gm.frame_floats + 64));
-  S_(salloc(c, &c->d_sift_tmp, (size_t)group * gm.tmp_floats + 64));
-  S_(salloc(c, &c->d_sift_cand, F * 4 * cap));
-  S_(salloc(c, &c->d_sift_ncand, F));
-  S_(salloc(c, &c->d_sift_raw, F * cap * 8));
-  S_(salloc(c, &c->d_sift_nraw, F));
-  S_(salloc(c, &c->d_sift_srt, F * cap * 8));
-  S_(salloc(c, &c->d_sift_kp, F * cap * 8));
-  S_(salloc(c, &c->d_sift_xy, F * cap * 2));
-  S_(salloc(c, &c->d_sift_desc, F * cap * 128));
-  S_(salloc(c, &c->d_sift_count, F));
-  S_(salloc(c, &c->d_sift_flags, F));
+  const size_t first = c->owned.size();
+  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
+#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); return rc; }
+  S_(dalloc(c, &c->d_sift_pyr, (size_t)group * gm.frame_floats + 64));
+  S_(dalloc(c, &c->d_sift_tmp, (size_t)group * gm.tmp_floats + 64));
+  S_(dalloc(c, &c->d_sift_cand, F * 4 * cap));
+  S_(dalloc(c, &c->d_sift_ncand, F));
+  S_(dalloc(c, &c->d_sift_raw, F * cap * 8));
+  S_(dalloc(c, &c->d_sift_nraw, F));
+  S_(dalloc(c, &c->d_sift_srt, F * cap * 8));
+  S_(dalloc(c, &c->d_sift_kp, F * cap * 8));
+  S_(dalloc(c, &c->d_sift_xy, F * cap * 2));
+  S_(dalloc(c, &c->d_sift_desc, F * cap * 128));
+  S_(dalloc(c, &c->d_sift_count, F));
+  S_(dalloc(c, &c->d_sift_flags, F));
 #undef S_
   EVH_HIP(c, hipMemsetAsync(c->d_sift_count, 0, F * sizeof(int), c->stream));
   EVH_HIP(c, hipMemsetAsync(c->d_sift_flags, 0, F * sizeof(int), c->stream));
   c->sift_cap = cap; c->sift_cand_cap = 4 * cap; c->sift_group = group;
   c->sift_pyr_frame_floats = gm.frame_floats; c->sift_tmp_frame_floats = gm.tmp_floats;
   return EVH_SUCCESS;
-}
-
-void evh_sift_free(evh_ctx* c) {
-  void* ptrs[] = {c->d_sift_pyr, c->d_sift_tmp, c->d_sift_cand, c->d_sift_ncand, c->d_sift_raw, c->d_sift_nraw, c->d_sift_srt,
-                  c->d_sift_kp, c->d_sift_xy, c->d_sift_desc, c->d_sift_count, c->d_sift_flags};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  c->d_sift_pyr = nullptr; c->d_sift_tmp = nullptr; c->d_sift_cand = nullptr; c->d_sift_ncand = nullptr; c->d_sift_raw = nullptr;
-  c->d_sift_nraw = nullptr; c->d_sift_srt = nullptr; c->d_sift_kp = nullptr; c->d_sift_xy = nullptr; c->d_sift_desc = nullptr;
-  c->d_sift_count = nullptr; c->d_sift_flags = nullptr; c->sift_cap = 0;
 }
 
 // SIFT on the frames whose gray level 0 is resident in the context's ORB pyramid (evh_launch_gray_level0 /

@@ -588,13 +588,6 @@ int64_t surf_tables(int w, int h, SurfTabs& T) {
   return off;
 }
 
-template <class T>
-int salloc(evh_ctx* c, T** p, size_t n) {
-  EVH_HIP(c, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  c->bytes_allocated += n * sizeof(T);
-  return EVH_SUCCESS;
-}
-
 }  // namespace
 
 int evh_surf_allocate(evh_ctx* c, int max_surf_features) {
@@ -610,34 +603,27 @@ int evh_surf_allocate(evh_ctx* c, int max_surf_features) {
   const int cap = (max_surf_features + 63) & ~63;
   const size_t F = (size_t)c->max_frames;
   int rc;
-#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { evh_surf_free(c); return rc; }   /* a partial allocation is released */
-  S_(salloc(c, &c->d_surf_tabs, sizeof(SurfTabs)));
-  S_(salloc(c, &c->d_surf_sum, (size_t)group * sum_ints + 64));
-  S_(salloc(c, &c->d_surf_det, (size_t)group * det_floats + 64));
-  S_(salloc(c, &c->d_surf_trace, (size_t)group * det_floats + 64));
-  S_(salloc(c, &c->d_surf_raw, F * cap * 8));
-  S_(salloc(c, &c->d_surf_nraw, F));
-  S_(salloc(c, &c->d_surf_srt, F * cap * 8));
-  S_(salloc(c, &c->d_surf_kp, F * cap * 8));
-  S_(salloc(c, &c->d_surf_xy, F * cap * 2));
-  S_(salloc(c, &c->d_surf_desc, F * cap * 128));
-  S_(salloc(c, &c->d_surf_count, F));
-  S_(salloc(c, &c->d_surf_flags, F));
+  const size_t first = c->owned.size();
+  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
+#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); return rc; }
+  S_(dalloc(c, &c->d_surf_tabs, sizeof(SurfTabs)));
+  S_(dalloc(c, &c->d_surf_sum, (size_t)group * sum_ints + 64));
+  S_(dalloc(c, &c->d_surf_det, (size_t)group * det_floats + 64));
+  S_(dalloc(c, &c->d_surf_trace, (size_t)group * det_floats + 64));
+  S_(dalloc(c, &c->d_surf_raw, F * cap * 8));
+  S_(dalloc(c, &c->d_surf_nraw, F));
+  S_(dalloc(c, &c->d_surf_srt, F * cap * 8));
+  S_(dalloc(c, &c->d_surf_kp, F * cap * 8));
+  S_(dalloc(c, &c->d_surf_xy, F * cap * 2));
+  S_(dalloc(c, &c->d_surf_desc, F * cap * 128));
+  S_(dalloc(c, &c->d_surf_count, F));
+  S_(dalloc(c, &c->d_surf_flags, F));
 #undef S_
   EVH_HIP(c, hipMemsetAsync(c->d_surf_count, 0, F * sizeof(int), c->stream));
   EVH_HIP(c, hipMemsetAsync(c->d_surf_flags, 0, F * sizeof(int), c->stream));
   c->surf_cap = cap; c->surf_group = group; c->surf_sum_frame_ints = sum_ints; c->surf_det_frame_floats = det_floats;
   c->surf_tab_w = c->surf_tab_h = 0;
   return EVH_SUCCESS;
-}
-
-void evh_surf_free(evh_ctx* c) {
-  void* ptrs[] = {c->d_surf_tabs, c->d_surf_sum, c->d_surf_det, c->d_surf_trace, c->d_surf_raw, c->d_surf_nraw, c->d_surf_srt,
-                  c->d_surf_kp, c->d_surf_xy, c->d_surf_desc, c->d_surf_count, c->d_surf_flags};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  c->d_surf_tabs = nullptr; c->d_surf_sum = nullptr; c->d_surf_det = nullptr; c->d_surf_trace = nullptr; c->d_surf_raw = nullptr;
-  c->d_surf_nraw = nullptr; c->d_surf_srt = nullptr; c->d_surf_kp = nullptr; c->d_surf_xy = nullptr; c->d_surf_desc = nullptr;
-  c->d_surf_count = nullptr; c->d_surf_flags = nullptr; c->surf_cap = 0;
 }
 
 // SURF on the frames whose gray level 0 is resident in the context's ORB pyramid

@@ -91,9 +91,34 @@ SIGNATURES = {
     "evh_ratio_unique_filter_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _d, _i, _vp, _pi, _pi]),
     "evh_pair_homography_batch_types": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp]),
     "evh_stream_homography_batch_types": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    # decoded 4:2:0 planes as the source (the second argument points at a Yuv420)
+    "evh_yuv420_to_bgr": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64]),
+    "evh_orb_detect_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "evh_stream_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "evh_stream_homography_batch_types_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
 }
 FEATURE_ORB, FEATURE_SIFT, FEATURE_SURF = 0, 1, 2
 FEATURE_CODES = {"ORB": FEATURE_ORB, "SIFT": FEATURE_SIFT, "SURF": FEATURE_SURF}
+
+
+class Yuv420(C.Structure):
+    """evh_yuv420 (include/evhip.h): three device plane pointers and their strides."""
+    _fields_ = [("d_y", _vp), ("d_cb", _vp), ("d_cr", _vp), ("y_stride", _i64), ("c_stride", _i64),
+                ("y_frame_stride", _i64), ("c_frame_stride", _i64), ("c_pixel_stride", C.c_int32)]
+
+
+def yuv420_size(w, h):
+    """Bytes of one packed I420 frame [w*h | cw*ch | cw*ch] and its chroma size (cw, ch)."""
+    cw, ch = (int(w) + 1) // 2, (int(h) + 1) // 2
+    return int(w) * int(h) + 2 * cw * ch, cw, ch
+
+
+def yuv420_views(packed, w, h):
+    """The (Y [n,h,w], Cb [n,ch,cw], Cr [n,ch,cw]) views of packed I420 frames [n, w*h + 2*cw*ch] (tensor or array)."""
+    _, cw, ch = yuv420_size(w, h)
+    n = packed.shape[0]
+    return (packed[:, :w * h].reshape(n, h, w), packed[:, w * h:w * h + cw * ch].reshape(n, ch, cw),
+            packed[:, w * h + cw * ch:w * h + 2 * cw * ch].reshape(n, ch, cw))
 
 
 class EvhError(RuntimeError):
@@ -391,6 +416,89 @@ class Context:
         self._check(self.lib.evh_multi_stream_homography_batch(
             self.h, frames.data_ptr(), S, F, w, h, cn, w * cn, w * h * cn, nfeatures, float(thr), int(max_iters),
             float(conf), int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
+            state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+
+    # ---- decoded 4:2:0 planes as the source ----
+    @staticmethod
+    def _yuv420(planes, size, check_device=None):
+        """-> (Yuv420, n, w, h).  planes: one uint8 CUDA tensor [n, w*h + 2*cw*ch] of packed I420 frames (size=(w, h)
+        required), or (y [n,h,w], cb [n,ch,cw], cr [n,ch,cw]) tensors or VIEWS: rows and frames may be strided, chroma may step
+        by 2 bytes per sample -- NV12 is (y, uv[..., 0], uv[..., 1]) of a [n,ch,cw,2] tensor."""
+        import torch
+        for t in (planes if isinstance(planes, (tuple, list)) else [planes]):
+            if t.dtype != torch.uint8:
+                raise ValueError("planes must be uint8 tensors")
+            if check_device is not None and (not t.is_cuda or t.device.index != check_device):
+                raise ValueError("planes must live on the context's device (cuda:%d)" % check_device)
+        if not isinstance(planes, (tuple, list)):
+            if size is None:
+                raise ValueError("packed I420 frames need size=(w, h)")
+            w, h = int(size[0]), int(size[1])
+            if planes.dim() != 2 or planes.shape[1] != yuv420_size(w, h)[0] or planes.stride(1) != 1:
+                raise ValueError("packed I420 frames are [n, w*h + 2*cw*ch] with contiguous rows")
+            _, cw, ch = yuv420_size(w, h)
+            d = Yuv420(planes.data_ptr(), planes.data_ptr() + w * h, planes.data_ptr() + w * h + cw * ch, w, cw,
+                       planes.stride(0), planes.stride(0), 1)
+            return d, planes.shape[0], w, h
+        y, cb, cr = planes
+        n, h, w = y.shape
+        cw, ch = (w + 1) // 2, (h + 1) // 2
+        if size is not None and (int(size[0]), int(size[1])) != (w, h):
+            raise ValueError("size does not match the luma plane")
+        if tuple(cb.shape) != (n, ch, cw) or tuple(cr.shape) != (n, ch, cw):
+            raise ValueError("chroma planes must be [n, (h+1)//2, (w+1)//2]")
+        # a dimension of extent 1 has no meaningful stride: give it the tight one
+        ys = [y.stride(0), y.stride(1), y.stride(2) if w > 1 else 1]
+        cs = [cb.stride(0), cb.stride(1), cb.stride(2) if cw > 1 else 1]
+        if cw == 1 and abs(cb.data_ptr() - cr.data_ptr()) == 1:
+            cs[2] = 2                                          # one interleaved chroma pair
+        if ys[2] != 1 or (cw > 1 and cr.stride(2) != cs[2]) or (ch > 1 and cr.stride(1) != cs[1]) or \
+                (n > 1 and cr.stride(0) != cs[0]):
+            raise ValueError("luma samples must be contiguous in a row; Cb and Cr must share their strides")
+        d = Yuv420(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), ys[1] if h > 1 else w, cs[1] if ch > 1 else cw * cs[2],
+                   ys[0], cs[0], cs[2])
+        return d, n, w, h
+
+    def yuv420_to_bgr(self, planes, out, size=None):
+        """planes (see _yuv420) -> out: CUDA uint8 [n,h,w,3] (rows / frames may be strided), the BGR bytes
+        cv2.VideoCapture.read() returns for the decoded picture (video_processing.py:58,70)."""
+        self._enter()
+        d, n, w, h = self._yuv420(planes, size, self.device)
+        if str(out.dtype) != "torch.uint8" or not out.is_cuda or tuple(out.shape) != (n, h, w, 3) or out.stride(3) != 1 or (w > 1 and out.stride(2) != 3):
+            raise ValueError("out must be a CUDA uint8 tensor [n,h,w,3] with packed pixels")
+        self._check(self.lib.evh_yuv420_to_bgr(self.h, C.byref(d), n, w, h, out.data_ptr(), out.stride(1) if h > 1 else 3 * w,
+                                               out.stride(0)))
+
+    def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
+        """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""
+        self._enter()
+        d, n, w, h = self._yuv420(planes, size, self.device)
+        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        self._check(self.lib.evh_orb_detect_batch_yuv420(self.h, C.byref(d), n, w, h, dw, dh, nfeatures))
+
+    def stream_homography_batch_yuv420(self, planes, size, out_H, out_status, state_in=None, state_out=None, nfeatures=500,
+                                       thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None):
+        """stream_homography_batch on decoded planes (see _yuv420): n >= 2 consecutive frames -> n-1 pairs."""
+        self._enter()
+        d, n, w, h = self._yuv420(planes, size, self.device)
+        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        self._check(self.lib.evh_stream_homography_batch_yuv420(
+            self.h, C.byref(d), n, w, h, dw, dh, nfeatures, float(thr), int(max_iters), float(conf), int(bool(force_max_iters)),
+            state_in.data_ptr() if state_in is not None else None, state_out.data_ptr() if state_out is not None else None,
+            out_H.data_ptr(), out_status.data_ptr()))
+
+    def stream_homography_batch_types_yuv420(self, planes, size, out_H, out_status, features, state_in=None, state_out=None,
+                                             nfeatures=500, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False,
+                                             resize_to=None):
+        """stream_homography_batch_types on decoded planes: converted once on the device, then the BGR path."""
+        self._enter()
+        d, n, w, h = self._yuv420(planes, size, self.device)
+        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        t = self._types(features)
+        self._multi_used = True
+        self._check(self.lib.evh_stream_homography_batch_types_yuv420(
+            self.h, C.byref(d), n, w, h, dw, dh, nfeatures, _hp(t), len(t), float(thr), int(max_iters), float(conf),
+            int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
             state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
 
     # ---- N4: SIFT + multi-type pairs ----

@@ -80,6 +80,7 @@ class VideoCapture:
     def __init__(self, path=None, data=None, bgr_mode=BGR_SWSCALE_X86, honour_edit_list=True):
         self._h = C.c_void_p()
         self._L = lib()
+        self.bgr_mode = int(bgr_mode)     # which conversion read() applies to the planes read_yuv420_into() delivers
         self.open_error = ""
         if data is not None:
             buf = np.frombuffer(bytes(data), np.uint8)
@@ -112,17 +113,28 @@ class VideoCapture:
         ok = self._check(self._L.evcap_read_bgr(self._h, frame.ctypes.data_as(C.c_void_p), frame.strides[0]))
         return (True, frame) if ok else (False, None)
 
+    def read_yuv420_into(self, y, cb, cr):
+        """The next frame's decoded planes into the caller's uint8 arrays y [h,w], cb / cr [(h+1)//2, (w+1)//2] (rows may
+        be strided, Cb and Cr share their row stride) -> True, or False once the frames are exhausted.  Raises CaptureError --
+        before a picture is taken from the decoder -- when the stream cannot be delivered as planes (odd crop offset)."""
+        if not self._h:
+            return False
+        cw, ch = (self.width + 1) // 2, (self.height + 1) // 2
+        for a, shape in ((y, (self.height, self.width)), (cb, (ch, cw)), (cr, (ch, cw))):
+            if a.dtype != np.uint8 or a.shape != shape or a.strides[1] != 1 or not a.flags.writeable:
+                raise ValueError("read_yuv420_into: planes are writable uint8 arrays %s with contiguous rows" % (shape,))
+        if cb.strides[0] != cr.strides[0]:
+            raise ValueError("read_yuv420_into: Cb and Cr must share their row stride")
+        return self._check(self._L.evcap_read_yuv420(self._h, y.ctypes.data_as(C.c_void_p), y.strides[0],
+                                                      cb.ctypes.data_as(C.c_void_p), cr.ctypes.data_as(C.c_void_p), cb.strides[0]))
+
     def read_yuv420(self):
         """-> (True, (Y, Cb, Cr)) planes as decoded, or (False, None)"""
-        if not self._h:
-            return False, None
         cw, ch = (self.width + 1) // 2, (self.height + 1) // 2
         y = np.empty((self.height, self.width), np.uint8)
         cb = np.empty((ch, cw), np.uint8)
         cr = np.empty((ch, cw), np.uint8)
-        ok = self._check(self._L.evcap_read_yuv420(self._h, y.ctypes.data_as(C.c_void_p), y.strides[0], cb.ctypes.data_as(C.c_void_p),
-                                                    cr.ctypes.data_as(C.c_void_p), cb.strides[0]))
-        return (True, (y, cb, cr)) if ok else (False, None)
+        return (True, (y, cb, cr)) if self.read_yuv420_into(y, cb, cr) else (False, None)
 
     def last_frame_info(self):
         """-> dict(poc, decode_index, slice_type 'P'|'B'|'I') of the frame most recently returned"""

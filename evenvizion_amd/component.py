@@ -74,6 +74,9 @@ def main(argv=None):
     ap.add_argument("--show_matching_visualization", default=False, help="not available: matching pictures are not rendered")
     ap.add_argument("--features", type=str, default="SURF,SIFT,ORB",
                     help="feature types in FrameProcessing order (extension; the reference hard-wires SURF,SIFT,ORB)")
+    ap.add_argument("--ingest", type=str, default="bgr", choices=("auto", "bgr", "yuv420"),
+                    help="how frames reach the GPU: BGR frames (default), the decoder's 4:2:0 planes when the capture offers them "
+                         "(auto), or planes only (extension; results do not depend on it)")
     args = ap.parse_args(argv)
     if _bool(args.show_matching_visualization):
         raise NotImplementedError("matching pictures are outside the MI355X hot path; leave --show_matching_visualization off")
@@ -90,7 +93,7 @@ def main(argv=None):
 
     result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
                                  none_H_processing=_bool(args.none_H_processing),
-                                 features_type_list=[f for f in args.features.split(",") if f])
+                                 features_type_list=[f for f in args.features.split(",") if f], ingest=args.ingest)
     path_to_homography_dict = os.path.join(save_folder, "dict_with_homography_matrix.json")
     with open(path_to_homography_dict, "w") as json_:
         json.dump(result, json_)

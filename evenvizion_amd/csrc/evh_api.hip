@@ -270,21 +270,43 @@ int solve_pairs(evh_ctx* c, EvhRansacArgs R, int npairs, int nstreams = 0, int p
 }
 
 
+// the argument checks of every entry that takes planes: nothing is launched on a description that fails them
+int check_yuv420(evh_ctx* c, const char* who, const evh_yuv420* s, int nframes, int w, int h) {
+  const std::string W = std::string(who) + ": ";
+  if (!c) return EVH_ERR_INVALID;
+  if (!s || !s->d_y || !s->d_cb || !s->d_cr) return evh_fail(c, EVH_ERR_INVALID, W + "NULL plane");
+  if (w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty source frame");
+  if (nframes < 1 || nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "between 1 and 65535 frames per call");
+  if (s->c_pixel_stride != 1 && s->c_pixel_stride != 2) return evh_fail(c, EVH_ERR_INVALID, W + "chroma pixel stride must be 1 or 2");
+  const int64_t cw = (w + 1) / 2, ch = (h + 1) / 2, crow = (cw - 1) * s->c_pixel_stride + 1;
+  if (s->y_stride < w) return evh_fail(c, EVH_ERR_INVALID, W + "luma row stride smaller than the width");
+  if (s->c_stride < crow) return evh_fail(c, EVH_ERR_INVALID, W + "chroma row stride smaller than a chroma row");
+  if (nframes > 1 && (s->y_frame_stride < (h - 1) * s->y_stride + w || s->c_frame_stride < (ch - 1) * s->c_stride + crow))
+    return evh_fail(c, EVH_ERR_INVALID, W + "frame stride smaller than a plane");
+  return EVH_SUCCESS;
+}
+
 // level 0 (gray) of every frame: (sw, sh) = size of the frames handed over, (w, h) = working size.  Different sizes =
-// fused ingest (N2).  Shared by every feature type of a call.
-int ingest_level0(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframes, int sw, int sh, int w, int h,
-                         int channels, int64_t row_stride, int64_t frame_stride, int nfeatures) {
-  if (!c || !d_frames) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": NULL argument");
+// fused ingest (N2).  Shared by every feature type of a call.  The one place where the frames of a detect / pair / stream
+// entry are checked.
+int ingest_level0(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures) {
+  if (!c) return EVH_ERR_INVALID;
+  if (F.yuv) {
+    if (int rc = check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  } else {
+    if (!F.packed) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (F.channels != 1 && F.channels != 3) return evh_fail(c, EVH_ERR_INVALID, "channels must be 1 or 3");
+    if (F.row_stride < (int64_t)sw * F.channels) return evh_fail(c, EVH_ERR_INVALID, "row_stride smaller than a row");
+    if (sw < 1 || sh < 1) return evh_fail(c, EVH_ERR_INVALID, "empty source frame");
+  }
   if (nframes < 1 || nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "nframes exceeds max_frames");
-  if (channels != 1 && channels != 3) return evh_fail(c, EVH_ERR_INVALID, "channels must be 1 or 3");
-  if (row_stride < (int64_t)sw * channels) return evh_fail(c, EVH_ERR_INVALID, "row_stride smaller than a row");
-  if (sw < 1 || sh < 1) return evh_fail(c, EVH_ERR_INVALID, "empty source frame");
   if (nframes > 65535 || h > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "too many frames / rows for one launch");
   int rc = configure(c, w, h, nfeatures);
   if (rc) return rc;
   EvhProfScope ps(c, EVH_ST_GRAY);
-  if (sw == w && sh == h) return evh_launch_gray_level0(c, d_frames, nframes, channels, row_stride, frame_stride);
-  return evh_launch_ingest_level0(c, d_frames, nframes, sw, sh, channels, row_stride, frame_stride, w, h);
+  if (!F.yuv && sw == w && sh == h)
+    return evh_launch_gray_level0(c, F.packed, nframes, F.channels, F.row_stride, F.frame_stride);
+  return evh_launch_ingest_level0(c, F, nframes, sw, sh, w, h);
 }
 
 // ORB K2..K6 on the frames whose level 0 is resident
@@ -302,12 +324,11 @@ int orb_stages(evh_ctx* c, int nframes, int share_group) {
   return EVH_SUCCESS;
 }
 
-int detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int w, int h, int channels,
-                        int64_t row_stride, int64_t frame_stride, int nfeatures) {
+int detect_batch(evh_ctx* c, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures) {
   if (!c) return EVH_ERR_INVALID;
   const int share_group = c->fast_share ? c->fast_share_group : 0;   // set by the pair / stream entries for THIS call only
   c->fast_share_group = 0;
-  int rc = ingest_level0(c, "evh_orb_detect_batch", d_frames, nframes, sw, sh, w, h, channels, row_stride, frame_stride, nfeatures);
+  int rc = ingest_level0(c, "evh_orb_detect_batch", F, nframes, sw, sh, w, h, nfeatures);
   if (rc) return rc;
   return orb_stages(c, nframes, share_group);
 }
@@ -330,9 +351,8 @@ int ensure_multitype(evh_ctx* c) {
 
 // frames -> H with a LIST of feature types, in list order (the reference's default list is SURF, SIFT, ORB):
 // per type detect, match, RANSAC #1, static filter; concatenate; remove_double_matching; compute_homography
-int pairs_types(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframes, int npairs, int stream_mode, int sw, int sh,
-                int w, int h, int channels, int64_t row_stride, int64_t frame_stride, int nfeatures, const int* types,
-                int ntypes, double thr, int max_iters, double conf, int force_max, const double* d_state_in, double* d_state_out,
+int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int npairs, int stream_mode, int sw, int sh,
+                int w, int h, int nfeatures, const int* types, int ntypes, double thr, int max_iters, double conf, int force_max, const double* d_state_in, double* d_state_out,
                 double* d_H, int32_t* d_status) {
   if (!types || ntypes < 1 || ntypes > 8) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad feature type list");
   bool want_orb = false, want_sift = false, want_surf = false;
@@ -354,7 +374,15 @@ int pairs_types(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframe
   if ((rc = join_solve(c))) return rc;
   const int share_group = c->fast_share ? (stream_mode ? nframes : 2) : 0;
   c->fast_share_group = 0;
-  if ((rc = ingest_level0(c, who, d_frames, nframes, sw, sh, w, h, channels, row_stride, frame_stride, nfeatures))) return rc;
+  EvhFrames P = F;
+  if (F.yuv) {      // SIFT and SURF read BGR through the shared front end: the chunk is converted once, then takes that path
+    const int64_t row = (int64_t)sw * 3, frame = row * sh;
+    if ((rc = check_yuv420(c, who, F.yuv, nframes, sw, sh))) return rc;
+    if ((rc = grow(c, &c->d_yuv_bgr, &c->yuv_bgr_bytes, (size_t)frame * nframes))) return rc;
+    if ((rc = evh_launch_yuv420_to_bgr(c, *F.yuv, nframes, sw, sh, c->d_yuv_bgr, row, frame))) return rc;
+    P = packed_frames(c->d_yuv_bgr, 3, row, frame);
+  }
+  if ((rc = ingest_level0(c, who, P, nframes, sw, sh, w, h, nfeatures))) return rc;
   if (want_sift && (rc = evh_launch_sift(c, nframes, w, h))) return rc;       // reads level 0 before ORB's kernels run on it
   if (want_surf && (rc = evh_launch_surf(c, nframes, w, h, 400.f))) return rc; // SURF_create(extended=1, hessianThreshold=400)
   if (want_orb && (rc = orb_stages(c, nframes, share_group))) return rc;
@@ -383,22 +411,21 @@ int pairs_types(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframe
 
 // ORB detect of `nframes` frames (FAST thresholds shared inside groups of share_group) + match of npairs pairs
 // (frame step + 1, frame step * p): the first half of every ORB pair / stream entry
-int detect_match(evh_ctx* c, const uint8_t* d_frames, int nframes, int share_group, int npairs, int step, int sw, int sh, int w,
-                 int h, int channels, int64_t row_stride, int64_t frame_stride, int nfeatures) {
+int detect_match(evh_ctx* c, const EvhFrames& F, int nframes, int share_group, int npairs, int step, int sw, int sh, int w,
+                 int h, int nfeatures) {
   c->fast_share_group = share_group;
-  int rc = detect_batch(c, d_frames, nframes, sw, sh, w, h, channels, row_stride, frame_stride, nfeatures);
+  int rc = detect_batch(c, F, nframes, sw, sh, w, h, nfeatures);
   if (rc) return rc;
   return match_orb_pairs(c, npairs, 1, step, 0, step);      // orders itself behind a pending async solve
 }
 
 // nstreams streams of frames_per_stream consecutive frames -> H per pair.  Pair slot p = (frame p + 1, frame p): a slot
 // that straddles two streams is computed and never read
-int stream_batch(evh_ctx* c, const uint8_t* d_frames, int nstreams, int frames_per_stream, int sw, int sh, int w, int h,
-                 int channels, int64_t row_stride, int64_t frame_stride, int nfeatures, double thr, int max_iters, double conf,
-                 int force_max, const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
+int stream_batch(evh_ctx* c, const EvhFrames& F, int nstreams, int frames_per_stream, int sw, int sh, int w, int h,
+                 int nfeatures, double thr, int max_iters, double conf, int force_max, const double* d_state_in,
+                 double* d_state_out, double* d_H, int32_t* d_status) {
   const int nframes = nstreams * frames_per_stream;
-  int rc = detect_match(c, d_frames, nframes, frames_per_stream, nframes - 1, 1, sw, sh, w, h, channels, row_stride, frame_stride,
-                        nfeatures);
+  int rc = detect_match(c, F, nframes, frames_per_stream, nframes - 1, 1, sw, sh, w, h, nfeatures);
   if (rc) return rc;
   EvhRansacArgs R = ransac_args(c, c->orb, thr, max_iters, conf, force_max);
   R.H = d_H; R.out_status = d_status;
@@ -742,12 +769,12 @@ int evh_transform_points(evh_ctx* c, const double* h_M, int nmat, const int32_t*
 
 int evh_orb_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
                          int64_t row_stride, int64_t frame_stride, int nfeatures) {
-  return detect_batch(c, d_frames, nframes, w, h, w, h, channels, row_stride, frame_stride, nfeatures);
+  return detect_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, w, h, w, h, nfeatures);
 }
 
 int evh_orb_detect_batch_resized(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
                                  int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures) {
-  return detect_batch(c, d_frames, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nfeatures);
+  return detect_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w, src_h, w, h, nfeatures);
 }
 
 int evh_orb_capacity(const evh_ctx* c) { return c ? c->kcap : EVH_ERR_INVALID; }
@@ -916,10 +943,10 @@ int evh_pair_homography_batch(evh_ctx* c, const uint8_t* d_frames, int npairs, i
   const int nframes = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 * npairs : npairs + 1;
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
   if (mode == EVH_MODE_STREAM)
-    return stream_batch(c, d_frames, 1, nframes, w, h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
-                        ransac_max_iters, ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
+    return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, w, h, w, h, nfeatures,
+                        ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
   // FAST thresholds are shared by the two frames of a pair
-  int rc = detect_match(c, d_frames, nframes, 2, npairs, 2, w, h, w, h, channels, row_stride, frame_stride, nfeatures);
+  int rc = detect_match(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, 2, npairs, 2, w, h, w, h, nfeatures);
   if (rc) return rc;
   EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
   R.H = d_H; R.out_status = d_status;
@@ -932,8 +959,8 @@ int evh_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nframes
                                 double* d_state_out, double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch: bad argument");
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return stream_batch(c, d_frames, 1, nframes, w, h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
-                      ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
+  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, w, h, w, h, nfeatures,
+                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
 }
 
 int evh_stream_homography_batch_resized(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
@@ -942,8 +969,8 @@ int evh_stream_homography_batch_resized(evh_ctx* c, const uint8_t* d_frames, int
                                         const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_resized: bad argument");
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return stream_batch(c, d_frames, 1, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nfeatures, ransac_thr,
-                      ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
+  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, src_w, src_h, w, h, nfeatures,
+                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
 }
 
 int evh_match_static_from_slots(evh_ctx* c, int cur_slot, int prev_slot, float* h_pts, int cap, int* h_count, int* h_status) {
@@ -986,8 +1013,9 @@ int evh_multi_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int n
     return evh_fail(c, EVH_ERR_INVALID, "evh_multi_stream_homography_batch: bad argument");
   if ((int64_t)nstreams * frames_per_stream > c->max_frames)
     return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  return stream_batch(c, d_frames, nstreams, frames_per_stream, w, h, w, h, channels, row_stride, frame_stride, nfeatures,
-                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
+  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), nstreams, frames_per_stream, w, h, w, h,
+                      nfeatures, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H,
+                      d_status);
 }
 
 int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
@@ -999,7 +1027,8 @@ int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, in
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "block needs more frame slots than max_frames");
   if (row_cap != c->kcap) return evh_fail(c, EVH_ERR_INVALID, "row_cap must equal evh_orb_capacity()");
   const int npairs = nframes - 1;
-  int rc = detect_match(c, d_frames, nframes, nframes, npairs, 1, w, h, w, h, channels, row_stride, frame_stride, nfeatures);
+  int rc = detect_match(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, nframes, npairs, 1, w, h, w, h,
+                        nfeatures);
   if (rc) return rc;
   EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
   { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, R, npairs); }
@@ -1053,7 +1082,8 @@ int evh_sift_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int 
   int rc = join_solve(c);
   if (rc) return rc;
   const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
-  if ((rc = ingest_level0(c, "evh_sift_detect_batch", d_frames, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nf)))
+  if ((rc = ingest_level0(c, "evh_sift_detect_batch", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w,
+                          src_h, w, h, nf)))
     return rc;
   c->nframes_resident = 0;            // level 0 was rewritten: the ORB results of an earlier call no longer match it
   return evh_launch_sift(c, nframes, w, h);
@@ -1129,9 +1159,9 @@ int evh_pair_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int npa
   if (mode != EVH_MODE_INDEPENDENT_PAIRS && mode != EVH_MODE_STREAM) return evh_fail(c, EVH_ERR_INVALID, "unknown mode");
   const int nframes = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 * npairs : npairs + 1;
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  return pairs_types(c, "evh_pair_homography_batch_types", d_frames, nframes, npairs, mode == EVH_MODE_STREAM, src_w, src_h, w, h,
-                     channels, row_stride, frame_stride, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf,
-                     force_max_iters, nullptr, nullptr, d_H, d_status);
+  return pairs_types(c, "evh_pair_homography_batch_types", packed_frames(d_frames, channels, row_stride, frame_stride), nframes,
+                     npairs, mode == EVH_MODE_STREAM, src_w, src_h, w, h, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters,
+                     ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
 }
 
 int evh_stream_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
@@ -1141,9 +1171,46 @@ int evh_stream_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int n
                                       double* d_H, int32_t* d_status) {
   if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_types: bad argument");
   if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return pairs_types(c, "evh_stream_homography_batch_types", d_frames, nframes, nframes - 1, 1, src_w, src_h, w, h, channels,
-                     row_stride, frame_stride, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf,
+  return pairs_types(c, "evh_stream_homography_batch_types", packed_frames(d_frames, channels, row_stride, frame_stride), nframes,
+                     nframes - 1, 1, src_w, src_h, w, h, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf,
                      force_max_iters, d_state_in, d_state_out, d_H, d_status);
+}
+
+// ---- decoded 4:2:0 planes as the source (video_processing.py:58,70) ----------------------------------------------------------
+int evh_yuv420_to_bgr(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int h, uint8_t* d_bgr, int64_t row_stride,
+                      int64_t frame_stride) {
+  if (int rc = check_yuv420(c, "evh_yuv420_to_bgr", src, nframes, w, h)) return rc;
+  if (!d_bgr) return evh_fail(c, EVH_ERR_INVALID, "evh_yuv420_to_bgr: d_bgr is NULL");
+  if (row_stride < (int64_t)w * 3 || (nframes > 1 && frame_stride < (h - 1) * row_stride + (int64_t)w * 3))
+    return evh_fail(c, EVH_ERR_INVALID, "evh_yuv420_to_bgr: output stride smaller than a row / frame");
+  return evh_launch_yuv420_to_bgr(c, *src, nframes, w, h, d_bgr, row_stride, frame_stride);
+}
+
+int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
+                                int nfeatures) {
+  return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);
+}
+
+int evh_stream_homography_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
+                                       int nfeatures, double ransac_thr, int ransac_max_iters, double ransac_conf,
+                                       int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
+                                       int32_t* d_status) {
+  if (!c || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_yuv420: bad argument");
+  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
+  return stream_batch(c, yuv420_frames(src), 1, nframes, src_w, src_h, w, h, nfeatures, ransac_thr, ransac_max_iters, ransac_conf,
+                      force_max_iters, d_state_in, d_state_out, d_H, d_status);
+}
+
+int evh_stream_homography_batch_types_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w,
+                                             int h, int nfeatures, const int32_t* h_types, int ntypes, double ransac_thr,
+                                             int ransac_max_iters, double ransac_conf, int force_max_iters,
+                                             const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
+  const char* who = "evh_stream_homography_batch_types_yuv420";
+  if (!c || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad argument");
+  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
+  return pairs_types(c, who, yuv420_frames(src), nframes, nframes - 1, 1, src_w, src_h, w, h, nfeatures,
+                     h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H,
+                     d_status);
 }
 
 
@@ -1162,7 +1229,8 @@ int evh_surf_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int 
   int rc = join_solve(c);
   if (rc) return rc;
   const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
-  if ((rc = ingest_level0(c, "evh_surf_detect_batch", d_frames, nframes, src_w, src_h, w, h, channels, row_stride, frame_stride, nf)))
+  if ((rc = ingest_level0(c, "evh_surf_detect_batch", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w,
+                          src_h, w, h, nf)))
     return rc;
   c->nframes_resident = 0;
   return evh_launch_surf(c, nframes, w, h, (float)hessian_threshold);

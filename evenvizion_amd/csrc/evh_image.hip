@@ -65,20 +65,67 @@ __global__ void k_resize_area_int(const uint8_t* __restrict__ src, int cn, int64
 // resized BGR image of video_processing.py:62,73 never exists in memory.
 __device__ __forceinline__ uint8_t gray_of(int b, int g, int r) { return (uint8_t)((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14); }
 
-__global__ __launch_bounds__(256) void k_ingest_area(const uint8_t* __restrict__ src, int cn, int64_t src_stride,
-                                                     int64_t src_img_stride, uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
+// The ingest kernels are templated on where a source pixel's channel bytes come from: SRC::row(img, y) hands out a row,
+// Row::px(x, v) the pixel's bytes v[0 .. channels).
+struct PackedSrc {       // rows of cn bytes per pixel (BGR or gray)
+  const uint8_t* p; int cn; int64_t stride, img_stride;
+  struct Row {
+    const uint8_t* r; int cn;
+    __device__ __forceinline__ void px(int x, int (&v)[3]) const {
+      const uint8_t* q = r + (int64_t)x * cn;
+#pragma unroll
+      for (int c = 0; c < 3; c++) if (c < cn) v[c] = q[c];
+    }
+  };
+  __device__ __forceinline__ int channels() const { return cn; }
+  __device__ __forceinline__ Row row(int img, int y) const { return {p + (int64_t)img * img_stride + (int64_t)y * stride, cn}; }
+};
+
+// yuv420p -> bgr24 as capture.read() delivers it (video_processing.py:58,70; EVCAP_BGR_SWSCALE_X86 of include/evcap.h,
+// SwsX86::px in capture/evcap_api.cpp): 13-bit BT.601 limited-range coefficients, arithmetic shifts, one saturation per
+// channel (the 16-bit saturations of the original never act).  The chroma terms are shared by the luma pixels of a sample.
+struct ChromaTerms { int b, g, r; };
+__device__ __forceinline__ ChromaTerms chroma_terms(int u, int v) {
+  const int cu = (u << 3) - 1024, cv = (v << 3) - 1024;
+  return {(cu * 16525) >> 16, ((cu * -3209) >> 16) + ((cv * -6660) >> 16), (cv * 13075) >> 16};
+}
+__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
+__device__ __forceinline__ void yuv_px(int y, const ChromaTerms& t, int (&v)[3]) {
+  const int Y = (((y << 3) - 128) * 9539) >> 16;
+  v[0] = sat8(Y + t.b); v[1] = sat8(Y + t.g); v[2] = sat8(Y + t.r);
+}
+struct Yuv420Src {       // 4:2:0 planes, chroma pixel stride cps = 1 (I420 / YV12) or 2 (NV12 / NV21)
+  const uint8_t* y; const uint8_t* cb; const uint8_t* cr;
+  int64_t ys, cs, yfs, cfs; int cps;
+  struct Row {
+    const uint8_t* y; const uint8_t* cb; const uint8_t* cr; int cps;
+    __device__ __forceinline__ void px(int x, int (&v)[3]) const {
+      const int cx = (x >> 1) * cps;
+      yuv_px(y[x], chroma_terms(cb[cx], cr[cx]), v);
+    }
+  };
+  __device__ __forceinline__ int channels() const { return 3; }
+  __device__ __forceinline__ Row row(int img, int yy) const {
+    const int64_t co = (int64_t)img * cfs + (int64_t)(yy >> 1) * cs;
+    return {y + (int64_t)img * yfs + (int64_t)yy * ys, cb + co, cr + co, cps};
+  }
+};
+
+template <class SRC>
+__global__ __launch_bounds__(256) void k_ingest_area(SRC src, uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
                                                      int dw, int dh, int dst_stride, AreaTabDev T) {
   const int img = blockIdx.z, dy = blockIdx.y;
   const int dx = blockIdx.x * blockDim.x + threadIdx.x;
   if (dx >= dw) return;
-  const uint8_t* S = src + (int64_t)img * src_img_stride;
+  const int cn = src.channels();
   const int x0 = T.xs[dx], xn = T.xcnt[dx], y0 = T.ys[dy], yn = T.ycnt[dy];
   float sum[3] = {0.f, 0.f, 0.f};
   for (int j = 0; j < yn; j++) {
-    const uint8_t* row = S + (int64_t)T.ysi[y0 + j] * src_stride;
+    const typename SRC::Row row = src.row(img, T.ysi[y0 + j]);
     float buf[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < xn; k++) {
-      const uint8_t* px = row + (int64_t)T.xsi[x0 + k] * cn;
+      int px[3] = {0, 0, 0};
+      row.px(T.xsi[x0 + k], px);
       const float a = T.xal[x0 + k];
 #pragma unroll
       for (int c = 0; c < 3; c++) if (c < cn) buf[c] = buf[c] + (float)px[c] * a;
@@ -93,20 +140,22 @@ __global__ __launch_bounds__(256) void k_ingest_area(const uint8_t* __restrict__
   pyr[(int64_t)img * pyr_frame_bytes + (int64_t)dy * dst_stride + dx] = cn == 3 ? gray_of(v[0], v[1], v[2]) : (uint8_t)v[0];
 }
 
-__global__ __launch_bounds__(256) void k_ingest_area_int(const uint8_t* __restrict__ src, int cn, int64_t src_stride,
-                                                         int64_t src_img_stride, uint8_t* __restrict__ pyr,
-                                                         int64_t pyr_frame_bytes, int dw, int dh, int dst_stride, int isx,
-                                                         int isy) {
+template <class SRC>
+__global__ __launch_bounds__(256) void k_ingest_area_int(SRC src, uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes, int dw,
+                                                         int dh, int dst_stride, int isx, int isy) {
   const int img = blockIdx.z, dy = blockIdx.y;
   const int dx = blockIdx.x * blockDim.x + threadIdx.x;
   if (dx >= dw) return;
-  const uint8_t* S = src + (int64_t)img * src_img_stride;
+  const int cn = src.channels();
   int sum[3] = {0, 0, 0};
   for (int j = 0; j < isy; j++) {
-    const uint8_t* row = S + (int64_t)(dy * isy + j) * src_stride + (int64_t)dx * isx * cn;
-    for (int i = 0; i < isx; i++)
+    const typename SRC::Row row = src.row(img, dy * isy + j);
+    for (int i = 0; i < isx; i++) {
+      int px[3] = {0, 0, 0};
+      row.px(dx * isx + i, px);
 #pragma unroll
-      for (int c = 0; c < 3; c++) if (c < cn) sum[c] += row[i * cn + c];
+      for (int c = 0; c < 3; c++) if (c < cn) sum[c] += px[c];
+    }
   }
   int v[3];
   const float scale = 1.f / (float)(isx * isy);
@@ -138,16 +187,6 @@ __device__ __forceinline__ LinAreaCoef lin_area_coef(int d, int ssize, double sc
   if (edge) { c.a0 = 2048; c.a1 = 0; }           // D[dx] = S[sx] * ONE beyond xmax
   return c;
 }
-__device__ __forceinline__ int lin_area_px(const uint8_t* S, int64_t stride, int cn, int c, int sw, int sh,
-                                           const LinAreaCoef& X, const LinAreaCoef& Y, int b0, int b1) {
-  const int y0 = min(Y.s, sh - 1), y1 = min(Y.s + 1, sh - 1);
-  const int x1 = min(X.s + 1, sw - 1);
-  const uint8_t* r0 = S + (int64_t)y0 * stride;
-  const uint8_t* r1 = S + (int64_t)y1 * stride;
-  const int h0 = r0[X.s * cn + c] * X.a0 + r0[x1 * cn + c] * X.a1;
-  const int h1 = r1[X.s * cn + c] * X.a0 + r1[x1 * cn + c] * X.a1;
-  return ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 0xFF;
-}
 // vertical coefficients: no edge substitution (the operator clips the ROWS instead)
 __device__ __forceinline__ void lin_area_beta(int dy, double scale, double inv, int& sy, int& b0, int& b1) {
   sy = (int)floor((double)dy * scale);
@@ -156,28 +195,114 @@ __device__ __forceinline__ void lin_area_beta(int dy, double scale, double inv, 
   b0 = min(max((int)rintf((1.f - f) * 2048.f), -32768), 32767);
   b1 = min(max((int)rintf(f * 2048.f), -32768), 32767);
 }
-template <bool INGEST>
-__global__ __launch_bounds__(256) void k_resize_linear_area(const uint8_t* __restrict__ src, int cn, int sw, int sh,
-                                                            int64_t src_stride, int64_t src_img_stride,
-                                                            uint8_t* __restrict__ dst, int dw, int dh, int64_t dst_stride,
-                                                            int64_t dst_img_stride, double scale_x, double inv_x,
-                                                            double scale_y, double inv_y) {
+template <bool INGEST, class SRC>
+__global__ __launch_bounds__(256) void k_resize_linear_area(SRC src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh,
+                                                            int64_t dst_stride, int64_t dst_img_stride, double scale_x,
+                                                            double inv_x, double scale_y, double inv_y) {
   const int img = blockIdx.z, dy = blockIdx.y;
   const int dx = blockIdx.x * blockDim.x + threadIdx.x;
   if (dx >= dw) return;
-  const uint8_t* S = src + (int64_t)img * src_img_stride;
+  const int cn = src.channels();
   const LinAreaCoef X = lin_area_coef(dx, sw, scale_x, inv_x);
-  LinAreaCoef Y; int b0, b1;
-  lin_area_beta(dy, scale_y, inv_y, Y.s, b0, b1);
-  Y.s = min(max(Y.s, 0), sh - 1);
+  int sy, b0, b1;
+  lin_area_beta(dy, scale_y, inv_y, sy, b0, b1);
+  sy = min(max(sy, 0), sh - 1);
+  const typename SRC::Row r0 = src.row(img, min(sy, sh - 1)), r1 = src.row(img, min(sy + 1, sh - 1));
+  const int x1 = min(X.s + 1, sw - 1);
+  int p00[3] = {0, 0, 0}, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
+  r0.px(X.s, p00); r0.px(x1, p01); r1.px(X.s, p10); r1.px(x1, p11);
   int v[3] = {0, 0, 0};
 #pragma unroll
-  for (int c = 0; c < 3; c++) if (c < cn) v[c] = lin_area_px(S, src_stride, cn, c, sw, sh, X, Y, b0, b1);
+  for (int c = 0; c < 3; c++) if (c < cn) {
+    const int h0 = p00[c] * X.a0 + p01[c] * X.a1;
+    const int h1 = p10[c] * X.a0 + p11[c] * X.a1;
+    v[c] = ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 0xFF;
+  }
   uint8_t* D = dst + (int64_t)img * dst_img_stride + (int64_t)dy * dst_stride;
   if (INGEST) D[dx] = cn == 3 ? gray_of(v[0], v[1], v[2]) : (uint8_t)v[0];
   else
 #pragma unroll
     for (int c = 0; c < 3; c++) if (c < cn) D[dx * cn + c] = (uint8_t)v[c];
+}
+
+// The stand-alone converter (evh_yuv420_to_bgr) and, with GRAY, level 0 of frames that are not resized.  A streaming
+// kernel: one thread owns 16 luma pixels of the TWO rows that share a chroma row, so chroma is fetched once -- per row one
+// 16-byte luma load, 8 + 8 chroma bytes (16 + 16 interleaved), three 16-byte BGR stores (one 16-byte gray store).  `vec`:
+// 0 = bytewise everywhere (some pointer or stride is not aligned for the wide form), 1 = planar chroma, 2 = interleaved
+// chroma with Cb first, 3 = with Cr first; runs cut by the right edge are always bytewise.  Bytes past a row's w pixels
+// are neither read nor written.
+#define YUV_RUN 16
+template <bool GRAY>
+__global__ __launch_bounds__(256) void k_yuv420_rows(Yuv420Src src, int w, int h, uint8_t* __restrict__ dst, int64_t dst_stride,
+                                                     int64_t dst_img_stride, int runs_per_row, int nruns, int vec) {
+  const int img = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nruns) return;
+  const int ry = t / runs_per_row, x = (t - ry * runs_per_row) * YUV_RUN;
+  const int n = min(YUV_RUN, w - x), nrows = min(2, h - 2 * ry);
+  const bool wide = vec != 0 && n == YUV_RUN;
+  const Yuv420Src::Row R0 = src.row(img, 2 * ry);
+  uint8_t u8[YUV_RUN / 2], v8[YUV_RUN / 2];
+  if (wide && vec == 1) {
+    const uint2 a = *reinterpret_cast<const uint2*>(R0.cb + (x >> 1)), b = *reinterpret_cast<const uint2*>(R0.cr + (x >> 1));
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      u8[k] = (uint8_t)(a.x >> (8 * k)); u8[4 + k] = (uint8_t)(a.y >> (8 * k));
+      v8[k] = (uint8_t)(b.x >> (8 * k)); v8[4 + k] = (uint8_t)(b.y >> (8 * k));
+    }
+  } else if (wide) {
+    const uint4 a = *reinterpret_cast<const uint4*>((vec == 2 ? R0.cb : R0.cr) + x);
+    const uint32_t q[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint8_t lo = (uint8_t)(q[k >> 1] >> (16 * (k & 1))), hi = (uint8_t)(q[k >> 1] >> (16 * (k & 1) + 8));
+      u8[k] = vec == 2 ? lo : hi; v8[k] = vec == 2 ? hi : lo;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < YUV_RUN / 2; k++) {
+      const bool in = 2 * k < n;
+      u8[k] = in ? R0.cb[((x >> 1) + k) * R0.cps] : 0; v8[k] = in ? R0.cr[((x >> 1) + k) * R0.cps] : 0;
+    }
+  }
+  ChromaTerms T[YUV_RUN / 2];
+#pragma unroll
+  for (int k = 0; k < YUV_RUN / 2; k++) T[k] = chroma_terms(u8[k], v8[k]);
+  for (int r = 0; r < nrows; r++) {
+    const uint8_t* yrow = R0.y + (int64_t)r * src.ys + x;
+    uint8_t* D = dst + (int64_t)img * dst_img_stride + (int64_t)(2 * ry + r) * dst_stride + (int64_t)x * (GRAY ? 1 : 3);
+    uint8_t y8[YUV_RUN];
+    if (wide) {
+      const uint4 a = *reinterpret_cast<const uint4*>(yrow);
+      const uint32_t q[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int k = 0; k < YUV_RUN; k++) y8[k] = (uint8_t)(q[k >> 2] >> (8 * (k & 3)));
+    } else {
+#pragma unroll
+      for (int k = 0; k < YUV_RUN; k++) y8[k] = k < n ? yrow[k] : 0;
+    }
+    uint32_t out[GRAY ? YUV_RUN / 4 : 3 * YUV_RUN / 4];
+#pragma unroll
+    for (int k = 0; k < (GRAY ? YUV_RUN / 4 : 3 * YUV_RUN / 4); k++) out[k] = 0;
+#pragma unroll
+    for (int k = 0; k < YUV_RUN; k++) {
+      int p[3];
+      yuv_px(y8[k], T[k >> 1], p);
+      if (GRAY) out[k >> 2] |= (uint32_t)gray_of(p[0], p[1], p[2]) << (8 * (k & 3));
+      else
+#pragma unroll
+        for (int c = 0; c < 3; c++) out[(3 * k + c) >> 2] |= (uint32_t)p[c] << (8 * ((3 * k + c) & 3));
+    }
+    if (wide) {
+#pragma unroll
+      for (int k = 0; k < (GRAY ? 1 : 3); k++)
+        reinterpret_cast<uint4*>(D)[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
+    } else {
+      const int nb = n * (GRAY ? 1 : 3);
+#pragma unroll
+      for (int k = 0; k < YUV_RUN * (GRAY ? 1 : 3); k++) if (k < nb) D[k] = (uint8_t)(out[k >> 2] >> (8 * (k & 3)));
+    }
+  }
 }
 
 // N3: fixed-plane coordinate field of processing_visualization.py:407-408 -- every pixel (x, y) of
@@ -299,9 +424,9 @@ int evh_launch_resize_area(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, i
   const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;
   const double scale_x = 1. / inv_x, scale_y = 1. / inv_y;
   if (scale_x < 1 || scale_y < 1) {          // enlarging: the operator's bilinear emulation of INTER_AREA
-    hipLaunchKernelGGL(k_resize_linear_area<false>, dim3((dw + 255) / 256, dh, nimg), dim3(256), 0, c->stream, d_src, cn, sw,
-                       sh, src_stride, src_img_stride, d_dst, dw, dh, dst_stride, dst_img_stride, scale_x, inv_x, scale_y,
-                       inv_y);
+    hipLaunchKernelGGL((k_resize_linear_area<false, PackedSrc>), dim3((dw + 255) / 256, dh, nimg), dim3(256), 0, c->stream,
+                       PackedSrc{d_src, cn, src_stride, src_img_stride}, sw, sh, d_dst, dw, dh, dst_stride, dst_img_stride,
+                       scale_x, inv_x, scale_y, inv_y);
     EVH_HIP(c, hipGetLastError());
     return EVH_SUCCESS;
   }
@@ -374,35 +499,74 @@ static int area_tables(evh_ctx* c, int sw, int sh, int dw, int dh, double scale_
 }
 
 // level 0 of every frame straight from the source frames (k_ingest_area* when shrinking, k_resize_linear_area when enlarging)
-int evh_launch_ingest_level0(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, int sh, int cn, int64_t src_stride,
-                             int64_t src_img_stride, int dw, int dh) {
+template <class SRC>
+static int launch_ingest(evh_ctx* c, const SRC& src, int nimg, int sw, int sh, int dw, int dh) {
   const EvhLevel& L = c->g.lv[0];
-  const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
   const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;      // the operator's own arithmetic
   const double sx = 1. / inv_x, sy = 1. / inv_y;
-  (void)scale_x; (void)scale_y;
   dim3 grid((dw + 255) / 256, dh, nimg);
-  c->level1_fused = false;
   if (sx < 1 || sy < 1) {                    // enlarging: bilinear emulation, gray weights on the rounded channels
-    hipLaunchKernelGGL(k_resize_linear_area<true>, grid, dim3(256), 0, c->stream, d_src, cn, sw, sh, src_stride,
-                       src_img_stride, c->d_pyr + L.off, dw, dh, (int64_t)L.stride, c->g.pyr_frame_bytes, sx, inv_x, sy, inv_y);
+    hipLaunchKernelGGL((k_resize_linear_area<true, SRC>), grid, dim3(256), 0, c->stream, src, sw, sh, c->d_pyr + L.off, dw, dh,
+                       (int64_t)L.stride, c->g.pyr_frame_bytes, sx, inv_x, sy, inv_y);
     EVH_HIP(c, hipGetLastError());
     return EVH_SUCCESS;
   }
   const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
   if (std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16) {
-    hipLaunchKernelGGL(k_ingest_area_int, grid, dim3(256), 0, c->stream, d_src, cn, src_stride, src_img_stride, c->d_pyr + L.off,
-                       c->g.pyr_frame_bytes, dw, dh, L.stride, isx, isy);
+    hipLaunchKernelGGL(k_ingest_area_int<SRC>, grid, dim3(256), 0, c->stream, src, c->d_pyr + L.off, c->g.pyr_frame_bytes, dw,
+                       dh, L.stride, isx, isy);
     EVH_HIP(c, hipGetLastError());
     return EVH_SUCCESS;
   }
   AreaTabDev T;
   int rc = area_tables(c, sw, sh, dw, dh, sx, sy, T);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_ingest_area, grid, dim3(256), 0, c->stream, d_src, cn, src_stride, src_img_stride, c->d_pyr + L.off,
-                     c->g.pyr_frame_bytes, dw, dh, L.stride, T);
+  hipLaunchKernelGGL(k_ingest_area<SRC>, grid, dim3(256), 0, c->stream, src, c->d_pyr + L.off, c->g.pyr_frame_bytes, dw, dh,
+                     L.stride, T);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;
+}
+
+static Yuv420Src yuv420_src(const evh_yuv420& s) {
+  return {s.d_y, s.d_cb, s.d_cr, s.y_stride, s.c_stride, s.y_frame_stride, s.c_frame_stride, s.c_pixel_stride};
+}
+
+// k_yuv420_rows over nimg frames: BGR rows (GRAY = false) or gray rows at dst
+template <bool GRAY>
+static int launch_yuv420_rows(evh_ctx* c, const evh_yuv420& s, int nimg, int w, int h, uint8_t* dst, int64_t dst_stride,
+                              int64_t dst_img_stride) {
+  // the wide form needs 16-byte luma loads and stores, 8-byte (planar) or 16-byte (interleaved pair) chroma loads; the
+  // frame strides of a single frame are never used
+  const uintptr_t yfs = nimg > 1 ? (uintptr_t)s.y_frame_stride : 0, cfs = nimg > 1 ? (uintptr_t)s.c_frame_stride : 0;
+  const uintptr_t dfs = nimg > 1 ? (uintptr_t)dst_img_stride : 0;
+  const uintptr_t a16 = (uintptr_t)s.d_y | (uintptr_t)s.y_stride | yfs | (uintptr_t)dst | (uintptr_t)dst_stride | dfs;
+  const uintptr_t ac = (uintptr_t)s.c_stride | cfs;
+  int vec = 0;
+  if (!(a16 & 15)) {
+    if (s.c_pixel_stride == 1 && !(((uintptr_t)s.d_cb | (uintptr_t)s.d_cr | ac) & 7)) vec = 1;
+    else if (s.c_pixel_stride == 2 && s.d_cr == s.d_cb + 1 && !(((uintptr_t)s.d_cb | ac) & 15)) vec = 2;
+    else if (s.c_pixel_stride == 2 && s.d_cb == s.d_cr + 1 && !(((uintptr_t)s.d_cr | ac) & 15)) vec = 3;
+  }
+  const int runs_per_row = (w + YUV_RUN - 1) / YUV_RUN, nruns = runs_per_row * ((h + 1) / 2);
+  hipLaunchKernelGGL(k_yuv420_rows<GRAY>, dim3((nruns + 255) / 256, nimg), dim3(256), 0, c->stream, yuv420_src(s), w, h, dst,
+                     dst_stride, dst_img_stride, runs_per_row, nruns, vec);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w, int h, uint8_t* d_dst, int64_t dst_stride,
+                             int64_t dst_img_stride) {
+  return launch_yuv420_rows<false>(c, src, nimg, w, h, d_dst, dst_stride, dst_img_stride);
+}
+
+int evh_launch_ingest_level0(evh_ctx* c, const EvhFrames& src, int nimg, int sw, int sh, int dw, int dh) {
+  c->level1_fused = false;
+  if (!src.yuv) return launch_ingest(c, PackedSrc{src.packed, src.channels, src.row_stride, src.frame_stride}, nimg, sw, sh, dw, dh);
+  if (sw == dw && sh == dh) {          // no resize: converted and weighted in one pass, level 1 by the ordinary pyramid kernel
+    const EvhLevel& L = c->g.lv[0];
+    return launch_yuv420_rows<true>(c, *src.yuv, nimg, dw, dh, c->d_pyr + L.off, L.stride, c->g.pyr_frame_bytes);
+  }
+  return launch_ingest(c, yuv420_src(*src.yuv), nimg, sw, sh, dw, dh);
 }
 
 int evh_launch_superposition_scan(evh_ctx* c, const double* d_H, int n, double* d_out) {

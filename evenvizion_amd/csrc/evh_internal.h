@@ -47,6 +47,16 @@ struct EvhSiftGeom {
   int64_t frame_floats, tmp_floats;
 };
 
+// the frames an entry was handed: packed rows of `channels` bytes per pixel, or (yuv) decoded 4:2:0 planes
+struct EvhFrames {
+  const uint8_t* packed = nullptr; int channels = 0; int64_t row_stride = 0, frame_stride = 0;
+  const evh_yuv420* yuv = nullptr;
+};
+inline EvhFrames packed_frames(const uint8_t* d, int channels, int64_t row_stride, int64_t frame_stride) {
+  EvhFrames F; F.packed = d; F.channels = channels; F.row_stride = row_stride; F.frame_stride = frame_stride; return F;
+}
+inline EvhFrames yuv420_frames(const evh_yuv420* src) { EvhFrames F; F.channels = 3; F.yuv = src; return F; }
+
 // per-pair working buffers of the matching / RANSAC stages (max_pairs = max_frames, row stride `cap` rows per pair)
 struct EvhPairBufs {
   int cap = 0;
@@ -119,6 +129,7 @@ struct evh_ctx {
   size_t scan_ws_bytes = 0;
   int* d_area_tab = nullptr; size_t area_tab_bytes = 0;     // INTER_AREA tables of the last ingest geometry (evh_launch_ingest_level0)
   int64_t area_key = -1; int area_nx = 0, area_ny = 0;
+  uint8_t* d_yuv_bgr = nullptr; size_t yuv_bgr_bytes = 0;   // BGR frames of evh_stream_homography_batch_types_yuv420's chunk
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv
   int order_mode = 1;             // EVH_ORDER_OPENCV
@@ -230,8 +241,9 @@ int grow(evh_ctx* c, T** p, size_t* bytes, size_t need) {
 // ---- kernel launchers (each enqueues on ctx->stream) ----
 int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int channels, int64_t row_stride,
                            int64_t frame_stride);
-int evh_launch_ingest_level0(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, int sh, int cn, int64_t src_stride,
-                             int64_t src_img_stride, int dw, int dh);
+int evh_launch_ingest_level0(evh_ctx* c, const EvhFrames& src, int nimg, int sw, int sh, int dw, int dh);
+int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w, int h, uint8_t* d_dst, int64_t dst_stride,
+                             int64_t dst_img_stride);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);

@@ -8,6 +8,10 @@ uploading chunk i+1 overlap the GPU work on chunk i), uploads a chunk once, and 
 pairs of the chunk in parallel, and the final RANSAC as the sequential scan the running superposition requires
 (utils.py:351-358, video_processing.py:102-103).  Consecutive chunks overlap by one frame and carry
 {H_sup, H_prev} on the device.
+
+With ingest="auto" / "yuv420" a capture that can hand over the decoder's own 4:2:0 planes (read_yuv420_into) is read that way: 1.5 bytes per pixel are
+staged and uploaded instead of 3, and the BGR conversion of capture.read() (video_processing.py:58,70) happens inside the
+ingest kernel (evh_stream_homography_batch_yuv420).  The dictionary is the same, bit for bit.
 """
 import logging
 
@@ -26,9 +30,38 @@ def resized_shape(frame_shape, resize_width):
     return int(resize_width), int(h0 * r)
 
 
+def _first_planes(capture, ingest):
+    """The first frame of `capture` as packed I420 bytes, or None when the frames are to be read as BGR.  Planes are taken
+    when the capture offers read_yuv420_into(y, cb, cr), declares the conversion the device implements (bgr_mode ==
+    BGR_SWSCALE_X86) and its first plane read succeeds -- a capture refuses, by raising capture.CaptureError, BEFORE it consumes a frame (libevcap: odd crop
+    offset), so the BGR path then starts from the same first frame.  -> (packed uint8 array or None, w, h)."""
+    from ..capture import BGR_SWSCALE_X86, CaptureError
+    from .._lib import yuv420_size, yuv420_views
+    able = callable(getattr(capture, "read_yuv420_into", None)) and getattr(capture, "bgr_mode", None) == BGR_SWSCALE_X86
+    if ingest == "bgr" or not able:
+        if ingest == "yuv420":
+            raise ValueError("ingest='yuv420': the capture does not deliver 4:2:0 planes in the swscale-x86 conversion")
+        return None, 0, 0
+    w, h = int(capture.width), int(capture.height)
+    packed = np.empty((1, yuv420_size(w, h)[0]), np.uint8)
+    y, cb, cr = yuv420_views(packed, w, h)
+    try:
+        ok = capture.read_yuv420_into(y[0], cb[0], cr[0])
+    except CaptureError as e:               # the capture's refusal: nothing was consumed; anything else is a bug and propagates
+        if ingest == "yuv420":
+            raise ValueError("ingest='yuv420': the capture refused to deliver planes (%s)" % e)
+        logging.info("capture refused 4:2:0 planes (%s): reading BGR frames", e)
+        return None, 0, 0
+    if not ok:
+        raise ValueError("Problem with video! Can't read first frame")
+    return packed[0], w, h
+
+
 def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_processing=True,
-                        nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES, features_type_list=None):
+                        nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES, features_type_list=None, ingest="bgr"):
     """capture: anything with read() -> (bool, BGR uint8 frame) (cv2.VideoCapture duck type).
+    ingest: "bgr" (always read(); the default until the plane path's end-to-end rates have been measured against it, see
+    DESIGN.md 3a), "auto" (planes when the capture can deliver them, see _first_planes), "yuv420" (planes or ValueError).
     features_type_list: the list the reference hands to FrameProcessing (frame_processing.py:37-40), e.g. ["SIFT", "ORB"];
     None = frame_processing.DEFAULT_FEATURES = the reference's own default ["SURF", "SIFT", "ORB"]; the north-star hot path
     is features_type_list=["ORB"] (one fused ORB pipeline, evh_stream_homography_batch_resized)."""
@@ -36,13 +69,17 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     if matching_path:
         raise NotImplementedError("matching visualisation (draw_matches + imwrite) is outside the MI355X hot path; "
                                   "call with matching_path=None")
-    success, first = capture.read()
-    if not success:
-        raise ValueError("Problem with video! Can't read first frame")
-    first = np.ascontiguousarray(first, np.uint8)
-    h0, w0 = first.shape[:2]
-    cn = 1 if first.ndim == 2 else first.shape[2]
-    dw, dh = resized_shape(first.shape, resize_width)
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    first, w0, h0 = _first_planes(capture, ingest)
+    planes = first is not None
+    if not planes:
+        success, first = capture.read()
+        if not success:
+            raise ValueError("Problem with video! Can't read first frame")
+        first = np.ascontiguousarray(first, np.uint8)
+        h0, w0 = first.shape[:2]
+    dw, dh = resized_shape((h0, w0), resize_width)
     # one staging buffer (pinned host / device) is capped in bytes: 4K BGR frames give 21-frame chunks, not 64
     from .frame_processing import DEFAULT_FEATURES
     features = list(features_type_list or DEFAULT_FEATURES)
@@ -74,7 +111,13 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     frame_no = [1]          # 1-based index of the newest frame already paired
 
     def launch(c, jb, nb, with_state):
-        if multi:       # frame_processing.py:91-104 over the type list: evh_stream_homography_batch_types
+        if planes:      # the same two entries with the decoder's planes as the source
+            kw = dict(state_in=state if with_state else None, state_out=state, nfeatures=nfeatures, resize_to=(dw, dh))
+            if multi:
+                c.stream_homography_batch_types_yuv420(devbuf[jb][:nb], (w0, h0), H_dev[jb], st_dev[jb], features, **kw)
+            else:
+                c.stream_homography_batch_yuv420(devbuf[jb][:nb], (w0, h0), H_dev[jb], st_dev[jb], **kw)
+        elif multi:       # frame_processing.py:91-104 over the type list: evh_stream_homography_batch_types
             c.stream_homography_batch_types(devbuf[jb][:nb], H_dev[jb], st_dev[jb], features,
                                             state_in=state if with_state else None, state_out=state, nfeatures=nfeatures,
                                             resize_to=(dw, dh))
@@ -156,6 +199,21 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
                                          "status %d)" % (fno, int(sts[k])))
             homography_dict[fno] = {"H": Hs[k].tolist()}
 
+    def read_into(slot):
+        """The capture's next frame into `slot`, a frame of the pinned staging chunk: the one host copy."""
+        if planes:
+            from .._lib import yuv420_views
+            y, cb, cr = yuv420_views(slot[None], w0, h0)
+            return bool(capture.read_yuv420_into(y[0], cb[0], cr[0]))
+        ok, frame = capture.read()
+        if not ok:
+            return False
+        frame = np.asarray(frame, np.uint8)
+        if frame.shape != first.shape:
+            raise ValueError("frame %d has shape %s, the first frame %s" % (frame_no[0] + n, frame.shape, first.shape))
+        slot[...] = frame
+        return True
+
     j, n = 0, 1
     host_np[0][0] = first
     have_state = False
@@ -164,14 +222,9 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     try:
         while True:
             while n < chunk_frames and not exhausted:
-                ok, frame = capture.read()
-                if not ok:
+                if not read_into(host_np[j][n]):
                     exhausted = True
                     break
-                frame = np.asarray(frame, np.uint8)
-                if frame.shape != first.shape:
-                    raise ValueError("frame %d has shape %s, the first frame %s" % (frame_no[0] + n, frame.shape, first.shape))
-                host_np[j][n] = frame                  # the one host copy: straight into pinned memory
                 n += 1
             launched = None
             if n >= 2:

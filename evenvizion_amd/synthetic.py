@@ -4,7 +4,8 @@ There is no video decoder in the image (no cv2 / ffmpeg), so every workload -- t
 on frames generated here: a piecewise-constant multi-scale block texture (dense FAST corners at every
 octave), frame B = inverse-bilinear warp of the canvas by a known H_true plus Gaussian noise.
 `SyntheticCapture` duck-types cv2.VideoCapture (`read() -> (bool, BGR uint8 frame)`), which is all that
-get_homography_dict needs (reference: evenvizion/processing/video_processing.py:58,70).
+get_homography_dict needs (reference: evenvizion/processing/video_processing.py:58,70).  `SyntheticYuvCapture` is the
+same over decoded 4:2:0 planes, for the plane path (`read_yuv420_into`).
 """
 import numpy as np
 
@@ -152,3 +153,58 @@ class SyntheticCapture:
         f = self._frames[self._i]
         self._i += 1
         return True, f
+
+
+def yuv420_to_bgr_host(y, cb, cr):
+    """The BGR frame capture.read() returns for decoded planes y u8[h,w], cb / cr u8[(h+1)//2, (w+1)//2]
+    (video_processing.py:58,70): libswscale's unscaled yuv420p -> bgr24 conversion as an x86-64 build computes it
+    (EVCAP_BGR_SWSCALE_X86, SwsX86::px in capture/evcap_api.cpp), stated in numpy.  All shifts are arithmetic; the chroma
+    sample of luma pixel (x, y) is (x >> 1, y >> 1).  -> u8[h,w,3]."""
+    y = np.asarray(y); h, w = y.shape
+    u = np.repeat(np.repeat(np.asarray(cb), 2, axis=0), 2, axis=1)[:h, :w].astype(np.int32)
+    v = np.repeat(np.repeat(np.asarray(cr), 2, axis=0), 2, axis=1)[:h, :w].astype(np.int32)
+    Y = (((y.astype(np.int32) << 3) - 128) * 9539) >> 16
+    cu = (u << 3) - 1024
+    cv = (v << 3) - 1024
+    b = Y + ((cu * 16525) >> 16)
+    g = Y + ((cu * -3209) >> 16) + ((cv * -6660) >> 16)
+    r = Y + ((cv * 13075) >> 16)
+    return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
+
+
+def chroma_for(rng, gray, amplitude=48, cell=16):
+    """Smooth, non-constant chroma planes for a gray frame u8[h,w]: 128 + a nearest-upsampled U{-amplitude..amplitude}
+    grid with cells of `cell` chroma samples.  -> (cb, cr) u8[(h+1)//2, (w+1)//2]."""
+    h, w = gray.shape
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    out = []
+    for _ in range(2):
+        g = rng.integers(-amplitude, amplitude + 1, size=(-(-ch // cell), -(-cw // cell)), dtype=np.int32)
+        out.append((128 + np.repeat(np.repeat(g, cell, axis=0), cell, axis=1)[:ch, :cw]).astype(np.uint8))
+    return out[0], out[1]
+
+
+class SyntheticYuvCapture:
+    """Duck-type of evenvizion_amd.capture.VideoCapture over an in-memory list of (y, cb, cr) plane triples: read() returns
+    the frame as capture.read() would (yuv420_to_bgr_host), read_yuv420_into() the planes themselves."""
+    bgr_mode = 0        # capture.BGR_SWSCALE_X86: the conversion read() applies
+
+    def __init__(self, planes):
+        self._planes = planes
+        self._i = 0
+        self.height, self.width = planes[0][0].shape if len(planes) else (0, 0)
+
+    def read(self):
+        if self._i >= len(self._planes):
+            return False, None
+        f = yuv420_to_bgr_host(*self._planes[self._i])
+        self._i += 1
+        return True, f
+
+    def read_yuv420_into(self, y, cb, cr):
+        if self._i >= len(self._planes):
+            return False
+        sy, scb, scr = self._planes[self._i]
+        y[...] = sy; cb[...] = scb; cr[...] = scr
+        self._i += 1
+        return True

@@ -56,7 +56,9 @@ int evcap_set_honour_edit_list(evcap* c, int on);
 /* capture.read() -- video_processing.py:58,70.  Writes the next frame in presentation order as 8-bit BGR, rows of
  * width*3 bytes at `stride`.  Returns EVCAP_OK, EVCAP_EOF or an error. */
 int evcap_read_bgr(evcap* c, uint8_t* dst, int64_t stride);
-/* The same frame as planar 4:2:0 (Y width x height, Cb/Cr ((width+1)/2) x ((height+1)/2)); for tests. */
+/* The same frame as planar 4:2:0 (Y width x height, Cb/Cr ((width+1)/2) x ((height+1)/2)), written straight into the
+ * caller's planes: the source of libevhip's evh_*_yuv420 entries.  EVCAP_ERR_INVALID, before a picture is taken from the
+ * decoder (no frame is lost), when the stream's crop offset is odd. */
 int evcap_read_yuv420(evcap* c, uint8_t* y, int64_t ystride, uint8_t* cb, uint8_t* cr, int64_t cstride);
 /* Picture order count, decode index and slice type (0 P, 1 B, 2 I) of the frame most recently returned. */
 int evcap_last_frame_info(evcap* c, int* poc, int* decode_index, int* slice_type);

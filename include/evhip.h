@@ -18,6 +18,8 @@
  *   evh_surf_detect_batch         cv2.xfeatures2d.SURF_create(extended=1, hessianThreshold=400).detectAndCompute   frame_processing.py:65-67
  *   evh_match_knn2_l2f32          knnMatch on float32[N,128] descriptors            matching.py:102-108
  *   evh_*_homography_batch_types  concatenate_all_features_types over a type list   frame_processing.py:91-104
+ *   evh_yuv420_to_bgr             the yuv420p -> bgr24 conversion inside cv2.VideoCapture.read()   video_processing.py:58,70
+ *   evh_*_yuv420                  capture.read() + imutils.resize + the entry of the same name without the suffix
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -355,6 +357,53 @@ int evh_stream_homography_batch_types(evh_ctx* ctx, const uint8_t* d_frames, int
                                       const int32_t* h_types, int ntypes, double ransac_thr, int ransac_max_iters,
                                       double ransac_conf, int force_max_iters, const double* d_state_in,
                                       double* d_state_out, double* d_H, int32_t* d_status);
+
+/* ---- decoded 4:2:0 planes as the source (video_processing.py:58,70: what capture.read() converts to BGR) ---------------- */
+/* One description for every common 8-bit 4:2:0 layout.  Luma is w x h, both chroma planes are ((w+1)/2) x ((h+1)/2) (odd
+ * sizes are legal); the chroma sample of luma pixel (x, y) is (x >> 1, y >> 1).  I420 / YV12: c_pixel_stride = 1, three
+ * planes.  NV12: c_pixel_stride = 2 and d_cr = d_cb + 1 (NV21: d_cb = d_cr + 1).  All pointers are DEVICE pointers, strides
+ * are in bytes.  A packed I420 frame [w*h | cw*ch | cw*ch] is y_stride = w, c_stride = cw, both frame strides =
+ * w*h + 2*cw*ch.  Refused with EVH_ERR_INVALID: a NULL plane, c_pixel_stride other than 1 or 2, a stride smaller than
+ * the row / frame it steps over.                                                                                        */
+typedef struct evh_yuv420 {
+  const uint8_t* d_y;
+  const uint8_t* d_cb;
+  const uint8_t* d_cr;
+  int64_t y_stride, c_stride;               /* row strides                                  */
+  int64_t y_frame_stride, c_frame_stride;   /* frame strides (ignored when nframes == 1)    */
+  int32_t c_pixel_stride;                   /* 1 (planar) or 2 (interleaved chroma)         */
+} evh_yuv420;
+/* The BGR bytes cv2.VideoCapture.read() hands to video_processing.py:58,70 for a decoded picture: libswscale's unscaled
+ * yuv420p -> bgr24 converter as an x86-64 build computes it (EVCAP_BGR_SWSCALE_X86 of include/evcap.h; BT.601 limited
+ * range, 13-bit coefficients), per pixel with arithmetic shifts:
+ *     Y = (((y << 3) - 128) * 9539) >> 16;  cu = (u << 3) - 1024;  cv = (v << 3) - 1024
+ *     B = sat8(Y + ((cu * 16525) >> 16));  G = sat8(Y + ((cu * -3209) >> 16) + ((cv * -6660) >> 16));  R = sat8(Y + ((cv * 13075) >> 16))
+ * nframes frames of w x h -> packed BGR at d_bgr (rows of w*3 bytes at row_stride, frames at frame_stride; bytes between
+ * rows are not written).  Does not synchronise.
+ * Speed, not results, depends on alignment: the converter (and level 0 of evh_*_yuv420 when (w, h) == (src_w, src_h)) moves
+ * 16 bytes per load / store when d_y, y_stride, d_bgr and row_stride are multiples of 16 and the chroma side is too --
+ * planar: d_cb, d_cr, c_stride multiples of 8; interleaved: the lower of d_cb / d_cr (they must be adjacent bytes) and
+ * c_stride multiples of 16 -- together with the frame strides when nframes > 1; anything else takes a bytewise form of the
+ * same kernel.  The resizing ingests read single bytes and have no such requirement.                                    */
+int evh_yuv420_to_bgr(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, uint8_t* d_bgr, int64_t row_stride,
+                      int64_t frame_stride);
+/* evh_orb_detect_batch_resized with the planes as the source, fused: level 0 comes straight from the planes (each source
+ * pixel converted as above, then INTER_AREA per channel and the gray weights exactly as for BGR frames); neither the
+ * full-size BGR frame nor the resized one exists in memory.  (w, h) == (src_w, src_h): no resize.                        */
+int evh_orb_detect_batch_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
+                                int nfeatures);
+/* evh_stream_homography_batch_resized on that ingest: what get_homography_dict runs per chunk of a capture that delivers
+ * planes (half the bytes of BGR over the host link).                                                                     */
+int evh_stream_homography_batch_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
+                                       int nfeatures, double ransac_thr, int ransac_max_iters, double ransac_conf,
+                                       int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
+                                       int32_t* d_status);
+/* evh_stream_homography_batch_types on planes: the chunk is converted once (evh_yuv420_to_bgr) into a workspace the
+ * context owns, then takes the BGR path of every detector in the list.                                                   */
+int evh_stream_homography_batch_types_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int src_w, int src_h, int w,
+                                             int h, int nfeatures, const int32_t* h_types, int ntypes, double ransac_thr,
+                                             int ransac_max_iters, double ransac_conf, int force_max_iters,
+                                             const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status);
 
 #ifdef __cplusplus
 }

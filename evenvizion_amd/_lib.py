@@ -65,6 +65,7 @@ SIGNATURES = {
     "evh_find_homography_ransac": (_i, [_vp, _vp, _i, _d, _i, _d, _vp, _vp, _pi, _vp]),
     "evh_find_homography_ransac_fixed": (_i, [_vp, _vp, _i, _d, _i, _d, _vp, _vp, _pi, _vp]),
     "evh_static_filter": (_i, [_vp, _vp, _vp, _i, _vp, _pi]),
+    "evh_remove_double_matching": (_i, [_vp, _vp, _i, _vp, _pi]),
     "evh_pair_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i, _d, _i, _d, _i, _vp, _vp]),
     "evh_stream_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_multi_stream_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -374,6 +375,14 @@ class Context:
         H = np.ascontiguousarray(H, np.float64).reshape(9)
         n = C.c_int()
         self._check(self.lib.evh_static_filter(self.h, _hp(H), pts.data_ptr(), pts.shape[0], out.data_ptr(), C.byref(n)))
+        return n.value
+
+    def remove_double_matching(self, pts, out):
+        """pts, out: CUDA float32 [n,4] rows (ax, ay, bx, by); -> rows written to out (utils.remove_double_matching)."""
+        self._enter()
+        n = C.c_int()
+        self._check(self.lib.evh_remove_double_matching(self.h, pts.data_ptr() if pts.shape[0] else None, pts.shape[0],
+                                                        out.data_ptr() if pts.shape[0] else None, C.byref(n)))
         return n.value
 
     # ---- fused ----

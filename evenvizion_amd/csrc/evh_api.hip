@@ -935,6 +935,31 @@ int evh_static_filter(evh_ctx* c, const double* h_H, const float* d_pts, int n, 
   return EVH_SUCCESS;
 }
 
+// the multi-type entries' merge stage on caller rows: one "pair" whose concatenation is the n rows themselves
+int evh_remove_double_matching(evh_ctx* c, const float* d_pts, int n, float* d_out, int* h_count) {
+  if (!c || (!d_pts && n > 0) || (!d_out && n > 0) || !h_count || n < 0)
+    return evh_fail(c, EVH_ERR_INVALID, "evh_remove_double_matching: bad argument");
+  // the largest concatenation a multi-type pair can hold: three feature types of up to 65 535 rows each
+  if (n > 3 * 65535) return evh_fail(c, EVH_ERR_CAPACITY, "evh_remove_double_matching: too many rows");
+  if ((((uintptr_t)d_pts) | ((uintptr_t)d_out)) & 15) return evh_fail(c, EVH_ERR_INVALID, "row buffers must be 16-byte aligned");
+  if (n == 0) { *h_count = 0; return EVH_SUCCESS; }
+  const uintptr_t lo = (uintptr_t)d_pts, lo2 = (uintptr_t)d_out, len = sizeof(float) * 4 * (size_t)n;
+  if (lo < lo2 + len && lo2 < lo + len)                 // k_merge reads a key's last row while other rows are being written
+    return evh_fail(c, EVH_ERR_INVALID, "evh_remove_double_matching: d_pts and d_out overlap");
+  { int jr = join_solve(c); if (jr) return jr; }        // d_small is the staging area of a one-pair solve still in flight
+  EvhSmall* S = c->d_small;
+  const int head[2] = {n, 0};                           // nacc, accstatus
+  EVH_HIP(c, hipMemcpyAsync(&S->merge.nacc, head, sizeof(head), hipMemcpyHostToDevice, c->stream));
+  EvhMergeArgs M{};
+  M.acc = d_pts; M.nacc = &S->merge.nacc; M.accstatus = &S->merge.accstatus; M.acc_stride = n;
+  M.out = d_out; M.nout = &S->merge.nout; M.status = &S->merge.status; M.out_stride = n;
+  int rc = evh_launch_merge(c, M, 1);
+  if (rc) return rc;
+  EVH_HIP(c, hipMemcpyAsync(h_count, &S->merge.nout, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  return EVH_SUCCESS;
+}
+
 int evh_pair_homography_batch(evh_ctx* c, const uint8_t* d_frames, int npairs, int mode, int w, int h, int channels,
                               int64_t row_stride, int64_t frame_stride, int nfeatures, double ransac_thr,
                               int ransac_max_iters, double ransac_conf, int force_max_iters, double* d_H, int32_t* d_status) {

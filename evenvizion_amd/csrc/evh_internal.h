@@ -74,7 +74,10 @@ struct EvhPairBufs {
 
 // the 64-double staging area of the single-problem entries (d_small): what each entry keeps where
 struct EvhSmall {
-  union { double H[16]; int count_status[2]; };        // +0: result matrix | ratio filter: row count, status
+  union {                                              // +0: result matrix | ratio filter: row count, status
+    double H[16]; int count_status[2];
+    struct { int nacc, accstatus, nout, status; } merge;   // evh_remove_double_matching: the one "pair" of k_merge_dup / k_merge
+  };
   union {                                              // +16 doubles
     double Hsup[16];                                   // superposition entering a one-pair final solve
     struct { int found, pad_, info[3]; };              // evh_find_homography_ransac*: found flag, +17 doubles: info

@@ -362,23 +362,31 @@ __device__ __forceinline__ bool find_homography_block(BlockLds<NW, LANES>& B, co
   return true;
 }
 
-// find_point_displacement + get_largest_group_points; rbin = int scratch [n] (global); returns kept count (uniform).
-// All threads of the workgroup; ends with a workgroup barrier.
+// find_point_displacement + get_largest_group_points; rbin = scratch of 16 bytes per row (global, 8-byte aligned): an int
+// bin per row and, behind them, the rounded displacement per row as a double for the quadratic path; returns kept count
+// (uniform).  All threads of the workgroup; ends with a workgroup barrier.
 template <int NW, bool LANES>
 __device__ __forceinline__ int static_filter_block(BlockLds<NW, LANES>& B, const double* H /*LDS*/, const float* rows, int n, int* rbin,
                                    float* out) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NT = NW * NL;
   for (int i = tid; i < HB; i += NT) B.u.h.hist[i] = 0u;
   __syncthreads();
-  int big = 0;
-  for (int i = tid; i < n; i += NT) {
+  // round(displacement) of row i: Python round(), half to even, as a double -- a Python int has no upper bound, and a
+  // point that H sends next to its line at infinity is displaced by more than any int holds
+  auto rounded = [&](int i) {
     double tx, ty, tw;
     hdot(H, (double)rows[4 * i], (double)rows[4 * i + 1], &tx, &ty, &tw);
     double dx = tx / tw - (double)rows[4 * i + 2], dy = ty / tw - (double)rows[4 * i + 3];
-    double dist = sqrt(dx * dx + dy * dy);
-    const int r = (int)__builtin_rint(dist);  // Python round(): half to even
+    return __builtin_rint(sqrt(dx * dx + dy * dy));
+  };
+  int big = 0;
+  for (int i = tid; i < n; i += NT) {
+    const double rd = rounded(i);
+    // HB: every displacement beyond the histogram.  A NaN displacement (0 / 0 where tw == 0; the reference raises there)
+    // converts to bin 0 on this device, as before; in the quadratic path it equals nothing and is in no group
+    const int r = rd >= (double)HB ? HB : (int)rd;
     rbin[i] = r;
-    if ((unsigned)r < (unsigned)HB) atomicAdd(&B.u.h.hist[r], 1u);
+    if (r < HB) atomicAdd(&B.u.h.hist[r], 1u);
     else big = 1;
   }
   __threadfence_block();
@@ -388,19 +396,24 @@ __device__ __forceinline__ int static_filter_block(BlockLds<NW, LANES>& B, const
   // member): the largest key over the POINTS (a point carries the population of its own bin) is the largest over the
   // bins -- no per-bin "first member" table is needed (it cost 8 KB of LDS in every solver workgroup)
   unsigned long long bestkey = 0;
+  double* rwide = reinterpret_cast<double*>(rbin + ((n + 1) & ~1));     // 4 (n + 1) + 8 n <= 16 n bytes
   if (!big) {
     for (int i = tid; i < n; i += NT) {
       const unsigned long long key = ((unsigned long long)B.u.h.hist[rbin[i]] << 32) | (unsigned)(0x7FFFFFFF - i);
       bestkey = key > bestkey ? key : bestkey;
     }
   } else {
+    // some displacement is 2048 or more: bins are compared as the rounded doubles themselves, which keeps apart every
+    // pair of values an int would saturate together (above 2^31)
+    for (int i = tid; i < n; i += NT) rwide[i] = rounded(i);
+    __threadfence_block();
+    __syncthreads();
     for (int i = tid; i < n; i += NT) {
-      const int r = rbin[i];
+      const double r = rwide[i];
       bool first = true;
       int cnt = 0;
       for (int j = 0; j < n; j++) {
-        const int rj = rbin[j];
-        if (rj == r) { cnt++; if (j < i) first = false; }
+        if (rwide[j] == r) { cnt++; if (j < i) first = false; }
       }
       if (first) {
         unsigned long long key = ((unsigned long long)cnt << 32) | (unsigned)(0x7FFFFFFF - i);
@@ -414,11 +427,12 @@ __device__ __forceinline__ int static_filter_block(BlockLds<NW, LANES>& B, const
   for (int w = 0; w < NW; w++) { const unsigned long long o = B.red[w]; bestkey = o > bestkey ? o : bestkey; }
   const int ibest = 0x7FFFFFFF - (int)(bestkey & 0xFFFFFFFFull);
   const int rbest = rbin[ibest];
+  const double wbest = big ? rwide[ibest] : 0.0;
   int mcount = 0;
   if (wave == 0) {
     for (int c0 = 0; c0 < n; c0 += NL) {
       const int i = c0 + lane;
-      const bool f = i < n && rbin[i] == rbest;
+      const bool f = i < n && (big ? rwide[i] == wbest : rbin[i] == rbest);
       const unsigned long long b = __ballot(f);
       if (f) *reinterpret_cast<float4*>(out + 4 * (mcount + __popcll(b & ((1ull << lane) - 1ull)))) =
           *reinterpret_cast<const float4*>(rows + 4 * i);

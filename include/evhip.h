@@ -14,6 +14,7 @@
  *   evh_transform_points          from_original_to_fix / from_fix_to_original       fixed_coordinate_system.py:19-122
  *   evh_find_homography_ransac    cv2.findHomography(a,b,cv2.RANSAC,3.0) matching.py:156-157; utils.py:356-358
  *   evh_static_filter             find_point_displacement + get_largest_group_points   utils.py:258-325
+ *   evh_remove_double_matching    utils.remove_double_matching           frame_processing.py:102-104; utils.py:41-68
  *   evh_sift_detect_batch         cv2.xfeatures2d.SIFT_create().detectAndCompute   frame_processing.py:62-64
  *   evh_surf_detect_batch         cv2.xfeatures2d.SURF_create(extended=1, hessianThreshold=400).detectAndCompute   frame_processing.py:65-67
  *   evh_match_knn2_l2f32          knnMatch on float32[N,128] descriptors            matching.py:102-108
@@ -230,6 +231,13 @@ int evh_find_homography_ransac_fixed(evh_ctx* ctx, const float* d_pts, int n, do
                                      double* h_H, uint8_t* h_mask, int* h_found, int* h_info);
 /* find_point_displacement + get_largest_group_points: rows of the most populated rounded-displacement bin */
 int evh_static_filter(evh_ctx* ctx, const double* h_H, const float* d_pts, int n, float* d_out_pts, int* h_count);
+/* remove_double_matching (utils.py:41-68) on n rows (ax, ay, bx, by): one row per distinct (ax, ay), in the order of
+ * first occurrence, with the (bx, by) of the key's LAST occurrence; +0.0 and -0.0 are the same key and the first
+ * occurrence's bits are kept.  This is the merge stage of the *_types entries (frame_processing.py:102-104) run on
+ * caller rows.  d_pts, d_out f32[n,4], 16-byte aligned, must not overlap (EVH_ERR_INVALID); h_count the number of rows written; rows of
+ * d_out past h_count are left untouched.  n = 0 gives 0 rows; n > 196 605 (three feature types of 65 535 rows each, the
+ * largest concatenation of a multi-type pair) is EVH_ERR_CAPACITY.  Synchronises.                                    */
+int evh_remove_double_matching(evh_ctx* ctx, const float* d_pts, int n, float* d_out, int* h_count);
 
 /* ---- fused batch entry: frames -> H -------------------------------------------------------------------------------- */
 /* mode EVH_MODE_INDEPENDENT_PAIRS: 2*npairs frames laid out (prev0, cur0, prev1, cur1, ...), H_sup = None.

@@ -484,6 +484,43 @@ __device__ __forceinline__ int fast_score_from_d(const i16 (&d)[16]) {
   return best > EVH_FAST_THR ? best - 1 : 0;
 }
 
+// Score byte of a pixel the segment test has already found to be a corner, from the raw bytes: v = centre, p[k] = ring,
+// m = 0xFF where the ring is the brighter side, 0 where it is the darker one.  A corner has exactly one polarity (two
+// 9-arcs of a 16-ring overlap, so a ring cannot hold nine pixels below centre - T and nine above centre + T), and on
+// the other side every arc then holds a pixel of the winning arc, whose difference has the wrong sign by more than T:
+// that side's candidate is below -T and never wins the max of fast_score_from_d.  The score is therefore one-sided,
+// best = max over arcs of min(v - p) = v - min over arcs of max(p) for a darker ring, and the same with every byte
+// complemented (v ^ 0xFF = 255 - v keeps the differences, swaps their sign) for a brighter one.  No subtraction per
+// ring pixel, unsigned 16-bit max / min only (the full-rate forms).  best > T is what the segment test proved, so
+// the byte best - 1 is returned without the comparison.  Same block prefix / suffix scans as fast_score_from_d.
+typedef unsigned short u16;
+__device__ __forceinline__ u16 mnu16(u16 a, u16 b) { return a < b ? a : b; }
+__device__ __forceinline__ u16 mxu16(u16 a, u16 b) { return a > b ? a : b; }
+__device__ __forceinline__ int fast_score_one_sided(uint32_t v, const uint32_t (&p)[16], uint32_t m) {
+  u16 q[16], Px[2][8], Sx[2][8];
+#pragma unroll
+  for (int k = 0; k < 16; k++) q[k] = (u16)(p[k] ^ m);
+#pragma unroll
+  for (int b = 0; b < 2; b++) {
+    Px[b][0] = q[8 * b];
+    Sx[b][7] = q[8 * b + 7];
+#pragma unroll
+    for (int r = 1; r < 8; r++) {
+      Px[b][r] = mxu16(Px[b][r - 1], q[8 * b + r]);
+      Sx[b][7 - r] = mxu16(Sx[b][8 - r], q[8 * b + 7 - r]);
+    }
+  }
+  u16 lo = mxu16(Sx[0][0], Px[1][0]);   // min over arcs of max(ring)
+#pragma unroll
+  for (int b = 0; b < 2; b++)
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      if (b == 0 && r == 0) continue;
+      lo = mnu16(lo, mxu16(Sx[b][r], Px[b ^ 1][r]));
+    }
+  return (int)(v ^ m) - (int)lo - 1;
+}
+
 #define FQ_PITCH (FS_DW * 4)   // score plane pitch in bytes (136)
 
 
@@ -586,6 +623,11 @@ __device__ __forceinline__ uint32_t swar_ge(uint32_t aH, uint32_t a, uint32_t b,
   const uint32_t t = aH - bL;
   return BITOP3(a, b, t, (A & ~B) | (~(A ^ B) & C));
 }
+// the same with the 7-bit difference handed in: for the brighter compare (ring | H) - chL = (ring & Lm) + (H - chL) per byte,
+// no carry or borrow (chL <= 127), ring & Lm is what the darker compare needs anyway and H - chL is one value per quad
+__device__ __forceinline__ uint32_t swar_ge_t(uint32_t a, uint32_t b, uint32_t t) {
+  return BITOP3(a, b, t, (A & ~B) | (~(A ^ B) & C));
+}
 __device__ __forceinline__ uint32_t pretest_pass4(uint32_t c, uint32_t rd, uint32_t rr, uint32_t ru, uint32_t rl, uint32_t K4) {
   const uint32_t H = 0x80808080u, Lm = 0x7F7F7F7Fu;
   const uint32_t t = (c | H) - K4;                          // 128 + (c & 127) - K per byte
@@ -611,14 +653,21 @@ __device__ __forceinline__ uint32_t pretest_pass4(uint32_t c, uint32_t rd, uint3
 // A3[k] = M[k] & M[k+1] & M[k+2], A9[k] = A3[k] & A3[k+3] & A3[k+6], any = OR_k A9[k] -- 40 v_bitop3 per polarity.
 // Used where every corner at the base threshold is wanted (reference key-point order): the exact score is then computed for the
 // corners only (~10 % of the pixels of a textured frame) instead of for every pixel.
-__device__ __forceinline__ uint32_t corner16_pass4(const uint32_t* p, uint32_t K4) {
+// The result is already masked with cmask (bit 7 of the bytes of the testable pixels) and carries the polarity: bit 6 of a corner's
+// byte is set where its arc is the brighter side (Bm), clear where it is the darker one (Dm) -- never both, two 9-arcs of a 16-ring
+// overlap.  The scorer of the queued corners evaluates that side only (fast_score_one_sided).
+// The brighter compare takes its 7-bit difference as (ring & Lm) + (H - chL): ring & Lm is shared with the darker compare and
+// H - chL is one value per quad, so a ring dword costs AND, SUB, ADD and two v_bitop3 for both compares (an OR less than swar_ge twice).
+__device__ __forceinline__ uint32_t corner16_pass4(const uint32_t* p, uint32_t K4, uint32_t cmask) {
   const uint32_t H = 0x80808080u, Lm = 0x7F7F7F7Fu;
   const uint32_t c = p[1];
   const uint32_t t = (c | H) - K4;
   const uint32_t cl = BITOP3(t, c, Lm, A & (B | C));
   const uint32_t u = (c & Lm) + K4;
   const uint32_t ch = BITOP3(u, c, H, A | (B & C));
-  const uint32_t clH = cl | H, chL = ch & Lm;
+  const uint32_t clH = cl | H;
+  uint32_t cB = H - (ch & Lm);
+  asm volatile("" : "+v"(cB));     // pinned: left alone the compiler folds (ring & Lm) + (H - chL) back into an add and a subtract per ring pixel
   uint32_t r[16];
   {
     const uint32_t* q = p + 3 * FR_DW;                       // row y + 3: ring 15, 0, 1
@@ -650,8 +699,9 @@ __device__ __forceinline__ uint32_t corner16_pass4(const uint32_t* p, uint32_t K
   uint32_t D[16], Bq[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
-    D[k] = swar_ge(clH, cl, r[k], r[k] & Lm);                // centre - (T + 1) >= ring: darker
-    Bq[k] = swar_ge(r[k] | H, r[k], ch, chL);                // ring >= centre + (T + 1): brighter
+    const uint32_t rL = r[k] & Lm;
+    D[k] = swar_ge(clH, cl, r[k], rL);                       // centre - (T + 1) >= ring: darker
+    Bq[k] = swar_ge_t(r[k], ch, rL + cB);                    // ring >= centre + (T + 1): brighter
   }
   uint32_t d3[16], b3[16];
 #pragma unroll
@@ -671,12 +721,15 @@ __device__ __forceinline__ uint32_t corner16_pass4(const uint32_t* p, uint32_t K
   }
   const uint32_t Dm = BITOP3(dany, c, t, A & (B | C));       // & (centre >= T + 1): centre - (T + 1) did not wrap
   const uint32_t Bm = BITOP3(bany, c, u, A & ~(B & C));      // & (centre + T + 1 <= 255)
-  return BITOP3(Dm, Bm, H, (A | B) & C);
+  const uint32_t pass = BITOP3(Dm, Bm, cmask, (A | B) & C);
+  return BITOP3(pass, Bm >> 1, cmask >> 1, A | (B & C));     // bit 6 beside a corner's bit 7: the ring is the brighter side
 }
 
 // lifted path: only scores >= T are produced.  Phase A: 4-point pre-test at T (any 9-arc holds two adjacent
 // compass points), four pixels per 32-bit operation; a quad with at least one passing pixel is queued
 // (quad index | pass bits << 16).  Phase B: exact score of the queued pixels, 4 lanes per queued quad.
+// FULL16 (reference key-point order, T = the base threshold): phase A is the whole segment test, every passing pixel is a corner
+// and is queued on its own with its polarity, and phase B scores one corner per lane on its own side of the ring only.
 template <bool FULL16 = false>
 __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, int x0, int y0, int T) {
   const uint32_t K4 = (uint32_t)(T + 1) * 0x01010101u;
@@ -709,7 +762,7 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
         if (INTERIOR || (rowok && cmask)) {
           const uint32_t* p = S.raw + mad24((uint32_t)(sr + 3), FR_DW, (uint32_t)sq);    // centre row, dword of x = xq-4
           if constexpr (FULL16) {
-            P[k] = corner16_pass4(p, K4) & cmask;
+            P[k] = corner16_pass4(p, K4, cmask);
           } else {
             const uint32_t Lc = p[0], Mc = p[1], Rc = p[2], Mu = p[1 - 3 * FR_DW], Md = p[1 + 3 * FR_DW];
             P[k] = pretest_pass4(Mc, Md, __builtin_amdgcn_alignbyte(Rc, Mc, 3), Mu, __builtin_amdgcn_alignbyte(Mc, Lc, 1), K4) &
@@ -749,9 +802,12 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
   };
   if constexpr (FULL16) {
     // every passing pixel IS a corner (a fifth of the pixels of a textured frame): one lane per corner.  Queue of 16-bit
-    // entries quad << 2 | pixel in the words of S.lst (2048 entries); a tile with more corners than that is scored densely.
+    // entries quad << 2 | pixel, bit 15 = the ring is the brighter side (bit 6 of the pass byte), in the words of S.lst
+    // (2048 entries); a tile with more corners than that is scored densely.
     uint16_t* pq = reinterpret_cast<uint16_t*>(S.lst);
     constexpr int PQ_CAP = 2 * (FS_H * FS_DW);
+    constexpr int PQ_POL = 15;
+    static_assert(((FS_H * FS_DW - 1) << 2 | 3) < (1 << PQ_POL), "quad index and pixel stay below the polarity bit of a queue entry");
     const int mine = __popc(P[0] & 0x80808080u) + __popc(P[1] & 0x80808080u) + __popc(P[2] & 0x80808080u) + __popc(P[3] & 0x80808080u);
     int at = mine ? atomicAdd(&S.qcnt, mine) : 0;
 #pragma unroll
@@ -760,7 +816,8 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
       while (m) {
         const int b = __ffs(m) - 1;                  // bit 7, 15, 23 or 31
         m &= m - 1;
-        if (at < PQ_CAP) pq[at] = (uint16_t)(((threadIdx.x + 256 * k) << 2) | (b >> 3));
+        const uint32_t pol = (P[k] >> (b - 1)) & 1u;
+        if (at < PQ_CAP) pq[at] = (uint16_t)(((threadIdx.x + 256 * k) << 2) | (b >> 3) | (pol << PQ_POL));
         at++;
       }
     }
@@ -770,9 +827,18 @@ __device__ __forceinline__ void fast_lift_scores(FastLds& S, const EvhLevel& L, 
       fast_dense_scores(S, L, x0, y0);
       return;
     }
+    // the segment test has decided both that the pixel is a corner (score >= T: the byte is written unconditionally) and
+    // which side its arc is on: fast_score_one_sided
     for (int e = threadIdx.x; e < np; e += 256) {
-      const int ent = pq[e];
-      score_pixel(ent >> 2, ent & 3, false);
+      const uint32_t ent = pq[e];
+      const uint32_t m = (0u - (ent >> PQ_POL)) & 0xFFu;
+      const int qi = (ent >> 2) & 0x3FFu, j = ent & 3;
+      const int sr2 = qi / FS_DW, sq2 = qi - sr2 * FS_DW;
+      const uint8_t* p = rawb + (sr2 + 3) * (FR_DW * 4) + sq2 * 4 + j + 4;
+      constexpr int W = FR_DW * 4;
+      const uint32_t ring[16] = {p[3 * W],      p[3 * W + 1],  p[2 * W + 2],  p[W + 3],  p[3],  p[-W + 3], p[-2 * W + 2], p[-3 * W + 1],
+                                 p[-3 * W],     p[-3 * W - 1], p[-2 * W - 2], p[-W - 3], p[-3], p[W - 3],  p[2 * W - 2],  p[3 * W - 1]};
+      scoreb[sr2 * FQ_PITCH + sq2 * 4 + j] = (uint8_t)fast_score_one_sided(p[0], ring, m);
     }
     return;
   }

@@ -1,7 +1,7 @@
 """GPU: FAST in the reference key-point order on frames that pin the polarity of every corner.
 
 k_fast_main's segment test hands the side of a corner's arc (ring darker / ring brighter than the centre) to the scorer,
-which then evaluates one side only, on the raw bytes (evh_detect.hip: corner16_pass4, fast_score_one_sided).  A wrong
+which then evaluates one side only, on the raw bytes (evh_detect_fast.h: corner16_pass4, fast_score_one_sided).  A wrong
 polarity bit, a wrong complement or a wrong arc gives another score byte, so the candidate lists (position and score of
 every corner that survives the 3 x 3 maximum test) are compared with the oracle's on frames with corners of both kinds, of
 one kind only, with the largest score a byte holds, and with scores right at the threshold at both ends of the grey range.

@@ -2,7 +2,7 @@
 // HBM section: "other access widths are uncalibrated: calibrate on a known byte count in your own access pattern").
 //
 // Every workgroup stages a tile footprint of R rows x (C16 x 16) bytes with one 16-byte load per lane, exactly like
-// fast_stage() (evh_detect.hip): item i = (row i / C16, column i % C16).  The image set is 2048 planes of 1280 x 720
+// fast_stage() (evh_detect_fast.h): item i = (row i / C16, column i % C16).  The image set is 2048 planes of 1280 x 720
 // bytes (1.9 GB, far beyond L2 + Infinity Cache), each plane is walked once per launch.  Patterns (one kernel name
 // each, so that rocprofv3 --pmc FETCH_SIZE reports them separately):
 //   0  FAST-like      36 rows x 144 B, first byte 16 B into a 128-B line, tile pitch 128 x 28 (halo overlap, as k_fast_main)

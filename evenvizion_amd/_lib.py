@@ -522,13 +522,17 @@ class Context:
         dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
         self._check(self.lib.evh_sift_detect_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh))
 
+    def _kp_download(self, det, frame, fields):
+        """A frame's SIFT / SURF key points: xy, desc and `fields` (the per-key-point arrays in the C entry's argument order)."""
+        cap = getattr(self.lib, "evh_%s_capacity" % det)(self.h)
+        out = dict(xy=np.zeros((cap, 2), np.float32), desc=np.zeros((cap, 128), np.float32))
+        for k in fields:
+            out[k] = np.zeros(cap, np.int32 if k in ("octave", "laplacian") else np.float32)
+        n = self._check(getattr(self.lib, "evh_%s_download" % det)(self.h, frame, *[_hp(a) for a in out.values()]))
+        return {k: a[:n].copy() for k, a in out.items()}
+
     def sift_download(self, frame):
-        cap = self.lib.evh_sift_capacity(self.h)
-        xy = np.zeros((cap, 2), np.float32); desc = np.zeros((cap, 128), np.float32); oc = np.zeros(cap, np.int32)
-        sz = np.zeros(cap, np.float32); an = np.zeros(cap, np.float32); rs = np.zeros(cap, np.float32)
-        n = self._check(self.lib.evh_sift_download(self.h, frame, _hp(xy), _hp(desc), _hp(oc), _hp(sz), _hp(an), _hp(rs)))
-        return dict(xy=xy[:n].copy(), desc=desc[:n].copy(), octave=oc[:n].copy(), size=sz[:n].copy(), angle=an[:n].copy(),
-                    response=rs[:n].copy())
+        return self._kp_download("sift", frame, ("octave", "size", "angle", "response"))
 
     def sift_octaves(self):
         out = []
@@ -561,12 +565,7 @@ class Context:
                                                    float(hessian_threshold)))
 
     def surf_download(self, frame):
-        cap = self.lib.evh_surf_capacity(self.h)
-        xy = np.zeros((cap, 2), np.float32); desc = np.zeros((cap, 128), np.float32); sz = np.zeros(cap, np.float32)
-        an = np.zeros(cap, np.float32); rs = np.zeros(cap, np.float32); oc = np.zeros(cap, np.int32); lp = np.zeros(cap, np.int32)
-        n = self._check(self.lib.evh_surf_download(self.h, frame, _hp(xy), _hp(desc), _hp(sz), _hp(an), _hp(rs), _hp(oc), _hp(lp)))
-        return dict(xy=xy[:n].copy(), desc=desc[:n].copy(), size=sz[:n].copy(), angle=an[:n].copy(), response=rs[:n].copy(),
-                    octave=oc[:n].copy(), laplacian=lp[:n].copy())
+        return self._kp_download("surf", frame, ("size", "angle", "response", "octave", "laplacian"))
 
     def surf_download_integral(self, frame):
         h, w = self._surf_shape

@@ -190,8 +190,11 @@ struct EvhFeatView {
   int cap;                                       // rows per frame slot
 };
 EvhFeatView feat_view(const evh_ctx* c, int type) {
-  if (type == EVH_FEATURE_SIFT) return {c->d_sift_count, c->d_sift_flags, c->d_sift_xy, c->d_sift_desc, 128, false, c->sift_cap};
-  if (type == EVH_FEATURE_SURF) return {c->d_surf_count, c->d_surf_flags, c->d_surf_xy, c->d_surf_desc, 0, true, c->surf_cap};
+  if (type == EVH_FEATURE_SIFT || type == EVH_FEATURE_SURF) {
+    const EvhKpList& L = type == EVH_FEATURE_SIFT ? c->sift : c->surf;
+    const bool f32 = type == EVH_FEATURE_SURF;
+    return {L.count, L.flags, L.xy, L.desc, f32 ? 0 : L.desc_row_bytes, f32, L.cap};
+  }
   return {c->d_kp_count, c->d_frame_flags, c->d_kp_xy, c->d_desc, 32, false, c->kcap};
 }
 
@@ -337,7 +340,7 @@ int detect_batch(evh_ctx* c, const EvhFrames& F, int nframes, int sw, int sh, in
 // ---- multi-type pairs (frame_processing.py:91-104) ---------------------------------------------------------------------------
 int ensure_multitype(evh_ctx* c) {
   if (c->mt.cap) return EVH_SUCCESS;
-  const int each = std::max(c->kcap, std::max(c->sift_cap, c->surf_cap)), cap = c->kcap + c->sift_cap + c->surf_cap;
+  const int each = std::max(c->kcap, std::max(c->sift.cap, c->surf.cap)), cap = c->kcap + c->sift.cap + c->surf.cap;
   if (each > 65536)
     return evh_fail(c, EVH_ERR_CAPACITY, "multi-type pairs: at most 65536 key points per frame and type");
   const size_t P = (size_t)c->max_frames, K = (size_t)cap, first = c->owned.size();
@@ -357,7 +360,7 @@ int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, in
   if (!types || ntypes < 1 || ntypes > 8) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad feature type list");
   bool want_orb = false, want_sift = false, want_surf = false;
   for (int i = 0; i < ntypes; i++) {
-    // the concatenation buffer holds one segment per detector (kcap + sift_cap + surf_cap rows): a type named twice would
+    // the concatenation buffer holds one segment per detector (kcap + sift.cap + surf.cap rows): a type named twice would
     // overflow it, so it is refused (the reference would simply match the same key points twice and deduplicate them)
     bool* seen = types[i] == EVH_FEATURE_ORB ? &want_orb : types[i] == EVH_FEATURE_SIFT ? &want_sift :
                  types[i] == EVH_FEATURE_SURF ? &want_surf : nullptr;
@@ -365,9 +368,9 @@ int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, in
     if (*seen) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": a feature type appears twice in the list");
     *seen = true;
   }
-  if (want_sift && !c->sift_cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SIFT in the list needs evh_sift_enable");
-  if (want_surf && !c->surf_cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SURF in the list needs evh_surf_enable");
-  if (c->mt.cap && c->mt.cap < c->kcap + c->sift_cap + c->surf_cap)
+  if (want_sift && !c->sift.cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SIFT in the list needs evh_sift_enable");
+  if (want_surf && !c->surf.cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SURF in the list needs evh_surf_enable");
+  if (c->mt.cap && c->mt.cap < c->kcap + c->sift.cap + c->surf.cap)
     return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": enable SIFT and SURF before the first multi-type call");
   int rc = ensure_multitype(c);
   if (rc) return rc;
@@ -388,7 +391,7 @@ int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, in
   if (want_orb && (rc = orb_stages(c, nframes, share_group))) return rc;
   const int q0 = 1, qstep = stream_mode ? 1 : 2, t0 = 0, tstep = stream_mode ? 1 : 2;
   EvhRansacArgs R = ransac_args(c, c->mt, thr, max_iters, conf, force_max);
-  const int each = std::max(c->kcap, std::max(c->sift_cap, c->surf_cap));   // one filter form for every type of the list
+  const int each = std::max(c->kcap, std::max(c->sift.cap, c->surf.cap));   // one filter form for every type of the list
   for (int i = 0; i < ntypes; i++) {
     // the solve was joined once, above: this path has no asynchronous solve of its own to overlap
     if ((rc = match_pairs(c, feat_view(c, types[i]), c->mt, each, false, npairs, q0, qstep, t0, tstep))) return rc;
@@ -474,6 +477,44 @@ void unpack_records(const std::vector<float>& rec, int n, float* h_xy, float* h_
     if (h_octave) memcpy(&h_octave[i], &r[5], 4);
     if (h_laplacian) memcpy(&h_laplacian[i], &r[6], 4);
   }
+}
+
+// ---- what SIFT and SURF share on their key-point lists (EvhKpList) ----
+// level 0 of a float detector's batch, then its launch
+template <class Launch>
+int kp_detect_batch(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
+                    int64_t row_stride, int64_t frame_stride, int w, int h, Launch launch) {
+  int rc = join_solve(c);
+  if (rc) return rc;
+  const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
+  if ((rc = ingest_level0(c, who, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w, src_h, w, h, nf)))
+    return rc;
+  c->nframes_resident = 0;            // level 0 was rewritten: the ORB results of an earlier call no longer match it
+  return launch();
+}
+
+// key points of a resident frame; a flagged frame is an error (`overflow`)
+int kp_count(evh_ctx* c, int type, const char* name, const char* overflow, int frame) {
+  if (!c || frame < 0 || frame >= (type == EVH_FEATURE_SIFT ? c->sift : c->surf).frames_resident)
+    return evh_fail(c, EVH_ERR_INVALID, std::string("bad ") + name + " frame slot");
+  int fl = 0;
+  const int n = frame_count(c, feat_view(c, type), frame, &fl);
+  if (n < 0) return n;
+  if (fl) return evh_fail(c, EVH_ERR_CAPACITY, overflow);
+  return n;
+}
+
+// the n records of a frame unpacked into the caller's arrays, its n descriptor rows as they are stored (h_desc_rows may be NULL)
+int kp_download(evh_ctx* c, const EvhKpList& L, int frame, int n, void* h_desc_rows, float* h_xy, float* h_size, float* h_angle,
+                float* h_response, int32_t* h_octave, int32_t* h_laplacian) {
+  const size_t o = (size_t)frame * L.cap;
+  std::vector<float> rec((size_t)n * 8);
+  EVH_HIP(c, hipMemcpyAsync(rec.data(), L.kp + o * 8, sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream));
+  if (h_desc_rows)
+    EVH_HIP(c, hipMemcpyAsync(h_desc_rows, L.desc + o * L.desc_row_bytes, (size_t)n * L.desc_row_bytes, hipMemcpyDeviceToHost, c->stream));
+  EVH_HIP(c, hipStreamSynchronize(c->stream));
+  unpack_records(rec, n, h_xy, h_size, h_angle, h_response, h_octave, h_laplacian);
+  return EVH_SUCCESS;
 }
 
 // evh_ratio_unique_filter / _f32: d2 holds integer squared distances, or (is_dist) the float32 bits of distances
@@ -1098,46 +1139,27 @@ int evh_sift_enable(evh_ctx* c, int max_sift_features) {
   return evh_sift_allocate(c, max_sift_features);
 }
 
-int evh_sift_capacity(const evh_ctx* c) { return c ? c->sift_cap : EVH_ERR_INVALID; }
+int evh_sift_capacity(const evh_ctx* c) { return c ? c->sift.cap : EVH_ERR_INVALID; }
 
 int evh_sift_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
                           int64_t row_stride, int64_t frame_stride, int w, int h) {
   if (!c) return EVH_ERR_INVALID;
-  if (!c->sift_cap) return evh_fail(c, EVH_ERR_INVALID, "evh_sift_detect_batch: call evh_sift_enable first");
-  int rc = join_solve(c);
-  if (rc) return rc;
-  const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
-  if ((rc = ingest_level0(c, "evh_sift_detect_batch", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w,
-                          src_h, w, h, nf)))
-    return rc;
-  c->nframes_resident = 0;            // level 0 was rewritten: the ORB results of an earlier call no longer match it
-  return evh_launch_sift(c, nframes, w, h);
+  if (!c->sift.cap) return evh_fail(c, EVH_ERR_INVALID, "evh_sift_detect_batch: call evh_sift_enable first");
+  return kp_detect_batch(c, "evh_sift_detect_batch", d_frames, nframes, src_w, src_h, channels, row_stride, frame_stride, w, h,
+                         [&] { return evh_launch_sift(c, nframes, w, h); });
 }
 
 int evh_sift_count(evh_ctx* c, int frame) {
-  if (!c || frame < 0 || frame >= c->sift_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "bad SIFT frame slot");
-  int fl = 0;
-  const int n = frame_count(c, feat_view(c, EVH_FEATURE_SIFT), frame, &fl);
-  if (n < 0) return n;
-  if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "more SIFT key points (or scale-space extrema) than evh_sift_enable reserved for a frame");
-  return n;
+  return kp_count(c, EVH_FEATURE_SIFT, "SIFT", "more SIFT key points (or scale-space extrema) than evh_sift_enable reserved for a frame", frame);
 }
 
 int evh_sift_download(evh_ctx* c, int frame, float* h_xy, float* h_desc, int32_t* h_octave, float* h_size, float* h_angle,
                       float* h_response) {
   const int n = evh_sift_count(c, frame);
   if (n <= 0) return n;
-  const size_t o = (size_t)frame * c->sift_cap;
-  std::vector<float> rec((size_t)n * 8);
-  std::vector<uint8_t> d8;
-  EVH_HIP(c, hipMemcpyAsync(rec.data(), c->d_sift_kp + o * 8, sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream));
-  if (h_desc) {
-    d8.resize((size_t)n * 128);
-    EVH_HIP(c, hipMemcpyAsync(d8.data(), c->d_sift_desc + o * 128, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
-  }
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  unpack_records(rec, n, h_xy, h_size, h_angle, h_response, h_octave, nullptr);
-  if (h_desc) for (size_t i = 0; i < (size_t)n * 128; i++) h_desc[i] = (float)d8[i];
+  std::vector<uint8_t> d8(h_desc ? (size_t)n * 128 : 0);
+  if (int rc = kp_download(c, c->sift, frame, n, h_desc ? d8.data() : nullptr, h_xy, h_size, h_angle, h_response, h_octave, nullptr)) return rc;
+  for (size_t i = 0; i < d8.size(); i++) h_desc[i] = (float)d8[i];
   return n;
 }
 
@@ -1152,8 +1174,8 @@ int evh_sift_download_gauss(evh_ctx* c, int frame, int octave, int layer, float*
   if (!c || !c->sift_geom_valid || !h_pixels || octave < 0 || octave >= c->sg.noct || layer < 0 || layer > 5 || frame < 0)
     return evh_fail(c, EVH_ERR_INVALID, "evh_sift_download_gauss: bad argument");
   // only the LAST group's scale space is resident
-  const int g0 = ((c->sift_frames_resident - 1) / c->sift_group) * c->sift_group;
-  if (frame < g0 || frame >= c->sift_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "evh_sift_download_gauss: that frame's scale space is no longer resident");
+  const int g0 = ((c->sift.frames_resident - 1) / c->sift.group) * c->sift.group;
+  if (frame < g0 || frame >= c->sift.frames_resident) return evh_fail(c, EVH_ERR_INVALID, "evh_sift_download_gauss: that frame's scale space is no longer resident");
   const EvhSiftGeom& g = c->sg;
   const float* src = c->d_sift_pyr + (int64_t)(frame - g0) * c->sift_pyr_frame_floats + g.ooff[octave] + (int64_t)layer * g.os[octave] * g.oh[octave];
   EVH_HIP(c, hipMemcpy2DAsync(h_pixels, sizeof(float) * g.ow[octave], src, sizeof(float) * g.os[octave], sizeof(float) * g.ow[octave],
@@ -1244,49 +1266,33 @@ int evh_surf_enable(evh_ctx* c, int max_surf_features) {
   if (!c) return EVH_ERR_INVALID;
   return evh_surf_allocate(c, max_surf_features);
 }
-int evh_surf_capacity(const evh_ctx* c) { return c ? c->surf_cap : EVH_ERR_INVALID; }
+int evh_surf_capacity(const evh_ctx* c) { return c ? c->surf.cap : EVH_ERR_INVALID; }
 
 int evh_surf_detect_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
                           int64_t row_stride, int64_t frame_stride, int w, int h, double hessian_threshold) {
   if (!c) return EVH_ERR_INVALID;
-  if (!c->surf_cap) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_detect_batch: call evh_surf_enable first");
+  if (!c->surf.cap) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_detect_batch: call evh_surf_enable first");
   if (!(hessian_threshold >= 0)) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_detect_batch: hessian_threshold must be >= 0");
-  int rc = join_solve(c);
-  if (rc) return rc;
-  const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
-  if ((rc = ingest_level0(c, "evh_surf_detect_batch", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w,
-                          src_h, w, h, nf)))
-    return rc;
-  c->nframes_resident = 0;
-  return evh_launch_surf(c, nframes, w, h, (float)hessian_threshold);
+  return kp_detect_batch(c, "evh_surf_detect_batch", d_frames, nframes, src_w, src_h, channels, row_stride, frame_stride, w, h,
+                         [&] { return evh_launch_surf(c, nframes, w, h, (float)hessian_threshold); });
 }
 
 int evh_surf_count(evh_ctx* c, int frame) {
-  if (!c || frame < 0 || frame >= c->surf_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "bad SURF frame slot");
-  int fl = 0;
-  const int n = frame_count(c, feat_view(c, EVH_FEATURE_SURF), frame, &fl);
-  if (n < 0) return n;
-  if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "more SURF key points than evh_surf_enable reserved for a frame");
-  return n;
+  return kp_count(c, EVH_FEATURE_SURF, "SURF", "more SURF key points than evh_surf_enable reserved for a frame", frame);
 }
 
 int evh_surf_download(evh_ctx* c, int frame, float* h_xy, float* h_desc, float* h_size, float* h_angle, float* h_response,
                       int32_t* h_octave, int32_t* h_laplacian) {
   const int n = evh_surf_count(c, frame);
   if (n <= 0) return n;
-  const size_t o = (size_t)frame * c->surf_cap;
-  std::vector<float> rec((size_t)n * 8);
-  EVH_HIP(c, hipMemcpyAsync(rec.data(), c->d_surf_kp + o * 8, sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream));
-  if (h_desc) EVH_HIP(c, hipMemcpyAsync(h_desc, c->d_surf_desc + o * 128, sizeof(float) * 128 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  unpack_records(rec, n, h_xy, h_size, h_angle, h_response, h_octave, h_laplacian);
+  if (int rc = kp_download(c, c->surf, frame, n, h_desc, h_xy, h_size, h_angle, h_response, h_octave, h_laplacian)) return rc;
   return n;
 }
 
 int evh_surf_download_integral(evh_ctx* c, int frame, int32_t* h_sum) {
   if (!c || !h_sum || !c->surf_tab_w || frame < 0) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_download_integral: bad argument");
-  const int g0 = ((c->surf_frames_resident - 1) / c->surf_group) * c->surf_group;
-  if (frame < g0 || frame >= c->surf_frames_resident) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_download_integral: that frame's integral image is no longer resident");
+  const int g0 = ((c->surf.frames_resident - 1) / c->surf.group) * c->surf.group;
+  if (frame < g0 || frame >= c->surf.frames_resident) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_download_integral: that frame's integral image is no longer resident");
   const int w = c->surf_tab_w, h = c->surf_tab_h, st = (w + 1 + 15) & ~15;
   EVH_HIP(c, hipMemcpy2DAsync(h_sum, sizeof(int) * (w + 1), c->d_surf_sum + (int64_t)(frame - g0) * c->surf_sum_frame_ints, sizeof(int) * st,
                               sizeof(int) * (w + 1), h + 1, hipMemcpyDeviceToHost, c->stream));

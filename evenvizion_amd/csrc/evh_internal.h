@@ -47,6 +47,23 @@ struct EvhSiftGeom {
   int64_t frame_floats, tmp_floats;
 };
 
+// N4: a float detector's (SIFT, SURF) per-frame key-point lists.  A record is 8 floats: x, y, size, angle, response,
+// octave bits, (SURF) laplacian bits, 0.  EvhKpDev is the part the kernels are handed.
+struct EvhKpDev {
+  float* raw = nullptr; int* nraw = nullptr;    // [F][cap][8] key points as detected, [F] how many (may exceed cap)
+  float* srt = nullptr;                         // [F][cap][8] in the operator's order
+  float* kp = nullptr;                          // [F][cap][8] final records
+  float* xy = nullptr;                          // [F][cap][2]
+  uint8_t* desc = nullptr;                      // [F][cap] descriptor rows (SIFT: 128 uint8 VALUES 0..255, SURF: 128 float)
+  int* count = nullptr; int* flags = nullptr;   // [F] final records; bit0: a buffer of this frame overflowed
+  int cap = 0;                                  // records per frame slot (0: the detector is not enabled)
+};
+struct EvhKpList : EvhKpDev {
+  int desc_row_bytes = 0;
+  int group = 0;                                // frames whose working buffers (scale space / integral + Hessian) are resident at once
+  int frames_resident = 0;                      // frames of the last launch
+};
+
 // the frames an entry was handed: packed rows of `channels` bytes per pixel, or (yuv) decoded 4:2:0 planes
 struct EvhFrames {
   const uint8_t* packed = nullptr; int channels = 0; int64_t row_stride = 0, frame_stride = 0;
@@ -153,30 +170,22 @@ struct evh_ctx {
   char* d_scratch = nullptr;      // growable scratch of the host-pointer entries (N1 / N3): no hipMalloc per call
   size_t scratch_bytes = 0;
   // ---- N4: SIFT (allocated by evh_sift_enable) ----
-  int sift_cap = 0, sift_cand_cap = 0, sift_group = 0, sift_frames_resident = 0;
+  EvhKpList sift;                 // the key-point lists; records: x, y, size, angle, response, octave bits
+  int sift_cand_cap = 0;
   EvhSiftGeom sg{}; bool sift_geom_valid = false;
   int64_t sift_pyr_frame_floats = 0, sift_tmp_frame_floats = 0;
   float* d_sift_pyr = nullptr;    // [group][frame_floats] Gaussian scale space
   float* d_sift_tmp = nullptr;    // [group][octave-0 layer] row-pass temporary
   uint32_t* d_sift_cand = nullptr; int* d_sift_ncand = nullptr;   // extrema: octave<<28 | layer<<26 | r<<13 | c
-  float* d_sift_raw = nullptr; int* d_sift_nraw = nullptr;        // [F][cap][8] key points before the sort
-  float* d_sift_srt = nullptr;    // [F][cap][8] sorted
-  float* d_sift_kp = nullptr;     // [F][cap][8] final records: x, y, size, angle, response, octave bits
-  float* d_sift_xy = nullptr;     // [F][cap][2]
-  uint8_t* d_sift_desc = nullptr; // [F][cap][128] descriptor VALUES (0..255; the operator returns them as float32)
-  int* d_sift_count = nullptr; int* d_sift_flags = nullptr;
   // ---- N4: SURF (allocated by evh_surf_enable) ----
-  int surf_cap = 0, surf_group = 0, surf_frames_resident = 0, surf_tab_w = 0, surf_tab_h = 0;
+  EvhKpList surf;                 // the key-point lists; records: ... octave bits, laplacian bits
+  int surf_tab_w = 0, surf_tab_h = 0;
   int64_t surf_sum_frame_ints = 0, surf_det_frame_floats = 0;
   char* d_surf_tabs = nullptr;    // SurfTabs: layer boxes, orientation / descriptor weights
   int* d_surf_sum = nullptr;      // [group] integral images, (h+1) x (w+1)
   float* d_surf_det = nullptr; float* d_surf_trace = nullptr;   // [group] the 20 Hessian layers
-  float* d_surf_raw = nullptr; int* d_surf_nraw = nullptr; float* d_surf_srt = nullptr;
-  float* d_surf_kp = nullptr;     // [F][cap][8] x, y, size, angle, response, octave bits, laplacian bits
-  float* d_surf_xy = nullptr; float* d_surf_desc = nullptr;     // [F][cap][2], [F][cap][128] float
-  int* d_surf_count = nullptr; int* d_surf_flags = nullptr;
   // multi-type pairs (frame_processing.py:91-104): per-type match / static rows, their concatenation, the merged rows
-  EvhPairBufs mt;                 // stride mt.cap = kcap + sift_cap + surf_cap
+  EvhPairBufs mt;                 // stride mt.cap = kcap + sift.cap + surf.cap
   float* d_acc = nullptr; int* d_nacc = nullptr; int* d_accstatus = nullptr;
   std::vector<void**> owned;      // the pointer members above that hold a live hipMalloc (dalloc / grow): what evh_destroy frees
   size_t bytes_allocated = 0;
@@ -230,6 +239,21 @@ void dfree(evh_ctx* c, T** p) {
   if (it == c->owned.end()) return;
   (void)hipFree(*p); *p = nullptr;
   c->owned.erase(it);
+}
+// the lists of a float detector (inside the caller's release-on-failure bracket): max_features records per frame slot,
+// descriptor rows of desc_row_bytes; `who` names the entry in the message
+inline int alloc_kp_list(evh_ctx* c, EvhKpList& L, const char* who, int max_features, int desc_row_bytes) {
+  if (max_features < 64 || max_features > 65536) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": capacity out of range (64..65536)");
+  const size_t F = (size_t)c->max_frames, cap = (size_t)((max_features + 63) & ~63);
+  int rc;
+  if ((rc = dalloc(c, &L.raw, F * cap * 8)) || (rc = dalloc(c, &L.nraw, F)) || (rc = dalloc(c, &L.srt, F * cap * 8)) ||
+      (rc = dalloc(c, &L.kp, F * cap * 8)) || (rc = dalloc(c, &L.xy, F * cap * 2)) ||
+      (rc = dalloc(c, &L.desc, F * cap * desc_row_bytes)) || (rc = dalloc(c, &L.count, F)) || (rc = dalloc(c, &L.flags, F)))
+    return rc;
+  EVH_HIP(c, hipMemsetAsync(L.count, 0, F * sizeof(int), c->stream));
+  EVH_HIP(c, hipMemsetAsync(L.flags, 0, F * sizeof(int), c->stream));
+  L.cap = (int)cap; L.desc_row_bytes = desc_row_bytes;
+  return EVH_SUCCESS;
 }
 // grow-on-demand workspace: kernels already enqueued may still use the old one, so the stream drains before it is freed
 template <class T>

@@ -37,11 +37,7 @@ struct SiftArgs {
   float* pyr; int64_t pyr_frame_floats;      // [group][frame_floats]
   float* tmp; int64_t tmp_frame_floats;      // [group][octave-0 layer]
   uint32_t* cand; int* ncand; int cand_cap;  // [F][cand_cap], [F]
-  float* raw; int* nraw;                     // [F][cap][8], [F]
-  float* srt;                                // [F][cap][8] sorted
-  float* kp;                                 // [F][cap][8] final: x, y, size, angle, response, octave bits
-  float* xy; uint8_t* desc; int* count; int* flags;
-  int cap;
+  EvhKpDev L;                                // final records: x, y, size, angle, response, octave bits; desc: 128 uint8
 };
 
 __device__ __forceinline__ int reflect101(int p, int n) {
@@ -373,7 +369,7 @@ __global__ __launch_bounds__(64 * SR_WAVES) void k_sift_refine(SiftArgs A, int f
     __builtin_amdgcn_wave_barrier();                         // s_map / s_val / s_hist are free for the next candidate
     if (pm) {
       int base = 0;
-      if (lane == 0) base = atomicAdd(A.nraw + f, __popcll(pm));
+      if (lane == 0) base = atomicAdd(A.L.nraw + f, __popcll(pm));
       base = __shfl(base, 0);
       if (peak) {
         float bin = (float)lane + 0.5f * (hl - hr) / (hl - 2 * hv + hr);
@@ -381,8 +377,8 @@ __global__ __launch_bounds__(64 * SR_WAVES) void k_sift_refine(SiftArgs A, int f
         float ang = 360.f - (float)((360.f / 36) * bin);
         if (fabsf(ang - 360.f) < FLT_EPSILON) ang = 0.f;
         const int slot = base + __popcll(pm & ((1ull << lane) - 1ull));
-        if (slot < A.cap) {
-          float* o = A.raw + ((int64_t)f * A.cap + slot) * 8;
+        if (slot < A.L.cap) {
+          float* o = A.L.raw + ((int64_t)f * A.L.cap + slot) * 8;
           o[0] = kx; o[1] = ky; o[2] = ksize; o[3] = ang; o[4] = kresp; o[5] = __int_as_float(koct); o[6] = 0.f; o[7] = 0.f;
         }
       }
@@ -408,10 +404,10 @@ __global__ __launch_bounds__(256) void k_sift_rank(SiftArgs A, int f0) {
   // extremum).  (Full records through LDS and two full comparisons per pair: 33.6 ms per 33 frames of 25 800 key points.)
   __shared__ float T[2048];
   const int f = f0 + blockIdx.y;
-  const int n = A.nraw[f];
-  if (n > A.cap || A.ncand[f] > A.cand_cap) return;        // flagged by k_sift_dedup
+  const int n = A.L.nraw[f];
+  if (n > A.L.cap || A.ncand[f] > A.cand_cap) return;        // flagged by k_sift_dedup
   if ((int)blockIdx.x * 256 >= n) return;
-  const float* R = A.raw + (int64_t)f * A.cap * 8;
+  const float* R = A.L.raw + (int64_t)f * A.L.cap * 8;
   const int i = blockIdx.x * 256 + threadIdx.x;
   KpRec me{0, 0, 0, 0, 0, 0};
   if (i < n) { const float* p = R + (int64_t)i * 8; me = KpRec{p[0], p[1], p[2], p[3], p[4], __float_as_int(p[5])}; }
@@ -447,7 +443,7 @@ __global__ __launch_bounds__(256) void k_sift_rank(SiftArgs A, int f0) {
     }
   }
   if (i < n) {
-    float* o = A.srt + ((int64_t)f * A.cap + rank) * 8;
+    float* o = A.L.srt + ((int64_t)f * A.L.cap + rank) * 8;
     o[0] = me.x; o[1] = me.y; o[2] = me.size; o[3] = me.angle; o[4] = me.resp; o[5] = __int_as_float(me.oct);
   }
 }
@@ -457,14 +453,14 @@ __global__ __launch_bounds__(1024) void k_sift_dedup(SiftArgs A, int f0) {
   __shared__ int wtot[16];
   __shared__ int s_base;
   const int f = f0 + blockIdx.x;
-  const int n = A.nraw[f];
-  if (n > A.cap || A.ncand[f] > A.cand_cap) {
-    if (threadIdx.x == 0) { A.count[f] = 0; A.flags[f] = 1; }
+  const int n = A.L.nraw[f];
+  if (n > A.L.cap || A.ncand[f] > A.cand_cap) {
+    if (threadIdx.x == 0) { A.L.count[f] = 0; A.L.flags[f] = 1; }
     return;
   }
   if (threadIdx.x == 0) s_base = 0;
   __syncthreads();
-  const float* S = A.srt + (int64_t)f * A.cap * 8;
+  const float* S = A.L.srt + (int64_t)f * A.L.cap * 8;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int c0 = 0; c0 < n; c0 += 1024) {
     const int i = c0 + threadIdx.x;
@@ -487,16 +483,16 @@ __global__ __launch_bounds__(1024) void k_sift_dedup(SiftArgs A, int f0) {
       int oct = __float_as_int(b[5]);
       oct = (oct & ~255) | ((oct + (-1)) & 255);
       const float scale = 1.f / (float)(1 << 1);
-      float* o = A.kp + ((int64_t)f * A.cap + slot) * 8;
+      float* o = A.L.kp + ((int64_t)f * A.L.cap + slot) * 8;
       const float x = b[0] * scale, y = b[1] * scale;
       o[0] = x; o[1] = y; o[2] = b[2] * scale; o[3] = b[3]; o[4] = b[4]; o[5] = __int_as_float(oct);
-      A.xy[((int64_t)f * A.cap + slot) * 2] = x; A.xy[((int64_t)f * A.cap + slot) * 2 + 1] = y;
+      A.L.xy[((int64_t)f * A.L.cap + slot) * 2] = x; A.L.xy[((int64_t)f * A.L.cap + slot) * 2 + 1] = y;
     }
     __syncthreads();
     if (threadIdx.x == 0) s_base += tot;
     __syncthreads();
   }
-  if (threadIdx.x == 0) { A.count[f] = s_base; A.flags[f] = 0; }
+  if (threadIdx.x == 0) { A.L.count[f] = s_base; A.L.flags[f] = 0; }
 }
 
 // ---- calcSIFTDescriptor: one workgroup per key point -------------------------------------------------------------------------
@@ -514,10 +510,10 @@ __global__ __launch_bounds__(256) void k_sift_desc(SiftArgs A, int f0) {
   __shared__ float s_scale;
   __shared__ unsigned s_map[160 * 8];            // per bin: which of the chunk's 256 samples fall on it
   const int gf = blockIdx.y, f = f0 + gf, ki = blockIdx.x, tid = threadIdx.x;
-  if (ki >= A.count[f]) return;
+  if (ki >= A.L.count[f]) return;
   for (int i = tid; i < 160 * 8; i += 256) s_map[i] = 0u;
   __syncthreads();                                             // before any sample ORs its bits in
-  const float* rec = A.kp + ((int64_t)f * A.cap + ki) * 8;
+  const float* rec = A.L.kp + ((int64_t)f * A.L.cap + ki) * 8;
   const int koct = __float_as_int(rec[5]);
   int oct = koct & 255;
   const int layer = (koct >> 8) & 255;
@@ -723,7 +719,7 @@ __global__ __launch_bounds__(256) void k_sift_desc(SiftArgs A, int f0) {
   __syncthreads();
   if (tid < 128) {
     const int v = (int)rintf(s_dst[tid] * s_scale);
-    A.desc[((int64_t)f * A.cap + ki) * 128 + tid] = (uint8_t)min(max(v, 0), 255);
+    A.L.desc[((int64_t)f * A.L.cap + ki) * 128 + tid] = (uint8_t)min(max(v, 0), 255);
   }
 }
 
@@ -768,9 +764,7 @@ SiftArgs sift_args(evh_ctx* c) {
   A.pyr = c->d_sift_pyr; A.pyr_frame_floats = c->sift_pyr_frame_floats;
   A.tmp = c->d_sift_tmp; A.tmp_frame_floats = c->sift_tmp_frame_floats;
   A.cand = c->d_sift_cand; A.ncand = c->d_sift_ncand; A.cand_cap = c->sift_cand_cap;
-  A.raw = c->d_sift_raw; A.nraw = c->d_sift_nraw; A.srt = c->d_sift_srt; A.kp = c->d_sift_kp;
-  A.xy = c->d_sift_xy; A.desc = c->d_sift_desc; A.count = c->d_sift_count; A.flags = c->d_sift_flags;
-  A.cap = c->sift_cap;
+  A.L = c->sift;
   return A;
 }
 
@@ -779,36 +773,25 @@ SiftArgs sift_args(evh_ctx* c) {
 // allocate the SIFT buffers of a context (once): max_sift_features key points per frame slot, the scale space of a
 // group of frames sized for the context's largest frame
 int evh_sift_allocate(evh_ctx* c, int max_sift_features) {
-  if (c->sift_cap) return max_sift_features <= c->sift_cap ? EVH_SUCCESS
+  if (c->sift.cap) return max_sift_features <= c->sift.cap ? EVH_SUCCESS
                                                             : evh_fail(c, EVH_ERR_CAPACITY, "evh_sift_enable: already enabled with a smaller capacity");
-  if (max_sift_features < 64 || max_sift_features > 65536) return evh_fail(c, EVH_ERR_INVALID, "evh_sift_enable: capacity out of range (64..65536)");
+  int rc;
+  const size_t first = c->owned.size();
+  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
+#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); c->sift = EvhKpList{}; return rc; }
+  S_(alloc_kp_list(c, c->sift, "evh_sift_enable", max_sift_features, 128));
   EvhSiftGeom gm;
   sift_geometry(c->max_w, c->max_h, gm);
   // frames whose scale space is resident at once: at most 8 GiB of pyramid
   const size_t per_frame = (size_t)(gm.frame_floats + gm.tmp_floats) * sizeof(float);
-  int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->max_frames, ((size_t)8 << 30) / per_frame));
-  const int cap = (max_sift_features + 63) & ~63;
-  const size_t F = (size_t)c->max_frames;
-  int rc;
-  const size_t first = c->owned.size();
-  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
-#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); return rc; }
+  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->max_frames, ((size_t)8 << 30) / per_frame));
+  const size_t F = (size_t)c->max_frames, cand_cap = 4 * (size_t)c->sift.cap;
   S_(dalloc(c, &c->d_sift_pyr, (size_t)group * gm.frame_floats + 64));
   S_(dalloc(c, &c->d_sift_tmp, (size_t)group * gm.tmp_floats + 64));
-  S_(dalloc(c, &c->d_sift_cand, F * 4 * cap));
+  S_(dalloc(c, &c->d_sift_cand, F * cand_cap));
   S_(dalloc(c, &c->d_sift_ncand, F));
-  S_(dalloc(c, &c->d_sift_raw, F * cap * 8));
-  S_(dalloc(c, &c->d_sift_nraw, F));
-  S_(dalloc(c, &c->d_sift_srt, F * cap * 8));
-  S_(dalloc(c, &c->d_sift_kp, F * cap * 8));
-  S_(dalloc(c, &c->d_sift_xy, F * cap * 2));
-  S_(dalloc(c, &c->d_sift_desc, F * cap * 128));
-  S_(dalloc(c, &c->d_sift_count, F));
-  S_(dalloc(c, &c->d_sift_flags, F));
 #undef S_
-  EVH_HIP(c, hipMemsetAsync(c->d_sift_count, 0, F * sizeof(int), c->stream));
-  EVH_HIP(c, hipMemsetAsync(c->d_sift_flags, 0, F * sizeof(int), c->stream));
-  c->sift_cap = cap; c->sift_cand_cap = 4 * cap; c->sift_group = group;
+  c->sift_cand_cap = (int)cand_cap; c->sift.group = group;
   c->sift_pyr_frame_floats = gm.frame_floats; c->sift_tmp_frame_floats = gm.tmp_floats;
   return EVH_SUCCESS;
 }
@@ -816,7 +799,7 @@ int evh_sift_allocate(evh_ctx* c, int max_sift_features) {
 // SIFT on the frames whose gray level 0 is resident in the context's ORB pyramid (evh_launch_gray_level0 /
 // evh_launch_ingest_level0 ran for (w, h)): scale space, extrema, key points, descriptors
 int evh_launch_sift(evh_ctx* c, int nframes, int w, int h) {
-  if (!c->sift_cap) return evh_fail(c, EVH_ERR_INVALID, "SIFT is not enabled on this context (evh_sift_enable)");
+  if (!c->sift.cap) return evh_fail(c, EVH_ERR_INVALID, "SIFT is not enabled on this context (evh_sift_enable)");
   if (w >= 4096 || h >= 4096) return evh_fail(c, EVH_ERR_UNSUPPORTED, "SIFT: frames must be smaller than 4096 in each dimension");
   EvhSiftGeom g;
   sift_geometry(w, h, g);
@@ -840,7 +823,7 @@ int evh_launch_sift(evh_ctx* c, int nframes, int w, int h) {
   const int threshold = (int)std::floor(0.5 * 0.04 / SL * 255);
   const EvhLevel& L0 = c->g.lv[0];
   EVH_HIP(c, hipMemsetAsync(c->d_sift_ncand, 0, sizeof(int) * (size_t)nframes, s));
-  EVH_HIP(c, hipMemsetAsync(c->d_sift_nraw, 0, sizeof(int) * (size_t)nframes, s));
+  EVH_HIP(c, hipMemsetAsync(c->sift.nraw, 0, sizeof(int) * (size_t)nframes, s));
   auto blur = [&](const float* src, float* dst, int o, int ng, const SiftTaps& T) {
     const int ow = g.ow[o], oh = g.oh[o], os = g.os[o];
     hipLaunchKernelGGL(k_sift_blur_row, dim3((ow + 255) / 256, oh, ng), dim3(256), 0, s, src, c->sift_pyr_frame_floats, c->d_sift_tmp,
@@ -848,8 +831,8 @@ int evh_launch_sift(evh_ctx* c, int nframes, int w, int h) {
     hipLaunchKernelGGL(k_sift_blur_col, dim3((ow + SC_W - 1) / SC_W, (oh + SC_H - 1) / SC_H, ng), dim3(256), 0, s, c->d_sift_tmp,
                        c->sift_tmp_frame_floats, dst, c->sift_pyr_frame_floats, ow, oh, os, T);
   };
-  for (int f0 = 0; f0 < nframes; f0 += c->sift_group) {
-    const int ng = std::min(c->sift_group, nframes - f0);
+  for (int f0 = 0; f0 < nframes; f0 += c->sift.group) {
+    const int ng = std::min(c->sift.group, nframes - f0);
     if (ng > 21845) return evh_fail(c, EVH_ERR_CAPACITY, "SIFT: too many frames in one group");
     auto LP = [&](int o, int l) { return c->d_sift_pyr + g.ooff[o] + (int64_t)l * g.os[o] * g.oh[o]; };
     // octave 0: frame x2 into the slot of layer 1 (overwritten below), blurred by sig_diff into layer 0
@@ -869,11 +852,11 @@ int evh_launch_sift(evh_ctx* c, int nframes, int w, int h) {
     }
     EVH_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(k_sift_refine, dim3(std::max(1, std::min(c->sift_cand_cap / SR_WAVES, 2048)), ng), dim3(64 * SR_WAVES), 0, s, A, f0);
-    hipLaunchKernelGGL(k_sift_rank, dim3((c->sift_cap + 255) / 256, ng), dim3(256), 0, s, A, f0);
+    hipLaunchKernelGGL(k_sift_rank, dim3((c->sift.cap + 255) / 256, ng), dim3(256), 0, s, A, f0);
     hipLaunchKernelGGL(k_sift_dedup, dim3(ng), dim3(1024), 0, s, A, f0);
-    hipLaunchKernelGGL(k_sift_desc, dim3(c->sift_cap, ng), dim3(256), 0, s, A, f0);
+    hipLaunchKernelGGL(k_sift_desc, dim3(c->sift.cap, ng), dim3(256), 0, s, A, f0);
     EVH_HIP(c, hipGetLastError());
   }
-  c->sift_frames_resident = nframes;
+  c->sift.frames_resident = nframes;
   return EVH_SUCCESS;
 }

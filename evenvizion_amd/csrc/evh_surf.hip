@@ -39,9 +39,7 @@ struct SurfArgs {
   const uint8_t* gray; int64_t gray_frame_bytes; int gstride; int w, h;
   int* sum; int64_t sum_frame_ints; int sstride;             // [group]
   float* det; float* trace; int64_t det_frame_floats;        // [group]
-  float* raw; int* nraw; float* srt; int* nsrt;              // [F][cap][8]
-  float* kp; float* xy; float* desc; int* count; int* flags; // final
-  int cap;
+  EvhKpDev L;     // final records: x, y, size, angle, response, octave bits, laplacian bits; desc: 128 float
 };
 
 // ---- integral image ---------------------------------------------------------------------------------------------------------
@@ -174,12 +172,12 @@ __global__ __launch_bounds__(256) void k_surf_maxima(SurfArgs A, int f0, float t
   if (m) {
     const int lane = threadIdx.x & 63;
     int basei = 0;
-    if (lane == 0) basei = atomicAdd(A.nraw + f0 + gf, __popcll(m));
+    if (lane == 0) basei = atomicAdd(A.L.nraw + f0 + gf, __popcll(m));
     basei = __shfl(basei, 0);
     if (hit) {
       const int slot = basei + __popcll(m & ((1ull << lane) - 1ull));
-      if (slot < A.cap) {
-        float* o = A.raw + ((int64_t)(f0 + gf) * A.cap + slot) * 8;
+      if (slot < A.L.cap) {
+        float* o = A.L.raw + ((int64_t)(f0 + gf) * A.L.cap + slot) * 8;
         o[0] = kx; o[1] = ky; o[2] = ksz; o[3] = -1.f; o[4] = val0; o[5] = __int_as_float(octave); o[6] = __int_as_float(lap); o[7] = 0.f;
       }
     }
@@ -204,10 +202,10 @@ __global__ __launch_bounds__(256) void k_surf_rank(SurfArgs A, int f0) {
   // comparison: a tile of responses goes through LDS, the full record is fetched only where they are equal.
   __shared__ float T[2048];
   const int f = f0 + blockIdx.y;
-  const int n = A.nraw[f];
-  if (n > A.cap) return;
+  const int n = A.L.nraw[f];
+  if (n > A.L.cap) return;
   if ((int)blockIdx.x * 256 >= n) return;
-  const float* R = A.raw + (int64_t)f * A.cap * 8;
+  const float* R = A.L.raw + (int64_t)f * A.L.cap * 8;
   const int i = blockIdx.x * 256 + threadIdx.x;
   SKp me{0, 0, 0, 0, 0};
   if (i < n) { const float* p = R + (int64_t)i * 8; me = SKp{p[0], p[1], p[2], p[4], __float_as_int(p[5])}; }
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(256) void k_surf_rank(SurfArgs A, int f0) {
   }
   if (i < n) {
     const float* p = R + (int64_t)i * 8;
-    float* o = A.srt + ((int64_t)f * A.cap + rank) * 8;
+    float* o = A.L.srt + ((int64_t)f * A.L.cap + rank) * 8;
 #pragma unroll
     for (int k = 0; k < 8; k++) o[k] = p[k];
   }
@@ -267,11 +265,11 @@ __global__ __launch_bounds__(1024) void k_surf_compact(SurfArgs A, int f0) {
   __shared__ int wtot[16];
   __shared__ int s_base;
   const int f = f0 + blockIdx.x;
-  const int n = A.nraw[f];
-  if (n > A.cap) { if (threadIdx.x == 0) { A.count[f] = 0; A.flags[f] = 1; } return; }
+  const int n = A.L.nraw[f];
+  if (n > A.L.cap) { if (threadIdx.x == 0) { A.L.count[f] = 0; A.L.flags[f] = 1; } return; }
   if (threadIdx.x == 0) s_base = 0;
   __syncthreads();
-  const float* S = A.srt + (int64_t)f * A.cap * 8;
+  const float* S = A.L.srt + (int64_t)f * A.L.cap * 8;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int c0 = 0; c0 < n; c0 += 1024) {
     const int i = c0 + threadIdx.x;
@@ -285,16 +283,16 @@ __global__ __launch_bounds__(1024) void k_surf_compact(SurfArgs A, int f0) {
     if (keep) {
       const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
       const float* b = S + (int64_t)i * 8;
-      float* o = A.kp + ((int64_t)f * A.cap + slot) * 8;
+      float* o = A.L.kp + ((int64_t)f * A.L.cap + slot) * 8;
 #pragma unroll
       for (int k = 0; k < 8; k++) o[k] = b[k];
-      A.xy[((int64_t)f * A.cap + slot) * 2] = b[0]; A.xy[((int64_t)f * A.cap + slot) * 2 + 1] = b[1];
+      A.L.xy[((int64_t)f * A.L.cap + slot) * 2] = b[0]; A.L.xy[((int64_t)f * A.L.cap + slot) * 2 + 1] = b[1];
     }
     __syncthreads();
     if (threadIdx.x == 0) s_base += tot;
     __syncthreads();
   }
-  if (threadIdx.x == 0) { A.count[f] = s_base; A.flags[f] = 0; }
+  if (threadIdx.x == 0) { A.L.count[f] = s_base; A.L.flags[f] = 0; }
 }
 
 // resizeHaarPattern for the two-box gradient wavelets (oldSize 4)
@@ -334,8 +332,9 @@ __global__ __launch_bounds__(256) void k_surf_describe(SurfArgs A, int f0, int w
   extern __shared__ float s_rowbuf[];              // [win_size][21] horizontal INTER_AREA sums (float, or int bits on the integer path)
   __shared__ DescLds S;
   const int gf = blockIdx.y, f = f0 + gf, ki = blockIdx.x, tid = threadIdx.x;
-  if (ki >= A.count[f]) return;
-  float* rec = A.kp + ((int64_t)f * A.cap + ki) * 8;
+  if (ki >= A.L.count[f]) return;
+  float* rec = A.L.kp + ((int64_t)f * A.L.cap + ki) * 8;
+  float* desc = reinterpret_cast<float*>(A.L.desc);            // SURF rows are 128 float
   const float cx = rec[0], cy = rec[1], size = rec[2];
   const int srows = A.h + 1, scols = A.w + 1;
   const float s = size * 1.2f / 9.0f;
@@ -398,7 +397,7 @@ __global__ __launch_bounds__(256) void k_surf_describe(SurfArgs A, int f0, int w
   const float sin_dir = S.sin_dir, cos_dir = S.cos_dir;
   const int win = (int)((float)(SU_PATCH + 1) * s);
   if (win < 1 || win > SU_WINMAX) {                 // cannot happen for sizes the detector emits (<= 264)
-    for (int k = tid; k < 128; k += 256) A.desc[((int64_t)f * A.cap + ki) * 128 + k] = 0.f;
+    for (int k = tid; k < 128; k += 256) desc[((int64_t)f * A.L.cap + ki) * 128 + k] = 0.f;
     return;
   }
   if (tid == 0) {                                   // start_x += sin_dir, start_y += cos_dir: float running sums over the rows
@@ -531,7 +530,7 @@ __global__ __launch_bounds__(256) void k_surf_describe(SurfArgs A, int f0, int w
     S.scale = (float)(1. / (sqrt(square_mag) + (double)FLT_EPSILON));
   }
   __syncthreads();
-  if (tid < 128) A.desc[((int64_t)f * A.cap + ki) * 128 + tid] = S.vec[tid] * S.scale;
+  if (tid < 128) desc[((int64_t)f * A.L.cap + ki) * 128 + tid] = S.vec[tid] * S.scale;
 }
 
 void gauss_kernel_f(int n, double sigma, std::vector<float>& k) {
@@ -591,44 +590,32 @@ int64_t surf_tables(int w, int h, SurfTabs& T) {
 }  // namespace
 
 int evh_surf_allocate(evh_ctx* c, int max_surf_features) {
-  if (c->surf_cap) return max_surf_features <= c->surf_cap ? EVH_SUCCESS
+  if (c->surf.cap) return max_surf_features <= c->surf.cap ? EVH_SUCCESS
                                                             : evh_fail(c, EVH_ERR_CAPACITY, "evh_surf_enable: already enabled with a smaller capacity");
-  if (max_surf_features < 64 || max_surf_features > 65536) return evh_fail(c, EVH_ERR_INVALID, "evh_surf_enable: capacity out of range (64..65536)");
+  int rc;
+  const size_t first = c->owned.size();
+  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
+#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); c->surf = EvhKpList{}; return rc; }
+  S_(alloc_kp_list(c, c->surf, "evh_surf_enable", max_surf_features, 128 * (int)sizeof(float)));
   SurfTabs T{};
   const int64_t det_floats = surf_tables(c->max_w, c->max_h, T);
   const int sstride = (c->max_w + 1 + 15) & ~15;
   const int64_t sum_ints = (int64_t)sstride * (c->max_h + 1);
   const size_t per_frame = (size_t)(2 * det_floats + sum_ints) * 4;
   const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->max_frames, ((size_t)4 << 30) / per_frame));
-  const int cap = (max_surf_features + 63) & ~63;
-  const size_t F = (size_t)c->max_frames;
-  int rc;
-  const size_t first = c->owned.size();
-  // a partial allocation is released: the capacity stays 0, the context usable, and a later enable may succeed
-#define S_(call) if ((rc = (call)) != EVH_SUCCESS) { dfree_from(c, first); return rc; }
   S_(dalloc(c, &c->d_surf_tabs, sizeof(SurfTabs)));
   S_(dalloc(c, &c->d_surf_sum, (size_t)group * sum_ints + 64));
   S_(dalloc(c, &c->d_surf_det, (size_t)group * det_floats + 64));
   S_(dalloc(c, &c->d_surf_trace, (size_t)group * det_floats + 64));
-  S_(dalloc(c, &c->d_surf_raw, F * cap * 8));
-  S_(dalloc(c, &c->d_surf_nraw, F));
-  S_(dalloc(c, &c->d_surf_srt, F * cap * 8));
-  S_(dalloc(c, &c->d_surf_kp, F * cap * 8));
-  S_(dalloc(c, &c->d_surf_xy, F * cap * 2));
-  S_(dalloc(c, &c->d_surf_desc, F * cap * 128));
-  S_(dalloc(c, &c->d_surf_count, F));
-  S_(dalloc(c, &c->d_surf_flags, F));
 #undef S_
-  EVH_HIP(c, hipMemsetAsync(c->d_surf_count, 0, F * sizeof(int), c->stream));
-  EVH_HIP(c, hipMemsetAsync(c->d_surf_flags, 0, F * sizeof(int), c->stream));
-  c->surf_cap = cap; c->surf_group = group; c->surf_sum_frame_ints = sum_ints; c->surf_det_frame_floats = det_floats;
+  c->surf.group = group; c->surf_sum_frame_ints = sum_ints; c->surf_det_frame_floats = det_floats;
   c->surf_tab_w = c->surf_tab_h = 0;
   return EVH_SUCCESS;
 }
 
 // SURF on the frames whose gray level 0 is resident in the context's ORB pyramid
 int evh_launch_surf(evh_ctx* c, int nframes, int w, int h, float hessian_threshold) {
-  if (!c->surf_cap) return evh_fail(c, EVH_ERR_INVALID, "SURF is not enabled on this context (evh_surf_enable)");
+  if (!c->surf.cap) return evh_fail(c, EVH_ERR_INVALID, "SURF is not enabled on this context (evh_surf_enable)");
   if (w > c->max_w || h > c->max_h) return evh_fail(c, EVH_ERR_CAPACITY, "SURF: frame larger than the size given to evh_create");
   hipStream_t s = c->stream;
   if (c->surf_tab_w != w || c->surf_tab_h != h) {
@@ -645,24 +632,23 @@ int evh_launch_surf(evh_ctx* c, int nframes, int w, int h, float hessian_thresho
   A.gray = c->d_pyr + L0.off; A.gray_frame_bytes = c->g.pyr_frame_bytes; A.gstride = L0.stride; A.w = w; A.h = h;
   A.sum = c->d_surf_sum; A.sum_frame_ints = c->surf_sum_frame_ints; A.sstride = (w + 1 + 15) & ~15;
   A.det = c->d_surf_det; A.trace = c->d_surf_trace; A.det_frame_floats = c->surf_det_frame_floats;
-  A.raw = c->d_surf_raw; A.nraw = c->d_surf_nraw; A.srt = c->d_surf_srt; A.kp = c->d_surf_kp; A.xy = c->d_surf_xy;
-  A.desc = c->d_surf_desc; A.count = c->d_surf_count; A.flags = c->d_surf_flags; A.cap = c->surf_cap;
-  EVH_HIP(c, hipMemsetAsync(c->d_surf_nraw, 0, sizeof(int) * (size_t)nframes, s));
+  A.L = c->surf;
+  EVH_HIP(c, hipMemsetAsync(c->surf.nraw, 0, sizeof(int) * (size_t)nframes, s));
   const size_t lds = sizeof(float) * 21 * SU_WINMAX, lds_small = sizeof(float) * 21 * SU_WINSMALL;
   EVH_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_surf_describe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  for (int f0 = 0; f0 < nframes; f0 += c->surf_group) {
-    const int ng = std::min(c->surf_group, nframes - f0);
+  for (int f0 = 0; f0 < nframes; f0 += c->surf.group) {
+    const int ng = std::min(c->surf.group, nframes - f0);
     if (ng > 3000) return evh_fail(c, EVH_ERR_CAPACITY, "SURF: too many frames in one group");
     hipLaunchKernelGGL(k_surf_integral_rows, dim3(h + 1, ng), dim3(256), 0, s, A, f0);
     hipLaunchKernelGGL(k_surf_integral_cols, dim3((w + 256) / 256, ng), dim3(256), 0, s, A);
     hipLaunchKernelGGL(k_surf_det, dim3((w + 63) / 64, (h + 3) / 4, SU_NL * ng), dim3(256), 0, s, A);
     hipLaunchKernelGGL(k_surf_maxima, dim3((w + 63) / 64, (h + 3) / 4, SU_OCT * SU_LAY * ng), dim3(256), 0, s, A, f0, hessian_threshold);
-    hipLaunchKernelGGL(k_surf_rank, dim3((c->surf_cap + 255) / 256, ng), dim3(256), 0, s, A, f0);
+    hipLaunchKernelGGL(k_surf_rank, dim3((c->surf.cap + 255) / 256, ng), dim3(256), 0, s, A, f0);
     hipLaunchKernelGGL(k_surf_compact, dim3(ng), dim3(1024), 0, s, A, f0);
-    hipLaunchKernelGGL(k_surf_describe, dim3(c->surf_cap, ng), dim3(256), lds_small, s, A, f0, 0, SU_WINSMALL);
-    hipLaunchKernelGGL(k_surf_describe, dim3(c->surf_cap, ng), dim3(256), lds, s, A, f0, SU_WINSMALL, SU_WINMAX);
+    hipLaunchKernelGGL(k_surf_describe, dim3(c->surf.cap, ng), dim3(256), lds_small, s, A, f0, 0, SU_WINSMALL);
+    hipLaunchKernelGGL(k_surf_describe, dim3(c->surf.cap, ng), dim3(256), lds, s, A, f0, SU_WINSMALL, SU_WINMAX);
     EVH_HIP(c, hipGetLastError());
   }
-  c->surf_frames_resident = nframes;
+  c->surf.frames_resident = nframes;
   return EVH_SUCCESS;
 }

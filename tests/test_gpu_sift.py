@@ -413,6 +413,57 @@ def test_surf_large_scales_and_image_borders():
         c.close()
 
 
+def _tied(*keys):
+    """How many rows share their (keys...) tuple with at least one other row."""
+    rows = np.stack([np.ascontiguousarray(k).view(np.uint32) for k in keys], axis=1)
+    _, inv, cnt = np.unique(rows, axis=0, return_inverse=True, return_counts=True)
+    return int((cnt[inv.reshape(-1)] > 1).sum())
+
+
+def test_sort_ties_and_lists_longer_than_a_tile():
+    """The rank kernels' tie path, their 2048-entry tile loop and the second 1024-wide chunk of the ordered compaction,
+    at a small frame: a 64x64 texture tiled 6x10 repeats its blobs, so most SURF key points of frame 0 share (response,
+    size, octave) and are ordered by y, then x -- the last two comparator levels -- and most SIFT key points share their x;
+    frame 1 is a plain textured frame of the same size.  Both lists of both frames are longer than one tile."""
+    w, h = 640, 384
+    frames = [np.tile(S.make_pair(23, 64, 64)[0], (6, 10)), S.make_pair(23, w, h)[0]]
+    assert frames[0].shape == (h, w)
+    want_sift = [O.sift_detect(f, cap=65536) for f in frames]
+    want_surf = [O.surf_detect(f) for f in frames]
+    for o in want_sift + want_surf:
+        assert len(o["xy"]) > 2048
+    s0 = want_surf[0]
+    assert _tied(s0["response"], s0["size"], s0["octave"]) > len(s0["xy"]) // 2
+    k0 = want_sift[0]
+    assert _tied(k0["xy"][:, 0], k0["xy"][:, 1], k0["size"]) > 0
+    c = make_ctx(w, h, frames=2, sift=32768)
+    try:
+        c.surf_enable(8192)
+        d = dev(np.stack(frames))
+        c.sift_detect_batch(d)
+        for f in range(2):
+            _same_keypoints(c.sift_download(f), want_sift[f])
+        c.surf_detect_batch(d)
+        for f in range(2):
+            _same_surf(c.surf_download(f), want_surf[f])
+    finally:
+        c.close()
+
+
+def test_surf_capacity_is_flagged():
+    from evenvizion_amd._lib import EvhError
+    a = S.make_pair(5, 400, 224)[0]                         # the frame has ~800 key points
+    c = make_surf_ctx(400, 224, frames=2, surf=64)
+    try:
+        c.surf_detect_batch(dev(np.stack([a, a])))
+        with pytest.raises(EvhError):
+            c.surf_download(0)
+        c.surf_detect_batch(dev(np.full((2, 224, 400), 77, np.uint8)))
+        assert len(c.surf_download(0)["xy"]) == 0             # the flag clears with the next batch
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("features", [["SURF"], ["SURF", "SIFT", "ORB"]])
 def test_reference_default_type_list_stream_vs_oracle(features):
     """The reference's default FrameProcessing list (frame_processing.py:40) end to end in stream semantics."""

@@ -138,7 +138,7 @@ int evh_launch_select(evh_ctx* c, int nframes) {
     B.mask_frame_words = c->cv_mask_frame_words;
     int mo = 0;
     for (int l = 0; l < EVH_NLEVELS; l++) { B.mask_off[l] = mo; mo += ((A.lv[l].w + 31) / 32) * A.lv[l].h; }
-    if (mo > c->cv_mask_frame_words) return evh_fail(c, EVH_ERR_CAPACITY, "evh_launch_select: corner bit plane larger than the context's");
+    if (mo > c->cv_mask_frame_words) return evh_fail(c, EVH_ERR_CAPACITY, "evh_launch_select: row-major table scratch larger than the context's");
     B.heap_cap = 2 * q0 + 2;
     B.tdesc = c->d_cv_tdesc; B.total_tiles = c->g.total_tiles;
     { const char* e = getenv("EVH_CV_PHASE"); B.phase_limit = e ? atoi(e) : 0; }

@@ -8,6 +8,7 @@
 #include "evh_internal.h"
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -17,55 +18,18 @@ struct AreaTabDev {
   const int* ys; const int* ycnt; const int* ysi; const float* yal;
 };
 
-__global__ void k_resize_area(const uint8_t* __restrict__ src, int cn, int64_t src_stride, int64_t src_img_stride,
-                              uint8_t* __restrict__ dst, int dw, int dh, int64_t dst_stride, int64_t dst_img_stride,
-                              AreaTabDev T) {
-  const int img = blockIdx.z;
-  const int dy = blockIdx.y;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;  // dx*cn + c
-  if (e >= dw * cn) return;
-  const int dx = e / cn, c = e - dx * cn;
-  const uint8_t* S = src + (int64_t)img * src_img_stride;
-  const int x0 = T.xs[dx], xn = T.xcnt[dx], y0 = T.ys[dy], yn = T.ycnt[dy];
-  float sum = 0.f;
-  for (int j = 0; j < yn; j++) {
-    const uint8_t* row = S + (int64_t)T.ysi[y0 + j] * src_stride + c;
-    float buf = 0.f;
-    for (int k = 0; k < xn; k++) buf = buf + (float)row[(int64_t)T.xsi[x0 + k] * cn] * T.xal[x0 + k];
-    float term = T.yal[y0 + j] * buf;
-    sum = j == 0 ? term : sum + term;
-  }
-  int v = (int)rintf(sum);
-  dst[(int64_t)img * dst_img_stride + (int64_t)dy * dst_stride + e] = (uint8_t)min(max(v, 0), 255);
-}
-
-__global__ void k_resize_area_int(const uint8_t* __restrict__ src, int cn, int64_t src_stride, int64_t src_img_stride,
-                                  uint8_t* __restrict__ dst, int dw, int dh, int64_t dst_stride, int64_t dst_img_stride,
-                                  int isx, int isy) {
-  const int img = blockIdx.z, dy = blockIdx.y;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= dw * cn) return;
-  const int dx = e / cn, c = e - dx * cn;
-  const uint8_t* S = src + (int64_t)img * src_img_stride;
-  int sum = 0;
-  for (int j = 0; j < isy; j++)
-    for (int i = 0; i < isx; i++) sum += S[(int64_t)(dy * isy + j) * src_stride + (int64_t)(dx * isx + i) * cn + c];
-  int v;
-  if (isx == 2 && isy == 2) v = (sum + 2) >> 2;
-  else {
-    const float scale = 1.f / (float)(isx * isy);
-    v = (int)rintf((float)sum * scale);
-  }
-  dst[(int64_t)img * dst_img_stride + (int64_t)dy * dst_stride + e] = (uint8_t)min(max(v, 0), 255);
-}
-
-// N2: fused ingest.  The full-size frame is read ONCE: per output pixel the INTER_AREA sums of its channels
-// (same float32 tables and accumulation order as k_resize_area, rounded to uint8 per channel exactly as the resized
-// image would hold them), then cvtColor's gray weights on those bytes, written straight into pyramid level 0.  The
-// resized BGR image of video_processing.py:62,73 never exists in memory.
+// One thread per output pixel computes the rounded uint8 of each of its channels; the INGEST flag of a kernel says where
+// they go.  !INGEST: the cn bytes into the caller's packed rows (the stand-alone resize).  INGEST, N2, the
+// fused ingest: the full-size frame is read ONCE, cvtColor's gray weights are applied to the rounded bytes -- exactly what
+// the resized image would hold -- and the gray goes straight into pyramid level 0; the resized BGR image of
+// video_processing.py:62,73 never exists in memory.  The store keeps its row offset inside the subscript: formed ahead of
+// the gray weights (a named offset, a helper) it reorders the INGEST kernels (profiles/match_image_fold_isa.txt).
 __device__ __forceinline__ uint8_t gray_of(int b, int g, int r) { return (uint8_t)((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14); }
+__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
+// level 0's row stride is an int; the caller's of the stand-alone resize is whatever the ABI hands in
+template <bool INGEST> using area_stride_t = std::conditional_t<INGEST, int, int64_t>;
 
-// The ingest kernels are templated on where a source pixel's channel bytes come from: SRC::row(img, y) hands out a row,
+// The kernels are templated on where a source pixel's channel bytes come from: SRC::row(img, y) hands out a row,
 // Row::px(x, v) the pixel's bytes v[0 .. channels).
 struct PackedSrc {       // rows of cn bytes per pixel (BGR or gray)
   const uint8_t* p; int cn; int64_t stride, img_stride;
@@ -89,7 +53,6 @@ __device__ __forceinline__ ChromaTerms chroma_terms(int u, int v) {
   const int cu = (u << 3) - 1024, cv = (v << 3) - 1024;
   return {(cu * 16525) >> 16, ((cu * -3209) >> 16) + ((cv * -6660) >> 16), (cv * 13075) >> 16};
 }
-__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
 __device__ __forceinline__ void yuv_px(int y, const ChromaTerms& t, int (&v)[3]) {
   const int Y = (((y << 3) - 128) * 9539) >> 16;
   v[0] = sat8(Y + t.b); v[1] = sat8(Y + t.g); v[2] = sat8(Y + t.r);
@@ -111,9 +74,10 @@ struct Yuv420Src {       // 4:2:0 planes, chroma pixel stride cps = 1 (I420 / YV
   }
 };
 
-template <class SRC>
-__global__ __launch_bounds__(256) void k_ingest_area(SRC src, uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
-                                                     int dw, int dh, int dst_stride, AreaTabDev T) {
+// INTER_AREA when shrinking by a non-integer ratio: float32 tables, accumulated in table order (see the head of the file)
+template <bool INGEST, class SRC>
+__global__ __launch_bounds__(256) void k_area(SRC src, uint8_t* __restrict__ dst, int64_t dst_img_stride, int dw, int dh,
+                                              area_stride_t<INGEST> dst_stride, AreaTabDev T) {
   const int img = blockIdx.z, dy = blockIdx.y;
   const int dx = blockIdx.x * blockDim.x + threadIdx.x;
   if (dx >= dw) return;
@@ -136,8 +100,36 @@ __global__ __launch_bounds__(256) void k_ingest_area(SRC src, uint8_t* __restric
   }
   int v[3];
 #pragma unroll
-  for (int c = 0; c < 3; c++) v[c] = min(max((int)rintf(sum[c]), 0), 255);
-  pyr[(int64_t)img * pyr_frame_bytes + (int64_t)dy * dst_stride + dx] = cn == 3 ? gray_of(v[0], v[1], v[2]) : (uint8_t)v[0];
+  for (int c = 0; c < 3; c++) v[c] = sat8((int)rintf(sum[c]));
+  if constexpr (INGEST) {
+    dst[(int64_t)img * dst_img_stride + (int64_t)dy * dst_stride + dx] = cn == 3 ? gray_of(v[0], v[1], v[2]) : (uint8_t)v[0];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; c++) if (c < cn) dst[(int64_t)img * dst_img_stride + (int64_t)dy * dst_stride + dx * cn + c] = (uint8_t)v[c];
+  }
+}
+
+// ... by integer ratios: integer block sums; 2 x 2 rounds as (sum + 2) >> 2, every other block through float32.  The two
+// forms keep kernels of their own: the stand-alone one with a thread per output pixel measured 0.6 % slower than this
+// thread per channel element (profiles/match_image_fold_stats.txt), so only the dispatch is shared.
+__global__ void k_resize_area_int(const uint8_t* __restrict__ src, int cn, int64_t src_stride, int64_t src_img_stride,
+                                  uint8_t* __restrict__ dst, int dw, int dh, int64_t dst_stride, int64_t dst_img_stride,
+                                  int isx, int isy) {
+  const int img = blockIdx.z, dy = blockIdx.y;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= dw * cn) return;
+  const int dx = e / cn, c = e - dx * cn;
+  const uint8_t* S = src + (int64_t)img * src_img_stride;
+  int sum = 0;
+  for (int j = 0; j < isy; j++)
+    for (int i = 0; i < isx; i++) sum += S[(int64_t)(dy * isy + j) * src_stride + (int64_t)(dx * isx + i) * cn + c];
+  int v;
+  if (isx == 2 && isy == 2) v = (sum + 2) >> 2;
+  else {
+    const float scale = 1.f / (float)(isx * isy);
+    v = (int)rintf((float)sum * scale);
+  }
+  dst[(int64_t)img * dst_img_stride + (int64_t)dy * dst_stride + e] = (uint8_t)min(max(v, 0), 255);
 }
 
 template <class SRC>
@@ -410,6 +402,72 @@ void build_area_tab(int ssize, int dsize, double scale, HostTab& t) {
   }
 }
 
+// INTER_AREA tables of one (source, destination) geometry, kept on the device by the context: a stream resizes every
+// chunk with the same geometry.  A change of geometry drains the stream once (the previous tables may still be in use)
+// and uploads; calls at the cached geometry enqueue nothing and never synchronise.
+int area_tables(evh_ctx* c, int sw, int sh, int dw, int dh, double scale_x, double scale_y, AreaTabDev& T) {
+  const int geom[4] = {sw, sh, dw, dh};
+  if (std::memcmp(c->area_geom, geom, sizeof geom) != 0 || !c->d_area_tab) {
+    HostTab xt, yt;
+    build_area_tab(sw, dw, scale_x, xt);
+    build_area_tab(sh, dh, scale_y, yt);
+    std::vector<int> blob;
+    for (const HostTab* t : {&xt, &yt}) {
+      blob.insert(blob.end(), t->start.begin(), t->start.end());
+      blob.insert(blob.end(), t->cnt.begin(), t->cnt.end());
+      blob.insert(blob.end(), t->si.begin(), t->si.end());
+      for (float f : t->al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
+    }
+    EVH_HIP(c, hipStreamSynchronize(c->stream));
+    std::memset(c->area_geom, 0, sizeof geom);              // no geometry until the upload below has succeeded
+    if (int rc = grow(c, &c->d_area_tab, &c->area_tab_bytes, blob.size() * sizeof(int))) return rc;
+    EVH_HIP(c, hipMemcpy(c->d_area_tab, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice));
+    std::memcpy(c->area_geom, geom, sizeof geom); c->area_nx = (int)xt.si.size(); c->area_ny = (int)yt.si.size();
+  }
+  int* p = c->d_area_tab;
+  const size_t nx = (size_t)c->area_nx, ny = (size_t)c->area_ny;
+  T.xs = p; p += dw; T.xcnt = p; p += dw; T.xsi = p; p += nx; T.xal = reinterpret_cast<float*>(p); p += nx;
+  T.ys = p; p += dh; T.ycnt = p; p += dh; T.ysi = p; p += ny; T.yal = reinterpret_cast<float*>(p);
+  return EVH_SUCCESS;
+}
+
+// nimg frames of sw x sh resized to dw x dh rows at dst (the sizes differ): gray rows of level 0 (INGEST) or the source's
+// channels packed.  Enlarging in either direction = k_resize_linear_area, integer ratios = k_ingest_area_int /
+// k_resize_area_int, else k_area.
+template <bool INGEST, class SRC>
+int launch_area(evh_ctx* c, const SRC& src, int nimg, int sw, int sh, uint8_t* dst, int dw, int dh, int64_t dst_stride,
+                int64_t dst_img_stride) {
+  const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;      // the operator's own arithmetic
+  const double sx = 1. / inv_x, sy = 1. / inv_y;
+  const dim3 grid((dw + 255) / 256, dh, nimg);
+  const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
+  const area_stride_t<INGEST> stride = (area_stride_t<INGEST>)dst_stride;
+  if (sx < 1 || sy < 1) {                    // the operator's bilinear emulation of INTER_AREA
+    hipLaunchKernelGGL((k_resize_linear_area<INGEST, SRC>), grid, dim3(256), 0, c->stream, src, sw, sh, dst, dw, dh, dst_stride,
+                       dst_img_stride, sx, inv_x, sy, inv_y);
+  } else if (std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16) {
+    if constexpr (INGEST) {
+      hipLaunchKernelGGL(k_ingest_area_int<SRC>, grid, dim3(256), 0, c->stream, src, dst, dst_img_stride, dw, dh, stride, isx, isy);
+    } else {                                 // PackedSrc: one thread per channel element
+      hipLaunchKernelGGL(k_resize_area_int, dim3((dw * src.cn + 255) / 256, dh, nimg), dim3(256), 0, c->stream, src.p, src.cn,
+                         src.stride, src.img_stride, dst, dw, dh, dst_stride, dst_img_stride, isx, isy);
+    }
+  } else {
+    AreaTabDev T;
+    if (int rc = area_tables(c, sw, sh, dw, dh, sx, sy, T)) return rc;
+    hipLaunchKernelGGL((k_area<INGEST, SRC>), grid, dim3(256), 0, c->stream, src, dst, dst_img_stride, dw, dh, stride, T);
+  }
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+// level 0 of every frame straight from the source frames
+template <class SRC>
+int launch_ingest(evh_ctx* c, const SRC& src, int nimg, int sw, int sh, int dw, int dh) {
+  const EvhLevel& L = c->g.lv[0];
+  return launch_area<true>(c, src, nimg, sw, sh, c->d_pyr + L.off, dw, dh, L.stride, c->g.pyr_frame_bytes);
+}
+
 }  // namespace
 
 int evh_launch_resize_area(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, int sh, int cn, int64_t src_stride,
@@ -421,110 +479,8 @@ int evh_launch_resize_area(evh_ctx* c, const uint8_t* d_src, int nimg, int sw, i
                                   (size_t)sw * cn, sh, hipMemcpyDeviceToDevice, c->stream));
     return EVH_SUCCESS;
   }
-  const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;
-  const double scale_x = 1. / inv_x, scale_y = 1. / inv_y;
-  if (scale_x < 1 || scale_y < 1) {          // enlarging: the operator's bilinear emulation of INTER_AREA
-    hipLaunchKernelGGL((k_resize_linear_area<false, PackedSrc>), dim3((dw + 255) / 256, dh, nimg), dim3(256), 0, c->stream,
-                       PackedSrc{d_src, cn, src_stride, src_img_stride}, sw, sh, d_dst, dw, dh, dst_stride, dst_img_stride,
-                       scale_x, inv_x, scale_y, inv_y);
-    EVH_HIP(c, hipGetLastError());
-    return EVH_SUCCESS;
-  }
-  dim3 grid((dw * cn + 255) / 256, dh, nimg);
-  const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
-  if (std::fabs(scale_x - isx) < 2.220446049250313e-16 && std::fabs(scale_y - isy) < 2.220446049250313e-16) {
-    hipLaunchKernelGGL(k_resize_area_int, grid, dim3(256), 0, c->stream, d_src, cn, src_stride, src_img_stride, d_dst, dw,
-                       dh, dst_stride, dst_img_stride, isx, isy);
-    EVH_HIP(c, hipGetLastError());
-    return EVH_SUCCESS;
-  }
-  HostTab xt, yt;
-  build_area_tab(sw, dw, scale_x, xt);
-  build_area_tab(sh, dh, scale_y, yt);
-  // one device allocation for all eight tables, released after the launch completes
-  const size_t nx = xt.si.size(), ny = yt.si.size();
-  std::vector<int> blob;
-  blob.insert(blob.end(), xt.start.begin(), xt.start.end());
-  blob.insert(blob.end(), xt.cnt.begin(), xt.cnt.end());
-  blob.insert(blob.end(), xt.si.begin(), xt.si.end());
-  for (float f : xt.al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
-  blob.insert(blob.end(), yt.start.begin(), yt.start.end());
-  blob.insert(blob.end(), yt.cnt.begin(), yt.cnt.end());
-  blob.insert(blob.end(), yt.si.begin(), yt.si.end());
-  for (float f : yt.al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
-  int* d_blob = nullptr;
-  EVH_HIP(c, hipMalloc(&d_blob, blob.size() * sizeof(int)));
-  hipError_t e = hipMemcpyAsync(d_blob, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) { (void)hipFree(d_blob); return evh_fail(c, EVH_ERR_HIP, "resize table upload failed"); }
-  AreaTabDev T;
-  int* p = d_blob;
-  T.xs = p; p += dw; T.xcnt = p; p += dw; T.xsi = p; p += nx; T.xal = reinterpret_cast<float*>(p); p += nx;
-  T.ys = p; p += dh; T.ycnt = p; p += dh; T.ysi = p; p += ny; T.yal = reinterpret_cast<float*>(p);
-  hipLaunchKernelGGL(k_resize_area, grid, dim3(256), 0, c->stream, d_src, cn, src_stride, src_img_stride, d_dst, dw, dh,
-                     dst_stride, dst_img_stride, T);
-  e = hipGetLastError();
-  (void)hipStreamSynchronize(c->stream);  // the pageable upload and the table lifetime both end here
-  (void)hipFree(d_blob);
-  if (e != hipSuccess) return evh_fail(c, EVH_ERR_HIP, std::string("k_resize_area: ") + hipGetErrorString(e));
-  return EVH_SUCCESS;
-}
-
-// INTER_AREA tables of one (source, destination) geometry, kept on the device by the context (a stream resizes
-// every chunk with the same geometry)
-static int area_tables(evh_ctx* c, int sw, int sh, int dw, int dh, double scale_x, double scale_y, AreaTabDev& T) {
-  const int64_t key = ((int64_t)sw << 48) ^ ((int64_t)sh << 32) ^ ((int64_t)dw << 16) ^ (int64_t)dh;
-  if (c->area_key != key || !c->d_area_tab) {
-    HostTab xt, yt;
-    build_area_tab(sw, dw, scale_x, xt);
-    build_area_tab(sh, dh, scale_y, yt);
-    std::vector<int> blob;
-    blob.insert(blob.end(), xt.start.begin(), xt.start.end());
-    blob.insert(blob.end(), xt.cnt.begin(), xt.cnt.end());
-    blob.insert(blob.end(), xt.si.begin(), xt.si.end());
-    for (float f : xt.al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
-    blob.insert(blob.end(), yt.start.begin(), yt.start.end());
-    blob.insert(blob.end(), yt.cnt.begin(), yt.cnt.end());
-    blob.insert(blob.end(), yt.si.begin(), yt.si.end());
-    for (float f : yt.al) { int v; std::memcpy(&v, &f, 4); blob.push_back(v); }
-    EVH_HIP(c, hipStreamSynchronize(c->stream));            // the previous tables may still be in use
-    if (int rc = grow(c, &c->d_area_tab, &c->area_tab_bytes, blob.size() * sizeof(int))) return rc;
-    EVH_HIP(c, hipMemcpy(c->d_area_tab, blob.data(), blob.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->area_key = key; c->area_nx = (int)xt.si.size(); c->area_ny = (int)yt.si.size();
-  }
-  int* p = c->d_area_tab;
-  const size_t nx = (size_t)c->area_nx, ny = (size_t)c->area_ny;
-  T.xs = p; p += dw; T.xcnt = p; p += dw; T.xsi = p; p += nx; T.xal = reinterpret_cast<float*>(p); p += nx;
-  T.ys = p; p += dh; T.ycnt = p; p += dh; T.ysi = p; p += ny; T.yal = reinterpret_cast<float*>(p);
-  return EVH_SUCCESS;
-}
-
-// level 0 of every frame straight from the source frames (k_ingest_area* when shrinking, k_resize_linear_area when enlarging)
-template <class SRC>
-static int launch_ingest(evh_ctx* c, const SRC& src, int nimg, int sw, int sh, int dw, int dh) {
-  const EvhLevel& L = c->g.lv[0];
-  const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;      // the operator's own arithmetic
-  const double sx = 1. / inv_x, sy = 1. / inv_y;
-  dim3 grid((dw + 255) / 256, dh, nimg);
-  if (sx < 1 || sy < 1) {                    // enlarging: bilinear emulation, gray weights on the rounded channels
-    hipLaunchKernelGGL((k_resize_linear_area<true, SRC>), grid, dim3(256), 0, c->stream, src, sw, sh, c->d_pyr + L.off, dw, dh,
-                       (int64_t)L.stride, c->g.pyr_frame_bytes, sx, inv_x, sy, inv_y);
-    EVH_HIP(c, hipGetLastError());
-    return EVH_SUCCESS;
-  }
-  const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
-  if (std::fabs(sx - isx) < 2.220446049250313e-16 && std::fabs(sy - isy) < 2.220446049250313e-16) {
-    hipLaunchKernelGGL(k_ingest_area_int<SRC>, grid, dim3(256), 0, c->stream, src, c->d_pyr + L.off, c->g.pyr_frame_bytes, dw,
-                       dh, L.stride, isx, isy);
-    EVH_HIP(c, hipGetLastError());
-    return EVH_SUCCESS;
-  }
-  AreaTabDev T;
-  int rc = area_tables(c, sw, sh, dw, dh, sx, sy, T);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_ingest_area<SRC>, grid, dim3(256), 0, c->stream, src, c->d_pyr + L.off, c->g.pyr_frame_bytes, dw, dh,
-                     L.stride, T);
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launch_area<false>(c, PackedSrc{d_src, cn, src_stride, src_img_stride}, nimg, sw, sh, d_dst, dw, dh, dst_stride,
+                            dst_img_stride);
 }
 
 static Yuv420Src yuv420_src(const evh_yuv420& s) {

@@ -147,8 +147,8 @@ struct evh_ctx {
   int* d_filter_ws = nullptr; size_t filter_ws_bytes = 0;   // k_filter<true>: work arrays of key-point budgets beyond the LDS form
   char* d_scan_ws = nullptr;      // fixed-iteration stream scan: state, sample table and hypothesis results (evh_ransac.hip, lazy)
   size_t scan_ws_bytes = 0;
-  int* d_area_tab = nullptr; size_t area_tab_bytes = 0;     // INTER_AREA tables of the last ingest geometry (evh_launch_ingest_level0)
-  int64_t area_key = -1; int area_nx = 0, area_ny = 0;
+  int* d_area_tab = nullptr; size_t area_tab_bytes = 0;     // INTER_AREA tables of the last (sw, sh, dw, dh): fused ingest and stand-alone resize alike
+  int area_geom[4] = {0, 0, 0, 0}; int area_nx = 0, area_ny = 0;   // {sw, sh, dw, dh} of the tables held, zeros: none
   uint8_t* d_yuv_bgr = nullptr; size_t yuv_bgr_bytes = 0;   // BGR frames of evh_stream_homography_batch_types_yuv420's chunk
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv

@@ -93,6 +93,8 @@ const char* evh_profile_stage_name(int stage);
 /* ---- K0: imutils.resize -> cv2.resize(INTER_AREA): area sums when shrinking, the operator's bilinear emulation
  * when enlarging (resize_width > frame width), identity = copy ------------------------------------------------- */
 /* nimg images of sh x sw x cn uint8 (row stride src_stride bytes, image stride src_img_stride bytes).          */
+/* Stream-ordered like every other entry: the result is complete after evh_synchronize() (or on the context's    */
+/* stream); a call whose geometry differs from the previous resize or fused ingest drains the stream once.     */
 int evh_resize_area_u8(evh_ctx* ctx, const uint8_t* d_src, int nimg, int sw, int sh, int cn, int64_t src_stride,
                        int64_t src_img_stride, uint8_t* d_dst, int dw, int dh, int64_t dst_stride,
                        int64_t dst_img_stride);

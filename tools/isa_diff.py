@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Compare device assembly files function by function (hipcc <library flags> --cuda-device-only -S unit.hip -o x.s).
 
-    tools/isa_diff.py parent.s [move.s ...] final.s
+    tools/isa_diff.py [--rename OLD=NEW ...] parent.s [move.s ...] final.s
 
 Every file after the first is compared against the FIRST.  Per function: instruction counts, the resource table of a
 kernel (VGPR, SGPR, LDS bytes, private segment bytes, SGPR / VGPR spills) and SAME or DIFF; for DIFF a unified diff of the
 instruction streams.  An instruction stream is what lies between the function's label and its end label without comments,
 directives and blank lines; branch-target labels are renumbered in order of appearance, so only addresses and label
 numbers may differ between two streams that compare SAME.  Exit status 1 if anything differs.
+
+Functions are paired by name.  --rename OLD=NEW pairs the first file's OLD with NEW in the others; both are names as the
+first column prints them, without a leading "void " (--rename 'k_ingest_area<PackedSrc>=k_area<true, PackedSrc>').
 """
 import difflib
 import re
@@ -65,34 +68,53 @@ def table(meta):
     return "-" if not meta else "v%d s%d lds%d priv%d spill%d/%d" % tuple(meta.get(k, 0) for k in META)
 
 
-def main(paths):
+def bare(name):
+    return name[5:] if name.startswith("void ") else name
+
+
+def main(paths, renames):
     parsed = [parse(p) for p in paths]
     base_f, base_m = parsed[0]
     names = demangle(list(base_f))
+    by_name = [{bare(d): n for n, d in demangle(list(f)).items()} for f, _ in parsed[1:]]
+    paired = [set() for _ in parsed[1:]]
     differs = False
     for fn in base_f:
         cols, diffs = ["%d %s" % (count(base_f[fn]), table(base_m.get(fn)))], []
-        for path, (f, m) in zip(paths[1:], parsed[1:]):
-            if fn not in f:
+        new = renames.get(bare(names[fn]))
+        for k, (path, (f, m)) in enumerate(zip(paths[1:], parsed[1:])):
+            other = by_name[k].get(new, fn) if new else fn      # a file from before the rename still has the old name
+            if other not in f:
                 cols.append("MISSING"); differs = True
                 continue
-            same = f[fn] == base_f[fn] and m.get(fn) == base_m.get(fn)
-            cols.append("%d %s %s" % (count(f[fn]), table(m.get(fn)), "SAME" if same else "DIFF"))
+            paired[k].add(other)
+            same = f[other] == base_f[fn] and m.get(other) == base_m.get(fn)
+            cols.append("%d %s %s" % (count(f[other]), table(m.get(other)), "SAME" if same else "DIFF"))
             if not same:
                 differs = True
-                diffs.append((path, list(difflib.unified_diff(base_f[fn], f[fn], paths[0], path, n=0, lineterm=""))))
-        print("%-28s | %s" % (names[fn], " | ".join(cols)))
+                diffs.append((path, list(difflib.unified_diff(base_f[fn], f[other], paths[0], path, n=0, lineterm=""))))
+        print("%-28s | %s" % (names[fn] + (" -> " + new if new else ""), " | ".join(cols)))
         for path, d in diffs:
             for ln in d:
                 print("    " + ln)
-    for path, (f, m) in zip(paths[1:], parsed[1:]):
+    for k, (path, (f, m)) in enumerate(zip(paths[1:], parsed[1:])):
         for fn in f:
-            if fn not in base_f:
+            if fn not in paired[k]:
                 print("%-28s | only in %s: %d" % (fn, path, count(f[fn]))); differs = True
     return 1 if differs else 0
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 3:
+    args, renames, it = [], {}, iter(sys.argv[1:])
+    for a in it:
+        if a != "--rename":
+            args.append(a)
+            continue
+        pair = next(it, "")
+        if "=" not in pair:
+            sys.exit("isa_diff.py: --rename takes OLD=NEW, got %r" % pair)
+        old, new = pair.split("=", 1)
+        renames[bare(old)] = bare(new)
+    if len(args) < 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1:]))
+    sys.exit(main(args, renames))

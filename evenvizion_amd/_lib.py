@@ -97,6 +97,9 @@ SIGNATURES = {
     "evh_orb_detect_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i]),
     "evh_stream_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_stream_homography_batch_types_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
+    "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
 }
 FEATURE_ORB, FEATURE_SIFT, FEATURE_SURF = 0, 1, 2
 FEATURE_CODES = {"ORB": FEATURE_ORB, "SIFT": FEATURE_SIFT, "SURF": FEATURE_SURF}
@@ -106,6 +109,11 @@ class Yuv420(C.Structure):
     """evh_yuv420 (include/evhip.h): three device plane pointers and their strides."""
     _fields_ = [("d_y", _vp), ("d_cb", _vp), ("d_cr", _vp), ("y_stride", _i64), ("c_stride", _i64),
                 ("y_frame_stride", _i64), ("c_frame_stride", _i64), ("c_pixel_stride", C.c_int32)]
+
+
+class StreamSeg(C.Structure):
+    """evh_stream_seg (include/evhip.h): one stream's consecutive frames inside a ragged batch."""
+    _fields_ = [("first_frame", C.c_int32), ("nframes", C.c_int32), ("start", C.c_int32), ("reserved", C.c_int32)]
 
 
 def yuv420_size(w, h):
@@ -426,6 +434,34 @@ class Context:
             self.h, frames.data_ptr(), S, F, w, h, cn, w * cn, w * h * cn, nfeatures, float(thr), int(max_iters),
             float(conf), int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
             state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+
+    def streams_homography_batch(self, frames, segments, out_H, out_status, features=("ORB",), state_in=None, state_out=None,
+                                 nfeatures=500, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None,
+                                 size=None):
+        """A ragged batch of several streams (evh_streams_homography_batch[_yuv420]).  frames: CUDA uint8 [n,h,w(,3)], or
+        decoded planes (see _yuv420; size=(w, h) for packed I420 frames); segments: a list of (first_frame, nframes, start)
+        that tiles the n frames, one stream each, start truthy = the stream begins here and its state_in row is not read.
+        out_H f64[n-1,9] / out_status i32[n-1]: pair k of a segment writes row first_frame + k, the row at a segment's last
+        frame is left alone.  state_in / state_out f64[len(segments),18] (may be the same tensor; state_in None only when
+        every segment starts).  features: a type list as in stream_homography_batch_types, ["ORB"] = the fused ORB path."""
+        self._enter()
+        segs = (StreamSeg * max(len(segments), 1))(*[StreamSeg(int(a), int(b), int(bool(st)), 0) for a, b, st in segments])
+        t = self._types(features)
+        if list(t) != [FEATURE_ORB]:
+            self._multi_used = True
+        tail = (nfeatures, _hp(t), len(t), C.cast(segs, C.c_void_p), len(segments), float(thr), int(max_iters), float(conf),
+                int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
+                state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr())
+        if isinstance(frames, (tuple, list)) or frames.dim() == 2:
+            d, n, w, h = self._yuv420(frames, size, self.device)
+            dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+            self._check(self.lib.evh_streams_homography_batch_yuv420(self.h, C.byref(d), n, w, h, dw, dh, *tail))
+            return
+        n, h, w = frames.shape[:3]
+        cn = 1 if frames.dim() == 3 else frames.shape[3]
+        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        self._check(self.lib.evh_streams_homography_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh,
+                                                          *tail))
 
     # ---- decoded 4:2:0 planes as the source ----
     @staticmethod

@@ -14,6 +14,8 @@ and, as a data file instead of the reference's rendered comparison video (:69-97
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
 It also takes a .npy file (uint8 [F,h,w,3] BGR or [F,h,w] gray) or "synthetic:<frames>:<w>x<h>[:<seed>]".
+--path_to_videos A B ... (extension) takes several of them and writes, per video, what the single form writes; the videos run
+together through get_homography_dicts (several captures per GPU call), main() then returns the list of folders.
 Differences, all deliberate: the heat-map and matching PICTURES are
 not rendered (--show_matching_visualization must stay off); --resize_width is honoured (the reference script parses
 it but never passes it on, so it always runs at 400 -- the default here).
@@ -66,6 +68,10 @@ def load_frames(spec):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="EvenVizion hot path on MI355X (argument surface of evenvizion_component.py)")
     ap.add_argument("--path_to_video", type=str, default="synthetic:16:400x224:1")
+    ap.add_argument("--path_to_videos", type=str, nargs="+", default=None,
+                    help="several videos at once (extension): per video the outputs of --path_to_video, computed together")
+    ap.add_argument("--max_streams", type=int, default=None, help="--path_to_videos: videos live in one GPU call")
+    ap.add_argument("--decode_threads", type=int, default=None, help="--path_to_videos: host threads reading frames")
     ap.add_argument("--experiment_name", type=str, default="test_video_processing")
     ap.add_argument("--resize_width", type=int, default=400, help="width to resize frames to")
     ap.add_argument("--path_to_original_coordinate", default=None, help="path to json with original coordinates")
@@ -81,19 +87,36 @@ def main(argv=None):
     if _bool(args.show_matching_visualization):
         raise NotImplementedError("matching pictures are outside the MI355X hot path; leave --show_matching_visualization off")
 
-    from .processing.video_processing import get_homography_dict
+    from .processing.video_processing import get_homography_dict, get_homography_dicts
+    features = [f for f in args.features.split(",") if f]
+    if args.path_to_videos:
+        opened = [open_capture(spec) for spec in args.path_to_videos]
+        kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
+        results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
+                                       none_H_processing=_bool(args.none_H_processing), features_type_list=features,
+                                       ingest=args.ingest, **kw)
+        folders = []
+        for n, (result, (_, original_shape, stem)) in enumerate(zip(results, opened)):
+            if [s for _, _, s in opened].count(stem) > 1:
+                stem = "%s_%d" % (stem, n)               # two videos of one name: one folder each
+            folders.append(write_outputs(args, result, original_shape, stem))
+        return folders
+    cap, original_shape, stem = open_capture(args.path_to_video)
+    result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
+                                 none_H_processing=_bool(args.none_H_processing),
+                                 features_type_list=features, ingest=args.ingest)
+    return write_outputs(args, result, original_shape, stem)
+
+
+def write_outputs(args, result, original_shape, stem):
+    """One video's files under <cwd>/<experiment_name>/<stem>/ (evenvizion_component.py:62-65,139-140) -> the folder."""
     from .processing.utils import read_homography_dict, superposition_dict, read_json_with_coordinates, \
         are_infinity_coordinates
     from .processing.fixed_coordinate_system import from_original_to_fix
     from . import heatmap
 
-    cap, original_shape, stem = open_capture(args.path_to_video)
     save_folder = os.path.join(os.getcwd(), args.experiment_name, stem)
     os.makedirs(save_folder, exist_ok=True)
-
-    result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
-                                 none_H_processing=_bool(args.none_H_processing),
-                                 features_type_list=[f for f in args.features.split(",") if f], ingest=args.ingest)
     path_to_homography_dict = os.path.join(save_folder, "dict_with_homography_matrix.json")
     with open(path_to_homography_dict, "w") as json_:
         json.dump(result, json_)

@@ -249,7 +249,9 @@ int join_solve(evh_ctx* c) {
 }
 
 // RANSAC #1 + static filter, then compute_homography, on the solve stream when asynchronous solve is enabled
-int solve_pairs(evh_ctx* c, EvhRansacArgs R, int npairs, int nstreams = 0, int pairs_per_stream = 0, int pitch = 0) {
+// (d_segs: the scans of a ragged batch, pairs_per_stream = the pairs of its longest stream)
+int solve_pairs(evh_ctx* c, EvhRansacArgs R, int npairs, int nstreams = 0, int pairs_per_stream = 0, int pitch = 0,
+                const evh_stream_seg* d_segs = nullptr) {
   hipStream_t main = c->stream;
   const bool async = c->async_solve && c->solve_stream;
   if (async) {
@@ -261,7 +263,8 @@ int solve_pairs(evh_ctx* c, EvhRansacArgs R, int npairs, int nstreams = 0, int p
   { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC, c->stream); rc = evh_launch_ransac_static(c, R, npairs); }
   if (!rc) {
     EvhProfScope ps(c, EVH_ST_RANSAC_FINAL, c->stream);
-    rc = evh_launch_ransac_final(c, R, nstreams > 0 ? pairs_per_stream : npairs, nstreams, pitch);
+    rc = d_segs ? evh_launch_ransac_final(c, R, npairs, nstreams, 0, d_segs, pairs_per_stream)
+                : evh_launch_ransac_final(c, R, nstreams > 0 ? pairs_per_stream : npairs, nstreams, pitch);
   }
   if (async) {
     hipError_t e = hipEventRecord(c->ev_solve_done, c->solve_stream);
@@ -352,13 +355,11 @@ int ensure_multitype(evh_ctx* c) {
   return rc;
 }
 
-// frames -> H with a LIST of feature types, in list order (the reference's default list is SURF, SIFT, ORB):
-// per type detect, match, RANSAC #1, static filter; concatenate; remove_double_matching; compute_homography
-int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int npairs, int stream_mode, int sw, int sh,
-                int w, int h, int nfeatures, const int* types, int ntypes, double thr, int max_iters, double conf, int force_max, const double* d_state_in, double* d_state_out,
-                double* d_H, int32_t* d_status) {
+// the type list of a *_types entry: every name known, none twice, SIFT / SURF enabled; -> which detectors it names
+struct EvhWanted { bool orb = false, sift = false, surf = false; };
+int check_types(evh_ctx* c, const char* who, const int* types, int ntypes, EvhWanted& want) {
   if (!types || ntypes < 1 || ntypes > 8) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad feature type list");
-  bool want_orb = false, want_sift = false, want_surf = false;
+  bool &want_orb = want.orb, &want_sift = want.sift, &want_surf = want.surf;
   for (int i = 0; i < ntypes; i++) {
     // the concatenation buffer holds one segment per detector (kcap + sift.cap + surf.cap rows): a type named twice would
     // overflow it, so it is refused (the reference would simply match the same key points twice and deduplicate them)
@@ -372,7 +373,49 @@ int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, in
   if (want_surf && !c->surf.cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SURF in the list needs evh_surf_enable");
   if (c->mt.cap && c->mt.cap < c->kcap + c->sift.cap + c->surf.cap)
     return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": enable SIFT and SURF before the first multi-type call");
-  int rc = ensure_multitype(c);
+  return EVH_SUCCESS;
+}
+
+// the device copy of a ragged batch's segment table, uploaded stream-ordered through pinned staging.  The turns are for the
+// HOST side: a call waits only for the upload EVH_SEG_TURNS calls back to have left its staging table, never for the device
+// to drain (the device tables are ordered by the stream: the upload sits behind this call's filter, which has joined the
+// previous call's solve)
+int upload_segs(evh_ctx* c, const evh_stream_seg* h_segs, int nstreams, const evh_stream_seg** d_out) {
+  const size_t per = (size_t)c->max_frames / 2;
+  if (!c->d_segs) {
+    int rc = dalloc(c, &c->d_segs, per * EVH_SEG_TURNS);
+    if (rc) return rc;
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_segs), per * EVH_SEG_TURNS * sizeof(evh_stream_seg), hipHostMallocDefault) != hipSuccess) {
+      c->h_segs = nullptr;
+      dfree(c, &c->d_segs);
+      return evh_fail(c, EVH_ERR_HIP, "segment table: pinned staging (hipHostMalloc) could not be allocated");
+    }
+  }
+  // (a call that fails below has used up its turn without recording an event: harmless, the turn's next user finds no
+  // event, or an older one that has long completed.  A table holds max_frames / 2 segments: streams_batch has refused
+  // segments of fewer than 2 frames and batches of more than max_frames frames, so nstreams cannot exceed that)
+  const unsigned t = c->seg_turn++ % EVH_SEG_TURNS;
+  if (!c->ev_segs[t]) EVH_HIP(c, hipEventCreateWithFlags(&c->ev_segs[t], hipEventDisableTiming));
+  else EVH_HIP(c, hipEventSynchronize(c->ev_segs[t]));              // the upload that used this turn last has left the staging
+  std::memcpy(c->h_segs + t * per, h_segs, sizeof(evh_stream_seg) * (size_t)nstreams);
+  EVH_HIP(c, hipMemcpyAsync(c->d_segs + t * per, c->h_segs + t * per, sizeof(evh_stream_seg) * (size_t)nstreams, hipMemcpyHostToDevice, c->stream));
+  EVH_HIP(c, hipEventRecord(c->ev_segs[t], c->stream));
+  *d_out = c->d_segs + t * per;
+  return EVH_SUCCESS;
+}
+
+// frames -> H with a LIST of feature types, in list order (the reference's default list is SURF, SIFT, ORB):
+// per type detect, match, RANSAC #1, static filter; concatenate; remove_double_matching; compute_homography.
+// h_segs: the nframes frames are a ragged batch of nstreams streams (max_pairs pairs in the longest); else one stream
+// (stream_mode) or independent pairs
+int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int npairs, int stream_mode, int sw, int sh,
+                int w, int h, int nfeatures, const int* types, int ntypes, double thr, int max_iters, double conf, int force_max, const double* d_state_in, double* d_state_out,
+                double* d_H, int32_t* d_status, const evh_stream_seg* h_segs = nullptr, int nstreams = 1, int max_pairs = 0) {
+  EvhWanted want;
+  int rc = check_types(c, who, types, ntypes, want);
+  if (rc) return rc;
+  const bool want_orb = want.orb, want_sift = want.sift, want_surf = want.surf;
+  rc = ensure_multitype(c);
   if (rc) return rc;
   if ((rc = join_solve(c))) return rc;
   const int share_group = c->fast_share ? (stream_mode ? nframes : 2) : 0;
@@ -408,7 +451,10 @@ int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, in
   if ((rc = evh_launch_merge(c, M, npairs))) return rc;
   R.H = d_H; R.out_status = d_status;
   with_state(R, d_state_in, d_state_out);
+  const evh_stream_seg* d_segs = nullptr;
+  if (h_segs && (rc = upload_segs(c, h_segs, nstreams, &d_segs))) return rc;
   EvhProfScope ps(c, EVH_ST_RANSAC_FINAL);
+  if (d_segs) return evh_launch_ransac_final(c, R, npairs, nstreams, 0, d_segs, max_pairs);
   return evh_launch_ransac_final(c, R, npairs, stream_mode ? 1 : 0, npairs);
 }
 
@@ -434,6 +480,47 @@ int stream_batch(evh_ctx* c, const EvhFrames& F, int nstreams, int frames_per_st
   R.H = d_H; R.out_status = d_status;
   with_state(R, d_state_in, d_state_out);
   return solve_pairs(c, R, nframes - 1, nstreams, frames_per_stream - 1, frames_per_stream);
+}
+
+// A ragged batch: total_frames frames cut into nstreams segments of consecutive frames, one stream each.  Everything up to the
+// static filter runs over all frames / pair slots at once (a slot that straddles two streams is computed and never read); the
+// scans run one workgroup per stream off the segment table.  A list of exactly {ORB} takes the fused ORB path, any other
+// pairs_types.  Every refusal comes before the first launch.
+int streams_batch(evh_ctx* c, const char* who, const EvhFrames& F, int total_frames, int sw, int sh, int w, int h, int nfeatures,
+                  const int32_t* h_types, int ntypes, const evh_stream_seg* h_segs, int nstreams, double thr, int max_iters,
+                  double conf, int force_max, const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
+  const std::string W = std::string(who) + ": ";
+  if (!c) return EVH_ERR_INVALID;
+  if (!d_H || !d_status || !h_segs || nstreams < 1 || total_frames < 2 || (!F.yuv && !F.packed))
+    return evh_fail(c, EVH_ERR_INVALID, W + "bad argument");
+  if (total_frames > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, W + "batch needs more frame slots than max_frames");
+  int next = 0, max_pairs = 0;
+  for (int s = 0; s < nstreams; s++) {
+    const evh_stream_seg& g = h_segs[s];
+    if (g.nframes < 2) return evh_fail(c, EVH_ERR_INVALID, W + "a segment needs at least 2 frames");
+    if (g.first_frame != next || g.nframes > total_frames - next)
+      return evh_fail(c, EVH_ERR_INVALID, W + "the segments must tile [0, total_frames) in ascending order");
+    if (g.reserved != 0) return evh_fail(c, EVH_ERR_INVALID, W + "evh_stream_seg.reserved must be 0");
+    if (!g.start && !d_state_in) return evh_fail(c, EVH_ERR_INVALID, W + "a segment with start == 0 needs d_state_in");
+    next += g.nframes;
+    max_pairs = std::max(max_pairs, g.nframes - 1);
+  }
+  if (next != total_frames) return evh_fail(c, EVH_ERR_INVALID, W + "the segments must tile [0, total_frames) in ascending order");
+  EvhWanted want;
+  int rc = check_types(c, who, h_types, ntypes, want);
+  if (rc) return rc;
+  if (ntypes != 1 || !want.orb)
+    return pairs_types(c, who, F, total_frames, total_frames - 1, 1, sw, sh, w, h, nfeatures, h_types, ntypes, thr, max_iters, conf,
+                       force_max, d_state_in, d_state_out, d_H, d_status, h_segs, nstreams, max_pairs);
+  // FAST thresholds are shared by the frames 2k, 2k + 1 of the batch, across segment borders too: a borrowed threshold that
+  // proves too high is redone, so sharing is exact per frame
+  if ((rc = detect_match(c, F, total_frames, total_frames, total_frames - 1, 1, sw, sh, w, h, nfeatures))) return rc;
+  const evh_stream_seg* d_segs = nullptr;
+  if ((rc = upload_segs(c, h_segs, nstreams, &d_segs))) return rc;
+  EvhRansacArgs R = ransac_args(c, c->orb, thr, max_iters, conf, force_max);
+  R.H = d_H; R.out_status = d_status;
+  with_state(R, d_state_in, d_state_out);
+  return solve_pairs(c, R, total_frames - 1, nstreams, max_pairs, 0, d_segs);
 }
 
 // final solve of pair slot 0 of the ORB buffers (its static rows are resident), optionally behind the superposition
@@ -635,6 +722,8 @@ void evh_destroy(evh_ctx* c) {
   for (auto e : c->prof_pool) (void)hipEventDestroy(e);
   if (c->solve_stream) { (void)hipStreamSynchronize(c->solve_stream); (void)hipStreamDestroy(c->solve_stream); }
   if (c->h_tabs) (void)hipHostFree(c->h_tabs);
+  if (c->h_segs) (void)hipHostFree(c->h_segs);
+  for (auto e : c->ev_segs) if (e) (void)hipEventDestroy(e);
   if (c->ev_tabs) (void)hipEventDestroy(c->ev_tabs);
   if (c->ev_match_done) (void)hipEventDestroy(c->ev_match_done);
   if (c->ev_solve_done) (void)hipEventDestroy(c->ev_solve_done);
@@ -1260,6 +1349,27 @@ int evh_stream_homography_batch_types_yuv420(evh_ctx* c, const evh_yuv420* src, 
                      d_status);
 }
 
+// ---- ragged batches of several streams -----------------------------------------------------------------------------------------
+int evh_streams_homography_batch(evh_ctx* c, const uint8_t* d_frames, int total_frames, int src_w, int src_h, int channels,
+                                 int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures, const int32_t* h_types,
+                                 int ntypes, const evh_stream_seg* h_segs, int nstreams, double ransac_thr, int ransac_max_iters,
+                                 double ransac_conf, int force_max_iters, const double* d_state_in, double* d_state_out,
+                                 double* d_H, int32_t* d_status) {
+  return streams_batch(c, "evh_streams_homography_batch", packed_frames(d_frames, channels, row_stride, frame_stride), total_frames,
+                       src_w, src_h, w, h, nfeatures, h_types, ntypes, h_segs, nstreams, ransac_thr, ransac_max_iters, ransac_conf,
+                       force_max_iters, d_state_in, d_state_out, d_H, d_status);
+}
+
+int evh_streams_homography_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int total_frames, int src_w, int src_h, int w, int h,
+                                        int nfeatures, const int32_t* h_types, int ntypes, const evh_stream_seg* h_segs,
+                                        int nstreams, double ransac_thr, int ransac_max_iters, double ransac_conf,
+                                        int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
+                                        int32_t* d_status) {
+  // (the planes are checked by the ingest of either path, before its first launch)
+  return streams_batch(c, "evh_streams_homography_batch_yuv420", yuv420_frames(src), total_frames, src_w, src_h, w, h, nfeatures,
+                       h_types, ntypes, h_segs, nstreams, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in,
+                       d_state_out, d_H, d_status);
+}
 
 // ---- N4: SURF --------------------------------------------------------------------------------------------------------------------
 int evh_surf_enable(evh_ctx* c, int max_surf_features) {

@@ -16,6 +16,7 @@
 #define EVH_FAST_OY 31
 #define EVH_K1CAP 4096       // stage-1 (FAST-score) survivors per level held in LDS
 #define EVH_K2CAP 1280       // stage-2 (Harris) survivors per level held in LDS
+#define EVH_SEG_TURNS 4      // segment tables of the ragged stream entries in rotation (evh_ctx::d_segs)
 
 struct EvhLevel {
   int w, h, stride;     // stride in bytes (64-byte aligned)
@@ -149,6 +150,13 @@ struct evh_ctx {
   size_t scan_ws_bytes = 0;
   int* d_area_tab = nullptr; size_t area_tab_bytes = 0;     // INTER_AREA tables of the last (sw, sh, dw, dh): fused ingest and stand-alone resize alike
   int area_geom[4] = {0, 0, 0, 0}; int area_nx = 0, area_ny = 0;   // {sw, sh, dw, dh} of the tables held, zeros: none
+  // segment tables of evh_streams_homography_batch: EVH_SEG_TURNS tables of max_frames / 2 segments each, taken in turn, in
+  // pinned staging (h_segs, one event per turn: the host must not overwrite a table whose upload is still queued) and on the
+  // device (d_segs, same turns for simplicity: the device side is ordered by the stream anyway -- an upload is enqueued
+  // behind the filter of its call, which has waited for the previous call's solve)
+  evh_stream_seg* d_segs = nullptr; evh_stream_seg* h_segs = nullptr;
+  hipEvent_t ev_segs[EVH_SEG_TURNS] = {};
+  unsigned seg_turn = 0;
   uint8_t* d_yuv_bgr = nullptr; size_t yuv_bgr_bytes = 0;   // BGR frames of evh_stream_homography_batch_types_yuv420's chunk
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv

@@ -36,4 +36,8 @@ int evh_launch_find_homography(evh_ctx* c, const EvhRansacArgs& A);
 int evh_launch_static_filter(evh_ctx* c, const double* d_H, const float* d_rows, int n, int* d_rbin, float* d_out,
                              int* d_count);
 int evh_launch_ransac_static(evh_ctx* c, const EvhRansacArgs& A, int npairs);
-int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A, int npairs, int nstreams, int pitch);
+// nstreams == 0: npairs independent pairs; else nstreams scans of npairs pairs, `pitch` pair slots apart; with d_segs (a device
+// table of nstreams segments): the scans of a ragged batch of npairs pair slots, max_pairs pairs in the longest stream
+struct evh_stream_seg;
+int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A, int npairs, int nstreams, int pitch,
+                            const evh_stream_seg* d_segs = nullptr, int max_pairs = 0);

@@ -774,6 +774,133 @@ __global__ __launch_bounds__(4 * NL) void k_scan_finish(EvhRansacArgs A, int p, 
   if (p == npairs - 1 && A.state_out && tid < 9) { A.state_out[18 * s + tid] = B.Hsup[tid]; A.state_out[18 * s + 9 + tid] = B.Hprev[tid]; }
 }
 
+// ---- ragged batches (evh_streams_homography_batch): the scans above and below once more with the streams taken from a segment
+// table.  The existing entries keep their own kernels (k_ransac_final_stream, k_scan_*): with the layout folded into them their
+// prologues changed and bench.py --config 3 fell outside the parent's run-to-run spread (profiles/r07_streams_ragged.txt).
+// KEEP IN STEP: k_ransac_final_ragged, k_scan_init_ragged, k_scan_hyp_ragged, k_scan_finish_ragged and launch_forced_ragged are
+// copies of k_ransac_final_stream, k_scan_init, k_scan_hyp, k_scan_finish and launch_forced_scan that differ only in where a
+// stream's slots, rows and start flag come from; a change to the scan goes into both.  tests/test_gpu_streams_ragged.py is what
+// holds them together: per stream it demands the bits of the single-stream entries, adaptive and forced, carried state included.
+// at(s) = stream s: its first pair slot (also its scratch slot), the first row of its
+// status and the first double of its H, its pair count, and whether it reads its row of the entering state (A.Hsup0 /
+// A.Hprev0, when the launch has them).
+struct StreamAt { int64_t slot0, out0, h0; int npairs; bool carried; };
+// a ragged batch (evh_streams_homography_batch): stream s owns the consecutive frames of segs[s]; pair k of it reads pair slot
+// first_frame + k and writes row first_frame + k; a segment with `start` set begins its stream whatever the state pointers hold
+struct RaggedStreams {
+  const evh_stream_seg* segs;
+  __device__ __forceinline__ StreamAt at(int s) const {
+    const int4 g = *reinterpret_cast<const int4*>(segs + s);     // first_frame, nframes, start, reserved
+    return {(int64_t)g.x, (int64_t)g.x, (int64_t)9 * g.x, g.y - 1, g.z == 0};
+  }
+};
+
+// phase 2, stream semantics (video_processing.py:83-105): sequential scan over the pairs of one stream with the
+// running superposition; a failed pair repeats the previous H (none_H_processing=True).
+// One workgroup per stream: block s scans the pairs of stream s (StreamAt).  (The arguments by value, the body in the kernel
+// itself: handed on by reference the argument block is read up front, see block_lds.)
+template <int NW, bool LANES>
+__global__ __launch_bounds__(NW * NL) void k_ransac_final_ragged(EvhRansacArgs A, RaggedStreams lay) {
+  BlockLds<NW, LANES>& B = block_lds<NW, LANES>(A.fast_solver);
+  const int tid = threadIdx.x, s = blockIdx.x;
+  const StreamAt T = lay.at(s);
+  const double* Hsup0 = A.Hsup0 && T.carried ? A.Hsup0 + 18 * s : nullptr;
+  const double* Hprev0 = A.Hprev0 && T.carried ? A.Hprev0 + 18 * s : nullptr;
+  const int64_t slot0 = T.slot0;                            // first pair slot of this stream; also its scratch slot
+  const int npairs = T.npairs;
+  double* Hout = A.H + T.h0;
+  int* stout = A.out_status + T.out0;
+  if (tid == 0) B.have_prev = Hprev0 ? 1 : 0;
+  if (tid < 9 && Hsup0) B.Hsup[tid] = Hsup0[tid];
+  if (tid < 9 && Hprev0) B.Hprev[tid] = Hprev0[tid];
+  __syncthreads();
+  bool first = Hsup0 == nullptr;
+  for (int p = 0; p < npairs; p++) {
+    int st = A.status[slot0 + p];
+    if (st == EVH_PAIR_OK) {
+      const int n = A.npts2[slot0 + p];
+      const float* rows = A.pts2 + (slot0 + p) * A.row_stride * 4;
+      // the scan is sequential: one pair's worth of scratch (the stream's first slot) serves all its pairs
+      st = compute_homography_block<NW, LANES>(B, rows, n, first ? nullptr : B.Hsup, A, A.mask + slot0 * A.row_stride,
+                                        A.pts + slot0 * A.row_stride * 4, A.crow + slot0 * A.row_stride * 4,
+                                        A.info ? A.info + 8 * (slot0 + p) + 4 : nullptr);
+    }
+    if (scan_step_tail<NW, LANES>(B, st, p, npairs, Hout, stout, first)) return;
+    first = false;
+  }
+  if (A.state_out && tid < 9) { A.state_out[18 * s + tid] = B.Hsup[tid]; A.state_out[18 * s + 9 + tid] = B.Hprev[tid]; }
+}
+__global__ __launch_bounds__(NL) void k_scan_init_ragged(EvhRansacArgs A, ScanWs W, RaggedStreams lay) {
+  const int s = blockIdx.x, tid = threadIdx.x;
+  ScanState& T = W.state[s];
+  const bool carried = lay.at(s).carried;
+  const double* Hsup0 = carried ? A.Hsup0 : nullptr;
+  const double* Hprev0 = carried ? A.Hprev0 : nullptr;
+  if (tid < 9) { T.Hsup[tid] = Hsup0 ? Hsup0[18 * s + tid] : 0.0; T.Hprev[tid] = Hprev0 ? Hprev0[18 * s + tid] : 0.0; }
+  if (tid == 0) { T.have_prev = Hprev0 ? 1 : 0; T.first = Hsup0 ? 0 : 1; T.aborted = 0; T.pad = 0; }
+}
+
+
+// the chunks of pair p of every stream that has one, rows in the fixed plane; grid (hmax / 16, nstreams)
+__global__ __launch_bounds__(4 * NL) void k_scan_hyp_ragged(EvhRansacArgs A, int p, RaggedStreams lay, ScanWs W) {
+  __shared__ HypLds B;
+  const int tid = threadIdx.x, s = blockIdx.y;
+  const ScanState& T = W.state[s];
+  const StreamAt at = lay.at(s);
+  if (p >= at.npairs || T.aborted) return;
+  const int64_t slot0 = at.slot0, slot = slot0 + p;
+  if (A.status[slot] != EVH_PAIR_OK) return;
+  const int n = A.npts2[slot];
+  if (n <= 4) return;
+  const float* use = A.pts2 + slot * A.row_stride * 4;
+  if (!T.first) {
+    // the rows in the fixed plane (compute_homography_block's transform).  Every workgroup of the pair writes the same
+    // values to the stream's one scratch slot and reads back what it wrote itself -- identical bits from every writer.
+    float* trow = A.pts + slot0 * A.row_stride * 4;
+    if (tid < 9) B.Hsup[tid] = T.Hsup[tid];
+    __syncthreads();
+    to_fixed_plane(B.Hsup, use, n, trow, 4 * NL);
+    __threadfence_block();
+    __syncthreads();
+    use = trow;
+  }
+  hyp_chunk(B, A, W, use, n, at.slot0 + p, s);
+}
+
+// the serial part of pair p: replay of the hypotheses, refinement, step of the scan; grid = nstreams (a stream with fewer
+// pairs has left)
+__global__ __launch_bounds__(4 * NL) void k_scan_finish_ragged(EvhRansacArgs A, int p, RaggedStreams lay, ScanWs W) {
+  BlockLds<4, false>& B = block_lds<4, false>(A.fast_solver);
+  const int tid = threadIdx.x, s = blockIdx.x;
+  ScanState& T = W.state[s];
+  const StreamAt at = lay.at(s);
+  const int npairs = at.npairs;
+  if (p >= npairs || T.aborted) return;
+  const int64_t slot0 = at.slot0;
+  double* Hout = A.H + at.h0;
+  int* stout = A.out_status + at.out0;
+  const bool first = T.first != 0;
+  if (tid == 0) B.have_prev = T.have_prev;
+  if (tid < 9) { B.Hsup[tid] = T.Hsup[tid]; B.Hprev[tid] = T.Hprev[tid]; }
+  __syncthreads();
+  int st = A.status[slot0 + p];
+  if (st == EVH_PAIR_OK) {
+    const int n = A.npts2[slot0 + p];
+    const float* rows = A.pts2 + (slot0 + p) * A.row_stride * 4;
+    const ScanPre pre{W.hyp + (int64_t)s * W.hmax, W.hypH + (int64_t)s * W.hmax * 9, W.hmax, n > 4 ? W.rng_after[at.slot0 + p] : 0ull};
+    st = compute_homography_block<4, false>(B, rows, n, first ? nullptr : B.Hsup, A, A.mask + slot0 * A.row_stride,
+                                            A.pts + slot0 * A.row_stride * 4, A.crow + slot0 * A.row_stride * 4,
+                                            A.info ? A.info + 8 * (slot0 + p) + 4 : nullptr, n > 4 ? &pre : nullptr);
+  }
+  if (scan_step_tail<4, false>(B, st, p, npairs, Hout, stout, first)) {
+    if (tid == 0) T.aborted = 1;
+    return;
+  }
+  if (tid < 9) { T.Hsup[tid] = B.Hsup[tid]; T.Hprev[tid] = B.Hprev[tid]; }
+  if (tid == 0) { T.have_prev = 1; T.first = 0; }
+  if (p == npairs - 1 && A.state_out && tid < 9) { A.state_out[18 * s + tid] = B.Hsup[tid]; A.state_out[18 * s + 9 + tid] = B.Hprev[tid]; }
+}
+
 // ---- fixed-iteration RANSAC #1 of a SMALL batch of pairs (a stream chunk): the same split -- k_static_hyp evaluates one
 // 16-hypothesis chunk per workgroup (grid: chunks x pairs), k_static_finish replays, refines and runs the static filter.
 // (One workgroup per pair with per-lane solvers is the throughput form for hundreds of pairs; alone it takes 4.8 ms.)
@@ -819,9 +946,8 @@ int waves_for(int nblocks, int force_max) {
 }
 
 // workspace of the fixed-iteration stream scan, grown on demand
-int scan_ws(evh_ctx* c, int nstreams, int npairs, int hmax, ScanWs* W) {
+int scan_ws(evh_ctx* c, int nstreams, size_t slots /* sample tables */, int hmax, ScanWs* W) {
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t slots = (size_t)nstreams * npairs;
   const size_t o_state = 0, o_rng = o_state + up(sizeof(ScanState) * nstreams), o_quads = o_rng + up(8 * slots),
                o_hyp = o_quads + up(sizeof(ushort4) * slots * hmax), o_H = o_hyp + up(sizeof(int) * (size_t)nstreams * hmax),
                total = o_H + up(sizeof(double) * 9 * (size_t)nstreams * hmax);
@@ -846,7 +972,7 @@ int launch_forced_static(evh_ctx* c, const EvhRansacArgs& A, int npairs) {
   if (A.row_stride > 65536) return evh_fail(c, EVH_ERR_INVALID, "fixed-iteration RANSAC: more than 65536 rows per pair");
   const int chunks = forced_chunks(A);
   ScanWs W;
-  int rc = scan_ws(c, npairs, 1, chunks * 4 * NG, &W);
+  int rc = scan_ws(c, npairs, (size_t)npairs, chunks * 4 * NG, &W);
   if (rc) return rc;
   hipLaunchKernelGGL(k_scan_quads, dim3(npairs), dim3(NL), 0, c->stream, A, 1, 1, W, 1);
   hipLaunchKernelGGL(k_static_hyp, dim3(chunks, npairs), dim3(4 * NL), 0, c->stream, A, W);
@@ -858,13 +984,32 @@ int launch_forced_scan(evh_ctx* c, const EvhRansacArgs& A, int npairs, int nstre
   if (A.row_stride > 65536) return evh_fail(c, EVH_ERR_INVALID, "fixed-iteration scan: more than 65536 rows per pair");
   const int chunks = forced_chunks(A);
   ScanWs W;
-  int rc = scan_ws(c, nstreams, npairs, chunks * 4 * NG, &W);
+  int rc = scan_ws(c, nstreams, (size_t)nstreams * npairs, chunks * 4 * NG, &W);
   if (rc) return rc;
   hipLaunchKernelGGL(k_scan_init, dim3(nstreams), dim3(NL), 0, c->stream, A, W);
   hipLaunchKernelGGL(k_scan_quads, dim3(nstreams * npairs), dim3(NL), 0, c->stream, A, npairs, pitch, W, 0);
   for (int p = 0; p < npairs; p++) {
     hipLaunchKernelGGL(k_scan_hyp, dim3(chunks, nstreams), dim3(4 * NL), 0, c->stream, A, p, npairs, pitch, W);
     hipLaunchKernelGGL(k_scan_finish, dim3(nstreams), dim3(4 * NL), 0, c->stream, A, p, npairs, pitch, W);
+  }
+  return EVH_SUCCESS;
+}
+
+// npairs: the pairs of the longest stream (the per-pair launches run that far).  The sample tables: one per pair of every
+// stream (quad_streams x quad_pairs of them, `pitch` slots apart) -- a ragged batch draws them for all its pair slots as one
+// run (1 x slots), the straddling ones included
+int launch_forced_ragged(evh_ctx* c, const EvhRansacArgs& A, int npairs, int nstreams, const RaggedStreams& lay, int quad_streams,
+                       int quad_pairs, int pitch) {
+  if (A.row_stride > 65536) return evh_fail(c, EVH_ERR_INVALID, "fixed-iteration scan: more than 65536 rows per pair");
+  const int chunks = forced_chunks(A);
+  ScanWs W;
+  int rc = scan_ws(c, nstreams, (size_t)quad_streams * quad_pairs, chunks * 4 * NG, &W);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_scan_init_ragged, dim3(nstreams), dim3(NL), 0, c->stream, A, W, lay);
+  hipLaunchKernelGGL(k_scan_quads, dim3(quad_streams * quad_pairs), dim3(NL), 0, c->stream, A, quad_pairs, pitch, W, 0);
+  for (int p = 0; p < npairs; p++) {
+    hipLaunchKernelGGL(k_scan_hyp_ragged, dim3(chunks, nstreams), dim3(4 * NL), 0, c->stream, A, p, lay, W);
+    hipLaunchKernelGGL(k_scan_finish_ragged, dim3(nstreams), dim3(4 * NL), 0, c->stream, A, p, lay, W);
   }
   return EVH_SUCCESS;
 }
@@ -904,7 +1049,8 @@ int evh_launch_ransac_static(evh_ctx* c, const EvhRansacArgs& A, int npairs) {
   EVH_LAUNCH_NW(waves_for(npairs, A.force_max), k_ransac_static, npairs, c->stream, A);
   return launched(c);
 }
-int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, int npairs, int nstreams, int pitch) {
+int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, int npairs, int nstreams, int pitch, const evh_stream_seg* d_segs,
+                            int max_pairs) {
   if (npairs <= 0) return EVH_SUCCESS;
   EvhRansacArgs A = A_;
   if (int rc = check_lane_scratch(c, A)) return rc;
@@ -918,11 +1064,14 @@ int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, int npairs, int
     }
     A.prof = d_prof;
   }
-  // nstreams == 0: independent pairs; otherwise nstreams sequential scans of npairs pairs each, `pitch` pair slots apart
+  // nstreams == 0: independent pairs; otherwise nstreams sequential scans of npairs pairs each, `pitch` pair slots apart;
+  // with d_segs: the nstreams scans of a ragged batch of npairs pair slots, max_pairs pairs in the longest
   if (nstreams > 0 && A.force_max && !getenv("EVH_SCAN_ONE_WG")) {
-    const int fr = launch_forced_scan(c, A, npairs, nstreams, pitch);
+    const int fr = d_segs ? launch_forced_ragged(c, A, max_pairs, nstreams, RaggedStreams{d_segs}, 1, npairs, 0)
+                          : launch_forced_scan(c, A, npairs, nstreams, pitch);
     if (fr) { if (d_prof) (void)hipFree(d_prof); return fr; }
-  } else if (nstreams > 0) EVH_LAUNCH_NW(waves_for(nstreams, A.force_max), k_ransac_final_stream, nstreams, c->stream, A, npairs, pitch);
+  } else if (d_segs) EVH_LAUNCH_NW(waves_for(nstreams, A.force_max), k_ransac_final_ragged, nstreams, c->stream, A, RaggedStreams{d_segs});
+  else if (nstreams > 0) EVH_LAUNCH_NW(waves_for(nstreams, A.force_max), k_ransac_final_stream, nstreams, c->stream, A, npairs, pitch);
   else EVH_LAUNCH_NW(waves_for(npairs, A.force_max), k_ransac_final_pairs, npairs, c->stream, A);
   {
     const hipError_t le = hipGetLastError();

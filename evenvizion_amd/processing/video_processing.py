@@ -57,6 +57,43 @@ def _first_planes(capture, ingest):
     return packed[0], w, h
 
 
+def rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, max_frames, run, overflowed, what):
+    """Some frame delivered more tied key points than a frame slot of `ctx` holds (a pair reported EVH_PAIR_CAPACITY).
+    The reference has no such bound (it carries on with every tie, frame_processing.py:59-61), so the work is done again
+    -- run(big), which starts from the state the work was entered with and waits for its results -- on a context whose
+    frame slots are twice as large (same nfeatures, so the same key points for every other frame), doubling again while
+    overflowed() still says so, up to the LDS limit of the matching filter.  `what` names the frames in the error."""
+    from .._lib import Context, MAX_FEATURES
+    # every list grows from what the context that overflowed actually had, each up to its own limit
+    feats = max(ctx.max_features, nfeatures)
+    sift0 = max(ctx.lib.evh_sift_capacity(ctx.h), runtime.sift_features_for(dw, dh)) if "SIFT" in features else 0
+    surf0 = max(ctx.lib.evh_surf_capacity(ctx.h), runtime.surf_features_for(dw, dh)) if "SURF" in features else 0
+    grow = 1
+    while True:
+        at_limit = feats >= MAX_FEATURES and (not sift0 or sift0 * grow >= runtime.TYPE_FEATURES_MAX) and \
+            (not surf0 or surf0 * grow >= runtime.TYPE_FEATURES_MAX)
+        feats = min(feats * 2, MAX_FEATURES)
+        grow *= 2
+        try:
+            if at_limit:
+                raise EvhError("giving up")
+            big = Context(device=runtime.device_index(), max_w=max(dw, 64), max_h=max(dh, 64),
+                          max_features=feats, max_frames=max_frames)
+            if sift0:
+                big.sift_enable(min(runtime.TYPE_FEATURES_MAX, sift0 * grow))
+            if surf0:
+                big.surf_enable(min(runtime.TYPE_FEATURES_MAX, surf0 * grow))
+        except EvhError:
+            raise EvhError("%s: more key points (ORB ties at the retainBest cut, or SIFT key points) than "
+                           "the largest frame slot this device path supports" % what)
+        try:
+            run(big)
+        finally:
+            big.close()
+        if not overflowed():
+            break
+
+
 def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_processing=True,
                         nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES, features_type_list=None, ingest="bgr"):
     """capture: anything with read() -> (bool, BGR uint8 frame) (cv2.VideoCapture duck type).
@@ -132,48 +169,23 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
             all_done[jb].record(cur)
 
     def rerun_with_larger_slots(jb, nb, later):
-        """A frame of chunk jb delivered more tied key points than a frame slot of `ctx` holds.  The reference has no
-        such bound (it carries on with every tie, frame_processing.py:59-61), so the chunk is re-run from the state it
-        was entered with on a context whose frame slots are twice as large (same nfeatures, so the same key points for
-        every other frame), doubling again if needed up to the LDS limit of the matching filter; the chunk launched
-        after it (computed from a state that is now stale) is then re-run as well."""
-        from .._lib import Context
+        """A frame of chunk jb delivered more tied key points than a frame slot of `ctx` holds: the chunk is re-run from
+        the state it was entered with (rerun_on_larger_slots); the chunk launched after it (computed from a state that is
+        now stale) is then re-run as well."""
         if cuda:
             torch.cuda.synchronize(dev)
-        from .._lib import MAX_FEATURES
-        # every list grows from what the context that overflowed actually had, each up to its own limit
-        feats = max(ctx.max_features, nfeatures)
-        sift0 = max(ctx.lib.evh_sift_capacity(ctx.h), runtime.sift_features_for(dw, dh)) if "SIFT" in features else 0
-        surf0 = max(ctx.lib.evh_surf_capacity(ctx.h), runtime.surf_features_for(dw, dh)) if "SURF" in features else 0
-        grow = 1
-        while True:
-            at_limit = feats >= MAX_FEATURES and (not sift0 or sift0 * grow >= runtime.TYPE_FEATURES_MAX) and \
-                (not surf0 or surf0 * grow >= runtime.TYPE_FEATURES_MAX)
-            feats = min(feats * 2, MAX_FEATURES)
-            grow *= 2
-            try:
-                if at_limit:
-                    raise EvhError("giving up")
-                big = Context(device=runtime.device_index(), max_w=max(dw, 64), max_h=max(dh, 64),
-                              max_features=feats, max_frames=chunk_frames)
-                if sift0:
-                    big.sift_enable(min(runtime.TYPE_FEATURES_MAX, sift0 * grow))
-                if surf0:
-                    big.surf_enable(min(runtime.TYPE_FEATURES_MAX, surf0 * grow))
-            except EvhError:
-                raise EvhError("frame %d..%d: more key points (ORB ties at the retainBest cut, or SIFT key points) than "
-                               "the largest frame slot this device path supports" % (frame_no[0], frame_no[0] + nb - 1))
-            try:
-                state.copy_(state_pre[jb])
-                launch(big, jb, nb, had_state[jb])
-                if cuda:
-                    torch.cuda.synchronize(dev)
-                else:
-                    big.synchronize()
-            finally:
-                big.close()
-            if not (st_host[jb][:nb - 1].numpy() == PAIR_CAPACITY).any():
-                break
+
+        def run(big):
+            state.copy_(state_pre[jb])
+            launch(big, jb, nb, had_state[jb])
+            if cuda:
+                torch.cuda.synchronize(dev)
+            else:
+                big.synchronize()
+
+        rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, chunk_frames, run,
+                              lambda: bool((st_host[jb][:nb - 1].numpy() == PAIR_CAPACITY).any()),
+                              "frame %d..%d" % (frame_no[0], frame_no[0] + nb - 1))
         if later is not None:                           # the chunk that was in flight behind it
             lj, ln = later
             state_pre[lj].copy_(state)
@@ -254,3 +266,308 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
             torch.cuda.synchronize(dev)                 # nothing of this call is left in flight on the shared buffers
     homography_dict["resize_info"] = {"h": dh, "w": dw}
     return homography_dict
+
+
+MAX_STREAMS = 16     # captures of get_homography_dicts live at once (one scan workgroup each)
+DECODE_THREADS = 8   # host threads reading frames for get_homography_dicts
+
+
+class _Stream:
+    """One capture inside get_homography_dicts: where it stands and what it has delivered."""
+
+    def __init__(self, index, capture, first, planes, w0, h0):
+        self.index, self.capture, self.first, self.planes, self.w0, self.h0 = index, capture, first, planes, w0, h0
+        self.frame_no = 1        # 1-based index of the newest frame already paired
+        self.read = 1            # frames taken from the capture so far
+        self.started = False     # a round has carried its {H_sup, H_prev} out
+        self.exhausted = False   # the capture has no further frame
+        self.last = None         # index of its newest frame inside its region of the round before (None: not read yet)
+        self.done = False        # its entry of the result list is final
+        self.result = {}
+
+
+def _read_frames(st, region, w0, h0):
+    """Decode-pool task: the capture's next frames into region[1:], a stream's frames of the pinned staging buffer (frame 0 is
+    the carried one).  -> (frames now in the region, error or None); sets st.exhausted when the capture ran dry."""
+    from .._lib import yuv420_views
+    n = 1
+    try:
+        while n < len(region):
+            if st.planes:
+                y, cb, cr = yuv420_views(region[n][None], w0, h0)
+                ok = bool(st.capture.read_yuv420_into(y[0], cb[0], cr[0]))
+            else:
+                ok, frame = st.capture.read()
+                if ok:
+                    frame = np.asarray(frame, np.uint8)
+                    if frame.shape != region[n].shape:
+                        raise ValueError("frame %d has shape %s, the first frame %s" % (st.read + 1, frame.shape, region[n].shape))
+                    region[n][...] = frame
+            if not ok:
+                st.exhausted = True
+                break
+            st.read += 1
+            n += 1
+    except Exception as e:          # the capture's own failure: this capture's result, the others go on
+        st.exhausted = True
+        return n, e
+    return n, None
+
+
+def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfeatures=runtime.NFEATURES,
+                         features_type_list=None, ingest="bgr", chunk_frames=CHUNK_FRAMES, max_streams=MAX_STREAMS,
+                         decode_threads=DECODE_THREADS, return_exceptions=False):
+    """get_homography_dict for several captures at once -> a list, entry i == get_homography_dict(captures[i], ...) with the
+    same options, whatever max_streams, chunk_frames, the captures' lengths and their order.
+
+    One capture alone cannot fill the card: its final RANSAC is a sequential scan (video_processing.py:83-105).  Here up to
+    max_streams captures are live; a round hands every live capture up to chunk_frames - 1 new frames behind the frame it
+    carries over, all of them go through one evh_streams_homography_batch call (detection and matching over all frames at
+    once, one scan per capture side by side), and every capture's {H_sup, H_prev} stay on the device between rounds.  A
+    capture that ended gives its place to the next waiting one.  Frames are read by `decode_threads` host threads, one
+    capture per task, straight into the pinned staging buffer (libevcap releases the GIL); the reads of round r + 1 overlap
+    the GPU work of round r, and one GPU round is in flight.  Captures are grouped by the geometry of their frames and by
+    whether they deliver planes (the rule of _first_planes, per capture); the groups run one after another.  A capture is
+    opened -- its first frame read, which decides its group -- only when a place is free for it, so what is held scales with
+    max_streams, not with the list; one that turns out to belong to another group waits, opened, for that group's turn.
+
+    A capture for which get_homography_dict would raise (ValueError: no first frame; AttributeError: a pair without H where
+    the reference has none; whatever its read() raises): with return_exceptions=False the call raises that exception for the
+    lowest such index once nothing of the call is in flight, with True the exception takes the capture's place in the list.
+    A round in which a pair reports EVH_PAIR_CAPACITY is re-run as a whole on larger frame slots (rerun_on_larger_slots)."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from .frame_processing import DEFAULT_FEATURES
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    features = list(features_type_list or DEFAULT_FEATURES)
+    for name in features:
+        if name not in ("ORB", "SIFT", "SURF"):
+            raise ValueError("You need to choose descriptors type")
+    captures = list(captures)
+    results = [None] * len(captures)
+    max_streams, chunk_frames = max(1, int(max_streams)), max(2, int(chunk_frames))
+    stop_after = [len(captures)]          # return_exceptions=False: captures behind the lowest failing index are not run
+
+    def fail(index, exc):
+        results[index] = exc
+        if not return_exceptions:
+            stop_after[0] = min(stop_after[0], index)
+
+    pending = list(enumerate(captures))   # not opened yet
+    deferred = {}                         # group key -> captures opened while another group was running, in list order
+
+    def open_next(key):
+        """The next capture of group `key` (None: of whatever group comes next), opened; captures of other groups met on the
+        way wait in `deferred`."""
+        if key is None and deferred:
+            key = next(iter(deferred))
+        if key in deferred:
+            st = deferred[key].pop(0)
+            if not deferred[key]:
+                del deferred[key]
+            return st
+        while pending:
+            i, capture = pending.pop(0)
+            if i > stop_after[0]:
+                continue
+            try:
+                first, w0, h0 = _first_planes(capture, ingest)
+                planes = first is not None
+                if not planes:
+                    success, first = capture.read()
+                    if not success:
+                        raise ValueError("Problem with video! Can't read first frame")
+                    first = np.ascontiguousarray(first, np.uint8)
+                    h0, w0 = first.shape[:2]
+            except Exception as e:
+                fail(i, e)
+                continue
+            st = _Stream(i, capture, first, planes, w0, h0)
+            st.key = (planes, first.shape, w0, h0)
+            if key is None or st.key == key:
+                return st
+            deferred.setdefault(st.key, []).append(st)
+        return None
+
+    dev = runtime.device()
+    cuda = dev.type == "cuda"          # (the host-loop unit tests drive this function on the CPU with a scripted context)
+    pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
+    try:
+        while True:
+            head = open_next(None)
+            if head is None:
+                break
+            key = head.key
+            planes, shape, w0, h0 = key
+            more = len(pending) + len(deferred.get(key, ()))          # at most this many further members
+            _run_group(head, lambda: open_next(key), 1 + more, planes, shape, w0, h0, resize_width, none_H_processing, nfeatures,
+                       features, chunk_frames, max_streams, pool, dev, cuda, fail, stop_after, results)
+    finally:
+        pool.shutdown(wait=True)
+        if cuda:
+            torch.cuda.synchronize(dev)                 # nothing of this call is left in flight on the shared buffers
+    if not return_exceptions and stop_after[0] < len(captures):
+        raise results[stop_after[0]]
+    return results
+
+
+def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, none_H_processing, nfeatures, features, chunk_frames, max_streams,
+               pool, dev, cuda, fail, stop_after, results):
+    """The captures of one geometry -- `head`, then whatever next_member() opens, at_most of them -- through rounds of
+    evh_streams_homography_batch (see get_homography_dicts)."""
+    import torch
+    dw, dh = resized_shape((h0, w0), resize_width)
+    # the staging buffer is capped in bytes: fewer live captures, then shorter chunks, for large frames
+    S = min(max_streams, at_most)
+    total = runtime.chunk_frames_for(int(np.prod(shape)), S * chunk_frames)
+    S = max(1, min(S, total // 2))
+    cf = max(2, min(chunk_frames, total // S))          # frames of one capture in a round, the carried one included
+    total = S * cf
+    ctx = runtime.get_context(dw, dh, total, nfeatures, sift="SIFT" in features, surf="SURF" in features)
+    B = runtime.staging((total,) + tuple(shape), dev)
+    host, host_np, devbuf = B["host"], B["host_np"], B["dev"]
+    H_dev, st_dev, H_host, st_host = B["H_dev"], B["st_dev"], B["H_host"], B["st_host"]
+    copy_stream, up_done, all_done = B["copy_stream"], B["up_done"], B["all_done"]
+    cur = torch.cuda.current_stream(dev) if cuda else None
+    state = torch.zeros(S, 18, dtype=torch.float64, device=dev)       # {H_sup, H_prev} of the capture reading in every place
+    waiting = [head]                                                  # opened, not placed yet
+    drained = [False]                                                 # next_member() has said that no more come
+    places = [None] * S                                               # the captures that are still being read
+
+    def finish(st, exc=None):
+        if exc is not None:
+            fail(st.index, exc)
+        else:
+            st.result["resize_info"] = {"h": dh, "w": dw}
+            results[st.index] = st.result
+        st.done = True
+
+    def start_reads(j):
+        """A waiting capture into every free place, then every place's next frames into its region of host buffer j, behind
+        the frame it carries over (consecutive rounds overlap by one frame)."""
+        reads = []
+        for k in range(S):
+            while places[k] is None and not drained[0]:
+                st = waiting.pop(0) if waiting else next_member()
+                if st is None:
+                    drained[0] = True
+                elif st.index < stop_after[0]:
+                    places[k] = st
+            st = places[k]
+            if st is None:
+                continue
+            region = host_np[j][k * cf:(k + 1) * cf]
+            if st.last is None:
+                region[0], st.first = st.first, None
+            else:
+                region[0] = host_np[1 - j][k * cf + st.last]
+            reads.append((k, st, pool.submit(_read_frames, st, region, w0, h0)))
+        return reads
+
+    def launch(c, j, table, state_in, state_out):
+        segs = [(a, n, not st.started) for (_, st, a, n, _) in table]
+        nb = segs[-1][0] + segs[-1][1]
+        c.streams_homography_batch(devbuf[j][:nb], segs, H_dev[j], st_dev[j], features=features, state_in=state_in,
+                                   state_out=state_out, nfeatures=nfeatures, resize_to=(dw, dh),
+                                   size=(w0, h0) if planes else None)
+        if cuda:
+            c.order_torch_after()
+        H_host[j][:nb - 1].copy_(H_dev[j][:nb - 1], non_blocking=True)
+        st_host[j][:nb - 1].copy_(st_dev[j][:nb - 1], non_blocking=True)
+        if cuda:
+            all_done[j].record(cur)
+
+    def collect(j, table, idx, state_in, state_out):
+        """The results of the round in flight: re-run on larger slots if a frame overflowed, the states back to their places,
+        every capture's pairs into its dictionary."""
+        if cuda:
+            all_done[j].synchronize()
+        rows = np.concatenate([np.arange(a, a + n - 1) for (_, _, a, n, _) in table])
+
+        def overflowed():
+            return bool((st_host[j].numpy()[rows] == PAIR_CAPACITY).any())
+
+        if overflowed():
+            if cuda:
+                torch.cuda.synchronize(dev)
+
+            def run(big):
+                launch(big, j, table, state_in, state_out)
+                if cuda:
+                    torch.cuda.synchronize(dev)
+                else:
+                    big.synchronize()
+
+            rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, total, run, overflowed,
+                                  "captures %s" % [st.index for (_, st, _, _, _) in table])
+        state[idx] = state_out
+        Hs = H_host[j].numpy().reshape(-1, 3, 3)
+        sts = st_host[j].numpy()
+        for (k, st, a, n, last_round) in table:
+            st.started = True
+            try:
+                for r in range(a, a + n - 1):
+                    st.frame_no += 1
+                    fno = st.frame_no
+                    if sts[r] != PAIR_OK:
+                        logging.info("capture %d, pair ending at frame %d: no homography (status %d)", st.index, fno, int(sts[r]))
+                        if not none_H_processing or not np.all(np.isfinite(Hs[r])):
+                            # reference behaviour (video_processing.py:94-101): H stays None and None.tolist() raises --
+                            # always for none_H_processing=False, and for a failing FIRST pair otherwise (SURVEY F11)
+                            raise AttributeError("'NoneType' object has no attribute 'tolist' (no homography for frame %d, "
+                                                 "status %d)" % (fno, int(sts[r])))
+                    st.result[fno] = {"H": Hs[r].tolist()}
+            except AttributeError as e:
+                finish(st, e)
+                if places[k] is st:
+                    places[k] = None
+                continue
+            if last_round:
+                finish(st)
+
+    j = 0
+    reads = start_reads(j)
+    inflight = None
+    while reads or inflight is not None:
+        counts = []
+        for k, st, fut in reads:                        # read while the round before this one runs on the GPU
+            n, err = fut.result()
+            st.last = n - 1
+            counts.append((k, st, n, err))
+        if inflight is not None:                        # one GPU round in flight: collected before the next is launched
+            collect(*inflight)
+            inflight = None
+        table, pos = [], 0
+        for k, st, n, err in counts:
+            if st.exhausted and places[k] is st:
+                places[k] = None                        # ran dry: the place goes to the next waiting capture
+            if st.done:
+                continue                                # failed in the round just collected
+            if st.index > stop_after[0]:
+                st.done = True                          # behind the lowest failing index nothing more is run
+                places[k] = None
+            elif err is not None:
+                finish(st, err)
+            elif n < 2:
+                finish(st)                              # nothing new: the capture has ended and leaves the table
+            else:
+                table.append((k, st, pos, n, st.exhausted))
+                pos += n
+        if table:
+            for (k, st, a, n, _) in table:              # the segments back to back on the device
+                if cuda:
+                    with torch.cuda.stream(copy_stream):
+                        devbuf[j][a:a + n].copy_(host[j][k * cf:k * cf + n], non_blocking=True)
+                else:
+                    devbuf[j][a:a + n].copy_(host[j][k * cf:k * cf + n])
+            if cuda:
+                up_done[j].record(copy_stream)
+                cur.wait_event(up_done[j])
+            idx = torch.tensor([k for (k, _, _, _, _) in table], dtype=torch.long, device=dev)
+            state_in = state[idx]                       # as the round is entered: what a re-run starts from
+            state_out = torch.zeros_like(state_in)
+            launch(ctx, j, table, state_in, state_out)
+            inflight = (j, table, idx, state_in, state_out)
+        j = 1 - j
+        reads = start_reads(j)                          # the next round's frames, while this one runs

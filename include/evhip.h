@@ -415,6 +415,45 @@ int evh_stream_homography_batch_types_yuv420(evh_ctx* ctx, const evh_yuv420* src
                                              int ransac_max_iters, double ransac_conf, int force_max_iters,
                                              const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status);
 
+
+/* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
+/* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */
+typedef struct evh_stream_seg {
+  int32_t first_frame;  /* index of the segment's first frame in the batch                          */
+  int32_t nframes;      /* >= 2 consecutive frames -> nframes - 1 pairs                             */
+  int32_t start;        /* non-zero: the stream starts in this call; its d_state_in row is not read */
+  int32_t reserved;     /* 0 */
+} evh_stream_seg;
+/* evh_multi_stream_homography_batch for streams of unequal length that start and end in different calls, with the ingests and
+ * the feature type lists of the single-stream entries: what get_homography_dicts (several captures at once) runs per round.
+ * d_frames holds total_frames frames of src_w x src_h, working size (w, h) as in evh_stream_homography_batch_resized (equal
+ * sizes = no resize); h_segs cuts them into nstreams segments that tile [0, total_frames) in ascending order (anything else,
+ * a segment of fewer than 2 frames, or reserved != 0: EVH_ERR_INVALID; total_frames > max_frames: EVH_ERR_CAPACITY).  Pair
+ * slot p is (frame p + 1, frame p) as in the stream entries; pair k of a segment writes d_H[first_frame + k] and
+ * d_status[first_frame + k] (d_H f64[total_frames - 1][9], d_status i32[total_frames - 1]); the row at a segment's last frame
+ * belongs to no stream and is never written.  d_state_in / d_state_out f64[nstreams][18] carry {H_sup, H_prev} of stream s in
+ * row s and may be the same buffer; a segment with start != 0 does not read its row, and d_state_in may be NULL only when every
+ * segment starts here (else EVH_ERR_INVALID).  h_types as in evh_stream_homography_batch_types: a list of exactly
+ * {EVH_FEATURE_ORB} takes the fused ORB path (with asynchronous solve when enabled), any other list the multi-type path; a
+ * bad list, a type named twice, SIFT / SURF without their _enable are refused with the codes of that entry.  Every refusal
+ * comes before the first launch: the outputs are untouched.  Everything up to the static filter runs over all frames and pair
+ * slots at once; the sequential scans then run concurrently, one workgroup per stream, a shorter stream leaving early (with
+ * force_max_iters the per-pair launches run up to the longest stream).  Per stream the results are bit-identical to that stream
+ * alone through evh_stream_homography_batch[_resized|_types] in the same chunks.  Does not synchronise.                        */
+int evh_streams_homography_batch(evh_ctx* ctx, const uint8_t* d_frames, int total_frames, int src_w, int src_h, int channels,
+                                 int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures, const int32_t* h_types,
+                                 int ntypes, const evh_stream_seg* h_segs, int nstreams, double ransac_thr, int ransac_max_iters,
+                                 double ransac_conf, int force_max_iters, const double* d_state_in, double* d_state_out,
+                                 double* d_H, int32_t* d_status);
+/* The same on decoded 4:2:0 planes (total_frames frames behind one evh_yuv420): the {ORB} list takes level 0 straight from the
+ * planes as evh_stream_homography_batch_yuv420 does, any other list converts the batch once as
+ * evh_stream_homography_batch_types_yuv420 does.  Bit-identical to the BGR form on the frames the planes convert to.          */
+int evh_streams_homography_batch_yuv420(evh_ctx* ctx, const evh_yuv420* src, int total_frames, int src_w, int src_h, int w, int h,
+                                        int nfeatures, const int32_t* h_types, int ntypes, const evh_stream_seg* h_segs,
+                                        int nstreams, double ransac_thr, int ransac_max_iters, double ransac_conf,
+                                        int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
+                                        int32_t* d_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,32 @@ def _hp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _packed(frames, lead=1):
+    """frames: contiguous uint8 tensor [*batch, h, w] (gray) or [*batch, h, w, c] with `lead` batch dimensions -> the seven
+    arguments of a packed-frame entry: pointer, first batch extent, w, h, channels, row stride, frame stride."""
+    h, w = frames.shape[lead:lead + 2]
+    cn = 1 if frames.dim() == lead + 2 else frames.shape[lead + 2]
+    return (frames.data_ptr(), frames.shape[0], w, h, cn, w * cn, w * h * cn)
+
+
+def _work_size(resize_to, w, h):
+    """The size ORB runs at: resize_to=(w, h), or the frames' own."""
+    return (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+
+
+def _ransac(thr, max_iters, conf, force_max_iters):
+    return (float(thr), int(max_iters), float(conf), int(bool(force_max_iters)))
+
+
+def _tail(ransac, state_in, state_out, out_H, out_status):
+    """What every stream entry ends with: the RANSAC parameters, the state in and out, the outputs."""
+    return _ransac(*ransac) + (_ptr(state_in), _ptr(state_out), out_H.data_ptr(), out_status.data_ptr())
+
+
 class Context:
     """One evh_ctx: one device, one HIP stream, device buffers sized at creation (reused across calls)."""
 
@@ -303,13 +329,11 @@ class Context:
         """frames: CUDA uint8 tensor [n,h,w] (gray) or [n,h,w,3] (BGR), contiguous.  resize_to=(w, h): the frames are
         shrunk to that working size inside the ingest kernel (imutils.resize fused into level 0)."""
         self._enter()
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        if resize_to is not None and tuple(resize_to) != (w, h):
-            self._check(self.lib.evh_orb_detect_batch_resized(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn,
-                                                              int(resize_to[0]), int(resize_to[1]), nfeatures))
+        p = _packed(frames)
+        if resize_to is not None and tuple(resize_to) != p[2:4]:
+            self._check(self.lib.evh_orb_detect_batch_resized(self.h, *p, int(resize_to[0]), int(resize_to[1]), nfeatures))
             return
-        self._check(self.lib.evh_orb_detect_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, nfeatures))
+        self._check(self.lib.evh_orb_detect_batch(self.h, *p, nfeatures))
 
     def orb_detect_compute(self, frame, nfeatures=500):
         """One frame (CUDA uint8 [h,w] or [h,w,3]) -> (xy f32[n,2], desc u8[n,32], octave i32[n]); the single-frame
@@ -397,11 +421,9 @@ class Context:
     def pair_homography_batch(self, frames, npairs, mode, out_H, out_status, nfeatures=500, thr=3.0, max_iters=2000,
                               conf=0.995, force_max_iters=False):
         self._enter()
-        h, w = frames.shape[1:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        self._check(self.lib.evh_pair_homography_batch(self.h, frames.data_ptr(), npairs, mode, w, h, cn, w * cn,
-                                                       w * h * cn, nfeatures, float(thr), int(max_iters), float(conf),
-                                                       int(bool(force_max_iters)), out_H.data_ptr(),
+        p = _packed(frames)
+        self._check(self.lib.evh_pair_homography_batch(self.h, p[0], npairs, mode, *p[2:], nfeatures,
+                                                       *_ransac(thr, max_iters, conf, force_max_iters), out_H.data_ptr(),
                                                        out_status.data_ptr()))
 
     def stream_homography_batch(self, frames, out_H, out_status, state_in=None, state_out=None, nfeatures=500, thr=3.0,
@@ -409,31 +431,22 @@ class Context:
         """frames: CUDA uint8 [n,h,w(,3)], n >= 2 consecutive frames of one stream -> n-1 pairs (stream semantics).
         resize_to=(w, h): full-size frames, the reference's resize_width fused into the ingest kernel."""
         self._enter()
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        if resize_to is not None and tuple(resize_to) != (w, h):
-            self._check(self.lib.evh_stream_homography_batch_resized(
-                self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, int(resize_to[0]), int(resize_to[1]), nfeatures,
-                float(thr), int(max_iters), float(conf), int(bool(force_max_iters)),
-                state_in.data_ptr() if state_in is not None else None,
-                state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+        p = _packed(frames)
+        tail = (nfeatures,) + _tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)
+        if resize_to is not None and tuple(resize_to) != p[2:4]:
+            self._check(self.lib.evh_stream_homography_batch_resized(self.h, *p, int(resize_to[0]), int(resize_to[1]), *tail))
             return
-        self._check(self.lib.evh_stream_homography_batch(
-            self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, nfeatures, float(thr), int(max_iters), float(conf),
-            int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-            state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+        self._check(self.lib.evh_stream_homography_batch(self.h, *p, *tail))
 
     def multi_stream_homography_batch(self, frames, out_H, out_status, state_in=None, state_out=None, nfeatures=500,
                                       thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False):
         """frames: CUDA uint8 [S,F,h,w(,3)] -- S independent streams of F consecutive frames each; out_H f64[S,F-1,9],
         out_status i32[S,F-1]; state_in / state_out f64[S,18] carry {H_sup, H_prev} of every stream between calls."""
         self._enter()
-        S, F, h, w = frames.shape[:4]
-        cn = 1 if frames.dim() == 4 else frames.shape[4]
+        p = _packed(frames, lead=2)
         self._check(self.lib.evh_multi_stream_homography_batch(
-            self.h, frames.data_ptr(), S, F, w, h, cn, w * cn, w * h * cn, nfeatures, float(thr), int(max_iters),
-            float(conf), int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-            state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+            self.h, p[0], p[1], frames.shape[1], *p[2:], nfeatures,
+            *_tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)))
 
     def streams_homography_batch(self, frames, segments, out_H, out_status, features=("ORB",), state_in=None, state_out=None,
                                  nfeatures=500, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None,
@@ -449,19 +462,14 @@ class Context:
         t = self._types(features)
         if list(t) != [FEATURE_ORB]:
             self._multi_used = True
-        tail = (nfeatures, _hp(t), len(t), C.cast(segs, C.c_void_p), len(segments), float(thr), int(max_iters), float(conf),
-                int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-                state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr())
+        tail = (nfeatures, _hp(t), len(t), C.cast(segs, C.c_void_p), len(segments)) + \
+            _tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)
         if isinstance(frames, (tuple, list)) or frames.dim() == 2:
             d, n, w, h = self._yuv420(frames, size, self.device)
-            dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
-            self._check(self.lib.evh_streams_homography_batch_yuv420(self.h, C.byref(d), n, w, h, dw, dh, *tail))
+            self._check(self.lib.evh_streams_homography_batch_yuv420(self.h, C.byref(d), n, w, h, *_work_size(resize_to, w, h), *tail))
             return
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
-        self._check(self.lib.evh_streams_homography_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh,
-                                                          *tail))
+        p = _packed(frames)
+        self._check(self.lib.evh_streams_homography_batch(self.h, *p, *_work_size(resize_to, *p[2:4]), *tail))
 
     # ---- decoded 4:2:0 planes as the source ----
     @staticmethod
@@ -518,19 +526,16 @@ class Context:
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""
         self._enter()
         d, n, w, h = self._yuv420(planes, size, self.device)
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
-        self._check(self.lib.evh_orb_detect_batch_yuv420(self.h, C.byref(d), n, w, h, dw, dh, nfeatures))
+        self._check(self.lib.evh_orb_detect_batch_yuv420(self.h, C.byref(d), n, w, h, *_work_size(resize_to, w, h), nfeatures))
 
     def stream_homography_batch_yuv420(self, planes, size, out_H, out_status, state_in=None, state_out=None, nfeatures=500,
                                        thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None):
         """stream_homography_batch on decoded planes (see _yuv420): n >= 2 consecutive frames -> n-1 pairs."""
         self._enter()
         d, n, w, h = self._yuv420(planes, size, self.device)
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
         self._check(self.lib.evh_stream_homography_batch_yuv420(
-            self.h, C.byref(d), n, w, h, dw, dh, nfeatures, float(thr), int(max_iters), float(conf), int(bool(force_max_iters)),
-            state_in.data_ptr() if state_in is not None else None, state_out.data_ptr() if state_out is not None else None,
-            out_H.data_ptr(), out_status.data_ptr()))
+            self.h, C.byref(d), n, w, h, *_work_size(resize_to, w, h), nfeatures,
+            *_tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)))
 
     def stream_homography_batch_types_yuv420(self, planes, size, out_H, out_status, features, state_in=None, state_out=None,
                                              nfeatures=500, thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False,
@@ -538,13 +543,11 @@ class Context:
         """stream_homography_batch_types on decoded planes: converted once on the device, then the BGR path."""
         self._enter()
         d, n, w, h = self._yuv420(planes, size, self.device)
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
         t = self._types(features)
         self._multi_used = True
         self._check(self.lib.evh_stream_homography_batch_types_yuv420(
-            self.h, C.byref(d), n, w, h, dw, dh, nfeatures, _hp(t), len(t), float(thr), int(max_iters), float(conf),
-            int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-            state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+            self.h, C.byref(d), n, w, h, *_work_size(resize_to, w, h), nfeatures, _hp(t), len(t),
+            *_tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)))
 
     # ---- N4: SIFT + multi-type pairs ----
     def sift_enable(self, max_sift_features=8192):
@@ -553,10 +556,8 @@ class Context:
     def sift_detect_batch(self, frames, resize_to=None):
         """frames: CUDA uint8 [n,h,w] or [n,h,w,3]; SIFT_create().detectAndCompute on each (frame_processing.py:62-64)."""
         self._enter()
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
-        self._check(self.lib.evh_sift_detect_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh))
+        p = _packed(frames)
+        self._check(self.lib.evh_sift_detect_batch(self.h, *p, *_work_size(resize_to, *p[2:4])))
 
     def _kp_download(self, det, frame, fields):
         """A frame's SIFT / SURF key points: xy, desc and `fields` (the per-key-point arrays in the C entry's argument order)."""
@@ -593,12 +594,10 @@ class Context:
         """frames: CUDA uint8 [n,h,w] or [n,h,w,3]; SURF_create(extended=1, hessianThreshold=400).detectAndCompute
         (frame_processing.py:65-67)."""
         self._enter()
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        p = _packed(frames)
+        dw, dh = _work_size(resize_to, *p[2:4])
         self._surf_shape = (dh, dw)
-        self._check(self.lib.evh_surf_detect_batch(self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh,
-                                                   float(hessian_threshold)))
+        self._check(self.lib.evh_surf_detect_batch(self.h, *p, dw, dh, float(hessian_threshold)))
 
     def surf_download(self, frame):
         return self._kp_download("surf", frame, ("size", "angle", "response", "octave", "laplacian"))
@@ -631,29 +630,24 @@ class Context:
     def pair_homography_batch_types(self, frames, npairs, mode, out_H, out_status, features, nfeatures=500, thr=3.0,
                                     max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None):
         self._enter()
-        h, w = frames.shape[1:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        p = _packed(frames)
         t = self._types(features)
         self._multi_used = True
         self._check(self.lib.evh_pair_homography_batch_types(
-            self.h, frames.data_ptr(), npairs, mode, w, h, cn, w * cn, w * h * cn, dw, dh, nfeatures, _hp(t), len(t), float(thr),
-            int(max_iters), float(conf), int(bool(force_max_iters)), out_H.data_ptr(), out_status.data_ptr()))
+            self.h, p[0], npairs, mode, *p[2:], *_work_size(resize_to, *p[2:4]), nfeatures, _hp(t), len(t),
+            *_ransac(thr, max_iters, conf, force_max_iters), out_H.data_ptr(), out_status.data_ptr()))
 
     def stream_homography_batch_types(self, frames, out_H, out_status, features, state_in=None, state_out=None, nfeatures=500,
                                       thr=3.0, max_iters=2000, conf=0.995, force_max_iters=False, resize_to=None):
         """stream_homography_batch with a list of feature types ("SIFT", "ORB", ... in the order the reference's
         FrameProcessing would loop over them, frame_processing.py:91-104)."""
         self._enter()
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
-        dw, dh = (w, h) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        p = _packed(frames)
         t = self._types(features)
         self._multi_used = True
         self._check(self.lib.evh_stream_homography_batch_types(
-            self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, dw, dh, nfeatures, _hp(t), len(t), float(thr),
-            int(max_iters), float(conf), int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-            state_out.data_ptr() if state_out is not None else None, out_H.data_ptr(), out_status.data_ptr()))
+            self.h, *p, *_work_size(resize_to, *p[2:4]), nfeatures, _hp(t), len(t),
+            *_tail((thr, max_iters, conf, force_max_iters), state_in, state_out, out_H, out_status)))
 
     def _torch_stream(self):
         """The context's (non-blocking) HIP stream as a torch stream, for ordering against torch work."""
@@ -678,8 +672,7 @@ class Context:
         (rows f32[n-1,cap,4], counts i32[n-1], status1 i32[n-1]) as CUDA tensors.  Asynchronous, but ordered with
         torch's current stream on both sides (inputs produced by torch ops, outputs consumed by torch ops / RCCL)."""
         import torch
-        n, h, w = frames.shape[:3]
-        cn = 1 if frames.dim() == 3 else frames.shape[3]
+        n = frames.shape[0]
         cap = self.lib.evh_orb_capacity(self.h)
         rows = torch.zeros((max(n - 1, 0), cap, 4), dtype=torch.float32, device=frames.device)
         counts = torch.zeros(max(n - 1, 0), dtype=torch.int32, device=frames.device)
@@ -688,8 +681,8 @@ class Context:
             return rows, counts, status1          # an empty block (more ranks than pairs)
         self.order_after_torch()
         self._check(self.lib.evh_stream_static_batch(
-            self.h, frames.data_ptr(), n, w, h, cn, w * cn, w * h * cn, nfeatures, float(thr), int(max_iters), float(conf),
-            int(bool(force_max_iters)), rows.data_ptr(), cap, counts.data_ptr(), status1.data_ptr()))
+            self.h, *_packed(frames), nfeatures, *_ransac(thr, max_iters, conf, force_max_iters), rows.data_ptr(), cap,
+            counts.data_ptr(), status1.data_ptr()))
         self.order_torch_after()
         return rows, counts, status1
 
@@ -705,9 +698,8 @@ class Context:
         st = torch.zeros(npairs, dtype=torch.int32, device=rows.device)
         self.order_after_torch()
         self._check(self.lib.evh_stream_scan(
-            self.h, rows.data_ptr(), cap, counts.data_ptr(), status1.data_ptr(), npairs, float(thr), int(max_iters),
-            float(conf), int(bool(force_max_iters)), state_in.data_ptr() if state_in is not None else None,
-            state_out.data_ptr() if state_out is not None else None, H.data_ptr(), st.data_ptr()))
+            self.h, rows.data_ptr(), cap, counts.data_ptr(), status1.data_ptr(), npairs,
+            *_tail((thr, max_iters, conf, force_max_iters), state_in, state_out, H, st)))
         self.order_torch_after()
         return H, st
 

@@ -1,4 +1,5 @@
-// evh_api.hip -- host side of libevhip.so: context, geometry, and the extern "C" entry points of include/evhip.h.
+// evh_api.hip -- host side of libevhip.so: context, geometry, settings, and the single-problem entry points of include/evhip.h
+// (the pair / stream / ragged batch entries are evh_batch.hip).
 #include "evh_internal.h"
 #include "evh_match.h"
 #include "evh_ransac.h"
@@ -137,104 +138,6 @@ int configure(evh_ctx* c, int w, int h, int nfeatures) {
   return EVH_SUCCESS;
 }
 
-// one set of per-pair buffers with `cap` rows per pair (the ORB path: kcap; the multi-type path: every type's rows)
-int alloc_pair_bufs(evh_ctx* c, EvhPairBufs& B, int cap) {
-  const size_t P = (size_t)c->max_frames, K = (size_t)cap;
-  int rc;
-#define A_(call) if ((rc = (call)) != EVH_SUCCESS) return rc
-  A_(dalloc(c, &B.knn_idx, P * K * 2));
-  A_(dalloc(c, &B.knn_d2, P * K * 2));
-  A_(dalloc(c, &B.pts, P * K * 4));
-  A_(dalloc(c, &B.pts2, P * K * 4));
-  A_(dalloc(c, &B.crow, P * K * 4));
-  A_(dalloc(c, &B.npts, P));
-  A_(dalloc(c, &B.npts2, P));
-  A_(dalloc(c, &B.pstatus, P));
-  A_(dalloc(c, &B.H1, P * 9));
-  A_(dalloc(c, &B.mask, P * K));
-  A_(dalloc(c, &B.lm, P * K * 4));
-  A_(dalloc(c, &B.info, P * 8));
-#undef A_
-  B.cap = cap;
-  return EVH_SUCCESS;
-}
-
-// fixed-iteration mode keeps the per-lane eigenvector matrices of its hypotheses in a global scratch (one block per
-// workgroup = per pair slot); allocated on first use
-int ensure_lane_scratch(evh_ctx* c) {
-  if (c->d_lane_v) return EVH_SUCCESS;
-  return dalloc(c, &c->d_lane_v, (size_t)c->max_frames * EVH_LANE_V_DOUBLES);
-}
-
-// the launchers report a lane scratch that could not be allocated (force_max without lane_v)
-EvhRansacArgs ransac_args(evh_ctx* c, const EvhPairBufs& B, double thr, int max_iters, double conf, int force_max) {
-  EvhRansacArgs R{};
-  R.fast_solver = c->solver_mode;
-  if (force_max && ensure_lane_scratch(c) == EVH_SUCCESS) R.lane_v = c->d_lane_v;
-  R.pts = B.pts; R.pts2 = B.pts2; R.row_stride = B.cap; R.npts = B.npts; R.npts2 = B.npts2;
-  R.status = B.pstatus; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
-  R.mask = B.mask; R.crow = B.crow; R.lm = B.lm; R.H1 = B.H1; R.info = B.info;
-  return R;
-}
-
-// stream state {H_sup, H_prev} entering (may be NULL: first pair of the stream) and leaving a batch
-void with_state(EvhRansacArgs& R, const double* d_state_in, double* d_state_out) {
-  if (d_state_in) { R.Hsup0 = d_state_in; R.Hprev0 = d_state_in + 9; }
-  R.state_out = d_state_out;
-}
-
-// one feature type's per-frame results, as the matching stages read them
-struct EvhFeatView {
-  const int* counts; const int* flags; const float* xy;
-  const void* desc; int desc_bytes; bool f32;    // uint8 rows of desc_bytes values, or (f32) rows of 128 floats
-  int cap;                                       // rows per frame slot
-};
-EvhFeatView feat_view(const evh_ctx* c, int type) {
-  if (type == EVH_FEATURE_SIFT || type == EVH_FEATURE_SURF) {
-    const EvhKpList& L = type == EVH_FEATURE_SIFT ? c->sift : c->surf;
-    const bool f32 = type == EVH_FEATURE_SURF;
-    return {L.count, L.flags, L.xy, L.desc, f32 ? 0 : L.desc_row_bytes, f32, L.cap};
-  }
-  return {c->d_kp_count, c->d_frame_flags, c->d_kp_xy, c->d_desc, 32, false, c->kcap};
-}
-
-// K7 + glue on resident slots for `npairs` pairs of one feature type, into the pair buffers B.  filter_kcap selects the
-// LDS or the global-scratch form of k_filter and sizes its work arrays.  join_solve_at_filter: the filter overwrites the
-// matched-row buffers the previous batch's (asynchronous) solve may still be reading, so it waits for that solve -- as
-// late as possible, K7 of this batch overlaps it
-int match_pairs(evh_ctx* c, const EvhFeatView& V, const EvhPairBufs& B, int filter_kcap, bool join_solve_at_filter, int npairs,
-                int q0, int qstep, int t0, int tstep) {
-  int rc;
-  if (V.f32) {            // real-valued float rows: the float matcher, distances carried as float bits
-    EvhKnnF32Args K{};
-    K.q = static_cast<const float*>(V.desc); K.t = K.q; K.dim = 128; K.n_arr = V.counts; K.slot_floats = (int64_t)V.cap * 128;
-    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
-    K.idx = B.knn_idx; K.dist = reinterpret_cast<float*>(B.knn_d2); K.out_stride = B.cap;
-    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2_f32(c, K, npairs); }
-  } else {
-    EvhKnnArgs K{};
-    K.q = static_cast<const uint8_t*>(V.desc); K.t = K.q; K.slot_bytes = (int64_t)V.cap * V.desc_bytes; K.desc_bytes = V.desc_bytes;
-    K.nq_arr = V.counts; K.nt_arr = V.counts;
-    K.q_slot0 = q0; K.q_slot_step = qstep; K.t_slot0 = t0; K.t_slot_step = tstep;
-    K.idx = B.knn_idx; K.d2 = B.knn_d2; K.out_stride = B.cap; K.hamming = 0;
-    { EvhProfScope ps(c, EVH_ST_KNN); rc = evh_launch_knn2(c, K, npairs); }
-  }
-  if (rc) return rc;
-  EvhFilterArgs F{};
-  F.idx = B.knn_idx; F.d2 = B.knn_d2; F.knn_stride = B.cap; F.d2_is_dist = V.f32 ? 1 : 0;
-  F.xy_q = V.xy; F.xy_t = V.xy; F.xy_slot_floats = (int64_t)V.cap * 2;
-  F.nq_arr = V.counts; F.nt_arr = V.counts; F.flags_arr = V.flags;
-  F.q_slot0 = q0; F.q_slot_step = qstep; F.t_slot0 = t0; F.t_slot_step = tstep;
-  F.ratio = 0.5; F.min_matches = 4;  // constants.py:25,28 (LOWES_RATIO, MINIMUM_MATCHING_POINTS)
-  F.pts = B.pts; F.pts_stride = B.cap; F.npts = B.npts; F.status = B.pstatus; F.kcap = filter_kcap;
-  if (join_solve_at_filter && c->solve_pending) EVH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_solve_done, 0));
-  EvhProfScope ps(c, EVH_ST_FILTER);
-  return evh_launch_filter(c, F, npairs);
-}
-int match_orb_pairs(evh_ctx* c, int npairs, int q0, int qstep, int t0, int tstep) {
-  return match_pairs(c, feat_view(c, EVH_FEATURE_ORB), c->orb, c->kcap, true, npairs, q0, qstep, t0, tstep);
-}
-
 // context-owned scratch of the host-pointer entries (evh_transform_points, evh_superposition_scan,
 // evh_fixed_plane_field): grown on demand, reused across calls (those entries synchronise before returning)
 int ensure_scratch(evh_ctx* c, size_t bytes) {
@@ -242,305 +145,11 @@ int ensure_scratch(evh_ctx* c, size_t bytes) {
   return grow(c, &c->d_scratch, &c->scratch_bytes, std::max(bytes, (size_t)1 << 16));
 }
 
-// entry points that reuse the pair buffers on the main stream first order themselves behind a pending async solve
-int join_solve(evh_ctx* c) {
-  if (c->solve_pending) EVH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_solve_done, 0));
-  return EVH_SUCCESS;
-}
-
-// RANSAC #1 + static filter, then compute_homography, on the solve stream when asynchronous solve is enabled
-// (d_segs: the scans of a ragged batch, pairs_per_stream = the pairs of its longest stream)
-int solve_pairs(evh_ctx* c, EvhRansacArgs R, int npairs, int nstreams = 0, int pairs_per_stream = 0, int pitch = 0,
-                const evh_stream_seg* d_segs = nullptr) {
-  hipStream_t main = c->stream;
-  const bool async = c->async_solve && c->solve_stream;
-  if (async) {
-    EVH_HIP(c, hipEventRecord(c->ev_match_done, main));
-    EVH_HIP(c, hipStreamWaitEvent(c->solve_stream, c->ev_match_done, 0));
-    c->stream = c->solve_stream;          // the launchers enqueue on c->stream
-  }
-  int rc;
-  { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC, c->stream); rc = evh_launch_ransac_static(c, R, npairs); }
-  if (!rc) {
-    EvhProfScope ps(c, EVH_ST_RANSAC_FINAL, c->stream);
-    rc = d_segs ? evh_launch_ransac_final(c, R, npairs, nstreams, 0, d_segs, pairs_per_stream)
-                : evh_launch_ransac_final(c, R, nstreams > 0 ? pairs_per_stream : npairs, nstreams, pitch);
-  }
-  if (async) {
-    hipError_t e = hipEventRecord(c->ev_solve_done, c->solve_stream);
-    c->stream = main;
-    c->solve_pending = true;
-    if (e != hipSuccess) return evh_fail(c, EVH_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
-  }
-  return rc;
-}
-
-
-// the argument checks of every entry that takes planes: nothing is launched on a description that fails them
-int check_yuv420(evh_ctx* c, const char* who, const evh_yuv420* s, int nframes, int w, int h) {
-  const std::string W = std::string(who) + ": ";
-  if (!c) return EVH_ERR_INVALID;
-  if (!s || !s->d_y || !s->d_cb || !s->d_cr) return evh_fail(c, EVH_ERR_INVALID, W + "NULL plane");
-  if (w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty source frame");
-  if (nframes < 1 || nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "between 1 and 65535 frames per call");
-  if (s->c_pixel_stride != 1 && s->c_pixel_stride != 2) return evh_fail(c, EVH_ERR_INVALID, W + "chroma pixel stride must be 1 or 2");
-  const int64_t cw = (w + 1) / 2, ch = (h + 1) / 2, crow = (cw - 1) * s->c_pixel_stride + 1;
-  if (s->y_stride < w) return evh_fail(c, EVH_ERR_INVALID, W + "luma row stride smaller than the width");
-  if (s->c_stride < crow) return evh_fail(c, EVH_ERR_INVALID, W + "chroma row stride smaller than a chroma row");
-  if (nframes > 1 && (s->y_frame_stride < (h - 1) * s->y_stride + w || s->c_frame_stride < (ch - 1) * s->c_stride + crow))
-    return evh_fail(c, EVH_ERR_INVALID, W + "frame stride smaller than a plane");
-  return EVH_SUCCESS;
-}
-
-// level 0 (gray) of every frame: (sw, sh) = size of the frames handed over, (w, h) = working size.  Different sizes =
-// fused ingest (N2).  Shared by every feature type of a call.  The one place where the frames of a detect / pair / stream
-// entry are checked.
-int ingest_level0(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures) {
-  if (!c) return EVH_ERR_INVALID;
-  if (F.yuv) {
-    if (int rc = check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
-  } else {
-    if (!F.packed) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (F.channels != 1 && F.channels != 3) return evh_fail(c, EVH_ERR_INVALID, "channels must be 1 or 3");
-    if (F.row_stride < (int64_t)sw * F.channels) return evh_fail(c, EVH_ERR_INVALID, "row_stride smaller than a row");
-    if (sw < 1 || sh < 1) return evh_fail(c, EVH_ERR_INVALID, "empty source frame");
-  }
-  if (nframes < 1 || nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "nframes exceeds max_frames");
-  if (nframes > 65535 || h > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "too many frames / rows for one launch");
-  int rc = configure(c, w, h, nfeatures);
-  if (rc) return rc;
-  EvhProfScope ps(c, EVH_ST_GRAY);
-  if (!F.yuv && sw == w && sh == h)
-    return evh_launch_gray_level0(c, F.packed, nframes, F.channels, F.row_stride, F.frame_stride);
-  return evh_launch_ingest_level0(c, F, nframes, sw, sh, w, h);
-}
-
-// ORB K2..K6 on the frames whose level 0 is resident
-int orb_stages(evh_ctx* c, int nframes, int share_group) {
-  int rc;
-  { EvhProfScope ps(c, EVH_ST_PYRAMID); rc = evh_launch_pyramid(c, nframes); }
-  if (rc) return rc;
-  { EvhProfScope ps(c, EVH_ST_FAST); rc = evh_launch_fast(c, nframes, share_group); }
-  if (rc) return rc;
-  { EvhProfScope ps(c, EVH_ST_SELECT); rc = evh_launch_select(c, nframes); }
-  if (rc) return rc;
-  { EvhProfScope ps(c, EVH_ST_DESCRIBE); rc = evh_launch_describe(c, nframes); }
-  if (rc) return rc;
-  c->nframes_resident = nframes;
-  return EVH_SUCCESS;
-}
-
+// the detect-only entries: unrelated frames, no FAST threshold sharing
 int detect_batch(evh_ctx* c, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures) {
-  if (!c) return EVH_ERR_INVALID;
-  const int share_group = c->fast_share ? c->fast_share_group : 0;   // set by the pair / stream entries for THIS call only
-  c->fast_share_group = 0;
-  int rc = ingest_level0(c, "evh_orb_detect_batch", F, nframes, sw, sh, w, h, nfeatures);
+  int rc = evh_ingest_level0(c, "evh_orb_detect_batch", F, nframes, sw, sh, w, h, nfeatures);
   if (rc) return rc;
-  return orb_stages(c, nframes, share_group);
-}
-
-
-// ---- multi-type pairs (frame_processing.py:91-104) ---------------------------------------------------------------------------
-int ensure_multitype(evh_ctx* c) {
-  if (c->mt.cap) return EVH_SUCCESS;
-  const int each = std::max(c->kcap, std::max(c->sift.cap, c->surf.cap)), cap = c->kcap + c->sift.cap + c->surf.cap;
-  if (each > 65536)
-    return evh_fail(c, EVH_ERR_CAPACITY, "multi-type pairs: at most 65536 key points per frame and type");
-  const size_t P = (size_t)c->max_frames, K = (size_t)cap, first = c->owned.size();
-  int rc = alloc_pair_bufs(c, c->mt, cap);
-  if (!rc) rc = dalloc(c, &c->d_acc, P * K * 4);
-  if (!rc) rc = dalloc(c, &c->d_nacc, P);
-  if (!rc) rc = dalloc(c, &c->d_accstatus, P);
-  if (rc) { dfree_from(c, first); c->mt.cap = 0; }     // a partial allocation is released: a later call starts afresh
-  return rc;
-}
-
-// the type list of a *_types entry: every name known, none twice, SIFT / SURF enabled; -> which detectors it names
-struct EvhWanted { bool orb = false, sift = false, surf = false; };
-int check_types(evh_ctx* c, const char* who, const int* types, int ntypes, EvhWanted& want) {
-  if (!types || ntypes < 1 || ntypes > 8) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad feature type list");
-  bool &want_orb = want.orb, &want_sift = want.sift, &want_surf = want.surf;
-  for (int i = 0; i < ntypes; i++) {
-    // the concatenation buffer holds one segment per detector (kcap + sift.cap + surf.cap rows): a type named twice would
-    // overflow it, so it is refused (the reference would simply match the same key points twice and deduplicate them)
-    bool* seen = types[i] == EVH_FEATURE_ORB ? &want_orb : types[i] == EVH_FEATURE_SIFT ? &want_sift :
-                 types[i] == EVH_FEATURE_SURF ? &want_surf : nullptr;
-    if (!seen) return evh_fail(c, EVH_ERR_INVALID, "unknown feature type");
-    if (*seen) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": a feature type appears twice in the list");
-    *seen = true;
-  }
-  if (want_sift && !c->sift.cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SIFT in the list needs evh_sift_enable");
-  if (want_surf && !c->surf.cap) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": SURF in the list needs evh_surf_enable");
-  if (c->mt.cap && c->mt.cap < c->kcap + c->sift.cap + c->surf.cap)
-    return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": enable SIFT and SURF before the first multi-type call");
-  return EVH_SUCCESS;
-}
-
-// the device copy of a ragged batch's segment table, uploaded stream-ordered through pinned staging.  The turns are for the
-// HOST side: a call waits only for the upload EVH_SEG_TURNS calls back to have left its staging table, never for the device
-// to drain (the device tables are ordered by the stream: the upload sits behind this call's filter, which has joined the
-// previous call's solve)
-int upload_segs(evh_ctx* c, const evh_stream_seg* h_segs, int nstreams, const evh_stream_seg** d_out) {
-  const size_t per = (size_t)c->max_frames / 2;
-  if (!c->d_segs) {
-    int rc = dalloc(c, &c->d_segs, per * EVH_SEG_TURNS);
-    if (rc) return rc;
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_segs), per * EVH_SEG_TURNS * sizeof(evh_stream_seg), hipHostMallocDefault) != hipSuccess) {
-      c->h_segs = nullptr;
-      dfree(c, &c->d_segs);
-      return evh_fail(c, EVH_ERR_HIP, "segment table: pinned staging (hipHostMalloc) could not be allocated");
-    }
-  }
-  // (a call that fails below has used up its turn without recording an event: harmless, the turn's next user finds no
-  // event, or an older one that has long completed.  A table holds max_frames / 2 segments: streams_batch has refused
-  // segments of fewer than 2 frames and batches of more than max_frames frames, so nstreams cannot exceed that)
-  const unsigned t = c->seg_turn++ % EVH_SEG_TURNS;
-  if (!c->ev_segs[t]) EVH_HIP(c, hipEventCreateWithFlags(&c->ev_segs[t], hipEventDisableTiming));
-  else EVH_HIP(c, hipEventSynchronize(c->ev_segs[t]));              // the upload that used this turn last has left the staging
-  std::memcpy(c->h_segs + t * per, h_segs, sizeof(evh_stream_seg) * (size_t)nstreams);
-  EVH_HIP(c, hipMemcpyAsync(c->d_segs + t * per, c->h_segs + t * per, sizeof(evh_stream_seg) * (size_t)nstreams, hipMemcpyHostToDevice, c->stream));
-  EVH_HIP(c, hipEventRecord(c->ev_segs[t], c->stream));
-  *d_out = c->d_segs + t * per;
-  return EVH_SUCCESS;
-}
-
-// frames -> H with a LIST of feature types, in list order (the reference's default list is SURF, SIFT, ORB):
-// per type detect, match, RANSAC #1, static filter; concatenate; remove_double_matching; compute_homography.
-// h_segs: the nframes frames are a ragged batch of nstreams streams (max_pairs pairs in the longest); else one stream
-// (stream_mode) or independent pairs
-int pairs_types(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int npairs, int stream_mode, int sw, int sh,
-                int w, int h, int nfeatures, const int* types, int ntypes, double thr, int max_iters, double conf, int force_max, const double* d_state_in, double* d_state_out,
-                double* d_H, int32_t* d_status, const evh_stream_seg* h_segs = nullptr, int nstreams = 1, int max_pairs = 0) {
-  EvhWanted want;
-  int rc = check_types(c, who, types, ntypes, want);
-  if (rc) return rc;
-  const bool want_orb = want.orb, want_sift = want.sift, want_surf = want.surf;
-  rc = ensure_multitype(c);
-  if (rc) return rc;
-  if ((rc = join_solve(c))) return rc;
-  const int share_group = c->fast_share ? (stream_mode ? nframes : 2) : 0;
-  c->fast_share_group = 0;
-  EvhFrames P = F;
-  if (F.yuv) {      // SIFT and SURF read BGR through the shared front end: the chunk is converted once, then takes that path
-    const int64_t row = (int64_t)sw * 3, frame = row * sh;
-    if ((rc = check_yuv420(c, who, F.yuv, nframes, sw, sh))) return rc;
-    if ((rc = grow(c, &c->d_yuv_bgr, &c->yuv_bgr_bytes, (size_t)frame * nframes))) return rc;
-    if ((rc = evh_launch_yuv420_to_bgr(c, *F.yuv, nframes, sw, sh, c->d_yuv_bgr, row, frame))) return rc;
-    P = packed_frames(c->d_yuv_bgr, 3, row, frame);
-  }
-  if ((rc = ingest_level0(c, who, P, nframes, sw, sh, w, h, nfeatures))) return rc;
-  if (want_sift && (rc = evh_launch_sift(c, nframes, w, h))) return rc;       // reads level 0 before ORB's kernels run on it
-  if (want_surf && (rc = evh_launch_surf(c, nframes, w, h, 400.f))) return rc; // SURF_create(extended=1, hessianThreshold=400)
-  if (want_orb && (rc = orb_stages(c, nframes, share_group))) return rc;
-  const int q0 = 1, qstep = stream_mode ? 1 : 2, t0 = 0, tstep = stream_mode ? 1 : 2;
-  EvhRansacArgs R = ransac_args(c, c->mt, thr, max_iters, conf, force_max);
-  const int each = std::max(c->kcap, std::max(c->sift.cap, c->surf.cap));   // one filter form for every type of the list
-  for (int i = 0; i < ntypes; i++) {
-    // the solve was joined once, above: this path has no asynchronous solve of its own to overlap
-    if ((rc = match_pairs(c, feat_view(c, types[i]), c->mt, each, false, npairs, q0, qstep, t0, tstep))) return rc;
-    { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, R, npairs); }
-    if (rc) return rc;
-    EvhAccArgs A{};
-    A.rows = c->mt.pts2; A.nrows = c->mt.npts2; A.status = c->mt.pstatus; A.row_stride = c->mt.cap;
-    A.acc = c->d_acc; A.nacc = c->d_nacc; A.accstatus = c->d_accstatus; A.acc_stride = c->mt.cap; A.first = i == 0;
-    if ((rc = evh_launch_accumulate(c, A, npairs))) return rc;
-  }
-  EvhMergeArgs M{};
-  M.acc = c->d_acc; M.nacc = c->d_nacc; M.accstatus = c->d_accstatus; M.acc_stride = c->mt.cap;
-  M.out = c->mt.pts2; M.nout = c->mt.npts2; M.status = c->mt.pstatus; M.out_stride = c->mt.cap;
-  if ((rc = evh_launch_merge(c, M, npairs))) return rc;
-  R.H = d_H; R.out_status = d_status;
-  with_state(R, d_state_in, d_state_out);
-  const evh_stream_seg* d_segs = nullptr;
-  if (h_segs && (rc = upload_segs(c, h_segs, nstreams, &d_segs))) return rc;
-  EvhProfScope ps(c, EVH_ST_RANSAC_FINAL);
-  if (d_segs) return evh_launch_ransac_final(c, R, npairs, nstreams, 0, d_segs, max_pairs);
-  return evh_launch_ransac_final(c, R, npairs, stream_mode ? 1 : 0, npairs);
-}
-
-// ORB detect of `nframes` frames (FAST thresholds shared inside groups of share_group) + match of npairs pairs
-// (frame step + 1, frame step * p): the first half of every ORB pair / stream entry
-int detect_match(evh_ctx* c, const EvhFrames& F, int nframes, int share_group, int npairs, int step, int sw, int sh, int w,
-                 int h, int nfeatures) {
-  c->fast_share_group = share_group;
-  int rc = detect_batch(c, F, nframes, sw, sh, w, h, nfeatures);
-  if (rc) return rc;
-  return match_orb_pairs(c, npairs, 1, step, 0, step);      // orders itself behind a pending async solve
-}
-
-// nstreams streams of frames_per_stream consecutive frames -> H per pair.  Pair slot p = (frame p + 1, frame p): a slot
-// that straddles two streams is computed and never read
-int stream_batch(evh_ctx* c, const EvhFrames& F, int nstreams, int frames_per_stream, int sw, int sh, int w, int h,
-                 int nfeatures, double thr, int max_iters, double conf, int force_max, const double* d_state_in,
-                 double* d_state_out, double* d_H, int32_t* d_status) {
-  const int nframes = nstreams * frames_per_stream;
-  int rc = detect_match(c, F, nframes, frames_per_stream, nframes - 1, 1, sw, sh, w, h, nfeatures);
-  if (rc) return rc;
-  EvhRansacArgs R = ransac_args(c, c->orb, thr, max_iters, conf, force_max);
-  R.H = d_H; R.out_status = d_status;
-  with_state(R, d_state_in, d_state_out);
-  return solve_pairs(c, R, nframes - 1, nstreams, frames_per_stream - 1, frames_per_stream);
-}
-
-// A ragged batch: total_frames frames cut into nstreams segments of consecutive frames, one stream each.  Everything up to the
-// static filter runs over all frames / pair slots at once (a slot that straddles two streams is computed and never read); the
-// scans run one workgroup per stream off the segment table.  A list of exactly {ORB} takes the fused ORB path, any other
-// pairs_types.  Every refusal comes before the first launch.
-int streams_batch(evh_ctx* c, const char* who, const EvhFrames& F, int total_frames, int sw, int sh, int w, int h, int nfeatures,
-                  const int32_t* h_types, int ntypes, const evh_stream_seg* h_segs, int nstreams, double thr, int max_iters,
-                  double conf, int force_max, const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
-  const std::string W = std::string(who) + ": ";
-  if (!c) return EVH_ERR_INVALID;
-  if (!d_H || !d_status || !h_segs || nstreams < 1 || total_frames < 2 || (!F.yuv && !F.packed))
-    return evh_fail(c, EVH_ERR_INVALID, W + "bad argument");
-  if (total_frames > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, W + "batch needs more frame slots than max_frames");
-  int next = 0, max_pairs = 0;
-  for (int s = 0; s < nstreams; s++) {
-    const evh_stream_seg& g = h_segs[s];
-    if (g.nframes < 2) return evh_fail(c, EVH_ERR_INVALID, W + "a segment needs at least 2 frames");
-    if (g.first_frame != next || g.nframes > total_frames - next)
-      return evh_fail(c, EVH_ERR_INVALID, W + "the segments must tile [0, total_frames) in ascending order");
-    if (g.reserved != 0) return evh_fail(c, EVH_ERR_INVALID, W + "evh_stream_seg.reserved must be 0");
-    if (!g.start && !d_state_in) return evh_fail(c, EVH_ERR_INVALID, W + "a segment with start == 0 needs d_state_in");
-    next += g.nframes;
-    max_pairs = std::max(max_pairs, g.nframes - 1);
-  }
-  if (next != total_frames) return evh_fail(c, EVH_ERR_INVALID, W + "the segments must tile [0, total_frames) in ascending order");
-  EvhWanted want;
-  int rc = check_types(c, who, h_types, ntypes, want);
-  if (rc) return rc;
-  if (ntypes != 1 || !want.orb)
-    return pairs_types(c, who, F, total_frames, total_frames - 1, 1, sw, sh, w, h, nfeatures, h_types, ntypes, thr, max_iters, conf,
-                       force_max, d_state_in, d_state_out, d_H, d_status, h_segs, nstreams, max_pairs);
-  // FAST thresholds are shared by the frames 2k, 2k + 1 of the batch, across segment borders too: a borrowed threshold that
-  // proves too high is redone, so sharing is exact per frame
-  if ((rc = detect_match(c, F, total_frames, total_frames, total_frames - 1, 1, sw, sh, w, h, nfeatures))) return rc;
-  const evh_stream_seg* d_segs = nullptr;
-  if ((rc = upload_segs(c, h_segs, nstreams, &d_segs))) return rc;
-  EvhRansacArgs R = ransac_args(c, c->orb, thr, max_iters, conf, force_max);
-  R.H = d_H; R.out_status = d_status;
-  with_state(R, d_state_in, d_state_out);
-  return solve_pairs(c, R, total_frames - 1, nstreams, max_pairs, 0, d_segs);
-}
-
-// final solve of pair slot 0 of the ORB buffers (its static rows are resident), optionally behind the superposition
-// h_Hsup; H and status to the host
-int final_solve_one(evh_ctx* c, const double* h_Hsup, double* h_H, int* h_status) {
-  EvhSmall* S = c->d_small;
-  EvhRansacArgs R = ransac_args(c, c->orb, 3.0, 2000, 0.995, 0);
-  R.H = S->H; R.out_status = &S->out_status;
-  if (h_Hsup) {
-    EVH_HIP(c, hipMemcpyAsync(S->Hsup, h_Hsup, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    R.Hsup0 = S->Hsup;
-  }
-  // the stream kernel with one pair applies the optional pre-transform; Hprev0 = Hsup0 only marks "not first"
-  R.Hprev0 = R.Hsup0;
-  int rc = evh_launch_ransac_final(c, R, 1, h_Hsup ? 1 : 0, 1);
-  if (rc) return rc;
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  EVH_HIP(c, hipMemcpy(h_H, S->H, 9 * sizeof(double), hipMemcpyDeviceToHost));
-  EVH_HIP(c, hipMemcpy(h_status, &S->out_status, sizeof(int), hipMemcpyDeviceToHost));
-  return EVH_SUCCESS;
+  return evh_orb_stages(c, nframes, 0);
 }
 
 // a frame slot's key-point count and flags word of one feature type, in one synchronisation
@@ -571,10 +180,10 @@ void unpack_records(const std::vector<float>& rec, int n, float* h_xy, float* h_
 template <class Launch>
 int kp_detect_batch(evh_ctx* c, const char* who, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
                     int64_t row_stride, int64_t frame_stride, int w, int h, Launch launch) {
-  int rc = join_solve(c);
+  int rc = evh_join_solve(c);
   if (rc) return rc;
   const int nf = c->geom_valid ? c->g.nfeatures : std::min(500, c->max_features);
-  if ((rc = ingest_level0(c, who, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w, src_h, w, h, nf)))
+  if ((rc = evh_ingest_level0(c, who, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, src_w, src_h, w, h, nf)))
     return rc;
   c->nframes_resident = 0;            // level 0 was rewritten: the ORB results of an earlier call no longer match it
   return launch();
@@ -585,7 +194,7 @@ int kp_count(evh_ctx* c, int type, const char* name, const char* overflow, int f
   if (!c || frame < 0 || frame >= (type == EVH_FEATURE_SIFT ? c->sift : c->surf).frames_resident)
     return evh_fail(c, EVH_ERR_INVALID, std::string("bad ") + name + " frame slot");
   int fl = 0;
-  const int n = frame_count(c, feat_view(c, type), frame, &fl);
+  const int n = frame_count(c, evh_feat_view(c, type), frame, &fl);
   if (n < 0) return n;
   if (fl) return evh_fail(c, EVH_ERR_CAPACITY, overflow);
   return n;
@@ -627,6 +236,105 @@ int ratio_filter(evh_ctx* c, const char* who, const int32_t* d_idx, const uint32
 }
 
 }  // namespace
+
+// ---- host stages shared with evh_batch.hip (declared in evh_internal.h) ----
+// one set of per-pair buffers with `cap` rows per pair (the ORB path: kcap; the multi-type path: every type's rows)
+int evh_alloc_pair_bufs(evh_ctx* c, EvhPairBufs& B, int cap) {
+  const size_t P = (size_t)c->max_frames, K = (size_t)cap;
+  int rc;
+#define A_(call) if ((rc = (call)) != EVH_SUCCESS) return rc
+  A_(dalloc(c, &B.knn_idx, P * K * 2));
+  A_(dalloc(c, &B.knn_d2, P * K * 2));
+  A_(dalloc(c, &B.pts, P * K * 4));
+  A_(dalloc(c, &B.pts2, P * K * 4));
+  A_(dalloc(c, &B.crow, P * K * 4));
+  A_(dalloc(c, &B.npts, P));
+  A_(dalloc(c, &B.npts2, P));
+  A_(dalloc(c, &B.pstatus, P));
+  A_(dalloc(c, &B.H1, P * 9));
+  A_(dalloc(c, &B.mask, P * K));
+  A_(dalloc(c, &B.lm, P * K * 4));
+  A_(dalloc(c, &B.info, P * 8));
+#undef A_
+  B.cap = cap;
+  return EVH_SUCCESS;
+}
+
+// fixed-iteration mode keeps the per-lane eigenvector matrices of its hypotheses in a global scratch (one block per
+// workgroup = per pair slot); allocated on first use
+int evh_ensure_lane_scratch(evh_ctx* c) {
+  if (c->d_lane_v) return EVH_SUCCESS;
+  return dalloc(c, &c->d_lane_v, (size_t)c->max_frames * EVH_LANE_V_DOUBLES);
+}
+
+EvhFeatView evh_feat_view(const evh_ctx* c, int type) {
+  if (type == EVH_FEATURE_SIFT || type == EVH_FEATURE_SURF) {
+    const EvhKpList& L = type == EVH_FEATURE_SIFT ? c->sift : c->surf;
+    const bool f32 = type == EVH_FEATURE_SURF;
+    return {L.count, L.flags, L.xy, L.desc, f32 ? 0 : L.desc_row_bytes, f32, L.cap};
+  }
+  return {c->d_kp_count, c->d_frame_flags, c->d_kp_xy, c->d_desc, 32, false, c->kcap};
+}
+
+// entry points that reuse the pair buffers on the main stream first order themselves behind a pending async solve
+int evh_join_solve(evh_ctx* c) {
+  if (c->solve_pending) EVH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_solve_done, 0));
+  return EVH_SUCCESS;
+}
+
+// the argument checks of every entry that takes planes: nothing is launched on a description that fails them
+int evh_check_yuv420(evh_ctx* c, const char* who, const evh_yuv420* s, int nframes, int w, int h) {
+  const std::string W = std::string(who) + ": ";
+  if (!c) return EVH_ERR_INVALID;
+  if (!s || !s->d_y || !s->d_cb || !s->d_cr) return evh_fail(c, EVH_ERR_INVALID, W + "NULL plane");
+  if (w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty source frame");
+  if (nframes < 1 || nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "between 1 and 65535 frames per call");
+  if (s->c_pixel_stride != 1 && s->c_pixel_stride != 2) return evh_fail(c, EVH_ERR_INVALID, W + "chroma pixel stride must be 1 or 2");
+  const int64_t cw = (w + 1) / 2, ch = (h + 1) / 2, crow = (cw - 1) * s->c_pixel_stride + 1;
+  if (s->y_stride < w) return evh_fail(c, EVH_ERR_INVALID, W + "luma row stride smaller than the width");
+  if (s->c_stride < crow) return evh_fail(c, EVH_ERR_INVALID, W + "chroma row stride smaller than a chroma row");
+  if (nframes > 1 && (s->y_frame_stride < (h - 1) * s->y_stride + w || s->c_frame_stride < (ch - 1) * s->c_stride + crow))
+    return evh_fail(c, EVH_ERR_INVALID, W + "frame stride smaller than a plane");
+  return EVH_SUCCESS;
+}
+
+// level 0 (gray) of every frame: (sw, sh) = size of the frames handed over, (w, h) = working size.  Different sizes =
+// fused ingest (N2).  Shared by every feature type of a call.  The one place where the frames of a detect / pair / stream
+// entry are checked.
+int evh_ingest_level0(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures) {
+  if (!c) return EVH_ERR_INVALID;
+  if (F.yuv) {
+    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  } else {
+    if (!F.packed) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (F.channels != 1 && F.channels != 3) return evh_fail(c, EVH_ERR_INVALID, "channels must be 1 or 3");
+    if (F.row_stride < (int64_t)sw * F.channels) return evh_fail(c, EVH_ERR_INVALID, "row_stride smaller than a row");
+    if (sw < 1 || sh < 1) return evh_fail(c, EVH_ERR_INVALID, "empty source frame");
+  }
+  if (nframes < 1 || nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "nframes exceeds max_frames");
+  if (nframes > 65535 || h > 65535) return evh_fail(c, EVH_ERR_CAPACITY, "too many frames / rows for one launch");
+  int rc = configure(c, w, h, nfeatures);
+  if (rc) return rc;
+  EvhProfScope ps(c, EVH_ST_GRAY);
+  if (!F.yuv && sw == w && sh == h)
+    return evh_launch_gray_level0(c, F.packed, nframes, F.channels, F.row_stride, F.frame_stride);
+  return evh_launch_ingest_level0(c, F, nframes, sw, sh, w, h);
+}
+
+// ORB K2..K6 on the frames whose level 0 is resident
+int evh_orb_stages(evh_ctx* c, int nframes, int share_group) {
+  int rc;
+  { EvhProfScope ps(c, EVH_ST_PYRAMID); rc = evh_launch_pyramid(c, nframes); }
+  if (rc) return rc;
+  { EvhProfScope ps(c, EVH_ST_FAST); rc = evh_launch_fast(c, nframes, share_group); }
+  if (rc) return rc;
+  { EvhProfScope ps(c, EVH_ST_SELECT); rc = evh_launch_select(c, nframes); }
+  if (rc) return rc;
+  { EvhProfScope ps(c, EVH_ST_DESCRIBE); rc = evh_launch_describe(c, nframes); }
+  if (rc) return rc;
+  c->nframes_resident = nframes;
+  return EVH_SUCCESS;
+}
 
 extern "C" {
 
@@ -703,7 +411,7 @@ int evh_create(int device, int max_w, int max_h, int max_features, int max_frame
     c->err = "hipMemset(d_fast_hint) failed";
     return fail(EVH_ERR_HIP);
   }
-  A_(alloc_pair_bufs(c, c->orb, c->kcap));
+  A_(evh_alloc_pair_bufs(c, c->orb, c->kcap));
   A_(dalloc(c, &c->d_small, 1));
 #undef A_
   e = hipMemset(c->d_kp_count, 0, F * sizeof(int));
@@ -912,7 +620,7 @@ int evh_orb_capacity(const evh_ctx* c) { return c ? c->kcap : EVH_ERR_INVALID; }
 int evh_orb_count(evh_ctx* c, int frame) {
   if (!c || frame < 0 || frame >= c->nframes_resident) return evh_fail(c, EVH_ERR_INVALID, "bad frame slot");
   int fl = 0;
-  const int n = frame_count(c, feat_view(c, EVH_FEATURE_ORB), frame, &fl);
+  const int n = frame_count(c, evh_feat_view(c, EVH_FEATURE_ORB), frame, &fl);
   if (n < 0) return n;
   if (fl & 2) return evh_fail(c, EVH_ERR_CAPACITY, "key-point selection: nth_element's depth limit was reached for this frame (heap-select fall-back)");
   if (fl) return evh_fail(c, EVH_ERR_CAPACITY, "a fixed-capacity keypoint list overflowed for this frame");
@@ -1018,12 +726,12 @@ static int find_homography_entry(evh_ctx* c, const float* d_pts, int n, double t
   if (!c || (!d_pts && n > 0) || n < 0 || !h_H || !h_found) return evh_fail(c, EVH_ERR_INVALID, "evh_find_homography_ransac: bad argument");
   if (n > c->kcap * c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "evh_find_homography_ransac: too many rows");
   if (((uintptr_t)d_pts) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_pts must be 16-byte aligned");
-  { int jr = join_solve(c); if (jr) return jr; }
+  { int jr = evh_join_solve(c); if (jr) return jr; }
   // scratch: the per-pair buffers viewed as one big problem
   EvhRansacArgs R{};
   R.fast_solver = c->solver_mode;
   R.pts = const_cast<float*>(d_pts); R.n_fixed = n; R.thr = thr; R.max_iters = max_iters; R.conf = conf; R.force_max = force_max;
-  if (force_max) { int lr = ensure_lane_scratch(c); if (lr) return lr; R.lane_v = c->d_lane_v; }
+  if (force_max) { int lr = evh_ensure_lane_scratch(c); if (lr) return lr; R.lane_v = c->d_lane_v; }
   EvhSmall* S = c->d_small;
   R.mask = c->orb.mask; R.crow = c->orb.crow; R.lm = c->orb.lm;
   R.H = S->H; R.found = &S->found; R.info = S->info;
@@ -1054,7 +762,7 @@ int evh_static_filter(evh_ctx* c, const double* h_H, const float* d_pts, int n, 
   if (!c || !h_H || (!d_pts && n > 0) || !d_out_pts || !h_count || n < 0) return evh_fail(c, EVH_ERR_INVALID, "evh_static_filter: bad argument");
   if (n > c->kcap * c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "evh_static_filter: too many rows");
   if ((((uintptr_t)d_pts) | ((uintptr_t)d_out_pts)) & 15) return evh_fail(c, EVH_ERR_INVALID, "row buffers must be 16-byte aligned");
-  { int jr = join_solve(c); if (jr) return jr; }
+  { int jr = evh_join_solve(c); if (jr) return jr; }
   EvhSmall* S = c->d_small;
   EVH_HIP(c, hipMemcpyAsync(S->H, h_H, 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   int* d_cnt = &S->count;
@@ -1076,7 +784,7 @@ int evh_remove_double_matching(evh_ctx* c, const float* d_pts, int n, float* d_o
   const uintptr_t lo = (uintptr_t)d_pts, lo2 = (uintptr_t)d_out, len = sizeof(float) * 4 * (size_t)n;
   if (lo < lo2 + len && lo2 < lo + len)                 // k_merge reads a key's last row while other rows are being written
     return evh_fail(c, EVH_ERR_INVALID, "evh_remove_double_matching: d_pts and d_out overlap");
-  { int jr = join_solve(c); if (jr) return jr; }        // d_small is the staging area of a one-pair solve still in flight
+  { int jr = evh_join_solve(c); if (jr) return jr; }        // d_small is the staging area of a one-pair solve still in flight
   EvhSmall* S = c->d_small;
   const int head[2] = {n, 0};                           // nacc, accstatus
   EVH_HIP(c, hipMemcpyAsync(&S->merge.nacc, head, sizeof(head), hipMemcpyHostToDevice, c->stream));
@@ -1089,138 +797,6 @@ int evh_remove_double_matching(evh_ctx* c, const float* d_pts, int n, float* d_o
   EVH_HIP(c, hipStreamSynchronize(c->stream));
   return EVH_SUCCESS;
 }
-
-int evh_pair_homography_batch(evh_ctx* c, const uint8_t* d_frames, int npairs, int mode, int w, int h, int channels,
-                              int64_t row_stride, int64_t frame_stride, int nfeatures, double ransac_thr,
-                              int ransac_max_iters, double ransac_conf, int force_max_iters, double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || npairs < 1) return evh_fail(c, EVH_ERR_INVALID, "evh_pair_homography_batch: bad argument");
-  if (mode != EVH_MODE_INDEPENDENT_PAIRS && mode != EVH_MODE_STREAM) return evh_fail(c, EVH_ERR_INVALID, "unknown mode");
-  const int nframes = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 * npairs : npairs + 1;
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  if (mode == EVH_MODE_STREAM)
-    return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, w, h, w, h, nfeatures,
-                        ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
-  // FAST thresholds are shared by the two frames of a pair
-  int rc = detect_match(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, 2, npairs, 2, w, h, w, h, nfeatures);
-  if (rc) return rc;
-  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  R.H = d_H; R.out_status = d_status;
-  return solve_pairs(c, R, npairs, 0, npairs, npairs);
-}
-
-int evh_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
-                                int64_t row_stride, int64_t frame_stride, int nfeatures, double ransac_thr,
-                                int ransac_max_iters, double ransac_conf, int force_max_iters, const double* d_state_in,
-                                double* d_state_out, double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch: bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, w, h, w, h, nfeatures,
-                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
-}
-
-int evh_stream_homography_batch_resized(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
-                                        int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures,
-                                        double ransac_thr, int ransac_max_iters, double ransac_conf, int force_max_iters,
-                                        const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_resized: bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), 1, nframes, src_w, src_h, w, h, nfeatures,
-                      ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H, d_status);
-}
-
-int evh_match_static_from_slots(evh_ctx* c, int cur_slot, int prev_slot, float* h_pts, int cap, int* h_count, int* h_status) {
-  if (!c || !h_count || !h_status || cur_slot < 0 || prev_slot < 0 || cur_slot >= c->nframes_resident ||
-      prev_slot >= c->nframes_resident)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_match_static_from_slots: bad argument");
-  { int jr = join_solve(c); if (jr) return jr; }
-  int rc = match_orb_pairs(c, 1, cur_slot, 0, prev_slot, 0);
-  if (rc) return rc;
-  EvhRansacArgs R = ransac_args(c, c->orb, 3.0, 2000, 0.995, 0);  // constants.py:22 THRESHOLD_FOR_FIND_HOMOGRAPHY
-  if ((rc = evh_launch_ransac_static(c, R, 1))) return rc;
-  int st = 0, n = 0;
-  EVH_HIP(c, hipMemcpyAsync(&st, c->orb.pstatus, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(&n, c->orb.npts2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  EVH_HIP(c, hipStreamSynchronize(c->stream));
-  *h_status = st; *h_count = n;
-  if (st == EVH_PAIR_OK && n > 0 && h_pts) {
-    if (n > cap) return evh_fail(c, EVH_ERR_CAPACITY, "h_pts too small");
-    EVH_HIP(c, hipMemcpy(h_pts, c->orb.pts2, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  return EVH_SUCCESS;
-}
-
-int evh_compute_homography(evh_ctx* c, const float* h_pts, int n, const double* h_Hsup, double* h_H, int* h_status) {
-  if (!c || (!h_pts && n > 0) || !h_H || !h_status || n < 0) return evh_fail(c, EVH_ERR_INVALID, "evh_compute_homography: bad argument");
-  if (n > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "evh_compute_homography: too many rows");
-  { int jr = join_solve(c); if (jr) return jr; }
-  const int zero = 0;
-  EVH_HIP(c, hipMemcpyAsync(c->orb.pts2, h_pts, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(c->orb.npts2, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(c->orb.pstatus, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  return final_solve_one(c, h_Hsup, h_H, h_status);
-}
-
-int evh_multi_stream_homography_batch(evh_ctx* c, const uint8_t* d_frames, int nstreams, int frames_per_stream, int w,
-                                      int h, int channels, int64_t row_stride, int64_t frame_stride, int nfeatures,
-                                      double ransac_thr, int ransac_max_iters, double ransac_conf, int force_max_iters,
-                                      const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || nstreams < 1 || frames_per_stream < 2)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_multi_stream_homography_batch: bad argument");
-  if ((int64_t)nstreams * frames_per_stream > c->max_frames)
-    return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  return stream_batch(c, packed_frames(d_frames, channels, row_stride, frame_stride), nstreams, frames_per_stream, w, h, w, h,
-                      nfeatures, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H,
-                      d_status);
-}
-
-int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels,
-                            int64_t row_stride, int64_t frame_stride, int nfeatures, double ransac_thr,
-                            int ransac_max_iters, double ransac_conf, int force_max_iters, float* d_rows, int row_cap,
-                            int32_t* d_counts, int32_t* d_status1) {
-  if (!c || !d_frames || !d_rows || !d_counts || !d_status1 || nframes < 2)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_stream_static_batch: bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "block needs more frame slots than max_frames");
-  if (row_cap != c->kcap) return evh_fail(c, EVH_ERR_INVALID, "row_cap must equal evh_orb_capacity()");
-  const int npairs = nframes - 1;
-  int rc = detect_match(c, packed_frames(d_frames, channels, row_stride, frame_stride), nframes, nframes, npairs, 1, w, h, w, h,
-                        nfeatures);
-  if (rc) return rc;
-  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, R, npairs); }
-  if (rc) return rc;
-  EVH_HIP(c, hipMemcpyAsync(d_rows, c->orb.pts2, sizeof(float) * 4 * (size_t)c->kcap * npairs, hipMemcpyDeviceToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(d_counts, c->orb.npts2, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  EVH_HIP(c, hipMemcpyAsync(d_status1, c->orb.pstatus, sizeof(int) * (size_t)npairs, hipMemcpyDeviceToDevice, c->stream));
-  return EVH_SUCCESS;
-}
-
-int evh_stream_scan(evh_ctx* c, const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1,
-                    int npairs, double ransac_thr, int ransac_max_iters, double ransac_conf, int force_max_iters,
-                    const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
-  if (!c || !d_rows || !d_counts || !d_status1 || !d_H || !d_status || npairs < 1)
-    return evh_fail(c, EVH_ERR_INVALID, "evh_stream_scan: bad argument");
-  if (row_cap < 1 || row_cap > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "row_cap larger than evh_orb_capacity()");
-  if (((uintptr_t)d_rows) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_rows must be 16-byte aligned");
-  { int jr = join_solve(c); if (jr) return jr; }                  // the scan uses slot 0 of the pair scratch
-  EvhRansacArgs R = ransac_args(c, c->orb, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters);
-  R.pts2 = const_cast<float*>(d_rows); R.npts2 = const_cast<int*>(d_counts); R.status = const_cast<int*>(d_status1);
-  R.row_stride = row_cap; R.info = nullptr;
-  R.H = d_H; R.out_status = d_status;
-  with_state(R, d_state_in, d_state_out);
-  int rc;
-  { EvhProfScope ps(c, EVH_ST_RANSAC_FINAL); rc = evh_launch_ransac_final(c, R, npairs, 1, npairs); }
-  return rc;
-}
-
-int evh_pair_from_slots(evh_ctx* c, int cur_slot, int prev_slot, const double* h_Hsup, double* h_H, int* h_status) {
-  if (!c || !h_H || !h_status) return evh_fail(c, EVH_ERR_INVALID, "evh_pair_from_slots: bad argument");
-  int n = 0, st = 0;
-  int rc = evh_match_static_from_slots(c, cur_slot, prev_slot, nullptr, 0, &n, &st);
-  if (rc) return rc;
-  if (st != EVH_PAIR_OK) { *h_status = st; memset(h_H, 0, 9 * sizeof(double)); return EVH_SUCCESS; }
-  return final_solve_one(c, h_Hsup, h_H, h_status);   // the static rows are already resident in pair slot 0
-}
-
 
 // ---- N4: SIFT ------------------------------------------------------------------------------------------------------------------
 int evh_sift_enable(evh_ctx* c, int max_sift_features) {
@@ -1287,35 +863,10 @@ int evh_ratio_unique_filter_f32(evh_ctx* c, const int32_t* d_idx, const float* d
                       ratio, min_matches, d_pts, h_count, h_status);
 }
 
-int evh_pair_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int npairs, int mode, int src_w, int src_h,
-                                    int channels, int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures,
-                                    const int32_t* h_types, int ntypes, double ransac_thr, int ransac_max_iters,
-                                    double ransac_conf, int force_max_iters, double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || npairs < 1) return evh_fail(c, EVH_ERR_INVALID, "evh_pair_homography_batch_types: bad argument");
-  if (mode != EVH_MODE_INDEPENDENT_PAIRS && mode != EVH_MODE_STREAM) return evh_fail(c, EVH_ERR_INVALID, "unknown mode");
-  const int nframes = mode == EVH_MODE_INDEPENDENT_PAIRS ? 2 * npairs : npairs + 1;
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "batch needs more frame slots than max_frames");
-  return pairs_types(c, "evh_pair_homography_batch_types", packed_frames(d_frames, channels, row_stride, frame_stride), nframes,
-                     npairs, mode == EVH_MODE_STREAM, src_w, src_h, w, h, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters,
-                     ransac_conf, force_max_iters, nullptr, nullptr, d_H, d_status);
-}
-
-int evh_stream_homography_batch_types(evh_ctx* c, const uint8_t* d_frames, int nframes, int src_w, int src_h, int channels,
-                                      int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures,
-                                      const int32_t* h_types, int ntypes, double ransac_thr, int ransac_max_iters,
-                                      double ransac_conf, int force_max_iters, const double* d_state_in, double* d_state_out,
-                                      double* d_H, int32_t* d_status) {
-  if (!c || !d_frames || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_types: bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return pairs_types(c, "evh_stream_homography_batch_types", packed_frames(d_frames, channels, row_stride, frame_stride), nframes,
-                     nframes - 1, 1, src_w, src_h, w, h, nfeatures, h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf,
-                     force_max_iters, d_state_in, d_state_out, d_H, d_status);
-}
-
 // ---- decoded 4:2:0 planes as the source (video_processing.py:58,70) ----------------------------------------------------------
 int evh_yuv420_to_bgr(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int h, uint8_t* d_bgr, int64_t row_stride,
                       int64_t frame_stride) {
-  if (int rc = check_yuv420(c, "evh_yuv420_to_bgr", src, nframes, w, h)) return rc;
+  if (int rc = evh_check_yuv420(c, "evh_yuv420_to_bgr", src, nframes, w, h)) return rc;
   if (!d_bgr) return evh_fail(c, EVH_ERR_INVALID, "evh_yuv420_to_bgr: d_bgr is NULL");
   if (row_stride < (int64_t)w * 3 || (nframes > 1 && frame_stride < (h - 1) * row_stride + (int64_t)w * 3))
     return evh_fail(c, EVH_ERR_INVALID, "evh_yuv420_to_bgr: output stride smaller than a row / frame");
@@ -1325,50 +876,6 @@ int evh_yuv420_to_bgr(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);
-}
-
-int evh_stream_homography_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
-                                       int nfeatures, double ransac_thr, int ransac_max_iters, double ransac_conf,
-                                       int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
-                                       int32_t* d_status) {
-  if (!c || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_homography_batch_yuv420: bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return stream_batch(c, yuv420_frames(src), 1, nframes, src_w, src_h, w, h, nfeatures, ransac_thr, ransac_max_iters, ransac_conf,
-                      force_max_iters, d_state_in, d_state_out, d_H, d_status);
-}
-
-int evh_stream_homography_batch_types_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w,
-                                             int h, int nfeatures, const int32_t* h_types, int ntypes, double ransac_thr,
-                                             int ransac_max_iters, double ransac_conf, int force_max_iters,
-                                             const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status) {
-  const char* who = "evh_stream_homography_batch_types_yuv420";
-  if (!c || !d_H || !d_status || nframes < 2) return evh_fail(c, EVH_ERR_INVALID, std::string(who) + ": bad argument");
-  if (nframes > c->max_frames) return evh_fail(c, EVH_ERR_CAPACITY, "chunk needs more frame slots than max_frames");
-  return pairs_types(c, who, yuv420_frames(src), nframes, nframes - 1, 1, src_w, src_h, w, h, nfeatures,
-                     h_types, ntypes, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in, d_state_out, d_H,
-                     d_status);
-}
-
-// ---- ragged batches of several streams -----------------------------------------------------------------------------------------
-int evh_streams_homography_batch(evh_ctx* c, const uint8_t* d_frames, int total_frames, int src_w, int src_h, int channels,
-                                 int64_t row_stride, int64_t frame_stride, int w, int h, int nfeatures, const int32_t* h_types,
-                                 int ntypes, const evh_stream_seg* h_segs, int nstreams, double ransac_thr, int ransac_max_iters,
-                                 double ransac_conf, int force_max_iters, const double* d_state_in, double* d_state_out,
-                                 double* d_H, int32_t* d_status) {
-  return streams_batch(c, "evh_streams_homography_batch", packed_frames(d_frames, channels, row_stride, frame_stride), total_frames,
-                       src_w, src_h, w, h, nfeatures, h_types, ntypes, h_segs, nstreams, ransac_thr, ransac_max_iters, ransac_conf,
-                       force_max_iters, d_state_in, d_state_out, d_H, d_status);
-}
-
-int evh_streams_homography_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int total_frames, int src_w, int src_h, int w, int h,
-                                        int nfeatures, const int32_t* h_types, int ntypes, const evh_stream_seg* h_segs,
-                                        int nstreams, double ransac_thr, int ransac_max_iters, double ransac_conf,
-                                        int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
-                                        int32_t* d_status) {
-  // (the planes are checked by the ingest of either path, before its first launch)
-  return streams_batch(c, "evh_streams_homography_batch_yuv420", yuv420_frames(src), total_frames, src_w, src_h, w, h, nfeatures,
-                       h_types, ntypes, h_segs, nstreams, ransac_thr, ransac_max_iters, ransac_conf, force_max_iters, d_state_in,
-                       d_state_out, d_H, d_status);
 }
 
 // ---- N4: SURF --------------------------------------------------------------------------------------------------------------------

@@ -69,11 +69,12 @@ struct EvhKpList : EvhKpDev {
 struct EvhFrames {
   const uint8_t* packed = nullptr; int channels = 0; int64_t row_stride = 0, frame_stride = 0;
   const evh_yuv420* yuv = nullptr;
+  bool planes = false;       // the entry takes planes (yuv may still be NULL: refused with the plane description)
 };
 inline EvhFrames packed_frames(const uint8_t* d, int channels, int64_t row_stride, int64_t frame_stride) {
   EvhFrames F; F.packed = d; F.channels = channels; F.row_stride = row_stride; F.frame_stride = frame_stride; return F;
 }
-inline EvhFrames yuv420_frames(const evh_yuv420* src) { EvhFrames F; F.channels = 3; F.yuv = src; return F; }
+inline EvhFrames yuv420_frames(const evh_yuv420* src) { EvhFrames F; F.channels = 3; F.yuv = src; F.planes = true; return F; }
 
 // per-pair working buffers of the matching / RANSAC stages (max_pairs = max_frames, row stride `cap` rows per pair)
 struct EvhPairBufs {
@@ -172,7 +173,6 @@ struct evh_ctx {
   bool fast_lift = true;
   bool fast_share = true;         // evh_set_fast_share
   bool fast_hint = true;          // evh_set_fast_hint
-  int fast_share_group = 0;       // frames per group of consecutive frames for this detect call (0: unrelated frames)
   EvhPairBufs orb;                // pair buffers of the ORB path, orb.cap = kcap
   EvhSmall* d_small = nullptr;    // small staging area for single-problem entries (H, counts)
   char* d_scratch = nullptr;      // growable scratch of the host-pointer entries (N1 / N3): no hipMalloc per call
@@ -272,6 +272,28 @@ int grow(evh_ctx* c, T** p, size_t* bytes, size_t need) {
   if (rc == EVH_SUCCESS) *bytes = need;
   return rc;
 }
+
+// ---- host stages shared by evh_api.hip (which defines them) and evh_batch.hip ----
+// one set of per-pair buffers with `cap` rows per pair (the ORB path: kcap; the multi-type path: every type's rows)
+int evh_alloc_pair_bufs(evh_ctx* c, EvhPairBufs& B, int cap);
+// the argument checks of every entry that takes planes: nothing is launched on a description that fails them
+int evh_check_yuv420(evh_ctx* c, const char* who, const evh_yuv420* s, int nframes, int w, int h);
+// level 0 (gray) of every frame: (sw, sh) = size of the frames handed over, (w, h) = working size; different sizes = fused
+// ingest (N2).  The one place where the frame description of a detect / pair / stream entry is checked and the geometry set.
+int evh_ingest_level0(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, int w, int h, int nfeatures);
+// ORB K2..K6 on the frames whose level 0 is resident; FAST thresholds shared inside groups of share_group frames (0: none)
+int evh_orb_stages(evh_ctx* c, int nframes, int share_group);
+// entry points that reuse the pair buffers on the main stream first order themselves behind a pending async solve
+int evh_join_solve(evh_ctx* c);
+// fixed-iteration mode keeps the per-lane eigenvector matrices of its hypotheses in a global scratch, allocated on first use
+int evh_ensure_lane_scratch(evh_ctx* c);
+// one feature type's per-frame results, as the matching stages and the downloads read them
+struct EvhFeatView {
+  const int* counts; const int* flags; const float* xy;
+  const void* desc; int desc_bytes; bool f32;    // uint8 rows of desc_bytes values, or (f32) rows of 128 floats
+  int cap;                                       // rows per frame slot
+};
+EvhFeatView evh_feat_view(const evh_ctx* c, int type);
 
 // ---- kernel launchers (each enqueues on ctx->stream) ----
 int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int channels, int64_t row_stride,

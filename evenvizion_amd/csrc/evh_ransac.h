@@ -36,8 +36,22 @@ int evh_launch_find_homography(evh_ctx* c, const EvhRansacArgs& A);
 int evh_launch_static_filter(evh_ctx* c, const double* d_H, const float* d_rows, int n, int* d_rbin, float* d_out,
                              int* d_count);
 int evh_launch_ransac_static(evh_ctx* c, const EvhRansacArgs& A, int npairs);
-// nstreams == 0: npairs independent pairs; else nstreams scans of npairs pairs, `pitch` pair slots apart; with d_segs (a device
-// table of nstreams segments): the scans of a ragged batch of npairs pair slots, max_pairs pairs in the longest stream
+// How the pair slots of a final solve hang together (host side only: the kernels take what they took).  npairs per kind:
+//   PAIRS    independent pairs, one workgroup each;
+//   STREAMS  the pairs of EACH of nstreams streams, scanned in order by one workgroup per stream; a stream's first pair slot
+//            lies `pitch` slots behind the previous stream's;
+//   RAGGED   ALL pair slots of the batch (frames - 1); d_segs, a device table of nstreams segments, says which belong to which
+//            stream, max_pairs = pairs of the longest one.
 struct evh_stream_seg;
-int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A, int npairs, int nstreams, int pitch,
-                            const evh_stream_seg* d_segs = nullptr, int max_pairs = 0);
+struct EvhSolveLayout {
+  enum Kind { PAIRS, STREAMS, RAGGED } kind;
+  int npairs, nstreams, pitch;
+  const evh_stream_seg* d_segs;
+  int max_pairs;
+  static EvhSolveLayout pairs(int npairs) { return {PAIRS, npairs, 0, 0, nullptr, 0}; }
+  static EvhSolveLayout streams(int pairs_each, int nstreams, int pitch) { return {STREAMS, pairs_each, nstreams, pitch, nullptr, 0}; }
+  static EvhSolveLayout ragged(int pair_slots, int nstreams, const evh_stream_seg* d_segs, int max_pairs) {
+    return {RAGGED, pair_slots, nstreams, 0, d_segs, max_pairs};
+  }
+};
+int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A, const EvhSolveLayout& L);

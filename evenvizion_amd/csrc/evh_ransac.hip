@@ -1049,9 +1049,8 @@ int evh_launch_ransac_static(evh_ctx* c, const EvhRansacArgs& A, int npairs) {
   EVH_LAUNCH_NW(waves_for(npairs, A.force_max), k_ransac_static, npairs, c->stream, A);
   return launched(c);
 }
-int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, int npairs, int nstreams, int pitch, const evh_stream_seg* d_segs,
-                            int max_pairs) {
-  if (npairs <= 0) return EVH_SUCCESS;
+int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, const EvhSolveLayout& L) {
+  if (L.npairs <= 0) return EVH_SUCCESS;
   EvhRansacArgs A = A_;
   if (int rc = check_lane_scratch(c, A)) return rc;
   static const bool want_prof = getenv("EVH_RANSAC_PROF") != nullptr;   // debugging aid: cycle accounting to stderr
@@ -1064,15 +1063,14 @@ int evh_launch_ransac_final(evh_ctx* c, const EvhRansacArgs& A_, int npairs, int
     }
     A.prof = d_prof;
   }
-  // nstreams == 0: independent pairs; otherwise nstreams sequential scans of npairs pairs each, `pitch` pair slots apart;
-  // with d_segs: the nstreams scans of a ragged batch of npairs pair slots, max_pairs pairs in the longest
-  if (nstreams > 0 && A.force_max && !getenv("EVH_SCAN_ONE_WG")) {
-    const int fr = d_segs ? launch_forced_ragged(c, A, max_pairs, nstreams, RaggedStreams{d_segs}, 1, npairs, 0)
-                          : launch_forced_scan(c, A, npairs, nstreams, pitch);
+  const bool ragged = L.kind == EvhSolveLayout::RAGGED;
+  if (L.kind != EvhSolveLayout::PAIRS && A.force_max && !getenv("EVH_SCAN_ONE_WG")) {
+    const int fr = ragged ? launch_forced_ragged(c, A, L.max_pairs, L.nstreams, RaggedStreams{L.d_segs}, 1, L.npairs, 0)
+                          : launch_forced_scan(c, A, L.npairs, L.nstreams, L.pitch);
     if (fr) { if (d_prof) (void)hipFree(d_prof); return fr; }
-  } else if (d_segs) EVH_LAUNCH_NW(waves_for(nstreams, A.force_max), k_ransac_final_ragged, nstreams, c->stream, A, RaggedStreams{d_segs});
-  else if (nstreams > 0) EVH_LAUNCH_NW(waves_for(nstreams, A.force_max), k_ransac_final_stream, nstreams, c->stream, A, npairs, pitch);
-  else EVH_LAUNCH_NW(waves_for(npairs, A.force_max), k_ransac_final_pairs, npairs, c->stream, A);
+  } else if (ragged) EVH_LAUNCH_NW(waves_for(L.nstreams, A.force_max), k_ransac_final_ragged, L.nstreams, c->stream, A, RaggedStreams{L.d_segs});
+  else if (L.kind == EvhSolveLayout::STREAMS) EVH_LAUNCH_NW(waves_for(L.nstreams, A.force_max), k_ransac_final_stream, L.nstreams, c->stream, A, L.npairs, L.pitch);
+  else EVH_LAUNCH_NW(waves_for(L.npairs, A.force_max), k_ransac_final_pairs, L.npairs, c->stream, A);
   {
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { if (d_prof) (void)hipFree(d_prof); return evh_fail(c, EVH_ERR_HIP, std::string("k_ransac_final: ") + hipGetErrorString(le)); }

@@ -57,10 +57,97 @@ def _first_planes(capture, ingest):
     return packed[0], w, h
 
 
+def _feature_list(features_type_list):
+    """-> the feature list a driver runs with (None: the reference's default); ValueError as the reference raises it."""
+    from .frame_processing import DEFAULT_FEATURES
+    features = list(features_type_list or DEFAULT_FEATURES)
+    for name in features:
+        if name not in ("ORB", "SIFT", "SURF"):
+            raise ValueError("You need to choose descriptors type")
+    return features
+
+
+def _open_capture(capture, ingest):
+    """The first frame of `capture`: planes where _first_planes takes them, else read().
+    -> (first frame: packed I420 bytes or a BGR array, planes?, w0, h0)"""
+    first, w0, h0 = _first_planes(capture, ingest)
+    if first is not None:
+        return first, True, w0, h0
+    success, first = capture.read()
+    if not success:
+        raise ValueError("Problem with video! Can't read first frame")
+    first = np.ascontiguousarray(first, np.uint8)
+    h0, w0 = first.shape[:2]
+    return first, False, w0, h0
+
+
+def _read_frame(capture, planes, slot, w0, h0, number):
+    """The capture's next frame (its `number`, 1-based, for the error) into `slot`, a frame of the pinned staging buffer: the
+    one host copy.  -> False when the capture has no further frame."""
+    if planes:
+        from .._lib import yuv420_views
+        y, cb, cr = yuv420_views(slot[None], w0, h0)
+        return bool(capture.read_yuv420_into(y[0], cb[0], cr[0]))
+    ok, frame = capture.read()
+    if not ok:
+        return False
+    frame = np.asarray(frame, np.uint8)
+    if frame.shape != slot.shape:
+        raise ValueError("frame %d has shape %s, the first frame %s" % (number, frame.shape, slot.shape))
+    slot[...] = frame
+    return True
+
+
+def _upload(B, j, spans, cur):
+    """Frames of pinned host buffer j to device buffer j on the copy stream, one copy per span (device frame, host frame,
+    frames); torch's current stream `cur` (None on the CPU) then waits for them."""
+    if cur is None:
+        for a, b, n in spans:
+            B["dev"][j][a:a + n].copy_(B["host"][j][b:b + n])
+        return
+    import torch
+    with torch.cuda.stream(B["copy_stream"]):
+        for a, b, n in spans:
+            B["dev"][j][a:a + n].copy_(B["host"][j][b:b + n], non_blocking=True)
+        B["up_done"][j].record(B["copy_stream"])
+    cur.wait_event(B["up_done"][j])
+
+
+def _results_to_host(c, B, j, npairs, cur):
+    """H and status of the first npairs pair slots of buffer j back through pinned memory, behind everything context `c` has
+    enqueued; all_done[j] marks their arrival (cur: torch's current stream, None on the CPU)."""
+    if cur is not None:
+        c.order_torch_after()
+    B["H_host"][j][:npairs].copy_(B["H_dev"][j][:npairs], non_blocking=True)
+    B["st_host"][j][:npairs].copy_(B["st_dev"][j][:npairs], non_blocking=True)
+    if cur is not None:
+        B["all_done"][j].record(cur)
+
+
+def _pairs_into(result, frame_no, Hs, sts, none_H_processing, capture_index=None):
+    """Consecutive pairs (Hs f64[k,3,3], sts i32[k]) of one capture into its dictionary: the pair ending at frame f becomes
+    result[f] = {"H": ...}.  frame_no: the newest frame already paired; -> the same after these.  capture_index names the
+    capture in the log line of the many-captures driver."""
+    for Hk, sk in zip(Hs, sts):
+        frame_no += 1
+        if sk != PAIR_OK:
+            if capture_index is None:
+                logging.info("pair ending at frame %d: no homography (status %d)", frame_no, int(sk))
+            else:
+                logging.info("capture %d, pair ending at frame %d: no homography (status %d)", capture_index, frame_no, int(sk))
+            if not none_H_processing or not np.all(np.isfinite(Hk)):
+                # reference behaviour (video_processing.py:94-101): H stays None and None.tolist() raises --
+                # always for none_H_processing=False, and for a failing FIRST pair otherwise (SURVEY F11)
+                raise AttributeError("'NoneType' object has no attribute 'tolist' (no homography for frame %d, "
+                                     "status %d)" % (frame_no, int(sk)))
+        result[frame_no] = {"H": Hk.tolist()}
+    return frame_no
+
+
 def rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, max_frames, run, overflowed, what):
     """Some frame delivered more tied key points than a frame slot of `ctx` holds (a pair reported EVH_PAIR_CAPACITY).
     The reference has no such bound (it carries on with every tie, frame_processing.py:59-61), so the work is done again
-    -- run(big), which starts from the state the work was entered with and waits for its results -- on a context whose
+    -- run(big), which starts from the state the work was entered with; its results are waited for here -- on a context whose
     frame slots are twice as large (same nfeatures, so the same key points for every other frame), doubling again while
     overflowed() still says so, up to the LDS limit of the matching filter.  `what` names the frames in the error."""
     from .._lib import Context, MAX_FEATURES
@@ -88,6 +175,11 @@ def rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, max_frames, run, ove
                            "the largest frame slot this device path supports" % what)
         try:
             run(big)
+            if runtime.device().type == "cuda":
+                import torch
+                torch.cuda.synchronize(runtime.device())
+            else:                   # (the host-loop unit tests: a scripted context on the CPU)
+                big.synchronize()
         finally:
             big.close()
         if not overflowed():
@@ -108,22 +200,15 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
                                   "call with matching_path=None")
     if ingest not in ("auto", "bgr", "yuv420"):
         raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
-    first, w0, h0 = _first_planes(capture, ingest)
-    planes = first is not None
-    if not planes:
-        success, first = capture.read()
-        if not success:
-            raise ValueError("Problem with video! Can't read first frame")
-        first = np.ascontiguousarray(first, np.uint8)
-        h0, w0 = first.shape[:2]
+    first, planes, w0, h0 = _open_capture(capture, ingest)
     dw, dh = resized_shape((h0, w0), resize_width)
-    # one staging buffer (pinned host / device) is capped in bytes: 4K BGR frames give 21-frame chunks, not 64
-    from .frame_processing import DEFAULT_FEATURES
-    features = list(features_type_list or DEFAULT_FEATURES)
-    for name in features:
-        if name not in ("ORB", "SIFT", "SURF"):
-            raise ValueError("You need to choose descriptors type")
+    features = _feature_list(features_type_list)
+    # the Context method of a chunk and what it takes besides frames, outputs and state, from planes x multi: the decoder's
+    # planes or BGR frames as the source; the fused ORB entry or frame_processing.py:91-104 over the type list
     multi = features != ["ORB"]
+    method = "stream_homography_batch" + ("_types" if multi else "") + ("_yuv420" if planes else "")
+    size, types = ((w0, h0),) if planes else (), (features,) if multi else ()
+    # one staging buffer (pinned host / device) is capped in bytes: 4K BGR frames give 21-frame chunks, not 64
     chunk_frames = runtime.chunk_frames_for(first.nbytes, max(2, int(chunk_frames)))
     # sized for the RESIZED frames: only those go through ORB (evh_resize_area_u8 does not depend on the context's
     # geometry), so a 4K source with resize_width=400 allocates 400-wide buffers
@@ -133,9 +218,8 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     # pinned memory and its upload runs on a copy stream; results come back through pinned buffers.  Chunk i is
     # launched BEFORE the results of chunk i-1 are collected, so the device queue never drains.
     B = runtime.staging((chunk_frames,) + first.shape, dev)
-    host, host_np, devbuf = B["host"], B["host_np"], B["dev"]
+    host_np, devbuf, all_done = B["host_np"], B["dev"], B["all_done"]
     H_dev, st_dev, H_host, st_host = B["H_dev"], B["st_dev"], B["H_host"], B["st_host"]
-    copy_stream, up_done, all_done = B["copy_stream"], B["up_done"], B["all_done"]
     state = torch.zeros(18, dtype=torch.float64, device=dev)
     # {H_sup, H_prev} as they ENTER each in-flight chunk (and whether there was a state at all): what a chunk is re-run
     # from when one of its frames overflows a frame slot (EVH_PAIR_CAPACITY)
@@ -148,25 +232,9 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     frame_no = [1]          # 1-based index of the newest frame already paired
 
     def launch(c, jb, nb, with_state):
-        if planes:      # the same two entries with the decoder's planes as the source
-            kw = dict(state_in=state if with_state else None, state_out=state, nfeatures=nfeatures, resize_to=(dw, dh))
-            if multi:
-                c.stream_homography_batch_types_yuv420(devbuf[jb][:nb], (w0, h0), H_dev[jb], st_dev[jb], features, **kw)
-            else:
-                c.stream_homography_batch_yuv420(devbuf[jb][:nb], (w0, h0), H_dev[jb], st_dev[jb], **kw)
-        elif multi:       # frame_processing.py:91-104 over the type list: evh_stream_homography_batch_types
-            c.stream_homography_batch_types(devbuf[jb][:nb], H_dev[jb], st_dev[jb], features,
-                                            state_in=state if with_state else None, state_out=state, nfeatures=nfeatures,
-                                            resize_to=(dw, dh))
-        else:
-            c.stream_homography_batch(devbuf[jb][:nb], H_dev[jb], st_dev[jb], state_in=state if with_state else None,
-                                      state_out=state, nfeatures=nfeatures, resize_to=(dw, dh))
-        if cuda:
-            c.order_torch_after()
-        H_host[jb][:nb - 1].copy_(H_dev[jb][:nb - 1], non_blocking=True)
-        st_host[jb][:nb - 1].copy_(st_dev[jb][:nb - 1], non_blocking=True)
-        if cuda:
-            all_done[jb].record(cur)
+        getattr(c, method)(devbuf[jb][:nb], *size, H_dev[jb], st_dev[jb], *types, state_in=state if with_state else None,
+                           state_out=state, nfeatures=nfeatures, resize_to=(dw, dh))
+        _results_to_host(c, B, jb, nb - 1, cur)
 
     def rerun_with_larger_slots(jb, nb, later):
         """A frame of chunk jb delivered more tied key points than a frame slot of `ctx` holds: the chunk is re-run from
@@ -178,10 +246,6 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
         def run(big):
             state.copy_(state_pre[jb])
             launch(big, jb, nb, had_state[jb])
-            if cuda:
-                torch.cuda.synchronize(dev)
-            else:
-                big.synchronize()
 
         rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, chunk_frames, run,
                               lambda: bool((st_host[jb][:nb - 1].numpy() == PAIR_CAPACITY).any()),
@@ -197,34 +261,8 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
             all_done[jb].synchronize()
         if (st_host[jb][:nb - 1].numpy() == PAIR_CAPACITY).any():
             rerun_with_larger_slots(jb, nb, later)
-        Hs = H_host[jb][:nb - 1].numpy().reshape(-1, 3, 3)
-        sts = st_host[jb][:nb - 1].numpy()
-        for k in range(nb - 1):
-            frame_no[0] += 1
-            fno = frame_no[0]
-            if sts[k] != PAIR_OK:
-                logging.info("pair ending at frame %d: no homography (status %d)", fno, int(sts[k]))
-                if not none_H_processing or not np.all(np.isfinite(Hs[k])):
-                    # reference behaviour (video_processing.py:94-101): H stays None and None.tolist() raises --
-                    # always for none_H_processing=False, and for a failing FIRST pair otherwise
-                    raise AttributeError("'NoneType' object has no attribute 'tolist' (no homography for frame %d, "
-                                         "status %d)" % (fno, int(sts[k])))
-            homography_dict[fno] = {"H": Hs[k].tolist()}
-
-    def read_into(slot):
-        """The capture's next frame into `slot`, a frame of the pinned staging chunk: the one host copy."""
-        if planes:
-            from .._lib import yuv420_views
-            y, cb, cr = yuv420_views(slot[None], w0, h0)
-            return bool(capture.read_yuv420_into(y[0], cb[0], cr[0]))
-        ok, frame = capture.read()
-        if not ok:
-            return False
-        frame = np.asarray(frame, np.uint8)
-        if frame.shape != first.shape:
-            raise ValueError("frame %d has shape %s, the first frame %s" % (frame_no[0] + n, frame.shape, first.shape))
-        slot[...] = frame
-        return True
+        frame_no[0] = _pairs_into(homography_dict, frame_no[0], H_host[jb][:nb - 1].numpy().reshape(-1, 3, 3),
+                                  st_host[jb][:nb - 1].numpy(), none_H_processing)
 
     j, n = 0, 1
     host_np[0][0] = first
@@ -234,19 +272,13 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     try:
         while True:
             while n < chunk_frames and not exhausted:
-                if not read_into(host_np[j][n]):
+                if not _read_frame(capture, planes, host_np[j][n], w0, h0, frame_no[0] + n):
                     exhausted = True
                     break
                 n += 1
             launched = None
             if n >= 2:
-                if cuda:
-                    with torch.cuda.stream(copy_stream):
-                        devbuf[j][:n].copy_(host[j][:n], non_blocking=True)
-                        up_done[j].record(copy_stream)
-                    cur.wait_event(up_done[j])
-                else:
-                    devbuf[j][:n].copy_(host[j][:n])
+                _upload(B, j, [(0, 0, n)], cur)
                 # K0 fused into the ingest kernel: level 0 comes straight from the full-size frames (N2); equal sizes
                 # are the plain gray conversion
                 state_pre[j].copy_(state)               # stream-ordered: after chunk i-1's kernels, before chunk i's
@@ -286,24 +318,13 @@ class _Stream:
         self.result = {}
 
 
-def _read_frames(st, region, w0, h0):
+def _read_frames(st, region):
     """Decode-pool task: the capture's next frames into region[1:], a stream's frames of the pinned staging buffer (frame 0 is
     the carried one).  -> (frames now in the region, error or None); sets st.exhausted when the capture ran dry."""
-    from .._lib import yuv420_views
     n = 1
     try:
         while n < len(region):
-            if st.planes:
-                y, cb, cr = yuv420_views(region[n][None], w0, h0)
-                ok = bool(st.capture.read_yuv420_into(y[0], cb[0], cr[0]))
-            else:
-                ok, frame = st.capture.read()
-                if ok:
-                    frame = np.asarray(frame, np.uint8)
-                    if frame.shape != region[n].shape:
-                        raise ValueError("frame %d has shape %s, the first frame %s" % (st.read + 1, frame.shape, region[n].shape))
-                    region[n][...] = frame
-            if not ok:
+            if not _read_frame(st.capture, st.planes, region[n], st.w0, st.h0, st.read + 1):
                 st.exhausted = True
                 break
             st.read += 1
@@ -337,13 +358,10 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
     A round in which a pair reports EVH_PAIR_CAPACITY is re-run as a whole on larger frame slots (rerun_on_larger_slots)."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
-    from .frame_processing import DEFAULT_FEATURES
+    from types import SimpleNamespace
     if ingest not in ("auto", "bgr", "yuv420"):
         raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
-    features = list(features_type_list or DEFAULT_FEATURES)
-    for name in features:
-        if name not in ("ORB", "SIFT", "SURF"):
-            raise ValueError("You need to choose descriptors type")
+    features = _feature_list(features_type_list)
     captures = list(captures)
     results = [None] * len(captures)
     max_streams, chunk_frames = max(1, int(max_streams)), max(2, int(chunk_frames))
@@ -372,14 +390,7 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
             if i > stop_after[0]:
                 continue
             try:
-                first, w0, h0 = _first_planes(capture, ingest)
-                planes = first is not None
-                if not planes:
-                    success, first = capture.read()
-                    if not success:
-                        raise ValueError("Problem with video! Can't read first frame")
-                    first = np.ascontiguousarray(first, np.uint8)
-                    h0, w0 = first.shape[:2]
+                first, planes, w0, h0 = _open_capture(capture, ingest)
             except Exception as e:
                 fail(i, e)
                 continue
@@ -393,16 +404,18 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
     dev = runtime.device()
     cuda = dev.type == "cuda"          # (the host-loop unit tests drive this function on the CPU with a scripted context)
     pool = ThreadPoolExecutor(max_workers=max(1, int(decode_threads)))
+    # what every group runs with: the call's options, and where its captures' results and failures go
+    opts = SimpleNamespace(resize_width=resize_width, none_H_processing=none_H_processing, nfeatures=nfeatures, features=features,
+                          chunk_frames=chunk_frames, max_streams=max_streams, pool=pool, dev=dev, fail=fail,
+                          stop_after=stop_after, results=results)
     try:
         while True:
             head = open_next(None)
             if head is None:
                 break
             key = head.key
-            planes, shape, w0, h0 = key
             more = len(pending) + len(deferred.get(key, ()))          # at most this many further members
-            _run_group(head, lambda: open_next(key), 1 + more, planes, shape, w0, h0, resize_width, none_H_processing, nfeatures,
-                       features, chunk_frames, max_streams, pool, dev, cuda, fail, stop_after, results)
+            _run_group(opts, head, lambda: open_next(key), 1 + more)
     finally:
         pool.shutdown(wait=True)
         if cuda:
@@ -412,23 +425,24 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
     return results
 
 
-def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, none_H_processing, nfeatures, features, chunk_frames, max_streams,
-               pool, dev, cuda, fail, stop_after, results):
-    """The captures of one geometry -- `head`, then whatever next_member() opens, at_most of them -- through rounds of
-    evh_streams_homography_batch (see get_homography_dicts)."""
+def _run_group(opts, head, next_member, at_most):
+    """The captures of one geometry (head.key) -- `head`, then whatever next_member() opens, at_most of them -- through rounds
+    of evh_streams_homography_batch (see get_homography_dicts).  opts: the call's options and result lists."""
     import torch
-    dw, dh = resized_shape((h0, w0), resize_width)
+    planes, shape, w0, h0 = head.key
+    nfeatures, features, chunk_frames, dev, stop_after = opts.nfeatures, opts.features, opts.chunk_frames, opts.dev, opts.stop_after
+    cuda = dev.type == "cuda"
+    dw, dh = resized_shape((h0, w0), opts.resize_width)
     # the staging buffer is capped in bytes: fewer live captures, then shorter chunks, for large frames
-    S = min(max_streams, at_most)
+    S = min(opts.max_streams, at_most)
     total = runtime.chunk_frames_for(int(np.prod(shape)), S * chunk_frames)
     S = max(1, min(S, total // 2))
     cf = max(2, min(chunk_frames, total // S))          # frames of one capture in a round, the carried one included
     total = S * cf
     ctx = runtime.get_context(dw, dh, total, nfeatures, sift="SIFT" in features, surf="SURF" in features)
     B = runtime.staging((total,) + tuple(shape), dev)
-    host, host_np, devbuf = B["host"], B["host_np"], B["dev"]
+    host_np, devbuf, all_done = B["host_np"], B["dev"], B["all_done"]
     H_dev, st_dev, H_host, st_host = B["H_dev"], B["st_dev"], B["H_host"], B["st_host"]
-    copy_stream, up_done, all_done = B["copy_stream"], B["up_done"], B["all_done"]
     cur = torch.cuda.current_stream(dev) if cuda else None
     state = torch.zeros(S, 18, dtype=torch.float64, device=dev)       # {H_sup, H_prev} of the capture reading in every place
     waiting = [head]                                                  # opened, not placed yet
@@ -437,10 +451,10 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
 
     def finish(st, exc=None):
         if exc is not None:
-            fail(st.index, exc)
+            opts.fail(st.index, exc)
         else:
             st.result["resize_info"] = {"h": dh, "w": dw}
-            results[st.index] = st.result
+            opts.results[st.index] = st.result
         st.done = True
 
     def start_reads(j):
@@ -462,7 +476,7 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
                 region[0], st.first = st.first, None
             else:
                 region[0] = host_np[1 - j][k * cf + st.last]
-            reads.append((k, st, pool.submit(_read_frames, st, region, w0, h0)))
+            reads.append((k, st, opts.pool.submit(_read_frames, st, region)))
         return reads
 
     def launch(c, j, table, state_in, state_out):
@@ -471,12 +485,7 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
         c.streams_homography_batch(devbuf[j][:nb], segs, H_dev[j], st_dev[j], features=features, state_in=state_in,
                                    state_out=state_out, nfeatures=nfeatures, resize_to=(dw, dh),
                                    size=(w0, h0) if planes else None)
-        if cuda:
-            c.order_torch_after()
-        H_host[j][:nb - 1].copy_(H_dev[j][:nb - 1], non_blocking=True)
-        st_host[j][:nb - 1].copy_(st_dev[j][:nb - 1], non_blocking=True)
-        if cuda:
-            all_done[j].record(cur)
+        _results_to_host(c, B, j, nb - 1, cur)
 
     def collect(j, table, idx, state_in, state_out):
         """The results of the round in flight: re-run on larger slots if a frame overflowed, the states back to their places,
@@ -492,14 +501,8 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
             if cuda:
                 torch.cuda.synchronize(dev)
 
-            def run(big):
-                launch(big, j, table, state_in, state_out)
-                if cuda:
-                    torch.cuda.synchronize(dev)
-                else:
-                    big.synchronize()
-
-            rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, total, run, overflowed,
+            rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, total,
+                                  lambda big: launch(big, j, table, state_in, state_out), overflowed,
                                   "captures %s" % [st.index for (_, st, _, _, _) in table])
         state[idx] = state_out
         Hs = H_host[j].numpy().reshape(-1, 3, 3)
@@ -507,17 +510,7 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
         for (k, st, a, n, last_round) in table:
             st.started = True
             try:
-                for r in range(a, a + n - 1):
-                    st.frame_no += 1
-                    fno = st.frame_no
-                    if sts[r] != PAIR_OK:
-                        logging.info("capture %d, pair ending at frame %d: no homography (status %d)", st.index, fno, int(sts[r]))
-                        if not none_H_processing or not np.all(np.isfinite(Hs[r])):
-                            # reference behaviour (video_processing.py:94-101): H stays None and None.tolist() raises --
-                            # always for none_H_processing=False, and for a failing FIRST pair otherwise
-                            raise AttributeError("'NoneType' object has no attribute 'tolist' (no homography for frame %d, "
-                                                 "status %d)" % (fno, int(sts[r])))
-                    st.result[fno] = {"H": Hs[r].tolist()}
+                st.frame_no = _pairs_into(st.result, st.frame_no, Hs[a:a + n - 1], sts[a:a + n - 1], opts.none_H_processing, st.index)
             except AttributeError as e:
                 finish(st, e)
                 if places[k] is st:
@@ -555,15 +548,7 @@ def _run_group(head, next_member, at_most, planes, shape, w0, h0, resize_width, 
                 table.append((k, st, pos, n, st.exhausted))
                 pos += n
         if table:
-            for (k, st, a, n, _) in table:              # the segments back to back on the device
-                if cuda:
-                    with torch.cuda.stream(copy_stream):
-                        devbuf[j][a:a + n].copy_(host[j][k * cf:k * cf + n], non_blocking=True)
-                else:
-                    devbuf[j][a:a + n].copy_(host[j][k * cf:k * cf + n])
-            if cuda:
-                up_done[j].record(copy_stream)
-                cur.wait_event(up_done[j])
+            _upload(B, j, [(a, k * cf, n) for (k, _, a, n, _) in table], cur)     # the segments back to back on the device
             idx = torch.tensor([k for (k, _, _, _, _) in table], dtype=torch.long, device=dev)
             state_in = state[idx]                       # as the round is entered: what a re-run starts from
             state_out = torch.zeros_like(state_in)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -262,6 +263,13 @@ inline int alloc_kp_list(evh_ctx* c, EvhKpList& L, const char* who, int max_feat
   EVH_HIP(c, hipMemsetAsync(L.flags, 0, F * sizeof(int), c->stream));
   L.cap = (int)cap; L.desc_row_bytes = desc_row_bytes;
   return EVH_SUCCESS;
+}
+// frames per group of a float detector: what fits the memory budget, at most what one launch takes (its grid bound), and at
+// most EVH_DETECT_GROUP=n where set (tests: several groups at small frames; read at enable time)
+inline int kp_group_size(size_t fits, int launch_limit) {
+  size_t group = std::max<size_t>(1, std::min<size_t>(fits, (size_t)launch_limit));
+  if (const char* e = getenv("EVH_DETECT_GROUP")) if (atoi(e) > 0) group = std::min<size_t>(group, (size_t)atoi(e));
+  return (int)group;
 }
 // grow-on-demand workspace: kernels already enqueued may still use the old one, so the stream drains before it is freed
 template <class T>

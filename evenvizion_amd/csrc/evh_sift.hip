@@ -784,7 +784,7 @@ int evh_sift_allocate(evh_ctx* c, int max_sift_features) {
   sift_geometry(c->max_w, c->max_h, gm);
   // frames whose scale space is resident at once: at most 8 GiB of pyramid
   const size_t per_frame = (size_t)(gm.frame_floats + gm.tmp_floats) * sizeof(float);
-  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->max_frames, ((size_t)8 << 30) / per_frame));
+  const int group = kp_group_size(std::min<size_t>((size_t)c->max_frames, ((size_t)8 << 30) / per_frame), 21845);
   const size_t F = (size_t)c->max_frames, cand_cap = 4 * (size_t)c->sift.cap;
   S_(dalloc(c, &c->d_sift_pyr, (size_t)group * gm.frame_floats + 64));
   S_(dalloc(c, &c->d_sift_tmp, (size_t)group * gm.tmp_floats + 64));

@@ -602,7 +602,7 @@ int evh_surf_allocate(evh_ctx* c, int max_surf_features) {
   const int sstride = (c->max_w + 1 + 15) & ~15;
   const int64_t sum_ints = (int64_t)sstride * (c->max_h + 1);
   const size_t per_frame = (size_t)(2 * det_floats + sum_ints) * 4;
-  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->max_frames, ((size_t)4 << 30) / per_frame));
+  const int group = kp_group_size(std::min<size_t>((size_t)c->max_frames, ((size_t)4 << 30) / per_frame), 3000);
   S_(dalloc(c, &c->d_surf_tabs, sizeof(SurfTabs)));
   S_(dalloc(c, &c->d_surf_sum, (size_t)group * sum_ints + 64));
   S_(dalloc(c, &c->d_surf_det, (size_t)group * det_floats + 64));

@@ -15,19 +15,7 @@ torch = pytest.importorskip("torch")
 
 from evenvizion_amd import synthetic as S  # noqa: E402
 from oracle import oracle as O  # noqa: E402
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def make_ctx(w, h, frames=4, sift=4096, feats=500):
-    from evenvizion_amd._lib import Context
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU; there is no CPU fallback")
-    c = Context(device=0, max_w=w, max_h=h, max_features=feats, max_frames=frames)
-    c.sift_enable(sift)
-    return c
+from detector_checks import _same_keypoints, _same_surf, dev, make_ctx, make_surf_ctx  # noqa: E402
 
 
 @pytest.mark.parametrize("w,h", [(400, 224), (333, 217)])
@@ -46,14 +34,6 @@ def test_sift_scale_space(w, h):
                         f, o, l, np.abs(got - want[o][l]).max())
     finally:
         c.close()
-
-
-def _same_keypoints(g, o):
-    assert len(g["xy"]) == len(o["xy"]), (len(g["xy"]), len(o["xy"]))
-    for k in ("xy", "size", "angle", "response"):
-        assert np.array_equal(g[k].view(np.uint32), o[k].view(np.uint32)), k
-    assert np.array_equal(g["octave"], o["octave"])
-    assert np.array_equal(g["desc"], o["desc"])
 
 
 @pytest.mark.parametrize("w,h,cap", [(400, 224, 4096), (333, 217, 4096), (1280, 720, 40960)])
@@ -354,22 +334,6 @@ def test_a_feature_type_named_twice_is_refused():
 
 
 # ---- SURF (frame_processing.py:65-67) ---------------------------------------------------------------------------------
-def make_surf_ctx(w, h, frames=4, surf=4096, sift=0):
-    from evenvizion_amd._lib import Context
-    c = Context(device=0, max_w=w, max_h=h, max_features=500, max_frames=frames)
-    c.surf_enable(surf)
-    if sift:
-        c.sift_enable(sift)
-    return c
-
-
-def _same_surf(g, o):
-    assert len(g["xy"]) == len(o["xy"]), (len(g["xy"]), len(o["xy"]))
-    for k in ("xy", "size", "angle", "response", "desc"):
-        assert np.array_equal(g[k].view(np.uint32), o[k].view(np.uint32)), k
-    assert np.array_equal(g["octave"], o["octave"]) and np.array_equal(g["laplacian"], o["laplacian"])
-
-
 @pytest.mark.parametrize("w,h,cap", [(400, 224, 4096), (333, 217, 4096), (1280, 720, 16384), (97, 131, 1024)])
 def test_surf_keypoints_and_descriptors(w, h, cap):
     """SURF_create(extended=1, hessianThreshold=400).detectAndCompute: the integral image, the key points in the operator's

@@ -20,6 +20,8 @@ ORDER_CANONICAL, ORDER_OPENCV = 0, 1
 SOLVER_EXACT, SOLVER_FAST = 0, 1
 MAX_FEATURES = 5984   # EVH_MAX_FEATURES (include/evhip.h): largest max_features a context accepts
 MODE_INDEPENDENT_PAIRS, MODE_STREAM = 0, 1
+WARP_EACH, WARP_HISTORY, WARP_MOSAIC = 0, 1, 2
+WARP_MODES = {"each": WARP_EACH, "history": WARP_HISTORY, "mosaic": WARP_MOSAIC}
 
 # every symbol include/evhip.h declares, with its ctypes signature
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -97,6 +99,9 @@ SIGNATURES = {
     "evh_orb_detect_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i]),
     "evh_stream_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_stream_homography_batch_types_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
+    # stabilised output: frames warped into the fixed plane
+    "evh_warp_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
+    "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -521,6 +526,57 @@ class Context:
             raise ValueError("out must be a CUDA uint8 tensor [n,h,w,3] with packed pixels")
         self._check(self.lib.evh_yuv420_to_bgr(self.h, C.byref(d), n, w, h, out.data_ptr(), out.stride(1) if h > 1 else 3 * w,
                                                out.stride(0)))
+
+    # ---- stabilised output ----
+    def _image_rows(self, t, cn, lead, what):
+        """A uint8 CUDA tensor or VIEW [*lead dims, h, w] (cn == 1) or [*lead dims, h, w, cn] with packed pixels; rows and
+        leading dimensions may be strided.  -> (pointer, w, h, row stride, stride of the first dimension)"""
+        import torch
+        if t.dtype != torch.uint8 or not t.is_cuda or t.device.index != self.device:
+            raise ValueError("%s must be a uint8 tensor on the context's device (cuda:%d)" % (what, self.device))
+        if t.dim() != lead + (2 if cn == 1 else 3) or (cn != 1 and t.shape[-1] != cn):
+            raise ValueError("%s must be [%sh, w%s]" % (what, "n, " * lead, "" if cn == 1 else ", %d" % cn))
+        h, w = t.shape[lead:lead + 2]
+        if (cn != 1 and t.stride(lead + 2) != 1) or (w > 1 and t.stride(lead + 1) != cn):
+            raise ValueError("%s must have packed pixels" % what)
+        return t.data_ptr(), int(w), int(h), (t.stride(lead) if h > 1 else w * cn), t.stride(0)
+
+    def warp_fixed_plane(self, frames, mats, out, mode, origin, background=None, inverse_map=False, size=None):
+        """Frames warped into the fixed plane (evh_warp_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h).
+        frames: CUDA uint8 [n,h,w] (gray) or [n,h,w,3] (BGR), rows and frames may be strided, or decoded planes (see _yuv420;
+        size=(w, h) for packed I420 frames; the canvas is then BGR).  mats: CUDA float64, n*9 contiguous elements, frame pixel
+        -> plane point (inverse_map=True: plane point -> frame pixel).  mode: "each" / "history" -> out [n,dh,dw(,3)],
+        "mosaic" -> out [dh,dw(,3)]; rows (and canvases) may be strided.  origin=(ox, oy): canvas pixel (x, y) is the plane
+        point (x + ox, y + oy).  background: [dh,dw(,3)] with out's row stride, or None = zeros; for "mosaic" it may be `out`
+        itself (a canvas carried from chunk to chunk).  Does not synchronise."""
+        import torch
+        self._enter()
+        mode = WARP_MODES[mode] if isinstance(mode, str) else int(mode)
+        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
+        if planes:
+            d, n, sw, sh = self._yuv420(frames, size, self.device)
+            cn = 3
+        else:
+            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
+            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
+            n = frames.shape[0]
+        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
+                or mats.numel() != 9 * n:
+            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        lead = 0 if mode == WARP_MOSAIC else 1
+        op, dw, dh, ors, ofs = self._image_rows(out, cn, lead, "out")
+        if lead and out.shape[0] != n:
+            raise ValueError("out must hold one canvas per frame")
+        bp = None
+        if background is not None:
+            bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
+            if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
+                raise ValueError("background must be [dh,dw(,3)] with out's row stride")
+        tail = (mats.data_ptr(), int(bool(inverse_map)), mode, bp, op, dw, dh, ors, ofs if lead else 0, int(origin[0]), int(origin[1]))
+        if planes:
+            self._check(self.lib.evh_warp_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
+        else:
+            self._check(self.lib.evh_warp_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

@@ -873,6 +873,54 @@ int evh_yuv420_to_bgr(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int
   return evh_launch_yuv420_to_bgr(c, *src, nframes, w, h, d_bgr, row_stride, frame_stride);
 }
 
+// ---- stabilised output: frames warped into the fixed plane (stabilization.py:129-172, 220-249) -------------------------------
+// the argument checks of both forms; every refusal comes before the launch
+static int warp_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
+                            int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh, int64_t out_stride,
+                            int64_t out_img_stride, int ox, int oy) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = std::string(who) + ": ";
+  const int cn = F.channels;
+  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
+  if (!d_M || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
+  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (mode != EVH_WARP_EACH && mode != EVH_WARP_HISTORY && mode != EVH_WARP_MOSAIC) return evh_fail(c, EVH_ERR_INVALID, W + "unknown mode");
+  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
+  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
+  if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  const bool many = mode != EVH_WARP_MOSAIC && nframes > 1;       // the canvases of out[0 .. nframes)
+  const int64_t canvas = (int64_t)(dh - 1) * out_stride + (int64_t)dw * cn;
+  if (out_stride < (int64_t)dw * cn || (many && out_img_stride < canvas))
+    return evh_fail(c, EVH_ERR_INVALID, W + "output stride smaller than a row / canvas");
+  if (!F.planes && (F.row_stride < (int64_t)sw * cn || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + (int64_t)sw * cn)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
+  if (d_bg && !(mode == EVH_WARP_MOSAIC && d_bg == d_out)) {      // only a mosaic may be carried in place
+    const int64_t out_bytes = canvas + (many ? (nframes - 1) * out_img_stride : 0);
+    if (d_bg < d_out + out_bytes && d_out < d_bg + canvas) return evh_fail(c, EVH_ERR_INVALID, W + "d_background overlaps d_out");
+  }
+  if (nframes == 0) return EVH_SUCCESS;
+  if (F.yuv)
+    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  return evh_launch_warp_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride,
+                                     out_img_stride, ox, oy);
+}
+
+int evh_warp_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                         int64_t frame_stride, const double* d_M, int inverse_map, int mode, const uint8_t* d_background,
+                         uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy) {
+  return warp_fixed_plane(c, "evh_warp_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
+                          d_M, inverse_map, mode, d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
+}
+
+int evh_warp_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy) {
+  return warp_fixed_plane(c, "evh_warp_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, mode,
+                          d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
+}
+
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);

@@ -385,6 +385,131 @@ __global__ __launch_bounds__(256) void k_transform_points(const double* __restri
   out[2 * i] = u; out[2 * i + 1] = v;
 }
 
+// Stabilised output (stabilization.py:129-172, 220-249): frames resampled through their superposed H onto a canvas of the
+// fixed plane; canvas pixel (x, y) is the plane point (x + ox, y + oy).  The arithmetic is the one include/evhip.h states
+// for evh_warp_fixed_plane, one IEEE float64 operation at a time (no fma: the tests restate it in numpy byte for byte).
+// A thread owns WARP_RUN adjacent canvas pixels of a row: the frame's matrix is formed once for them, and their bytes
+// leave as 32-bit words (`wide`: every pointer and stride involved is a multiple of 4; runs cut by the right edge go
+// bytewise).  Bytes past a row's dw pixels are neither read nor written.
+#define WARP_RUN 4
+struct WarpMap { double a[9]; };
+// canvas -> frame: M itself (inverse_map) or its adjugate -- not divided by the determinant, a projective map does not care
+__device__ __forceinline__ WarpMap warp_map(const double* __restrict__ M, int inverse_map) {
+  const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5], m6 = M[6], m7 = M[7], m8 = M[8];
+  if (inverse_map) return {{m0, m1, m2, m3, m4, m5, m6, m7, m8}};
+  return {{m4 * m8 - m5 * m7, m2 * m7 - m1 * m8, m1 * m5 - m2 * m4,
+           m5 * m6 - m3 * m8, m0 * m8 - m2 * m6, m2 * m3 - m0 * m5,
+           m3 * m7 - m4 * m6, m1 * m6 - m0 * m7, m0 * m4 - m1 * m3}};
+}
+// Frame `img` at plane point (X, Y): false = the frame does not cover it (v is left alone).  The source position comes in
+// 1/32 pixels (INTER_BITS = 5), rounded half to even; the comparisons are made in double, so NaN and +-inf (a zero, singular
+// or NaN matrix, the horizon) cover nothing.  A covered position has 0 <= sx <= sw - 1, and sx + 1 is read only with fx != 0,
+// i.e. sx <= sw - 2 (rows alike): no tap leaves the frame.
+template <class SRC>
+__device__ __forceinline__ bool warp_sample(const SRC& src, int img, const WarpMap& A, double X, double Y, int sw, int sh,
+                                            int (&v)[3]) {
+  const double tx = (A.a[0] * X + A.a[1] * Y) + A.a[2];
+  const double ty = (A.a[3] * X + A.a[4] * Y) + A.a[5];
+  const double tw = (A.a[6] * X + A.a[7] * Y) + A.a[8];
+  const double U = __builtin_rint(tx / tw * 32.0), V = __builtin_rint(ty / tw * 32.0);
+  if (!(U >= 0.0 && U <= (double)(32 * (sw - 1)) && V >= 0.0 && V <= (double)(32 * (sh - 1)))) return false;
+  const int u = (int)U, w = (int)V;
+  const int sx = u >> 5, fx = u & 31, sy = w >> 5, fy = w & 31;
+  const int cn = src.channels();
+  int p00[3] = {0, 0, 0}, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
+  const typename SRC::Row r0 = src.row(img, sy);
+  r0.px(sx, p00);
+  if (fx) r0.px(sx + 1, p01);
+  if (fy) {
+    const typename SRC::Row r1 = src.row(img, sy + 1);
+    r1.px(sx, p10);
+    if (fx) r1.px(sx + 1, p11);
+  }
+  const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+#pragma unroll
+  for (int c = 0; c < 3; c++) if (c < cn) v[c] = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + 512) >> 10;
+  return true;
+}
+// the n <= WARP_RUN pixels of a run, CN bytes each, from / to canvas rows
+template <int CN>
+__device__ __forceinline__ void warp_run_load(const uint8_t* S, int n, bool wide, int (&v)[WARP_RUN][3]) {
+  if (wide) {
+    uint32_t q[CN];
+#pragma unroll
+    for (int k = 0; k < CN; k++) q[k] = reinterpret_cast<const uint32_t*>(S)[k];
+#pragma unroll
+    for (int k = 0; k < WARP_RUN * CN; k++) v[k / CN][k % CN] = (q[k >> 2] >> (8 * (k & 3))) & 255;
+  } else {
+#pragma unroll
+    for (int k = 0; k < WARP_RUN * CN; k++) if (k < n * CN) v[k / CN][k % CN] = S[k];
+  }
+}
+template <int CN>
+__device__ __forceinline__ void warp_run_store(uint8_t* D, int n, bool wide, const int (&v)[WARP_RUN][3]) {
+  if (wide) {
+    uint32_t q[CN];
+#pragma unroll
+    for (int k = 0; k < CN; k++) q[k] = 0;
+#pragma unroll
+    for (int k = 0; k < WARP_RUN * CN; k++) q[k >> 2] |= (uint32_t)v[k / CN][k % CN] << (8 * (k & 3));
+#pragma unroll
+    for (int k = 0; k < CN; k++) reinterpret_cast<uint32_t*>(D)[k] = q[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < WARP_RUN * CN; k++) if (k < n * CN) D[k] = (uint8_t)v[k / CN][k % CN];
+  }
+}
+// MODE EVH_WARP_EACH: grid.y = frame, out[k] = frame k over the background.  EVH_WARP_HISTORY: the frames upward with the
+// run in registers, out[k] stored at every step (the last covering frame wins).  EVH_WARP_MOSAIC: the frames downward, a
+// pixel is settled by the first frame that covers it; bg may BE out (a thread reads only the bytes it writes, before it
+// writes them), hence no __restrict__ on either.
+template <int MODE, int CN, class SRC>
+__global__ __launch_bounds__(256) void k_warp_fixed_plane(SRC src, int nframes, int sw, int sh, const double* __restrict__ M,
+                                                          int inverse_map, const uint8_t* bg, uint8_t* out, int dw,
+                                                          int64_t out_stride, int64_t out_img_stride, int ox, int oy,
+                                                          int runs_per_row, unsigned nruns, int vec) {
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nruns) return;
+  const int y = (int)(t / (unsigned)runs_per_row), x0 = ((int)t - y * runs_per_row) * WARP_RUN;
+  const int n = min(WARP_RUN, dw - x0);
+  const bool wide = vec != 0 && n == WARP_RUN;
+  const int64_t at = (int64_t)y * out_stride + (int64_t)x0 * CN;
+  const double Y = (double)((int64_t)y + oy);
+  double X[WARP_RUN];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) X[p] = (double)((int64_t)x0 + p + ox);
+  int v[WARP_RUN][3];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) v[p][0] = v[p][1] = v[p][2] = 0;
+  if constexpr (MODE == EVH_WARP_HISTORY) {
+    if (bg) warp_run_load<CN>(bg + at, n, wide, v);
+    for (int k = 0; k < nframes; k++) {
+      const WarpMap A = warp_map(M + 9 * (int64_t)k, inverse_map);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) if (p < n) warp_sample(src, k, A, X[p], Y, sw, sh, v[p]);
+      warp_run_store<CN>(out + (int64_t)k * out_img_stride + at, n, wide, v);
+    }
+  } else {
+    unsigned open = (1u << n) - 1;                      // pixels of the run no frame has covered yet
+    const int first = MODE == EVH_WARP_EACH ? (int)blockIdx.y : nframes - 1, last = MODE == EVH_WARP_EACH ? first : 0;
+    for (int k = first; k >= last && open; k--) {
+      const WarpMap A = warp_map(M + 9 * (int64_t)k, inverse_map);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++)
+        if (((open >> p) & 1) && warp_sample(src, k, A, X[p], Y, sw, sh, v[p])) open &= ~(1u << p);
+    }
+    if (open && bg) {
+      int b[WARP_RUN][3];
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) b[p][0] = b[p][1] = b[p][2] = 0;
+      warp_run_load<CN>(bg + at, n, wide, b);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) if ((open >> p) & 1) { v[p][0] = b[p][0]; v[p][1] = b[p][1]; v[p][2] = b[p][2]; }
+    }
+    warp_run_store<CN>(out + (MODE == EVH_WARP_EACH ? (int64_t)blockIdx.y * out_img_stride : 0) + at, n, wide, v);
+  }
+}
+
 struct HostTab { std::vector<int> start, cnt, si; std::vector<float> al; };
 
 void build_area_tab(int ssize, int dsize, double scale, HostTab& t) {
@@ -523,6 +648,40 @@ int evh_launch_ingest_level0(evh_ctx* c, const EvhFrames& src, int nimg, int sw,
     return launch_yuv420_rows<true>(c, *src.yuv, nimg, dw, dh, c->d_pyr + L.off, L.stride, c->g.pyr_frame_bytes);
   }
   return launch_ingest(c, yuv420_src(*src.yuv), nimg, sw, sh, dw, dh);
+}
+
+// k_warp_fixed_plane over the canvas (the entry has checked dw * dh <= INT_MAX, so the runs fit an unsigned)
+template <int CN, class SRC>
+static int launch_warp(evh_ctx* c, const SRC& src, int nframes, int sw, int sh, const double* d_M, int inverse_map, int mode,
+                       const uint8_t* bg, uint8_t* out, int dw, int dh, int64_t out_stride, int64_t out_img_stride, int ox,
+                       int oy) {
+  const int runs_per_row = (dw + WARP_RUN - 1) / WARP_RUN;
+  const unsigned nruns = (unsigned)runs_per_row * (unsigned)dh;
+  // the image stride is only used between the canvases of EACH / HISTORY
+  const uintptr_t ois = (mode != EVH_WARP_MOSAIC && nframes > 1) ? (uintptr_t)out_img_stride : 0;
+  const int vec = (((uintptr_t)out | (uintptr_t)bg | (uintptr_t)out_stride | ois) & 3) == 0;
+  const dim3 grid((nruns + 255) / 256, mode == EVH_WARP_EACH ? nframes : 1);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, src, nframes, sw, sh, d_M, inverse_map, bg, out, dw, out_stride,
+                       out_img_stride, ox, oy, runs_per_row, nruns, vec);
+  };
+  if (mode == EVH_WARP_EACH) go(k_warp_fixed_plane<EVH_WARP_EACH, CN, SRC>);
+  else if (mode == EVH_WARP_HISTORY) go(k_warp_fixed_plane<EVH_WARP_HISTORY, CN, SRC>);
+  else go(k_warp_fixed_plane<EVH_WARP_MOSAIC, CN, SRC>);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh,
+                                int64_t out_stride, int64_t out_img_stride, int ox, int oy) {
+  if (src.yuv)
+    return launch_warp<3>(c, yuv420_src(*src.yuv), nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride,
+                          out_img_stride, ox, oy);
+  const PackedSrc P{src.packed, src.channels, src.row_stride, src.frame_stride};
+  if (src.channels == 3)
+    return launch_warp<3>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
+  return launch_warp<1>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
 }
 
 int evh_launch_superposition_scan(evh_ctx* c, const double* d_H, int n, double* d_out) {

@@ -309,6 +309,9 @@ int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int
 int evh_launch_ingest_level0(evh_ctx* c, const EvhFrames& src, int nimg, int sw, int sh, int dw, int dh);
 int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w, int h, uint8_t* d_dst, int64_t dst_stride,
                              int64_t dst_img_stride);
+int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh,
+                                int64_t out_stride, int64_t out_img_stride, int ox, int oy);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);

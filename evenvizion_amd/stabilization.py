@@ -1,0 +1,198 @@
+"""Stabilised view -- the geometry of evenvizion/visualization/stabilization.py:100-290 with the frames kept on the device.
+
+The reference shows a frame "in the fixed coordinate system" by pasting the resized frame at int(H_sup . (0, 0, 1)) onto a
+canvas that accumulates the frames (stabilize_view, :129-172), i.e. it only translates.  Here a frame is placed by
+evh_warp_fixed_plane (include/evhip.h), either way:
+
+    placement="translate"   the reference's paste, byte for byte: the frame resized on the device (evh_resize_area_u8), the
+                            reference's canvas (get_reference_system / initialize_background, :100-126, :241-249);
+    placement="warp"        the projective warp of the full-size frame through diag(s,s,1) . H_sup . diag(kx,ky,1).
+
+Drawing -- the white frame border, the text, the HSV dimming of earlier frames, the side-by-side picture and its PNG -- is
+not done here: stabilized_frames yields the canvases as arrays.
+"""
+import math
+
+import numpy as np
+
+from . import runtime
+from ._lib import WARP_MODES, WARP_MOSAIC
+
+MAX_PIXELS = 1 << 26          # canvas pixels fixed_plane_bounds accepts by default (201 MB of BGR)
+CHUNK_BYTES = 512 << 20       # cap of the canvases of one "each" / "history" chunk on the device
+
+
+def _frames_of(superposition_homography_dict):
+    return [k for k in superposition_homography_dict if k != "resize_info"]
+
+
+def _matrix(H):
+    """A frame's matrix as f64[3,3], or None when it has none or it is not finite."""
+    if H is None:
+        return None
+    m = np.asarray(H, np.float64)
+    return m.reshape(3, 3) if m.size == 9 and np.all(np.isfinite(m)) else None
+
+
+def get_reference_system(superposition_homography_dict):
+    """{"max_x", "min_x", "max_y", "min_y"} of the frames' upper left corners in the fixed plane, truncated with int() as the
+    reference does (stabilization.py:100-126)."""
+    x_corner, y_corner = [], []
+    for k in _frames_of(superposition_homography_dict):
+        v = np.dot(np.asarray(superposition_homography_dict[k], np.float64), [0, 0, 1])
+        v = v[:-1] / v[-1]
+        x_corner.append(v[0])
+        y_corner.append(v[1])
+    return {"max_x": int(np.max(x_corner)), "min_x": int(np.min(x_corner)),
+            "max_y": int(np.max(y_corner)), "min_y": int(np.min(y_corner))}
+
+
+def panorama_shape(corner_dict, frame_shape):
+    """[h, w] of the reference's canvas for resized frames of frame_shape = (h, w, ...) (stabilization.py:241-244)."""
+    return [int(np.abs(corner_dict["min_y"]) + corner_dict["max_y"] + frame_shape[0] + 10),
+            int(np.abs(corner_dict["min_x"]) + corner_dict["max_x"] + frame_shape[1] + 10)]
+
+
+def translate_offset(H):
+    """(x_offset, y_offset) of stabilize_view (stabilization.py:159-161): int() of H . (0, 0, 1) after the division."""
+    v = np.dot(np.asarray(H, np.float64), [0, 0, 1])
+    return int(v[0] / v[2]), int(v[1] / v[2])
+
+
+def fixed_plane_bounds(superposition_homography_dict, resize_info, scale=1.0, max_pixels=MAX_PIXELS):
+    """(ox, oy, dw, dh) of the canvas that holds every warped frame: floor and ceiling of the four corners (0, 0), (w, 0),
+    (0, h), (w, h) of the resized frame, times `scale`, under every finite matrix of the dictionary; canvas pixel (x, y) is
+    the plane point (x + ox, y + oy).  ValueError when no matrix is finite, a corner lies on or behind a frame's horizon,
+    or dw * dh exceeds max_pixels."""
+    w, h = float(resize_info["w"]), float(resize_info["h"])
+    corners = np.array([[0, 0, 1], [w, 0, 1], [0, h, 1], [w, h, 1]], np.float64).T
+    lo, hi = np.array([np.inf, np.inf]), np.array([-np.inf, -np.inf])
+    for k in _frames_of(superposition_homography_dict):
+        m = _matrix(superposition_homography_dict[k])
+        if m is None:
+            continue
+        with np.errstate(all="ignore"):
+            p = np.dot(m, corners)
+            if not (np.all(p[2] > 0) or np.all(p[2] < 0)):
+                raise ValueError("frame %s: the horizon of its matrix crosses the frame, its picture in the plane is unbounded" % k)
+            xy = p[:2] / p[2] * float(scale)
+        lo, hi = np.minimum(lo, xy.min(axis=1)), np.maximum(hi, xy.max(axis=1))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("no frame with a finite matrix: the fixed plane has no extent")
+    ox, oy = int(math.floor(lo[0])), int(math.floor(lo[1]))
+    dw, dh = int(math.ceil(hi[0])) - ox + 1, int(math.ceil(hi[1])) - oy + 1
+    if dw * dh > int(max_pixels):
+        raise ValueError("the fixed plane is %d x %d pixels, more than max_pixels = %d" % (dw, dh, int(max_pixels)))
+    return ox, oy, dw, dh
+
+
+def _placement(superposition_homography_dict, resize_info, placement, scale, frame_w, frame_h, max_pixels):
+    """-> (ox, oy, dw, dh, matrix_of(frame_no) -> f64[9], NaN for a frame that leaves the canvas alone)"""
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    nan = np.full(9, np.nan)
+    if placement == "translate":
+        if float(scale) != 1.0:
+            raise ValueError("placement='translate' is the reference's paste: scale must be 1")
+        corner = get_reference_system(superposition_homography_dict)
+        dh, dw = panorama_shape(corner, (h, w))
+        ox, oy = -int(np.abs(corner["min_x"])), -int(np.abs(corner["min_y"]))
+
+        def matrix_of(frame_no):
+            m = _matrix(superposition_homography_dict.get(frame_no))
+            if m is None or m[2][2] == 0:
+                return nan
+            dx, dy = translate_offset(m)
+            return np.array([1, 0, dx, 0, 1, dy, 0, 0, 1], np.float64)
+    elif placement == "warp":
+        ox, oy, dw, dh = fixed_plane_bounds(superposition_homography_dict, resize_info, scale, max_pixels)
+        S = np.diag([float(scale), float(scale), 1.0])
+        K = np.diag([w / frame_w, h / frame_h, 1.0])          # from_original_to_fix: original pixels -> resized pixels
+
+        def matrix_of(frame_no):
+            m = _matrix(superposition_homography_dict.get(frame_no))
+            return nan if m is None else np.dot(np.dot(S, m), K).reshape(9)
+    else:
+        raise ValueError("placement must be 'warp' or 'translate'")
+    if dw * dh > int(max_pixels):
+        raise ValueError("the canvas is %d x %d pixels, more than max_pixels = %d" % (dw, dh, int(max_pixels)))
+    return ox, oy, dw, dh, matrix_of
+
+
+def stabilized_frames(capture, superposition_homography_dict, resize_info, mode="history", placement="warp", scale=1.0,
+                      chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS):
+    """Generator of (frame_no, uint8 ndarray [dh,dw,3]): the frames of `capture` (frame_no counts from 1, as the
+    dictionary's keys do) placed in the fixed plane on the device.
+
+    mode "history": per frame, the canvas after this frame -- the picture create_video_comparison shows (without its
+    drawing); "each": per frame, this frame alone on black; "mosaic": yields once, the last frame_no and the canvas of all
+    frames.  placement, scale: see the module text and fixed_plane_bounds.  Frames are read and uploaded chunk_frames at a
+    time (as 4:2:0 planes where ingest allows, see video_processing.get_homography_dict) and the canvas stays on the device
+    between chunks.  A frame whose matrix is missing, None or not finite leaves the canvas as it was."""
+    import torch
+    from .processing.video_processing import _open_capture, _read_frame
+    if mode not in WARP_MODES:
+        raise ValueError("mode must be 'each', 'history' or 'mosaic'")
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    first, planes, w0, h0 = _open_capture(capture, ingest)
+    ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
+    dev = runtime.device()
+    per_frame = WARP_MODES[mode] != WARP_MOSAIC
+    chunk = max(1, int(chunk_frames))
+    if per_frame:
+        chunk = max(1, min(chunk, CHUNK_BYTES // (dw * dh * 3)))
+    host = np.empty((chunk,) + first.shape, np.uint8)
+    canvas = torch.zeros((dh, dw, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty((chunk, dh, dw, 3), dtype=torch.uint8, device=dev) if per_frame else None
+    resize = placement == "translate" and (w, h) != (w0, h0)
+    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and resize else None
+    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    host[0] = first
+    n, frame_no, exhausted = 1, 0, False
+    while n:
+        while n < chunk and not exhausted:
+            if _read_frame(capture, planes, host[n], w0, h0, frame_no + n + 1):
+                n += 1
+            else:
+                exhausted = True
+        src = torch.from_numpy(host[:n]).to(dev)
+        mats = torch.from_numpy(np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])).to(dev)
+        size = (w0, h0) if planes else None
+        if resize:
+            if planes:
+                ctx.yuv420_to_bgr(src, bgr[:n], size=size)
+                src = bgr[:n]
+            ctx.resize_area(src, small[:n])
+            src, size = small[:n], None
+        if per_frame:
+            ctx.warp_fixed_plane(src, mats, out[:n], mode, (ox, oy), background=canvas if mode == "history" else None, size=size)
+            ctx.order_torch_after()
+            if mode == "history":
+                canvas.copy_(out[n - 1])
+            pictures = out[:n].cpu().numpy()
+            for k in range(n):
+                yield frame_no + 1 + k, pictures[k]
+        else:
+            ctx.warp_fixed_plane(src, mats, canvas, mode, (ox, oy), background=canvas, size=size)
+            ctx.order_torch_after()
+        frame_no += n
+        n = 0
+        if not exhausted and _read_frame(capture, planes, host[0], w0, h0, frame_no + 1):
+            n = 1
+        else:
+            exhausted = True
+    if not per_frame:
+        yield frame_no, canvas.cpu().numpy()
+
+
+def write_ppm(path, image):
+    """image u8[h,w,3] in BGR order (as the frames are) -> a binary P6 file (RGB, maxval 255)."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("write_ppm takes a uint8 [h, w, 3] image")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (image.shape[1], image.shape[0]))
+        f.write(np.ascontiguousarray(image[:, :, ::-1]).tobytes())
+

@@ -21,6 +21,8 @@
  *   evh_*_homography_batch_types  concatenate_all_features_types over a type list   frame_processing.py:91-104
  *   evh_yuv420_to_bgr             the yuv420p -> bgr24 conversion inside cv2.VideoCapture.read()   video_processing.py:58,70
  *   evh_*_yuv420                  capture.read() + imutils.resize + the entry of the same name without the suffix
+ *   evh_warp_fixed_plane[_yuv420] stabilize_view / initialize_background: a frame placed on the fixed plane
+ *                                 visualization/stabilization.py:129-172, 220-249
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -415,6 +417,49 @@ int evh_stream_homography_batch_types_yuv420(evh_ctx* ctx, const evh_yuv420* src
                                              int ransac_max_iters, double ransac_conf, int force_max_iters,
                                              const double* d_state_in, double* d_state_out, double* d_H, int32_t* d_status);
 
+/* ---- stabilised output: frames warped into the fixed plane (stabilization.py:129-172, 220-249) ---------------------------- */
+/* What stabilize_view / initialize_background do with a frame and its superposed H -- place it on a canvas of the fixed
+ * coordinate system that accumulates the frames -- for nframes frames of sw x sh and their matrices d_M f64[nframes,9] (DEVICE;
+ * M maps frame pixels to plane points, as the superposed H does; inverse_map != 0: M maps plane points to frame pixels and is
+ * used as it is).  The canvas is dw x dh pixels of the source's channels (the plane form: BGR); canvas pixel (x, y) is the plane
+ * point (x + ox, y + oy).  The reference only pastes the frame at int(H.(0,0,1)) (a pure translation: hand in that M, it is
+ * reproduced byte for byte); a general M gives the projective warp.
+ * Arithmetic, all IEEE float64 with one rounding per operation (no fma):
+ *   A = M if inverse_map, else the adjugate of M, each entry one difference of two products (a0 = m4*m8 - m5*m7,
+ *   a1 = m2*m7 - m1*m8, a2 = m1*m5 - m2*m4, a3 = m5*m6 - m3*m8, a4 = m0*m8 - m2*m6, a5 = m2*m3 - m0*m5, a6 = m3*m7 - m4*m6,
+ *   a7 = m1*m6 - m0*m7, a8 = m0*m4 - m1*m3), not divided by the determinant;
+ *   X = (double)(x + ox), Y = (double)(y + oy), the sums formed in int64;
+ *   tx = (a0*X + a1*Y) + a2, ty = (a3*X + a4*Y) + a5, tw = (a6*X + a7*Y) + a8;
+ *   U = rint(tx / tw * 32), V = rint(ty / tw * 32), halves to even: the source position in 1/32 pixels.
+ * Frame k COVERS the pixel iff 0 <= U <= 32*(sw-1) and 0 <= V <= 32*(sh-1), compared in double: a zero, singular, NaN or huge
+ * matrix (the stream entries hand out NaN for a failed first pair) and pixels on or beyond the horizon cover nothing and read
+ * nothing.  A covered pixel takes, per channel, with sx = U >> 5, fx = U & 31, sy = V >> 5, fy = V & 31,
+ *   (p00*(32-fx)*(32-fy) + p01*fx*(32-fy) + p10*(32-fx)*fy + p11*fx*fy + 512) >> 10
+ * where a tap of weight 0 is not read (the only way sx + 1 == sw or sy + 1 == sh occurs).  So identity copies the frame and an
+ * integer translation is an exact paste.  The five fraction bits are OpenCV's INTER_BITS, but this is NOT
+ * cv2.warpPerspective to the byte: that fades the edge taps into its constant border and sums its coordinates block-wise.
+ * mode, frames taken in order:
+ *   EVH_WARP_EACH     out[k] = frame k over the background;
+ *   EVH_WARP_HISTORY  out[k] = frames 0..k over the background, the last covering frame wins (the picture
+ *                     create_video_comparison shows for frame k);
+ *   EVH_WARP_MOSAIC   one canvas at d_out = all frames over the background (out_frame_stride unused); d_background == d_out
+ *                     is allowed in this mode only, so that a canvas is carried from chunk to chunk.
+ * d_background: dh rows of dw*channels bytes at out_row_stride, or NULL = zeros.  Every byte of every output row inside
+ * dw*channels is written, bytes between rows are not.  Only caller buffers are used: nothing depends on the sizes given to
+ * evh_create.  Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: a NULL pointer, channels not 1 or 3,
+ * sw, sh, dw or dh < 1, a stride shorter than its row / frame, an unknown mode, d_background overlapping d_out (except as
+ * above); EVH_ERR_CAPACITY: sw or sh >= 2^26, dw*dh > INT_MAX, nframes > 65535.  nframes == 0 succeeds and does nothing.
+ * The plane form converts every tap as evh_yuv420_to_bgr does and then interpolates: it equals evh_yuv420_to_bgr followed by
+ * the BGR form.  Speed, not results, depends on alignment: d_out, d_background and the output strides multiples of 4 let a
+ * thread store its four pixels as words.  Neither entry synchronises.                                                       */
+enum { EVH_WARP_EACH = 0, EVH_WARP_HISTORY = 1, EVH_WARP_MOSAIC = 2 };
+int evh_warp_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                         int64_t row_stride, int64_t frame_stride, const double* d_M, int inverse_map, int mode,
+                         const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride,
+                         int64_t out_frame_stride, int ox, int oy);
+int evh_warp_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

@@ -1,0 +1,325 @@
+"""evh_warp_fixed_plane / evh_warp_fixed_plane_yuv420 on the device.  Every assertion is equality of bytes with the numpy
+restatement of the header's arithmetic (tests/warp_checks.py, itself checked against plain pastes in test_warp_host.py)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import warp_checks as W
+
+pytestmark = pytest.mark.gpu
+SENTINEL = 0xCD
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from evenvizion_amd._lib import Context
+    c = Context(device=0, max_w=64, max_h=64, max_features=500, max_frames=2)     # the entry does not depend on these sizes
+    yield c
+    c.close()
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def run(ctx, frames, mats, mode, dw, dh, origin=(0, 0), background=None, inverse_map=False, src_pad=0, out_pad=0, out_skip=0):
+    """frames u8[n,sh,sw(,c)] through Context.warp_fixed_plane -> the canvases as numpy.  src_pad / out_pad: extra pixels per
+    source / output row (views of wider tensors, the padding holds SENTINEL and must survive); out_skip: the output view
+    starts that many pixels into its rows (an unaligned base)."""
+    import torch
+    frames = np.asarray(frames)
+    n, sh, sw = frames.shape[:3]
+    tail = frames.shape[3:]
+    src = torch.full((n, sh + 1, sw + src_pad) + tail, SENTINEL, dtype=torch.uint8, device="cuda")
+    src[:, :sh, :sw] = dev(frames)
+    lead = () if mode == "mosaic" else (n,)
+    inside = (slice(None),) * len(lead) + (slice(0, dh), slice(out_skip, out_skip + dw))
+    full = torch.full(lead + (dh + 1, out_skip + dw + out_pad) + tail, SENTINEL, dtype=torch.uint8, device="cuda")
+    bg = None
+    if background is not None:
+        bgfull = torch.full((dh + 1, out_skip + dw + out_pad) + tail, SENTINEL, dtype=torch.uint8, device="cuda")
+        bg = bgfull[:dh, out_skip:out_skip + dw]
+        bg.copy_(dev(np.asarray(background, np.uint8).reshape((dh, dw) + tail)))
+    ctx.warp_fixed_plane(src[:, :sh, :sw], dev(np.asarray(mats, np.float64).reshape(n, 9)), full[inside], mode, origin,
+                         background=bg, inverse_map=inverse_map)
+    ctx.synchronize()
+    got = full.cpu().numpy()
+    gaps = np.ones(got.shape, bool)
+    gaps[inside] = False
+    assert (got[gaps] == SENTINEL).all(), "bytes outside the canvas rows were written"
+    return got[inside]
+
+
+def check(ctx, frames, mats, mode, dw, dh, origin=(0, 0), background=None, inverse_map=False, **kw):
+    want = W.warp_canvases(frames, mats, mode, dw, dh, origin, background, inverse_map)
+    got = run(ctx, frames, mats, mode, dw, dh, origin, background, inverse_map, **kw)
+    print("%s %dx%d origin %s: differing bytes %d of %d" % (mode, dw, dh, origin, (got != want).sum(), want.size))
+    assert np.array_equal(got, want)
+    return got
+
+
+def frames_of(seed, n, w, h, gray=False):
+    return np.random.default_rng(seed).integers(0, 256, (n, h, w) if gray else (n, h, w, 3), dtype=np.uint8)
+
+
+def rot_zoom_persp(deg, zoom, tx, ty, px, py):
+    c, s = zoom * np.cos(np.deg2rad(deg)), zoom * np.sin(np.deg2rad(deg))
+    return np.array([[c, -s, tx], [s, c, ty], [px, py, 1.0]], np.float64)
+
+
+# ---- identity and integer translation ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("gray", [False, True])
+@pytest.mark.parametrize("pads", [(0, 0, 0), (3, 1, 0), (1, 2, 0), (0, 1, 1)])   # (source, output, skipped) pixels per row
+def test_identity_and_integer_translation(ctx, gray, pads):
+    f = frames_of(21, 1, 23, 17, gray)
+    kw = dict(src_pad=pads[0], out_pad=pads[1], out_skip=pads[2])
+    got = check(ctx, f, [np.eye(3)], "each", 23, 17, **kw)
+    assert np.array_equal(got[0], f[0])                                 # identity copies the frame byte for byte
+    for origin in ((-6, -4), (5, 3), (0, 0)):
+        for mode in ("each", "mosaic"):
+            got = check(ctx, f, [W.translation(4, -2)], mode, 31, 22, origin, **kw)
+            got = got[0] if mode == "each" else got
+            want = np.zeros_like(got)
+            x, y = 4 - origin[0], -2 - origin[1]                        # an exact paste, clipped by the canvas
+            x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + 23, 31), min(y + 17, 22)
+            want[y0:y1, x0:x1] = f[0][y0 - y:y1 - y, x0 - x:x1 - x]
+            assert np.array_equal(got, want)
+
+
+# ---- projective H ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("gray", [False, True])
+@pytest.mark.parametrize("inverse_map", [False, True])
+@pytest.mark.parametrize("fill", [0, 255])
+def test_projective(ctx, gray, inverse_map, fill):
+    f = frames_of(22, 1, 37, 29, gray)
+    H = rot_zoom_persp(17.0, 1.3, 3.5, -2.25, 1e-3, -2e-3)
+    if inverse_map:
+        H = rot_zoom_persp(-11.0, 0.8, 14.0, 9.5, -8e-4, 1.5e-3)
+    bg = np.full((48, 64) + f.shape[3:], fill, np.uint8)
+    cov = W.warp_frame(f[0], H, 64, 48, (-20, -10), inverse_map)[1]
+    assert 200 < cov.sum() < 64 * 48 - 200                              # the frame's outline crosses the canvas
+    check(ctx, f, [H], "each", 64, 48, (-20, -10), bg, inverse_map)
+    check(ctx, f, [H], "mosaic", 64, 48, (-20, -10), bg, inverse_map, out_pad=1)
+
+
+# ---- matrices that cover nothing and must not fault ------------------------------------------------------------------------------
+NOTHING = {
+    # tw = 0.05 X - 1 changes sign at X = 20 inside the canvas; tx = 1e6 keeps both sides outside the frame
+    "horizon": (np.array([[0, 0, 1e6], [0, 1, 0], [0.05, 0, -1]], np.float64), True),
+    "zero": (np.zeros((3, 3)), False),
+    "zero_inverse": (np.zeros((3, 3)), True),
+    "singular_rank1": (np.outer([1.0, 2.0, 0.5], [3.0, -1.0, 2.0]), False),
+    "singular_rank2": (np.array([[1, 2, 3], [2, 4, 6], [1, 1, 1]], np.float64), False),      # every point -> (1, -2)
+    "nan": (np.full((3, 3), np.nan), False),
+    "nan_inverse": (np.full((3, 3), np.nan), True),
+    "one_nan": (np.array([[1, 0, 0], [0, 1, 0], [0, 0, np.nan]]), False),
+    "huge": (1e300 * np.array([[1, 0.5, 2], [0.25, 1, 3], [0.125, 0.0625, 1]]), False),
+    "tiny": (1e-300 * np.array([[1, 0.5, 2], [0.25, 1, 3], [0.125, 0.0625, 1]]), False),
+    "inf": (np.array([[np.inf, 0, 0], [0, 1, 0], [0, 0, 1]]), True),
+}
+
+
+@pytest.mark.parametrize("name", sorted(NOTHING))
+def test_nothing_covered_nothing_faulted(ctx, name):
+    M, inverse_map = NOTHING[name]
+    f = frames_of(23, 2, 37, 29)
+    with np.errstate(all="ignore"):
+        cov = W.warp_frame(f[0], M, 64, 48, (-20, -10), inverse_map)[1]
+        if name == "horizon":
+            tw = 0.05 * (np.arange(64) - 20.0) - 1
+            assert (tw < 0).any() and (tw > 0).any() and (tw == 0).any()
+    assert not cov.any()
+    bg = frames_of(24, 1, 64, 48)[0]
+    for mode in ("each", "history", "mosaic"):
+        got = check(ctx, f, [M, M], mode, 64, 48, (-20, -10), bg, inverse_map)
+        assert np.array_equal(got, np.broadcast_to(bg, got.shape))
+    # a good frame between two bad ones is not disturbed
+    check(ctx, frames_of(25, 3, 37, 29), [M, np.eye(3), M], "history", 64, 48, (-20, -10), bg, inverse_map)
+
+
+# ---- the smallest sizes and the frame edge ---------------------------------------------------------------------------------------
+def test_one_by_one(ctx):
+    f = frames_of(26, 1, 1, 1)
+    assert np.array_equal(check(ctx, f, [np.eye(3)], "each", 1, 1)[0], f[0])
+    check(ctx, f, [np.eye(3)], "mosaic", 1, 1, (1, 0), np.full((1, 1, 3), 9, np.uint8))       # the plane point (1, 0): not covered
+    check(ctx, f, [W.translation(2, 1)], "each", 5, 3)
+    check(ctx, frames_of(27, 1, 37, 29), [rot_zoom_persp(5, 1.1, 0, 0, 0, 0)], "each", 1, 1, (12, 9))
+    g = frames_of(28, 1, 1, 1, gray=True)
+    assert check(ctx, g, [np.eye(3)], "history", 1, 1)[0, 0, 0] == g[0, 0, 0]
+
+
+def test_frame_tiling_the_canvas_edge(ctx):
+    """The frame's last column and row land on the canvas' last column and row: sx + 1 == sw with fx == 0 (rows alike)."""
+    f = frames_of(29, 1, 23, 17)
+    got = check(ctx, f, [W.translation(9, 5)], "each", 32, 22)
+    assert np.array_equal(got[0, 5:, 9:], f[0]) and not got[0, :5].any() and not got[0, :, :9].any()
+    U = np.rint((np.arange(32.0) - 9) / 1.0 * 32)
+    assert ((U.astype(np.int64) >> 5) + 1 == 23).any()
+    # half a pixel short of the edge: the last column needs a tap at sx + 1 == sw and is not covered
+    check(ctx, f, [W.translation(9.5, 5.5)], "each", 34, 24)
+    check(ctx, f, [W.translation(9 + 1 / 64, 5 - 1 / 64)], "each", 34, 24)                   # halves of 1/32: ties to even
+
+
+# ---- the three modes over several frames -----------------------------------------------------------------------------------------
+def five_frames():
+    f = frames_of(30, 5, 23, 17)
+    mats = [np.eye(3), rot_zoom_persp(12, 1.2, 8, 3, 5e-4, -3e-4), W.translation(-3, 6), rot_zoom_persp(-20, 0.9, 14, 10, 0, 1e-3),
+            W.translation(6.25, 2.75)]
+    bg = (np.add.outer(np.arange(30) * 7, np.arange(44) * 3)[..., None] + np.array([0, 85, 170])).astype(np.uint8)
+    return f, np.stack(mats), bg
+
+
+def test_mosaic_of_five_frames_and_its_chunks(ctx):
+    import torch
+    f, mats, bg = five_frames()
+    dw, dh, origin = 44, 30, (-5, -4)
+    whole = check(ctx, f, mats, "mosaic", dw, dh, origin, bg)
+    covers = [W.warp_frame(f[k], mats[k], dw, dh, origin)[1] for k in range(5)]
+    assert all(c.any() for c in covers) and (np.sum(covers, axis=0) >= 2).sum() > 100 and not np.any(covers, axis=0).all()
+    # three frames, then two onto the same canvas in place
+    canvas = dev(bg)
+    d_f, d_m = dev(f), dev(mats.reshape(5, 9))
+    ctx.warp_fixed_plane(d_f[:3], d_m[:3], canvas, "mosaic", origin, background=canvas)
+    ctx.warp_fixed_plane(d_f[3:], d_m[3:], canvas, "mosaic", origin, background=canvas)
+    ctx.synchronize()
+    assert np.array_equal(canvas.cpu().numpy(), whole)
+    # not in place: the background stays as it was
+    d_bg, out = dev(bg), torch.zeros((dh, dw, 3), dtype=torch.uint8, device="cuda")
+    ctx.warp_fixed_plane(d_f, d_m, out, "mosaic", origin, background=d_bg)
+    ctx.synchronize()
+    assert np.array_equal(out.cpu().numpy(), whole) and np.array_equal(d_bg.cpu().numpy(), bg)
+
+
+@pytest.mark.parametrize("gray", [False, True])
+def test_history_and_each_of_five_frames(ctx, gray):
+    f, mats, bg = five_frames()
+    if gray:
+        f, bg = f[..., 1], bg[..., 1]
+    dw, dh, origin = 44, 30, (-5, -4)
+    hist = check(ctx, f, mats, "history", dw, dh, origin, bg, out_pad=1)
+    for k in range(5):
+        assert np.array_equal(hist[k], W.warp_canvases(f[:k + 1], mats[:k + 1], "mosaic", dw, dh, origin, bg))
+    each = check(ctx, f, mats, "each", dw, dh, origin, bg)
+    for k in range(5):                                                   # frames do not leak into each other
+        assert np.array_equal(each[k], W.warp_canvases(f[k:k + 1], mats[k:k + 1], "mosaic", dw, dh, origin, bg))
+    check(ctx, f, mats, "each", dw, dh, origin, None)                    # no background: zeros
+
+
+# ---- planes ------------------------------------------------------------------------------------------------------------------------
+def test_planes_equal_the_bgr_entry_on_the_converted_frames(ctx):
+    import torch
+    rng = np.random.default_rng(31)
+    n, w, h, cw, ch = 3, 23, 17, 12, 9
+    planes = [(rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (ch, cw), dtype=np.uint8),
+               rng.integers(0, 256, (ch, cw), dtype=np.uint8)) for _ in range(n)]
+    bgr = W.planes_to_bgr(planes)
+    mats = np.stack([np.eye(3), rot_zoom_persp(12, 1.2, 8, 3, 5e-4, -3e-4), W.translation(6.25, 2.75)])
+    dw, dh, origin = 44, 30, (-5, -4)
+    bg = frames_of(32, 1, dw, dh)[0]
+    d_m, d_bg = dev(mats.reshape(n, 9)), dev(bg)
+    y, cb, cr = (dev(np.stack([p[i] for p in planes])) for i in range(3))
+    uv = torch.stack([cb, cr], dim=-1).contiguous()
+    packed = dev(np.stack([np.concatenate([a.reshape(-1) for a in p]) for p in planes]))
+    conv = torch.zeros((n, h, w, 3), dtype=torch.uint8, device="cuda")
+    ctx.yuv420_to_bgr((y, cb, cr), conv)
+    ctx.synchronize()
+    assert np.array_equal(conv.cpu().numpy(), bgr)
+    for mode in ("each", "history", "mosaic"):
+        want = W.warp_canvases(bgr, mats, mode, dw, dh, origin, bg)
+        shape = (dh, dw, 3) if mode == "mosaic" else (n, dh, dw, 3)
+        via_bgr = torch.zeros(shape, dtype=torch.uint8, device="cuda")
+        ctx.warp_fixed_plane(conv, d_m, via_bgr, mode, origin, background=d_bg)
+        ctx.synchronize()
+        assert np.array_equal(via_bgr.cpu().numpy(), want), mode
+        for name, src, size in (("i420", (y, cb, cr), None), ("nv12", (y, uv[..., 0], uv[..., 1]), None), ("packed", packed, (w, h))):
+            out = torch.full(shape, SENTINEL, dtype=torch.uint8, device="cuda")
+            ctx.warp_fixed_plane(src, d_m, out, mode, origin, background=d_bg, size=size)
+            ctx.synchronize()
+            assert np.array_equal(out.cpu().numpy(), want), (mode, name)
+
+
+# ---- offsets beyond 2^31 -----------------------------------------------------------------------------------------------------------
+def test_mosaic_canvas_beyond_two_gib(ctx):
+    """27000 x 27000 x 3 = 2 187 000 000 bytes: the frame sits in the last rows, every byte offset there is above 2^31."""
+    import torch
+    side, top = 27000, 26980
+    f = np.maximum(frames_of(33, 1, 16, 16), 1)                         # no zero byte: the frame's bytes can be counted
+    M = W.translation(26975.5, 26984.0)                                  # columns interpolate, rows paste; cut by nothing
+    out = torch.full((side, side, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+    assert out.numel() > 2 ** 31
+    ctx.warp_fixed_plane(dev(f), dev(M.reshape(1, 9)), out, "mosaic", (0, 0))
+    ctx.synchronize()
+    want = W.warp_canvases(f, [M], "mosaic", side, side - top, (0, top))      # the last rows, restated with a shifted origin
+    assert np.count_nonzero(want) == 15 * 16 * 3
+    assert np.array_equal(out[top:].cpu().numpy(), want)
+    assert int(torch.count_nonzero(out)) == np.count_nonzero(want)       # everything else was written, as background zeros
+    del out
+    torch.cuda.empty_cache()
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_output_alone(ctx):
+    import torch
+    from evenvizion_amd._lib import Yuv420
+    INVALID, CAPACITY = -1, -3
+    n, sw, sh, dw, dh = 2, 23, 17, 31, 22
+    src = dev(frames_of(34, n, sw, sh))
+    mats = dev(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
+    out = torch.full((n + 1, dh, dw, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+    elsewhere = torch.full((dh, dw, 3), 7, dtype=torch.uint8, device="cuda")
+    f, m, o, b = src.data_ptr(), mats.data_ptr(), out.data_ptr(), elsewhere.data_ptr()
+    ors, ofs = dw * 3, dw * dh * 3
+    good = dict(ctx=ctx.h, frames=f, n=n, sw=sw, sh=sh, cn=3, rs=sw * 3, fs=sw * sh * 3, M=m, inv=0, mode=0, bg=b, out=o, dw=dw,
+                dh=dh, ors=ors, ofs=ofs, ox=0, oy=0)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return ctx.lib.evh_warp_fixed_plane(a["ctx"], a["frames"], a["n"], a["sw"], a["sh"], a["cn"], a["rs"], a["fs"], a["M"],
+                                            a["inv"], a["mode"], a["bg"], a["out"], a["dw"], a["dh"], a["ors"], a["ofs"],
+                                            a["ox"], a["oy"])
+
+    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(out=None), dict(cn=2), dict(cn=0), dict(cn=4), dict(sw=0),
+               dict(sh=0), dict(dw=0), dict(dh=-1), dict(n=-1), dict(rs=sw * 3 - 1), dict(fs=sw * sh * 3 - 1), dict(ors=ors - 1),
+               dict(ofs=ofs - 1), dict(mode=1, ofs=ofs - 1), dict(mode=3), dict(mode=-1),
+               dict(bg=o), dict(mode=1, bg=o), dict(bg=o + ofs), dict(bg=o + ofs + ors), dict(bg=o - ors),      # overlaps
+               dict(mode=2, bg=o + 3), dict(mode=2, bg=o + ors), dict(mode=2, bg=o - ors)]                         # mosaic: only bg == out
+    for kw in invalid:
+        assert call(**kw) == INVALID, kw
+        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+    big = 1 << 26
+    capacity = [dict(sw=big, rs=big * 3, fs=big * 3 * sh), dict(sh=big, fs=sw * 3 * big), dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40),
+                dict(n=65536)]
+    for kw in capacity:
+        assert call(**kw) == CAPACITY, kw
+    assert call(sw=big - 1, rs=(big - 1) * 3 - 1) == INVALID            # just below the limit the ordinary checks apply
+    # the plane form: its own description, then the same checks
+    y = torch.zeros((n, sh, sw), dtype=torch.uint8, device="cuda")
+    c = torch.zeros((2, n, 9, 12), dtype=torch.uint8, device="cuda")
+    yuv = dict(d_y=y.data_ptr(), d_cb=c[0].data_ptr(), d_cr=c[1].data_ptr(), y_stride=sw, c_stride=12, y_frame_stride=sw * sh,
+               c_frame_stride=12 * 9, c_pixel_stride=1)
+
+    def call_yuv(desc, **kw):
+        a = dict(good, **kw)
+        d = None if desc is None else ctypes.byref(Yuv420(**desc))
+        return ctx.lib.evh_warp_fixed_plane_yuv420(a["ctx"], d, a["n"], a["sw"], a["sh"], a["M"], a["inv"], a["mode"], a["bg"],
+                                                   a["out"], a["dw"], a["dh"], a["ors"], a["ofs"], a["ox"], a["oy"])
+
+    assert call_yuv(None) == INVALID
+    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=sw - 1), dict(c_stride=11),
+                dict(y_frame_stride=sw * sh - 1), dict(c_frame_stride=12 * 9 - 1)):
+        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
+    for kw in (dict(M=None), dict(out=None), dict(dw=0), dict(mode=7), dict(ors=ors - 1), dict(bg=o)):
+        assert call_yuv(yuv, **kw) == INVALID, kw
+    for kw in (dict(sw=big), dict(n=65536), dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40)):
+        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    # no frames: success, and nothing is done
+    assert call(n=0) == 0 and call(n=0, mode=2, bg=o) == 0 and call_yuv(yuv, n=0) == 0
+    ctx.synchronize()
+    assert (out == SENTINEL).all() and (elsewhere == 7).all()
+    # and the same arguments unrefused do write
+    assert call() == 0 and call_yuv(yuv, mode=2, out=o + 2 * ofs, bg=None) == 0
+    ctx.synchronize()
+    assert np.array_equal(out[:n, :sh, :sw].cpu().numpy(), src.cpu().numpy()) and (out[0, sh:] == 7).all()
+    assert (out[2] != SENTINEL).any()

@@ -102,6 +102,8 @@ SIGNATURES = {
     # stabilised output: frames warped into the fixed plane
     "evh_warp_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
+    # heat-map pictures: colour index, table, blend over the frame
+    "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -577,6 +579,29 @@ class Context:
             self._check(self.lib.evh_warp_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
         else:
             self._check(self.lib.evh_warp_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+
+    def heatmap_render(self, Hsup, out, lut, frames=None, heatmap_constant=1000.0, alpha=0.8, saturate=False):
+        """The heat-map pictures of n superposed matrices (evh_heatmap_render, the arithmetic is stated in include/evhip.h).
+        Hsup: CUDA float64, n*9 contiguous elements.  out: CUDA uint8 [n,h,w,3] (BGR), rows and pictures may be strided.
+        lut: CUDA uint8 [256,3] contiguous, the colour table in BGR order (heatmap.jet_lut()).  frames: CUDA uint8 [n,h,w,3]
+        laid under the colours, or None = black.  Does not synchronise."""
+        import torch
+        self._enter()
+        op, w, h, ors, ofs = self._image_rows(out, 3, 1, "out")
+        n = out.shape[0]
+        if Hsup.dtype != torch.float64 or not Hsup.is_cuda or Hsup.device.index != self.device or not Hsup.is_contiguous() \
+                or Hsup.numel() != 9 * n:
+            raise ValueError("Hsup must be a contiguous CUDA float64 tensor of n*9 elements")
+        if lut.dtype != torch.uint8 or not lut.is_cuda or lut.device.index != self.device or not lut.is_contiguous() \
+                or tuple(lut.shape) != (256, 3):
+            raise ValueError("lut must be a contiguous CUDA uint8 tensor [256,3]")
+        fp, frs, ffs = None, 0, 0
+        if frames is not None:
+            fp, fw, fh, frs, ffs = self._image_rows(frames, 3, 1, "frames")
+            if (frames.shape[0], fw, fh) != (n, w, h):
+                raise ValueError("frames must be [n,h,w,3] like out")
+        self._check(self.lib.evh_heatmap_render(self.h, Hsup.data_ptr(), n, w, h, fp, frs, ffs, lut.data_ptr(), float(heatmap_constant),
+                                                float(alpha), int(bool(saturate)), op, ors, ofs))
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

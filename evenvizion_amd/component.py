@@ -8,7 +8,10 @@ writes, like the reference, under  <cwd>/<experiment_name>/<video stem>/ :
     dict_with_homography_matrix.json   {frame_no: {"H": 3x3}, ..., "resize_info": {"h","w"}}   (:139-140)
     metrics_file.txt                   "Maximum movement during the entire video: <f64>"        (:62-65)
 and, as a data file instead of the reference's rendered comparison video (:69-97),
-    fixed_coordinates.json             from_original_to_fix(original coordinates) per frame.
+    fixed_coordinates.json             from_original_to_fix(original coordinates) per frame;
+with --heatmap_pictures 1 (extension, default off) also the reference's heat-map pictures without their drawing,
+    heatmap_visualization/img%06d.ppm  the colours of heatmap_frame_processing over the resized frame, one per frame
+                                       (heatmap.heatmap_frames: evh_heatmap_render; no grid lines, arrows or text; PPM, not PNG).
 
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
@@ -16,8 +19,8 @@ cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenv
 It also takes a .npy file (uint8 [F,h,w,3] BGR or [F,h,w] gray) or "synthetic:<frames>:<w>x<h>[:<seed>]".
 --path_to_videos A B ... (extension) takes several of them and writes, per video, what the single form writes; the videos run
 together through get_homography_dicts (several captures per GPU call), main() then returns the list of folders.
-Differences, all deliberate: the heat-map and matching PICTURES are
-not rendered (--show_matching_visualization must stay off); --resize_width is honoured (the reference script parses
+Differences, all deliberate: the matching PICTURES are not rendered (--show_matching_visualization must stay off) and the
+heat-map pictures only on request and without part_line's drawing; --resize_width is honoured (the reference script parses
 it but never passes it on, so it always runs at 400 -- the default here).
 """
 import argparse
@@ -77,6 +80,9 @@ def main(argv=None):
     ap.add_argument("--path_to_original_coordinate", default=None, help="path to json with original coordinates")
     ap.add_argument("--none_H_processing", default=True, help="If True use H_prev as H, False - do nothing")
     ap.add_argument("--heatmap_visualization", default=True, help="write metrics_file.txt (pictures are not rendered)")
+    ap.add_argument("--heatmap_pictures", default=False,
+                    help="also write heatmap_visualization/img%%06d.ppm: the heat-map colours over every resized frame, "
+                         "without grid, arrows or text (extension; the video is read a second time)")
     ap.add_argument("--show_matching_visualization", default=False, help="not available: matching pictures are not rendered")
     ap.add_argument("--features", type=str, default="SURF,SIFT,ORB",
                     help="feature types in FrameProcessing order (extension; the reference hard-wires SURF,SIFT,ORB)")
@@ -99,17 +105,18 @@ def main(argv=None):
         for n, (result, (_, original_shape, stem)) in enumerate(zip(results, opened)):
             if [s for _, _, s in opened].count(stem) > 1:
                 stem = "%s_%d" % (stem, n)               # two videos of one name: one folder each
-            folders.append(write_outputs(args, result, original_shape, stem))
+            folders.append(write_outputs(args, result, original_shape, stem, args.path_to_videos[n]))
         return folders
     cap, original_shape, stem = open_capture(args.path_to_video)
     result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
                                  none_H_processing=_bool(args.none_H_processing),
                                  features_type_list=features, ingest=args.ingest)
-    return write_outputs(args, result, original_shape, stem)
+    return write_outputs(args, result, original_shape, stem, args.path_to_video)
 
 
-def write_outputs(args, result, original_shape, stem):
-    """One video's files under <cwd>/<experiment_name>/<stem>/ (evenvizion_component.py:62-65,139-140) -> the folder."""
+def write_outputs(args, result, original_shape, stem, spec=None):
+    """One video's files under <cwd>/<experiment_name>/<stem>/ (evenvizion_component.py:62-65,139-140) -> the folder.
+    spec: what the video was opened from, to read it again for --heatmap_pictures."""
     from .processing.utils import read_homography_dict, superposition_dict, read_json_with_coordinates, \
         are_infinity_coordinates
     from .processing.fixed_coordinate_system import from_original_to_fix
@@ -130,6 +137,13 @@ def write_outputs(args, result, original_shape, stem):
             txt_.write("Maximum movement during the entire video: {}".format(np.max(max_movement)))
             if are_infinity_coordinates(max_movement):
                 txt_.write("There are some frames with undefined coordinates")
+    if _bool(args.heatmap_pictures):
+        from .stabilization import write_ppm
+        pictures = os.path.join(save_folder, "heatmap_visualization")
+        os.makedirs(pictures, exist_ok=True)
+        cap = open_capture(spec)[0]                              # visualize_heatmap opens the video again too (:52)
+        for frame_no, picture in heatmap.heatmap_frames(cap, reformat, resize_info, ingest=args.ingest):
+            write_ppm(os.path.join(pictures, "img%06d.ppm" % int(frame_no)), picture)
     if args.path_to_original_coordinate:
         original_coordinates = read_json_with_coordinates(args.path_to_original_coordinate)
         fixed = from_original_to_fix(original_coordinates, reformat, original_shape, [resize_info["h"], resize_info["w"]])

@@ -921,6 +921,32 @@ int evh_warp_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, 
                           d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
 }
 
+// ---- heat-map pictures (processing_visualization.py:336-344) -----------------------------------------------------------------------
+int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
+                       int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
+                       uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = "evh_heatmap_render: ";
+  if (!d_Hsup || !d_lut || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (n < 0 || w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty grid or negative n");
+  if (!std::isfinite(heatmap_constant) || heatmap_constant <= 0) return evh_fail(c, EVH_ERR_INVALID, W + "heatmap_constant must be finite and positive");
+  if (!std::isfinite(alpha) || alpha < 0) return evh_fail(c, EVH_ERR_INVALID, W + "alpha must be finite and not negative");
+  if (n > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 matrices per call");
+  if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "w * h above INT_MAX");
+  const int64_t row = (int64_t)w * 3;
+  if (out_row_stride < row || (d_frames && row_stride < row)) return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a row");
+  const int64_t picture = (h - 1) * out_row_stride + row, frame = d_frames ? (h - 1) * row_stride + row : 0;
+  if (n > 1 && (out_frame_stride < picture || (d_frames && frame_stride < frame)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a frame");
+  if (d_frames && n > 0) {
+    const int64_t out_bytes = picture + (n - 1) * out_frame_stride, frames_bytes = frame + (n - 1) * frame_stride;
+    if (d_frames < d_out + out_bytes && d_out < d_frames + frames_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_frames overlaps d_out");
+  }
+  if (n == 0) return EVH_SUCCESS;
+  return evh_launch_heatmap_render(c, d_Hsup, n, w, h, d_frames, row_stride, frame_stride, d_lut, heatmap_constant, alpha, saturate,
+                                   d_out, out_row_stride, out_frame_stride);
+}
+
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);

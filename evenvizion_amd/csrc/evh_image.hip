@@ -510,6 +510,66 @@ __global__ __launch_bounds__(256) void k_warp_fixed_plane(SRC src, int nframes, 
   }
 }
 
+// Heat-map pictures (processing_visualization.py:336-344 without part_line): k_fixed_plane's field taken to a colour index,
+// looked up in a 256-entry BGR table and laid over the frame, in the arithmetic include/evhip.h states for evh_heatmap_render.
+// grid.y = frame; a thread owns WARP_RUN adjacent pixels of a row and moves their 12 bytes as three words where the pointers and
+// strides allow (vec bit 0: output, bit 1: frames), bytewise otherwise and in runs cut by the right edge.  The table is staged
+// in LDS once per workgroup, one packed entry per thread.  GENERAL = false: the entry is staged already multiplied,
+// a = min(255, rint(c * alpha)), and a pixel is min(255, p + a) -- what rint(c * alpha + p) gives when p = 0 (no frames) or
+// alpha is exactly 0.8 (c * 0.8 is never within 0.1 of a half; the launcher tests for the constant).  GENERAL = true: the
+// float64 blend per byte.  The 256 threads of a block all reach the barrier; those past the last run then leave.
+__device__ __forceinline__ int heat_index(const double* __restrict__ H, double x, double y, double heatmap_constant, int saturate) {
+  double tx, ty, tw;
+  hdot(H, x, y, &tx, &ty, &tw);
+  const double u = tx / tw, v = ty / tw;
+  const double s = u * u + v * v;
+  const double t = 255.0 * (__builtin_sqrt(s) / heatmap_constant);
+  if (saturate && t >= 255.0) return 255;                  // +inf included; NaN fails every comparison and ends as 0
+  return (t >= 0.0 && t < 2147483648.0) ? ((int)t & 255) : 0;
+}
+template <bool GENERAL>
+__global__ __launch_bounds__(256) void k_heatmap_render(const double* __restrict__ Hs, int w, const uint8_t* __restrict__ frames,
+                                                        int64_t row_stride, int64_t frame_stride,
+                                                        const uint8_t* __restrict__ lut, double heatmap_constant, double alpha,
+                                                        int saturate, uint8_t* __restrict__ out, int64_t out_stride,
+                                                        int64_t out_img_stride, int runs_per_row, unsigned nruns, int vec) {
+  __shared__ uint32_t table[256];
+  {
+    uint32_t e = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      uint32_t c = lut[3 * threadIdx.x + ch];
+      if (!GENERAL) c = (uint32_t)fmin(255.0, __builtin_rint((double)c * alpha));
+      e |= c << (8 * ch);
+    }
+    table[threadIdx.x] = e;
+  }
+  __syncthreads();
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nruns) return;
+  const int f = blockIdx.y;
+  const double* H = Hs + 9 * (int64_t)f;
+  const int y = (int)(t / (unsigned)runs_per_row), x0 = ((int)t - y * runs_per_row) * WARP_RUN;
+  const int n = min(WARP_RUN, w - x0);
+  const bool full = n == WARP_RUN;
+  int v[WARP_RUN][3];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) v[p][0] = v[p][1] = v[p][2] = 0;
+  if (frames) warp_run_load<3>(frames + (int64_t)f * frame_stride + (int64_t)y * row_stride + (int64_t)x0 * 3, n, full && (vec & 2), v);
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) {
+    if (p >= n) break;
+    const uint32_t e = table[heat_index(H, (double)(x0 + p), (double)y, heatmap_constant, saturate)];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const int c = (e >> (8 * ch)) & 255;
+      if (GENERAL) v[p][ch] = (int)fmin(255.0, __builtin_rint((double)c * alpha + (double)v[p][ch]));
+      else v[p][ch] = min(255, v[p][ch] + c);
+    }
+  }
+  warp_run_store<3>(out + (int64_t)f * out_img_stride + (int64_t)y * out_stride + (int64_t)x0 * 3, n, full && (vec & 1), v);
+}
+
 struct HostTab { std::vector<int> start, cnt, si; std::vector<float> al; };
 
 void build_area_tab(int ssize, int dsize, double scale, HostTab& t) {
@@ -682,6 +742,27 @@ int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, i
   if (src.channels == 3)
     return launch_warp<3>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
   return launch_warp<1>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
+}
+
+// k_heatmap_render over n frames of w x h (the entry has checked w * h <= INT_MAX and n <= 65535)
+int evh_launch_heatmap_render(evh_ctx* c, const double* d_H, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
+                              int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
+                              uint8_t* d_out, int64_t out_stride, int64_t out_img_stride) {
+  const int runs_per_row = (w + WARP_RUN - 1) / WARP_RUN;
+  const unsigned nruns = (unsigned)runs_per_row * (unsigned)h;
+  // the frame strides are only used between the pictures of a call
+  const uintptr_t ois = n > 1 ? (uintptr_t)out_img_stride : 0, fs = n > 1 ? (uintptr_t)frame_stride : 0;
+  const int vec = ((((uintptr_t)d_out | (uintptr_t)out_stride | ois) & 3) == 0 ? 1 : 0) |
+                  (d_frames && (((uintptr_t)d_frames | (uintptr_t)row_stride | fs) & 3) == 0 ? 2 : 0);
+  const dim3 grid((nruns + 255) / 256, n);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, d_H, w, d_frames, row_stride, frame_stride, d_lut, heatmap_constant,
+                       alpha, saturate, d_out, out_stride, out_img_stride, runs_per_row, nruns, vec);
+  };
+  if (!d_frames || alpha == 0.8) go(k_heatmap_render<false>);      // the integer blend, behind the exact test for its constant
+  else go(k_heatmap_render<true>);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
 }
 
 int evh_launch_superposition_scan(evh_ctx* c, const double* d_H, int n, double* d_out) {

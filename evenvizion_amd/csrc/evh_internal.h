@@ -320,6 +320,9 @@ int evh_launch_superposition_scan(evh_ctx* c, const double* d_H, int n, double* 
 int evh_launch_transform_points(evh_ctx* c, const double* d_M, const int* d_idx, const double* d_pts, int n, double kx,
                                 double ky, int decimals, double* d_out);
 int evh_launch_fixed_plane(evh_ctx* c, const double* d_H, int n, int w, int h, double* d_field, unsigned long long* d_max);
+int evh_launch_heatmap_render(evh_ctx* c, const double* d_H, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
+                              int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
+                              uint8_t* d_out, int64_t out_stride, int64_t out_img_stride);
 // N4: SIFT (evh_sift.hip)
 int evh_sift_allocate(evh_ctx* c, int max_sift_features);
 int evh_launch_sift(evh_ctx* c, int nframes, int w, int h);

@@ -23,6 +23,8 @@
  *   evh_*_yuv420                  capture.read() + imutils.resize + the entry of the same name without the suffix
  *   evh_warp_fixed_plane[_yuv420] stabilize_view / initialize_background: a frame placed on the fixed plane
  *                                 visualization/stabilization.py:129-172, 220-249
+ *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
+ *                                 visualization/processing_visualization.py:336-344
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -460,6 +462,35 @@ int evh_warp_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int
 int evh_warp_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
                                 int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
                                 int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy);
+
+/* ---- heat-map pictures: the colouring of heatmap_frame_processing (processing_visualization.py:336-344) ------------------------ */
+/* What heatmap_frame_processing does with the field of evh_fixed_plane_field and the resized frame, without part_line's grid,
+ * arrows and text: for each of n superposed matrices d_Hsup f64[n,9] (DEVICE) a BGR picture of w x h, frame k into
+ * d_out + k*out_frame_stride, rows of 3*w bytes at out_row_stride.  d_frames: n BGR frames of w x h (rows at row_stride, frames
+ * at frame_stride), or NULL = black frames.  d_lut u8[256,3] (DEVICE) is the colour table in BGR order, what
+ * cv2.applyColorMap(np.arange(256, dtype=np.uint8), cv2.COLORMAP_JET) returns for the reference's pictures.
+ * Field and colour index of pixel (x, y), all IEEE float64 with one rounding per operation:
+ *   tx = fma(h0, x, h1*y) + h2, ty and tw alike (the order of evh_fixed_plane_field); u = tx / tw, v = ty / tw;
+ *   s = u*u + v*v (each product rounded, then the sum; no fma); r = sqrt(s); t = 255 * (r / heatmap_constant) (a true division,
+ *   then the product);
+ *   i = (int64)trunc(t) & 255 when t is finite and 0 <= t < 2^31, else i = 0;
+ *   with saturate != 0: i = 255 for t >= 255 and for t = +inf, i = 0 for NaN.
+ * The wrap (saturate == 0) is what np.uint8(255 * heatmap) gives on the reference's platform for every value whose cast is
+ * defined.  For NaN, +inf and t >= 2^31 the C cast is undefined and numpy versions differ: index 0 there is this library's
+ * choice, not the reference's.
+ * Blend, per channel ch: c = d_lut[3*i + ch], p = the frame's byte (0 without frames), o = rint((double)c * alpha + (double)p)
+ * (the product rounded, then the sum; halves to even) clamped to [0, 255]: heatmap * hif + image followed by the conversion
+ * cv2.imwrite applies to float64 pixels (cvRound, saturating); hif = alpha = 0.8 in the reference.
+ * Every byte of every output row inside 3*w is written, bytes between rows are not.  Only caller buffers are used: nothing
+ * depends on the sizes given to evh_create.  Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: a NULL
+ * d_Hsup, d_lut or d_out, w or h < 1, n < 0, a stride shorter than its row / frame (frame strides count when n > 1),
+ * heatmap_constant not finite or <= 0, alpha not finite or < 0, d_frames overlapping d_out; EVH_ERR_CAPACITY: n > 65535,
+ * w*h > INT_MAX (the limits of evh_fixed_plane_field).  n == 0 succeeds and does nothing.  Speed, not results, depends on
+ * alignment: d_out and the output strides multiples of 4 let a thread store its four pixels as words (d_frames and its
+ * strides: load them so).  Does not synchronise.                                                                              */
+int evh_heatmap_render(evh_ctx* ctx, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
+                       int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
+                       uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(64 * DW_PER_BLOCK, 8) void k_describe(DescribeArgs 
       uint32_t sum = 32768u;
 #pragma unroll
       for (int q = 0; q < 4; q++) sum = __builtin_amdgcn_udot2(P[(r >> 1) + q], (r & 1) ? WO[q] : WE[q], sum, false);
-      blurp[r * DB_N + lane] = (uint8_t)(sum >> 16);
+      blurp[r * DB_N + lane] = (uint8_t)(min(sum, 0x00FFFFFFu) >> 16);   // saturating store: 255 * 257 * 257 + 32768 >> 16 = 257
     }
   }
   WAVE_LDS_SYNC();

@@ -66,7 +66,7 @@ long evo_orb_depth_limit_hits(void);   /* nth_element calls so far that fell bac
 void evo_set_sift_blur_mode(int mode);
 int evo_get_sift_blur_mode(void);
 int evo_orb_level_candidates(const uint8_t* img, int w, int h, int quota, int* xs, int* ys, int* scores, int cap);
-/* 7x7/sigma=2 8-bit Gaussian blur with reflect-101 borders (K6 first half) */
+/* 7x7/sigma=2 8-bit Gaussian blur with reflect-101 borders, saturating store (K6 first half) */
 void evo_gaussian_blur7(const uint8_t* src, int w, int h, uint8_t* dst);
 /* full detectAndCompute on a gray frame. Outputs (cap entries each): xy f32[cap,2], desc u8[cap,32],
  * octave i32, lx/ly i32 (level coords), response f32, angle f32 (degrees).  Order: per level, as retainBest leaves it (evo_set_orb_order).

@@ -562,7 +562,10 @@ extern "C" int evo_orb_level_candidates(const uint8_t* img, int w, int h, int qu
 }
 
 /* GaussianBlur(7x7, sigma 2) on 8-bit data: separable, coefficients quantised to 8 fractional bits per pass
- * (cvRound(k*256)), 32-bit sums, one rounding at the end: (v + 32768) >> 16; BORDER_REFLECT_101.        */
+ * (cvRound(k*256)), 32-bit sums, one rounding at the end: (v + 32768) >> 16, stored with a saturating cast
+ * (the taps sum to 257, a gain of 257/256 per pass: a neighbourhood whose weighted mean is >= 253.52 rounds to
+ * 256 or 257, which saturate_cast<uchar> stores as 255 and a plain byte cast would store as 0 or 1);
+ * BORDER_REFLECT_101.                                                                                    */
 namespace {
 void gauss_kernel7(int* k) {
   float cf[7]; double sum = 0;
@@ -586,7 +589,7 @@ extern "C" void evo_gaussian_blur7(const uint8_t* src, int w, int h, uint8_t* ds
     for (int x = 0; x < w; x++) {
       int s = 0;
       for (int j = -3; j <= 3; j++) s += k[j + 3] * tmp[(size_t)reflect101(y + j, h) * w + x];
-      dst[(size_t)y * w + x] = (uint8_t)((s + 32768) >> 16);
+      dst[(size_t)y * w + x] = (uint8_t)std::min((s + 32768) >> 16, 255);
     }
 }
 

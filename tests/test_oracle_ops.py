@@ -118,6 +118,15 @@ def test_gaussian_blur_kernel():
     want = (np.outer(k, k) * 255 + 32768) >> 16
     assert np.array_equal(b[7:14, 7:14], want)
     assert (O.gaussian_blur7(np.full((30, 30), 100, np.uint8)) == ((257 * 257 * 100 + 32768) >> 16)).all()
+    # the taps sum to 257: from 253.52 upwards the rounded value is 256 or 257 and the store saturates (a byte cast gave 0 and 1)
+    for v in (253, 254, 255):
+        assert (O.gaussian_blur7(np.full((30, 30), v, np.uint8)) == 255).all(), v
+    hole = np.full((21, 21), 255, np.uint8); hole[10, 10] = 0
+    b = O.gaussian_blur7(hole).astype(int)
+    want = np.minimum(((257 * 257 - np.outer(k, k)) * 255 + 32768) >> 16, 255)
+    assert np.array_equal(b[7:14, 7:14], want) and want.min() == 245 and want.max() == 255
+    b[7:14, 7:14] = 255
+    assert (b == 255).all()
 
 
 def test_jacobi_against_numpy():

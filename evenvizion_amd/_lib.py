@@ -22,6 +22,8 @@ MAX_FEATURES = 5984   # EVH_MAX_FEATURES (include/evhip.h): largest max_features
 MODE_INDEPENDENT_PAIRS, MODE_STREAM = 0, 1
 WARP_EACH, WARP_HISTORY, WARP_MOSAIC = 0, 1, 2
 WARP_MODES = {"each": WARP_EACH, "history": WARP_HISTORY, "mosaic": WARP_MOSAIC}
+DRAW_REFERENCE, DRAW_OWN_FRAME = 0, 1
+DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
 
 # every symbol include/evhip.h declares, with its ctypes signature
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -104,6 +106,10 @@ SIGNATURES = {
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     # heat-map pictures: colour index, table, blend over the frame
     "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
+    # matching pictures: the rows a batch handed to its final solve, and the two frames side by side with a line per row
+    "evh_batch_static_info": (_i, [_vp, _pi, _pi]),
+    "evh_batch_static_rows": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "evh_draw_matches": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i, C.c_uint32, _vp, _i64, _i64]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -602,6 +608,69 @@ class Context:
                 raise ValueError("frames must be [n,h,w,3] like out")
         self._check(self.lib.evh_heatmap_render(self.h, Hsup.data_ptr(), n, w, h, fp, frs, ffs, lut.data_ptr(), float(heatmap_constant),
                                                 float(alpha), int(bool(saturate)), op, ors, ofs))
+
+    # ---- matching pictures ----
+    def batch_static_info(self):
+        """-> (pair slots, rows per pair slot) of the last batch whose static rows are still resident; (0, 0): none."""
+        n = C.c_int(); cap = C.c_int()
+        self._check(self.lib.evh_batch_static_info(self.h, C.byref(n), C.byref(cap)))
+        return n.value, cap.value
+
+    def batch_static_rows(self, first_pair=0, npairs=None, rows=None, counts=None, status=None):
+        """The rows that entered the last batch's final solve (evh_batch_static_rows), pair slots first_pair .. + npairs
+        (default: to the last) -> (rows f32[npairs,cap,4] as (ax, ay, bx, by) with a = the current frame, counts i32[npairs],
+        front status i32[npairs]) CUDA tensors; the three may be handed in (contiguous, cap = batch_static_info()[1]).
+        Enqueued on the context's stream: complete after synchronize() or order_torch_after()."""
+        import torch
+        slots, cap = self.batch_static_info()
+        if npairs is None:
+            npairs = slots - int(first_pair)
+        npairs = int(npairs)
+        dev = "cuda:%d" % self.device
+        if rows is None:
+            rows = torch.empty((max(npairs, 0), cap, 4), dtype=torch.float32, device=dev)
+        if counts is None:
+            counts = torch.empty(max(npairs, 0), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(max(npairs, 0), dtype=torch.int32, device=dev)
+        for t, dt, numel, what in ((rows, torch.float32, npairs * cap * 4, "rows"), (counts, torch.int32, npairs, "counts"),
+                                   (status, torch.int32, npairs, "status")):
+            if t.dtype != dt or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or \
+                    t.numel() < max(numel, 0):
+                raise ValueError("%s must be a contiguous CUDA %s tensor of at least %d elements" % (what, dt, numel))
+        self._enter()
+        self._check(self.lib.evh_batch_static_rows(self.h, int(first_pair), npairs, rows.data_ptr(), rows.shape[1] if rows.dim() == 3 else cap,
+                                                   counts.data_ptr(), status.data_ptr()))
+        return rows, counts, status
+
+    def draw_matches(self, frames, rows, counts, out, status=None, frame_step=1, points="reference", color=(0, 255, 0)):
+        """The matching pictures (evh_draw_matches, the line rule is stated in include/evhip.h).  frames: uint8 [n,h,w,3] BGR,
+        rows and frames may be strided; out: uint8 [npairs,h,2w,3], rows and pictures may be strided: picture p = frame
+        p*frame_step | frame p*frame_step + 1 with one line per row r < counts[p] of rows f32[npairs,cap,4] (contiguous);
+        status i32[npairs] or None: a picture whose status is not PAIR_OK gets no lines.  points: "reference" (the reference's
+        picture: the (ax, ay) end on the left half) or "own_frame"; color: (b, g, r).  Does not synchronise."""
+        import torch
+        self._enter()
+        points = DRAW_POINTS[points] if isinstance(points, str) else int(points)
+        fp, w, h, frs, ffs = self._image_rows(frames, 3, 1, "frames")
+        op, ow, oh, ors, ofs = self._image_rows(out, 3, 1, "out")
+        npairs = out.shape[0]
+        if (ow, oh) != (2 * w, h):
+            raise ValueError("out must be [npairs,h,2w,3] for frames [n,h,w,3]")
+        if npairs and frames.shape[0] < (npairs - 1) * int(frame_step) + 2:
+            raise ValueError("frames holds fewer frames than the pictures take")
+        if rows.dtype != torch.float32 or not rows.is_cuda or rows.device.index != self.device or rows.dim() != 3 or \
+                rows.shape[2] != 4 or rows.shape[0] < npairs or not rows.is_contiguous():
+            raise ValueError("rows must be a contiguous CUDA float32 tensor [npairs,cap,4]")
+        for t, what in ((counts, "counts"), (status, "status")):
+            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device or
+                                  not t.is_contiguous() or t.numel() < npairs):
+                raise ValueError("%s must be a contiguous CUDA int32 tensor of npairs elements" % what)
+        b, g, r = (int(v) for v in color)
+        if min(b, g, r) < 0 or max(b, g, r) > 255:
+            raise ValueError("color is (b, g, r) with bytes")
+        self._check(self.lib.evh_draw_matches(self.h, fp, npairs, int(frame_step), w, h, frs, ffs, rows.data_ptr(), rows.shape[1],
+                                              counts.data_ptr(), _ptr(status), points, b | g << 8 | r << 16, op, ors, ofs))
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

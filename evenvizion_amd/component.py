@@ -12,6 +12,10 @@ and, as a data file instead of the reference's rendered comparison video (:69-97
 with --heatmap_pictures 1 (extension, default off) also the reference's heat-map pictures without their drawing,
     heatmap_visualization/img%06d.ppm  the colours of heatmap_frame_processing over the resized frame, one per frame
                                        (heatmap.heatmap_frames: evh_heatmap_render; no grid lines, arrows or text; PPM, not PNG).
+with --matching_pictures 1 (extension, default off) also the reference's matching pictures (:113-137, video_processing.py:76-81),
+    matching_visualization/matching_vis_{i}.png   the resized frames i-1 | i and one green line per static match, for every
+                                       pair whose matching succeeded (get_homography_dict(matching_sink=): evh_draw_matches,
+                                       drawn in the same pass; --path_to_video only).
 
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
@@ -19,8 +23,8 @@ cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenv
 It also takes a .npy file (uint8 [F,h,w,3] BGR or [F,h,w] gray) or "synthetic:<frames>:<w>x<h>[:<seed>]".
 --path_to_videos A B ... (extension) takes several of them and writes, per video, what the single form writes; the videos run
 together through get_homography_dicts (several captures per GPU call), main() then returns the list of folders.
-Differences, all deliberate: the matching PICTURES are not rendered (--show_matching_visualization must stay off) and the
-heat-map pictures only on request and without part_line's drawing; --resize_width is honoured (the reference script parses
+Differences, all deliberate: the matching pictures come under their own flag (--show_matching_visualization still has to stay
+off: it refuses and names --matching_pictures) and the heat-map pictures only on request and without part_line's drawing; --resize_width is honoured (the reference script parses
 it but never passes it on, so it always runs at 400 -- the default here).
 """
 import argparse
@@ -83,7 +87,10 @@ def main(argv=None):
     ap.add_argument("--heatmap_pictures", default=False,
                     help="also write heatmap_visualization/img%%06d.ppm: the heat-map colours over every resized frame, "
                          "without grid, arrows or text (extension; the video is read a second time)")
-    ap.add_argument("--show_matching_visualization", default=False, help="not available: matching pictures are not rendered")
+    ap.add_argument("--show_matching_visualization", default=False, help="not taken: use --matching_pictures")
+    ap.add_argument("--matching_pictures", default=False,
+                    help="also write matching_visualization/matching_vis_{i}.png: the resized frames i-1 | i with a green line "
+                         "per static match (extension; drawn on the device in the same pass; --path_to_video only)")
     ap.add_argument("--features", type=str, default="SURF,SIFT,ORB",
                     help="feature types in FrameProcessing order (extension; the reference hard-wires SURF,SIFT,ORB)")
     ap.add_argument("--ingest", type=str, default="bgr", choices=("auto", "bgr", "yuv420"),
@@ -91,11 +98,14 @@ def main(argv=None):
                          "(auto), or planes only (extension; results do not depend on it)")
     args = ap.parse_args(argv)
     if _bool(args.show_matching_visualization):
-        raise NotImplementedError("matching pictures are outside the MI355X hot path; leave --show_matching_visualization off")
+        raise NotImplementedError("--show_matching_visualization is not taken: leave it off and ask for the matching pictures "
+                                  "with --matching_pictures 1")
 
     from .processing.video_processing import get_homography_dict, get_homography_dicts
     features = [f for f in args.features.split(",") if f]
     if args.path_to_videos:
+        if _bool(args.matching_pictures):
+            raise ValueError("--matching_pictures takes one video (--path_to_video)")
         opened = [open_capture(spec) for spec in args.path_to_videos]
         kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
         results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
@@ -108,10 +118,22 @@ def main(argv=None):
             folders.append(write_outputs(args, result, original_shape, stem, args.path_to_videos[n]))
         return folders
     cap, original_shape, stem = open_capture(args.path_to_video)
+    sink = None
+    if _bool(args.matching_pictures):
+        from .matching_pictures import write_png
+        pictures = os.path.join(output_folder(args, stem), "matching_visualization")      # evenvizion_component.py:134-137
+        os.makedirs(pictures, exist_ok=True)
+
+        def sink(frame_no, picture):
+            write_png(os.path.join(pictures, "matching_vis_{}.png".format(frame_no)), picture)
     result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
                                  none_H_processing=_bool(args.none_H_processing),
-                                 features_type_list=features, ingest=args.ingest)
+                                 features_type_list=features, ingest=args.ingest, matching_sink=sink)
     return write_outputs(args, result, original_shape, stem, args.path_to_video)
+
+
+def output_folder(args, stem):
+    return os.path.join(os.getcwd(), args.experiment_name, stem)
 
 
 def write_outputs(args, result, original_shape, stem, spec=None):
@@ -122,7 +144,7 @@ def write_outputs(args, result, original_shape, stem, spec=None):
     from .processing.fixed_coordinate_system import from_original_to_fix
     from . import heatmap
 
-    save_folder = os.path.join(os.getcwd(), args.experiment_name, stem)
+    save_folder = output_folder(args, stem)
     os.makedirs(save_folder, exist_ok=True)
     path_to_homography_dict = os.path.join(save_folder, "dict_with_homography_matrix.json")
     with open(path_to_homography_dict, "w") as json_:

@@ -947,6 +947,34 @@ int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, co
                                    d_out, out_row_stride, out_frame_stride);
 }
 
+// ---- matching pictures (processing_visualization.py:22-57) -------------------------------------------------------------------------
+int evh_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
+                     int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status,
+                     int points, uint32_t color_bgr, uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = "evh_draw_matches: ";
+  if (!d_frames || !d_rows || !d_counts || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (npairs < 0 || w < 1 || h < 1 || row_cap < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame, no row capacity or negative npairs");
+  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
+  if (points != EVH_DRAW_REFERENCE && points != EVH_DRAW_OWN_FRAME) return evh_fail(c, EVH_ERR_INVALID, W + "unknown points value");
+  if (color_bgr >> 24) return evh_fail(c, EVH_ERR_INVALID, W + "color_bgr has bits above 24 set");
+  if (w > 16383) return evh_fail(c, EVH_ERR_CAPACITY, W + "w above 16383 (a picture's columns are held in 16 bits)");
+  const int64_t row = (int64_t)w * 3;
+  if (row_stride < row || out_row_stride < 2 * row) return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a row");
+  const int64_t frame = (h - 1) * row_stride + row, picture = (h - 1) * out_row_stride + 2 * row;
+  if ((npairs >= 1 && frame_stride < frame) || (npairs > 1 && out_frame_stride < picture))
+    return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a frame");
+  if (npairs == 0) return EVH_SUCCESS;
+  const int64_t out_bytes = picture + (npairs - 1) * out_frame_stride;
+  const int64_t frames_bytes = frame + ((int64_t)(npairs - 1) * frame_step + 1) * frame_stride;
+  const int64_t rows_bytes = (int64_t)npairs * row_cap * 4 * (int64_t)sizeof(float);
+  const uint8_t* rows8 = reinterpret_cast<const uint8_t*>(d_rows);
+  if (d_frames < d_out + out_bytes && d_out < d_frames + frames_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_frames overlaps d_out");
+  if (rows8 < d_out + out_bytes && d_out < rows8 + rows_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_rows overlaps d_out");
+  return evh_launch_draw_matches(c, d_frames, npairs, frame_step, w, h, row_stride, frame_stride, d_rows, row_cap, d_counts, d_status,
+                                 points, color_bgr, d_out, out_row_stride, out_frame_stride);
+}
+
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);

@@ -276,6 +276,11 @@ int detect_match_types(evh_ctx* c, const EvhBatch& B, const EvhBatchShape& S, co
   return evh_launch_merge(c, M, S.npairs);
 }
 
+// the context's record of the last batch whose static rows are resident (evh_batch_static_info / _rows): every entry that
+// writes pts2 / npts2 / pstatus of c->orb or c->mt forgets it first, a batch that ran through sets it
+void forget_static(evh_ctx* c) { c->static_bufs = nullptr; c->static_pairs = 0; }
+void record_static(evh_ctx* c, const EvhPairBufs& B, int npairs) { c->static_bufs = &B; c->static_pairs = npairs; }
+
 // frames -> H per pair slot.  Every refusal comes before the first launch and before anything is written (one exception as
 // before: a list entry on planes converts them before the geometry is set).
 int run_batch(evh_ctx* c, const EvhBatch& B) {
@@ -288,6 +293,7 @@ int run_batch(evh_ctx* c, const EvhBatch& B) {
   bool multi = B.list.use != EVH_LIST_FUSED_ORB;
   if (multi && (rc = check_types(c, B.who, B.list.types, B.list.ntypes, want))) return rc;
   if (B.list.use == EVH_LIST_MULTI_UNLESS_ORB && B.list.ntypes == 1 && want.orb) multi = false;
+  forget_static(c);
   if ((rc = multi ? detect_match_types(c, B, S, want) : detect_match_orb(c, B, S))) return rc;
   const EvhPairing& P = B.pairing;
   const evh_stream_seg* d_segs = nullptr;
@@ -296,7 +302,9 @@ int run_batch(evh_ctx* c, const EvhBatch& B) {
                            P.kind == EVH_PAIRS_UNIFORM ? EvhSolveLayout::streams((int)P.n - 1, P.nstreams, (int)P.n) :
                                                          EvhSolveLayout::ragged(S.npairs, P.nstreams, d_segs, S.max_pairs);
   const EvhRansacArgs R = solve_args(c, multi ? c->mt : c->orb, B.ransac, B.io);
-  return multi ? final_solve(c, R, L) : solve_pairs(c, R, S.npairs, L);     // (the multi-type front has done RANSAC #1 per type)
+  rc = multi ? final_solve(c, R, L) : solve_pairs(c, R, S.npairs, L);       // (the multi-type front has done RANSAC #1 per type)
+  if (!rc) record_static(c, multi ? c->mt : c->orb, S.npairs);              // the final solve only reads the static rows
+  return rc;
 }
 
 // final solve of pair slot 0 of the ORB buffers (its static rows are resident), optionally behind the superposition
@@ -435,12 +443,39 @@ int evh_stream_static_batch(evh_ctx* c, const uint8_t* d_frames, int nframes, in
   int rc = check_batch(c, B, S);
   if (rc) return rc;
   if (row_cap != c->kcap) return evh_fail(c, EVH_ERR_INVALID, "evh_stream_static_batch: row_cap must equal evh_orb_capacity()");
+  forget_static(c);
   if ((rc = detect_match_orb(c, B, S))) return rc;
   { EvhProfScope ps(c, EVH_ST_RANSAC_STATIC); rc = evh_launch_ransac_static(c, ransac_args(c, c->orb, B.ransac), S.npairs); }
   if (rc) return rc;
   EVH_HIP(c, hipMemcpyAsync(d_rows, c->orb.pts2, sizeof(float) * 4 * (size_t)c->kcap * S.npairs, hipMemcpyDeviceToDevice, c->stream));
   EVH_HIP(c, hipMemcpyAsync(d_counts, c->orb.npts2, sizeof(int) * (size_t)S.npairs, hipMemcpyDeviceToDevice, c->stream));
   EVH_HIP(c, hipMemcpyAsync(d_status1, c->orb.pstatus, sizeof(int) * (size_t)S.npairs, hipMemcpyDeviceToDevice, c->stream));
+  record_static(c, c->orb, S.npairs);
+  return EVH_SUCCESS;
+}
+
+int evh_batch_static_info(const evh_ctx* c, int* npairs, int* row_cap) {
+  if (!c || !npairs || !row_cap) return EVH_ERR_INVALID;
+  *npairs = c->static_bufs ? c->static_pairs : 0;
+  *row_cap = c->static_bufs ? c->static_bufs->cap : 0;
+  return EVH_SUCCESS;
+}
+
+int evh_batch_static_rows(evh_ctx* c, int first_pair, int npairs, float* d_rows, int row_cap, int32_t* d_counts,
+                          int32_t* d_status1) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = "evh_batch_static_rows: ";
+  if (!d_rows || !d_counts || !d_status1) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  const EvhPairBufs* B = c->static_bufs;
+  if (!B) return evh_fail(c, EVH_ERR_INVALID, W + "no batch whose static rows are still resident");
+  if (first_pair < 0 || npairs < 1 || npairs > c->static_pairs - first_pair)
+    return evh_fail(c, EVH_ERR_INVALID, W + "pair range outside the batch's pair slots");
+  if (row_cap != B->cap) return evh_fail(c, EVH_ERR_INVALID, W + "row_cap must equal the capacity evh_batch_static_info reports");
+  { int jr = evh_join_solve(c); if (jr) return jr; }           // RANSAC #1 and the static filter may run on the solve stream
+  const size_t p0 = (size_t)first_pair, n = (size_t)npairs;
+  EVH_HIP(c, hipMemcpyAsync(d_rows, B->pts2 + p0 * B->cap * 4, sizeof(float) * 4 * (size_t)B->cap * n, hipMemcpyDeviceToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(d_counts, B->npts2 + p0, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
+  EVH_HIP(c, hipMemcpyAsync(d_status1, B->pstatus + p0, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
   return EVH_SUCCESS;
 }
 
@@ -452,6 +487,7 @@ int evh_stream_scan(evh_ctx* c, const float* d_rows, int row_cap, const int32_t*
   if (row_cap < 1 || row_cap > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "row_cap larger than evh_orb_capacity()");
   if (((uintptr_t)d_rows) & 15) return evh_fail(c, EVH_ERR_INVALID, "d_rows must be 16-byte aligned");
   { int jr = evh_join_solve(c); if (jr) return jr; }                  // the scan uses slot 0 of the pair scratch
+  forget_static(c);
   EvhRansacArgs R = solve_args(c, c->orb, {ransac_thr, ransac_max_iters, ransac_conf, force_max_iters},
                                {d_state_in, d_state_out, d_H, d_status});
   R.pts2 = const_cast<float*>(d_rows); R.npts2 = const_cast<int*>(d_counts); R.status = const_cast<int*>(d_status1);
@@ -464,6 +500,7 @@ int evh_match_static_from_slots(evh_ctx* c, int cur_slot, int prev_slot, float* 
       prev_slot >= c->nframes_resident)
     return evh_fail(c, EVH_ERR_INVALID, "evh_match_static_from_slots: bad argument");
   { int jr = evh_join_solve(c); if (jr) return jr; }
+  forget_static(c);
   int rc = match_orb_pairs(c, 1, cur_slot, prev_slot, 0);
   if (rc) return rc;
   if ((rc = evh_launch_ransac_static(c, ransac_args(c, c->orb, kReferenceRansac), 1))) return rc;
@@ -483,6 +520,7 @@ int evh_compute_homography(evh_ctx* c, const float* h_pts, int n, const double* 
   if (!c || (!h_pts && n > 0) || !h_H || !h_status || n < 0) return evh_fail(c, EVH_ERR_INVALID, "evh_compute_homography: bad argument");
   if (n > c->kcap) return evh_fail(c, EVH_ERR_CAPACITY, "evh_compute_homography: too many rows");
   { int jr = evh_join_solve(c); if (jr) return jr; }
+  forget_static(c);
   const int zero = 0;
   EVH_HIP(c, hipMemcpyAsync(c->orb.pts2, h_pts, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   EVH_HIP(c, hipMemcpyAsync(c->orb.npts2, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));

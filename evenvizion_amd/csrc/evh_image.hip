@@ -570,6 +570,76 @@ __global__ __launch_bounds__(256) void k_heatmap_render(const double* __restrict
   warp_run_store<3>(out + (int64_t)f * out_img_stride + (int64_t)y * out_stride + (int64_t)x0 * 3, n, full && (vec & 1), v);
 }
 
+// Matching pictures (processing_visualization.py:22-57 as video_processing.py:78-81 calls it), in the rule include/evhip.h states
+// for evh_draw_matches: two launches, the frames first and the lines on top.
+// k_draw_paste: picture p = frame p * frame_step | frame p * frame_step + 1.  grid.x covers the runs of a picture row, both
+// halves; rows and pictures are walked by grid.y / grid.z.  A thread owns WARP_RUN adjacent pixels of one half and moves their 12
+// bytes as three words where the pointers and strides allow (vec bit 1: frames, bit 0: the left half of the pictures, bit 2: the
+// right half, which begins 3*w bytes into a row), bytewise otherwise and in runs cut by a half's right edge.
+__global__ __launch_bounds__(256) void k_draw_paste(const uint8_t* __restrict__ frames, int npairs, int frame_step, int w, int h,
+                                                    int64_t row_stride, int64_t frame_stride, uint8_t* __restrict__ out,
+                                                    int64_t out_stride, int64_t out_img_stride, int runs_per_half, int vec) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= 2 * runs_per_half) return;
+  const int half = u >= runs_per_half ? 1 : 0, x0 = (u - half * runs_per_half) * WARP_RUN;
+  const int n = min(WARP_RUN, w - x0);
+  const bool full = n == WARP_RUN, wide_in = full && (vec & 2), wide_out = full && (vec & (half ? 4 : 1));
+  for (int p = blockIdx.z; p < npairs; p += gridDim.z) {
+    const uint8_t* S = frames + ((int64_t)p * frame_step + half) * frame_stride + (int64_t)x0 * 3;
+    uint8_t* D = out + (int64_t)p * out_img_stride + ((int64_t)half * w + x0) * 3;
+    for (int y = blockIdx.y; y < h; y += gridDim.y) {
+      int v[WARP_RUN][3];
+#pragma unroll
+      for (int q = 0; q < WARP_RUN; q++) v[q][0] = v[q][1] = v[q][2] = 0;
+      warp_run_load<3>(S + (int64_t)y * row_stride, n, wide_in, v);
+      warp_run_store<3>(D + (int64_t)y * out_stride, n, wide_out, v);
+    }
+  }
+}
+// k_draw_lines: one wave per line, the waves of grid.x stride over the rows of a pair, grid.y over the pairs.  The lanes take
+// the pixels k = lane, lane + 64, ... <= D of the walk through the closed form of the minor offset, (2*d*k + D - 1) div (2*D): in
+// 32 bits while D < 2^15 (2*d*k + D - 1 < 2^31 then, as d <= D and k <= D), in 64 bits for the long lines that leave the picture
+// (D <= 81 918).  Every line of a call stores the same three bytes, so lines that share pixels need no order.
+__global__ __launch_bounds__(256) void k_draw_lines(const float* __restrict__ rows, int row_cap, const int32_t* __restrict__ counts,
+                                                    const int32_t* __restrict__ status, int npairs, int points, int w, int h,
+                                                    uint32_t color, uint8_t* __restrict__ out, int64_t out_stride,
+                                                    int64_t out_img_stride) {
+  const int lane = threadIdx.x & 63, wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = gridDim.x * (blockDim.x >> 6);
+  const uint8_t c0 = (uint8_t)color, c1 = (uint8_t)(color >> 8), c2 = (uint8_t)(color >> 16);
+  for (int p = blockIdx.y; p < npairs; p += gridDim.y) {
+    if (status && status[p] != EVH_PAIR_OK) continue;
+    const int n = min(max(counts[p], 0), row_cap);
+    uint8_t* pic = out + (int64_t)p * out_img_stride;
+    for (int r = wave; r < n; r += nwaves) {
+      const float* q = rows + ((int64_t)p * row_cap + r) * 4;
+      const float t0 = truncf(q[0]), t1 = truncf(q[1]), t2 = truncf(q[2]), t3 = truncf(q[3]);
+      // NaN and +-inf fail a comparison too; inside the range the conversions are exact
+      if (!(t0 >= -32768.f && t0 <= 32767.f && t1 >= -32768.f && t1 <= 32767.f && t2 >= -32768.f && t2 <= 32767.f &&
+            t3 >= -32768.f && t3 <= 32767.f))
+        continue;
+      int x1, y1, x2, y2;
+      if (points == EVH_DRAW_REFERENCE) { x1 = (int)t0; y1 = (int)t1; x2 = (int)t2 + w; y2 = (int)t3; }
+      else { x1 = (int)t2; y1 = (int)t3; x2 = (int)t0 + w; y2 = (int)t1; }
+      int dx = x2 - x1, dy = y2 - y1;
+      if (dx < 0) { x1 = x2; y1 = y2; dx = -dx; dy = -dy; }       // leftToRight: the walk starts at the left end
+      const int sy = dy < 0 ? -1 : 1, ady = dy < 0 ? -dy : dy;
+      const bool steep = ady > dx;                                // the major axis is y
+      const int D = steep ? ady : dx, d = steep ? dx : ady;
+      for (int k = lane; k <= D; k += 64) {
+        int m = 0;
+        if (D > 0)
+          m = D < 32768 ? (int)((2u * (unsigned)d * (unsigned)k + (unsigned)D - 1u) / (2u * (unsigned)D))
+                        : (int)((2ull * (unsigned)d * (unsigned)k + (unsigned)D - 1ull) / (2ull * (unsigned)D));
+        const int x = steep ? x1 + m : x1 + k, y = steep ? y1 + sy * k : y1 + sy * m;
+        if ((unsigned)x < 2u * (unsigned)w && (unsigned)y < (unsigned)h) {
+          uint8_t* o = pic + (int64_t)y * out_stride + 3 * (int64_t)x;
+          o[0] = c0; o[1] = c1; o[2] = c2;
+        }
+      }
+    }
+  }
+}
+
 struct HostTab { std::vector<int> start, cnt, si; std::vector<float> al; };
 
 void build_area_tab(int ssize, int dsize, double scale, HostTab& t) {
@@ -761,6 +831,28 @@ int evh_launch_heatmap_render(evh_ctx* c, const double* d_H, int n, int w, int h
   };
   if (!d_frames || alpha == 0.8) go(k_heatmap_render<false>);      // the integer blend, behind the exact test for its constant
   else go(k_heatmap_render<true>);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+// k_draw_paste, then k_draw_lines on top, over npairs >= 1 pictures (the entry has checked the arguments: w <= 16383)
+int evh_launch_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
+                            int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts,
+                            const int32_t* d_status, int points, uint32_t color_bgr, uint8_t* d_out, int64_t out_stride,
+                            int64_t out_img_stride) {
+  const int runs_per_half = (w + WARP_RUN - 1) / WARP_RUN;
+  // the pictures' stride is only used between the pictures of a call; the frames' always (a picture takes two frames)
+  const uintptr_t ois = npairs > 1 ? (uintptr_t)out_img_stride : 0;
+  const bool out_words = (((uintptr_t)d_out | (uintptr_t)out_stride | ois) & 3) == 0;
+  const int vec = (out_words ? 1 : 0) | ((((uintptr_t)d_frames | (uintptr_t)row_stride | (uintptr_t)frame_stride) & 3) == 0 ? 2 : 0) |
+                  (out_words && (w & 3) == 0 ? 4 : 0);
+  const dim3 pgrid((2 * runs_per_half + 255) / 256, std::min(h, 65535), std::min(npairs, 65535));
+  hipLaunchKernelGGL(k_draw_paste, pgrid, dim3(256), 0, c->stream, d_frames, npairs, frame_step, w, h, row_stride, frame_stride,
+                     d_out, out_stride, out_img_stride, runs_per_half, vec);
+  EVH_HIP(c, hipGetLastError());
+  const dim3 lgrid(std::min(64, (row_cap + 3) / 4), std::min(npairs, 65535));
+  hipLaunchKernelGGL(k_draw_lines, lgrid, dim3(256), 0, c->stream, d_rows, row_cap, d_counts, d_status, npairs, points, w, h,
+                     color_bgr, d_out, out_stride, out_img_stride);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;
 }

@@ -195,6 +195,9 @@ struct evh_ctx {
   float* d_surf_det = nullptr; float* d_surf_trace = nullptr;   // [group] the 20 Hessian layers
   // multi-type pairs (frame_processing.py:91-104): per-type match / static rows, their concatenation, the merged rows
   EvhPairBufs mt;                 // stride mt.cap = kcap + sift.cap + surf.cap
+  // the last batch whose static rows (pts2, npts2, pstatus) are still resident: which of orb / mt it used and its pair
+  // slots (evh_batch_static_info / _rows); NULL, 0: none.  Set and cleared in evh_batch.hip, by the entries evhip.h names.
+  const EvhPairBufs* static_bufs = nullptr; int static_pairs = 0;
   float* d_acc = nullptr; int* d_nacc = nullptr; int* d_accstatus = nullptr;
   std::vector<void**> owned;      // the pointer members above that hold a live hipMalloc (dalloc / grow): what evh_destroy frees
   size_t bytes_allocated = 0;
@@ -323,6 +326,10 @@ int evh_launch_fixed_plane(evh_ctx* c, const double* d_H, int n, int w, int h, d
 int evh_launch_heatmap_render(evh_ctx* c, const double* d_H, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
                               int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
                               uint8_t* d_out, int64_t out_stride, int64_t out_img_stride);
+int evh_launch_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
+                            int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts,
+                            const int32_t* d_status, int points, uint32_t color_bgr, uint8_t* d_out, int64_t out_stride,
+                            int64_t out_img_stride);
 // N4: SIFT (evh_sift.hip)
 int evh_sift_allocate(evh_ctx* c, int max_sift_features);
 int evh_launch_sift(evh_ctx* c, int nframes, int w, int h);

@@ -113,23 +113,29 @@ def _upload(B, j, spans, cur):
     cur.wait_event(B["up_done"][j])
 
 
-def _results_to_host(c, B, j, npairs, cur):
+def _results_to_host(c, B, j, npairs, cur, extra=()):
     """H and status of the first npairs pair slots of buffer j back through pinned memory, behind everything context `c` has
-    enqueued; all_done[j] marks their arrival (cur: torch's current stream, None on the CPU)."""
+    enqueued; all_done[j] marks their arrival (cur: torch's current stream, None on the CPU).  extra: further (host, device)
+    tensors whose first npairs entries come back with them."""
     if cur is not None:
         c.order_torch_after()
     B["H_host"][j][:npairs].copy_(B["H_dev"][j][:npairs], non_blocking=True)
     B["st_host"][j][:npairs].copy_(B["st_dev"][j][:npairs], non_blocking=True)
+    for host, device in extra:
+        host[:npairs].copy_(device[:npairs], non_blocking=True)
     if cur is not None:
         B["all_done"][j].record(cur)
 
 
-def _pairs_into(result, frame_no, Hs, sts, none_H_processing, capture_index=None):
+def _pairs_into(result, frame_no, Hs, sts, none_H_processing, capture_index=None, before_pair=None):
     """Consecutive pairs (Hs f64[k,3,3], sts i32[k]) of one capture into its dictionary: the pair ending at frame f becomes
     result[f] = {"H": ...}.  frame_no: the newest frame already paired; -> the same after these.  capture_index names the
-    capture in the log line of the many-captures driver."""
-    for Hk, sk in zip(Hs, sts):
+    capture in the log line of the many-captures driver.  before_pair(k, f) is called for pair k of these, ending at frame f,
+    before its status is looked at: what the reference does between matching and compute_homography."""
+    for k, (Hk, sk) in enumerate(zip(Hs, sts)):
         frame_no += 1
+        if before_pair is not None:
+            before_pair(k, frame_no)
         if sk != PAIR_OK:
             if capture_index is None:
                 logging.info("pair ending at frame %d: no homography (status %d)", frame_no, int(sk))
@@ -186,21 +192,81 @@ def rerun_on_larger_slots(ctx, features, nfeatures, dw, dh, max_frames, run, ove
             break
 
 
+class _MatchingPictures:
+    """What get_homography_dict(matching_sink=) adds to a chunk: the resized BGR frames, the rows that entered the final solve
+    and the pictures on the device, and the pictures and front statuses back through pinned memory with the chunk's results."""
+
+    def __init__(self, B, chunk_frames, planes, w0, h0, dw, dh, points, dev):
+        import torch
+        from .._lib import DRAW_POINTS
+        if points not in DRAW_POINTS:
+            raise ValueError("matching_points must be one of %s" % sorted(DRAW_POINTS))
+        self.points, self.planes, self.size, self.dev = points, planes, (w0, h0), dev
+        npairs = chunk_frames - 1
+        self.bgr = torch.empty((chunk_frames, h0, w0, 3), dtype=torch.uint8, device=dev) if planes else None
+        self.small = torch.empty((chunk_frames, dh, dw, 3), dtype=torch.uint8, device=dev) if (dw, dh) != (w0, h0) else None
+        # the picture and front-status buffers live with the staging set B (runtime.staging: pinning is slow, a service
+        # processes many videos of one size) and go when it goes
+        key = ("pictures", dw, dh)
+        if key not in B:
+            pin = runtime._pin if dev.type == "cuda" else (lambda t: t)
+            B[key] = ([torch.empty((npairs, dh, 2 * dw, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
+                      [pin(torch.empty((npairs, dh, 2 * dw, 3), dtype=torch.uint8)) for _ in range(2)],
+                      [torch.empty(npairs, dtype=torch.int32, device=dev) for _ in range(2)],
+                      [pin(torch.empty(npairs, dtype=torch.int32)) for _ in range(2)])
+        self.pic_dev, self.pic_host, self.st1_dev, self.st1_host = B[key]
+        self.rows = {}          # row capacity of a context -> (rows, counts): a re-run on larger slots has its own
+
+    def draw(self, c, frames, j):
+        """Behind the batch entry `c` has just run on `frames` (the chunk as uploaded): the pictures of its pairs into
+        pic_dev[j], their front statuses into st1_dev[j].  -> what _results_to_host brings back besides H and status."""
+        import torch
+        nb = frames.shape[0]
+        src = frames
+        if self.planes:
+            c.yuv420_to_bgr(src, self.bgr[:nb], size=self.size)
+            src = self.bgr[:nb]
+        if self.small is not None:
+            c.resize_area(src, self.small[:nb])
+            src = self.small[:nb]
+        cap = c.batch_static_info()[1]
+        if cap not in self.rows:
+            self.rows[cap] = (torch.empty((self.pic_dev[0].shape[0], cap, 4), dtype=torch.float32, device=self.dev),
+                              torch.empty(self.pic_dev[0].shape[0], dtype=torch.int32, device=self.dev))
+        rows, counts = self.rows[cap]
+        c.batch_static_rows(0, nb - 1, rows, counts, self.st1_dev[j])
+        c.draw_matches(src, rows, counts, self.pic_dev[j][:nb - 1], status=self.st1_dev[j], frame_step=1, points=self.points)
+        return [(self.pic_host[j], self.pic_dev[j]), (self.st1_host[j], self.st1_dev[j])]
+
+
 def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_processing=True,
-                        nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES, features_type_list=None, ingest="bgr"):
+                        nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES, features_type_list=None, ingest="bgr",
+                        matching_sink=None, matching_points="reference"):
     """capture: anything with read() -> (bool, BGR uint8 frame) (cv2.VideoCapture duck type).
     ingest: "bgr" (always read(); the default until the plane path's end-to-end rates have been measured against it, see
     DESIGN.md 3a), "auto" (planes when the capture can deliver them, see _first_planes), "yuv420" (planes or ValueError).
     features_type_list: the list the reference hands to FrameProcessing (frame_processing.py:37-40), e.g. ["SIFT", "ORB"];
     None = frame_processing.DEFAULT_FEATURES = the reference's own default ["SURF", "SIFT", "ORB"]; the north-star hot path
-    is features_type_list=["ORB"] (one fused ORB pipeline, evh_stream_homography_batch_resized)."""
+    is features_type_list=["ORB"] (one fused ORB pipeline, evh_stream_homography_batch_resized).
+    matching_sink: a callable matching_sink(frame_no, picture) that receives the reference's matching picture of every pair
+    whose matching succeeded (front status OK: the reference draws before compute_homography, so a pair that then fails still
+    has one, a pair without matches has none), in frame order, frame_no being the number of the pair's newer frame (the i of
+    matching_vis_{i}.png, first 2) and picture a uint8 array [h, 2w, 3] (BGR, the resized previous frame | the resized current
+    frame, one green line per static match; the array is the sink's to keep).  When the call raises for a pair, the pictures
+    up to that pair have been delivered.  matching_points: "reference" draws what video_processing.py:69-80 draws -- the newer
+    frame's points on the older frame's half and vice versa --, "own_frame" each point on its own frame.  A capture of gray
+    frames is refused with a sink (ValueError).  None: nothing of this is computed."""
     import torch
     if matching_path:
-        raise NotImplementedError("matching visualisation (draw_matches + imwrite) is outside the MI355X hot path; "
-                                  "call with matching_path=None")
+        raise NotImplementedError("matching_path (draw_matches + imwrite into a directory) is not taken: pass "
+                                  "matching_sink=callable(frame_no, picture) -- matching_pictures.write_png stores a picture; "
+                                  "the command line has --matching_pictures")
     if ingest not in ("auto", "bgr", "yuv420"):
         raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
     first, planes, w0, h0 = _open_capture(capture, ingest)
+    if matching_sink is not None and not planes and first.ndim != 3:
+        raise ValueError("matching_sink takes BGR frames [h,w,3] or decoded planes: the picture is a BGR picture, and the "
+                         "reference's capture delivers no gray frames")
     dw, dh = resized_shape((h0, w0), resize_width)
     features = _feature_list(features_type_list)
     # the Context method of a chunk and what it takes besides frames, outputs and state, from planes x multi: the decoder's
@@ -209,7 +275,9 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     method = "stream_homography_batch" + ("_types" if multi else "") + ("_yuv420" if planes else "")
     size, types = ((w0, h0),) if planes else (), (features,) if multi else ()
     # one staging buffer (pinned host / device) is capped in bytes: 4K BGR frames give 21-frame chunks, not 64
-    chunk_frames = runtime.chunk_frames_for(first.nbytes, max(2, int(chunk_frames)))
+    # (with a sink, a pair's picture of 6*dw*dh bytes is staged too)
+    chunk_frames = runtime.chunk_frames_for(max(first.nbytes, 6 * dw * dh if matching_sink is not None else 0),
+                                            max(2, int(chunk_frames)))
     # sized for the RESIZED frames: only those go through ORB (evh_resize_area_u8 does not depend on the context's
     # geometry), so a 4K source with resize_width=400 allocates 400-wide buffers
     ctx = runtime.get_context(dw, dh, chunk_frames, nfeatures, sift="SIFT" in features, surf="SURF" in features)
@@ -228,13 +296,19 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     cuda = dev.type == "cuda"          # (the host-loop unit test drives this function on the CPU with a scripted context)
     cur = torch.cuda.current_stream(dev) if cuda else None
 
+    pictures = None
+    if matching_sink is not None:
+        pictures = _MatchingPictures(B, chunk_frames, planes, w0, h0, dw, dh, matching_points, dev)
+
     homography_dict = {}
     frame_no = [1]          # 1-based index of the newest frame already paired
 
     def launch(c, jb, nb, with_state):
         getattr(c, method)(devbuf[jb][:nb], *size, H_dev[jb], st_dev[jb], *types, state_in=state if with_state else None,
                            state_out=state, nfeatures=nfeatures, resize_to=(dw, dh))
-        _results_to_host(c, B, jb, nb - 1, cur)
+        # the pictures are drawn here so that a re-run on larger slots draws them again from its own rows
+        extra = pictures.draw(c, devbuf[jb][:nb], jb) if pictures is not None else ()
+        _results_to_host(c, B, jb, nb - 1, cur, extra)
 
     def rerun_with_larger_slots(jb, nb, later):
         """A frame of chunk jb delivered more tied key points than a frame slot of `ctx` holds: the chunk is re-run from
@@ -261,8 +335,15 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
             all_done[jb].synchronize()
         if (st_host[jb][:nb - 1].numpy() == PAIR_CAPACITY).any():
             rerun_with_larger_slots(jb, nb, later)
+        deliver = None
+        if pictures is not None:
+            st1, pics = pictures.st1_host[jb].numpy(), pictures.pic_host[jb].numpy()
+
+            def deliver(k, f):
+                if st1[k] == PAIR_OK:
+                    matching_sink(f, pics[k].copy())
         frame_no[0] = _pairs_into(homography_dict, frame_no[0], H_host[jb][:nb - 1].numpy().reshape(-1, 3, 3),
-                                  st_host[jb][:nb - 1].numpy(), none_H_processing)
+                                  st_host[jb][:nb - 1].numpy(), none_H_processing, before_pair=deliver)
 
     j, n = 0, 1
     host_np[0][0] = first

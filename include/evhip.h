@@ -25,6 +25,10 @@
  *                                 visualization/stabilization.py:129-172, 220-249
  *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
  *                                 visualization/processing_visualization.py:336-344
+ *   evh_batch_static_info         the length of the static point lists that reach draw_matches   video_processing.py:69
+ *   evh_batch_static_rows         concatenate_all_features_types' two point lists as draw_matches gets them   video_processing.py:69,78-80
+ *   evh_draw_matches              draw_matches + imwrite: matching_vis_{i}.png   video_processing.py:78-81,
+ *                                 visualization/processing_visualization.py:22-57
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -491,6 +495,71 @@ int evh_warp_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes
 int evh_heatmap_render(evh_ctx* ctx, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
                        int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
                        uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride);
+
+/* ---- matching pictures: draw_matches (processing_visualization.py:22-57) as video_processing.py:78-81 calls it -------------------- */
+/* The rows a batch handed to compute_homography, read back out of the context.  A context records its LAST BATCH: which pair
+ * buffers it used (the fused ORB path or the multi-type path, after accumulate and merge) and how many pair slots it had (pair
+ * slot p as in the entry that ran: (frame 2p + 1, frame 2p) for independent pairs, else (frame p + 1, frame p); the slots
+ * between two streams of a multi-stream / ragged batch are computed and belong to no stream).  The record is set by every
+ * batch entry -- evh_pair_homography_batch[_types], evh_stream_homography_batch[_resized|_types|_yuv420|_types_yuv420],
+ * evh_multi_stream_homography_batch, evh_streams_homography_batch[_yuv420] -- and by evh_stream_static_batch, when they return
+ * EVH_SUCCESS.  It is cleared by every other entry that writes those pair buffers: evh_match_static_from_slots,
+ * evh_pair_from_slots, evh_compute_homography, evh_stream_scan; a batch entry that returns an error may leave it cleared.
+ * (The detect entries, the matchers and filters on caller buffers, evh_find_homography_ransac* and evh_static_filter use other
+ * buffers and leave it alone.)
+ * evh_batch_static_info: the pair slots and the row capacity (rows per pair slot) of that batch; 0, 0 when there is none.   */
+int evh_batch_static_info(const evh_ctx* ctx, int* npairs, int* row_cap);
+/* Pair slots first_pair .. first_pair + npairs - 1 of that batch into caller DEVICE buffers: d_rows f32[npairs][row_cap][4], rows
+ * (ax, ay, bx, by) with a = the current frame and b = the previous frame as evh_stream_static_batch lays them out, rows past a
+ * pair's count hold whatever the buffers held; d_counts i32[npairs]; d_status1 i32[npairs] the FRONT status (EVH_PAIR_* of
+ * detect, match and static filter -- what evh_stream_static_batch calls the phase-1 status -- not the final one: a pair whose
+ * front status is EVH_PAIR_OK entered compute_homography with these rows, whatever came of it).  Three contiguous device-to-device
+ * copies on the context's stream, ordered behind an asynchronous solve by a stream wait; never synchronises the host, nothing is
+ * ever truncated.  Refused with EVH_ERR_INVALID before anything is enqueued, outputs untouched: a NULL pointer, first_pair < 0,
+ * npairs < 1, first_pair + npairs beyond the batch's pair slots, no resident batch, row_cap other than the reported capacity. */
+int evh_batch_static_rows(evh_ctx* ctx, int first_pair, int npairs, float* d_rows, int row_cap, int32_t* d_counts,
+                          int32_t* d_status1);
+/* The matching pictures.  Picture p (into d_out + p*out_frame_stride, rows at out_row_stride) is BGR, h rows of 2*w pixels: the
+ * left half is frame p*frame_step of d_frames (BGR, w x h, rows at row_stride, frames at frame_stride) -- the PREVIOUS frame --
+ * the right half frame p*frame_step + 1, the CURRENT frame; frame_step is 1 for streams and ragged batches and 2 for
+ * independent pairs.  On top, one line of colour color_bgr = b | g << 8 | r << 16 (the reference draws (0, 255, 0) = 0x00ff00) per
+ * row r < min(d_counts[p], row_cap) of d_rows f32[npairs][row_cap][4] (a count above row_cap is taken as row_cap, a negative one as
+ * 0: nothing is read past a pair's rows); with d_status given (it may be NULL) a picture whose d_status[p] != EVH_PAIR_OK gets no
+ * lines and is the two frames only.
+ * Ends of the line of row (ax, ay, bx, by), trunc toward zero as Python's int():
+ *   points == EVH_DRAW_REFERENCE (0): (trunc(ax), trunc(ay)) and (trunc(bx) + w, trunc(by)).  With the rows of a batch (a = the
+ *     current frame) the current frame's points land on the previous frame's half and vice versa: that is what
+ *     video_processing.py:69-80 draws, because concatenate_all_features_types returns self's (the newer frame's) points first
+ *     and draw_matches puts its first point list on its first image.  The quirk is kept as the default.
+ *   points == EVH_DRAW_OWN_FRAME (1): (trunc(bx), trunc(by)) and (trunc(ax) + w, trunc(ay)): each point on its own frame.
+ * A row with a coordinate that is not finite, or whose truncated value lies outside [-32768, 32767], is skipped (the reference
+ * would raise there: this library's choice).
+ * The line is the 8-connected walk of OpenCV 3.4.2's LineIterator with leftToRight, which cv2.line(..., thickness=1) uses, from
+ * pt1 (first end above) to pt2:
+ *   1. (dx, dy) = pt2 - pt1.  If dx < 0 the ends are swapped and (dx, dy) negated; with dx == 0 the walk starts at pt1.
+ *   2. sy = sign(dy), dy = |dy|.  If dy > dx the major axis is y, stepped by sy, and the minor axis is x, stepped by +1;
+ *      otherwise the major axis is x, stepped by +1, and the minor axis is y, stepped by sy.
+ *   3. With D the major and d the minor extent: err = D - 2d, and D + 1 pixels are emitted, the first at the start.
+ *   4. After each pixel: if err < 0 the minor axis steps and err += 2D; then, always, the major axis steps and err -= 2d.
+ * Equivalently pixel k = 0..D has the minor offset (2*d*k + D - 1) div (2*D) for D > 0, which is how the kernel shares a line
+ * among lanes.  (0,0) -> (5,2) and (5,2) -> (0,0) both give (0,0) (1,0) (2,1) (3,1) (4,2) (5,2).
+ * Pixels outside [0, 2w) x [0, h) are not written.  cv2.line clips the segment to the image first, which can shift interior
+ * pixels of a line that leaves it, so equality with cv2.line is claimed only for lines inside the picture (key points never
+ * leave their frame) -- and that claim rests on the rule above as restated from OpenCV's source: no OpenCV binary was at hand
+ * to compare pictures with.
+ * Two launches on the context's stream, the frames first and the lines on top; all lines of a call share one colour, so
+ * lines that cross or coincide need no order.  Every byte of every output row inside 6*w is written, bytes between rows are
+ * not.  Only caller buffers are used: nothing depends on the sizes given to evh_create.  Refused before anything is launched,
+ * outputs untouched -- EVH_ERR_INVALID: a NULL d_frames, d_rows, d_counts or d_out, w, h or row_cap < 1, npairs < 0, frame_step
+ * not 1 or 2, an unknown points value, bits above 24 set in color_bgr, a stride shorter than its row / frame (row strides
+ * always; frame_stride when npairs >= 1, out_frame_stride when npairs > 1), d_out overlapping d_frames or d_rows;
+ * EVH_ERR_CAPACITY: w > 16383.  npairs == 0 succeeds and does nothing.  Speed, not results, depends on alignment: the paste moves
+ * 4 pixels as three words where the pointers, strides and w allow it.  Does not synchronise.                                  */
+enum { EVH_DRAW_REFERENCE = 0, EVH_DRAW_OWN_FRAME = 1 };
+int evh_draw_matches(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
+                     int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts,
+                     const int32_t* d_status /* may be NULL */, int points, uint32_t color_bgr, uint8_t* d_out,
+                     int64_t out_row_stride, int64_t out_frame_stride);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

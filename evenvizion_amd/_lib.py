@@ -104,6 +104,8 @@ SIGNATURES = {
     # stabilised output: frames warped into the fixed plane
     "evh_warp_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
+    "evh_trail_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
+    "evh_trail_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     # heat-map pictures: colour index, table, blend over the frame
     "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
     # matching pictures: the rows a batch handed to its final solve, and the two frames side by side with a line per row
@@ -585,6 +587,40 @@ class Context:
             self._check(self.lib.evh_warp_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
         else:
             self._check(self.lib.evh_warp_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+
+    def trail_fixed_plane(self, frames, mats, canvas, origin, out=None, rects=None, inverse_map=False, size=None):
+        """The trail of the stabilised view (evh_trail_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h): per
+        frame the canvas takes the frame, the picture of it goes to out[k] with the white outline of rects[k], and the canvas
+        is dimmed.  frames: CUDA uint8 [n,h,w,3] (BGR), rows and frames may be strided, or decoded planes (see _yuv420;
+        size=(w, h) for packed I420 frames).  mats: CUDA float64, n*9 contiguous elements, as for warp_fixed_plane.  canvas:
+        CUDA uint8 [dh,dw,3], rows may be strided: read, carried through the frames and written back.  out: [n,dh,dw,3], rows
+        and pictures may be strided, or None = the canvas only advances.  rects: CUDA int32, n*4 contiguous elements
+        (x0, y0, x1, y1) in canvas pixels, or None.  origin=(ox, oy) as for warp_fixed_plane.  Does not synchronise."""
+        import torch
+        self._enter()
+        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
+        if planes:
+            d, n, sw, sh = self._yuv420(frames, size, self.device)
+        else:
+            fp, sw, sh, frs, ffs = self._image_rows(frames, 3, 1, "frames")
+            n = frames.shape[0]
+        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
+                or mats.numel() != 9 * n:
+            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        if rects is not None and (rects.dtype != torch.int32 or not rects.is_cuda or rects.device.index != self.device or
+                                  not rects.is_contiguous() or rects.numel() != 4 * n):
+            raise ValueError("rects must be a contiguous CUDA int32 tensor of n*4 elements")
+        cp, dw, dh, crs, _ = self._image_rows(canvas, 3, 0, "canvas")
+        op, ors, ofs = None, 0, 0
+        if out is not None:
+            op, ow, oh, ors, ofs = self._image_rows(out, 3, 1, "out")
+            if (out.shape[0], ow, oh) != (n, dw, dh):
+                raise ValueError("out must be [n,dh,dw,3] for a canvas [dh,dw,3]")
+        tail = (mats.data_ptr(), int(bool(inverse_map)), _ptr(rects), cp, crs, op, ors, ofs, dw, dh, int(origin[0]), int(origin[1]))
+        if planes:
+            self._check(self.lib.evh_trail_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
+        else:
+            self._check(self.lib.evh_trail_fixed_plane(self.h, fp, n, sw, sh, frs, ffs, *tail))
 
     def heatmap_render(self, Hsup, out, lut, frames=None, heatmap_constant=1000.0, alpha=0.8, saturate=False):
         """The heat-map pictures of n superposed matrices (evh_heatmap_render, the arithmetic is stated in include/evhip.h).

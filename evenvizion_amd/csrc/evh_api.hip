@@ -921,6 +921,67 @@ int evh_warp_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, 
                           d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
 }
 
+// ---- the trail: the fixed plane with earlier frames dimmed and the frame outlined (stabilization.py:21-97, 129-172) ----------
+// the argument checks of both forms; every refusal comes before the launch
+static int trail_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
+                             int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride, uint8_t* d_out,
+                             int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = std::string(who) + ": ";
+  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
+  if (!d_M || !d_canvas) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
+  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
+  if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  const int64_t row = (int64_t)dw * 3, srow = (int64_t)sw * 3;
+  const int64_t canvas = (dh - 1) * canvas_stride + row, picture = (dh - 1) * out_stride + row;
+  if (canvas_stride < row || (d_out && (out_stride < row || (nframes > 1 && out_img_stride < picture))))
+    return evh_fail(c, EVH_ERR_INVALID, W + "canvas or output stride smaller than a row / picture");
+  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
+  if (nframes == 0) return EVH_SUCCESS;
+  if (F.yuv)
+    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  // the byte ranges the launch reads and writes: canvas and pictures apart from each other and from the frames
+  struct Span { const uint8_t* p; int64_t n; };
+  const auto meet = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
+  const Span cv{d_canvas, canvas}, pic{d_out, d_out ? picture + (nframes - 1) * out_img_stride : 0};
+  Span srcs[3]; int nsrc = 1;
+  if (F.yuv) {
+    const evh_yuv420& s = *F.yuv;
+    const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
+    const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
+    const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
+    srcs[0] = {s.d_y, yb}; srcs[1] = {s.d_cb, cb}; srcs[2] = {s.d_cr, cb}; nsrc = 3;
+  } else {
+    srcs[0] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride};
+  }
+  if (d_out && meet(pic, cv)) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps d_canvas");
+  for (int i = 0; i < nsrc; i++) {
+    if (d_out && meet(pic, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps the frames");
+    if (meet(cv, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_canvas overlaps the frames");
+  }
+  return evh_launch_trail_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, d_rect, d_canvas, canvas_stride, d_out, out_stride,
+                                      out_img_stride, dw, dh, ox, oy);
+}
+
+int evh_trail_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int64_t row_stride,
+                          int64_t frame_stride, const double* d_M, int inverse_map, const int32_t* d_rect, uint8_t* d_canvas,
+                          int64_t canvas_row_stride, uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride, int dw,
+                          int dh, int ox, int oy) {
+  return trail_fixed_plane(c, "evh_trail_fixed_plane", packed_frames(d_frames, 3, row_stride, frame_stride), nframes, sw, sh, d_M,
+                           inverse_map, d_rect, d_canvas, canvas_row_stride, d_out, out_row_stride, out_frame_stride, dw, dh, ox, oy);
+}
+
+int evh_trail_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_row_stride,
+                                 uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride, int dw, int dh, int ox, int oy) {
+  return trail_fixed_plane(c, "evh_trail_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, d_rect,
+                           d_canvas, canvas_row_stride, d_out, out_row_stride, out_frame_stride, dw, dh, ox, oy);
+}
+
 // ---- heat-map pictures (processing_visualization.py:336-344) -----------------------------------------------------------------------
 int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
                        int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,

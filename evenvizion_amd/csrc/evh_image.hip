@@ -510,6 +510,107 @@ __global__ __launch_bounds__(256) void k_warp_fixed_plane(SRC src, int nframes, 
   }
 }
 
+// The trail (stabilization.py:21-44, 129-172, 252-290): EVH_WARP_HISTORY with the colour step include/evhip.h states for
+// evh_trail_fixed_plane between the frames.  g_trail_tab holds S[256] | H[256], built by the launcher on the host in double
+// and uploaded once per context; a workgroup stages it in LDS, two entries per thread (the look-ups are per lane).
+__device__ int32_t g_trail_tab[512];
+// BGR -> (h, s, v), int32: h in [0, 179], s and v in [0, 255]
+__device__ __forceinline__ void trail_to_hsv(const int32_t* tab, const int (&p)[3], int& h, int& s, int& v) {
+  const int b = p[0], g = p[1], r = p[2];
+  v = max(b, max(g, r));
+  const int d = v - min(b, min(g, r));
+  s = (d * tab[v] + 2048) >> 12;
+  const int t = v == r ? g - b : v == g ? b - r + 2 * d : r - g + 4 * d;
+  h = (t * tab[256 + d] + 2048) >> 12;
+  if (h < 0) h += 180;
+}
+// (h, s, v) -> BGR, IEEE float32 with one rounding per operation (the unit is built with -ffp-contract=off; the intrinsics say
+// so where a product feeds a sum).  s == 0 needs no case of its own: sf = 0 makes every entry of tab vf * 1.
+__device__ __forceinline__ void trail_from_hsv(int h, int s, int v, int (&o)[3]) {
+  float hf = __fmul_rn((float)h, __uint_as_float(0x3D088889u));   // 6.f / 180.f
+  while (hf >= 6.f) hf = __fsub_rn(hf, 6.f);
+  const int k = (int)hf;                                         // floor: hf >= 0
+  const float f = __fsub_rn(hf, (float)k);
+  const float K = __uint_as_float(0x3B808081u);                  // 1.f / 255.f
+  const float sf = __fmul_rn((float)s, K), vf = __fmul_rn((float)v, K);
+  const float t0 = vf, t1 = __fmul_rn(vf, __fsub_rn(1.f, sf)), t2 = __fmul_rn(vf, __fsub_rn(1.f, __fmul_rn(sf, f))),
+              t3 = __fmul_rn(vf, __fsub_rn(1.f, __fmul_rn(sf, __fsub_rn(1.f, f))));
+  // sector k -> which of t0..t3 is b, g, r: {1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0}, two bits per sector
+  const unsigned sel[3] = {0x835u, 0x583u, 0x358u};
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    const unsigned i = (sel[ch] >> (2 * k)) & 3u;
+    const float x = i == 0 ? t0 : i == 1 ? t1 : i == 2 ? t2 : t3;
+    o[ch] = (int)fminf(fmaxf(__builtin_rintf(__fmul_rn(x, 255.f)), 0.f), 255.f);
+  }
+}
+// canvas and out are distinct buffers (the entry refuses an overlap); a thread reads only the canvas bytes it later writes.
+// vec bit 0: out moves as words, bit 1: canvas does.  The 256 threads of a block all reach the barrier; those past the last
+// run then leave.
+template <class SRC>
+__global__ __launch_bounds__(256) void k_trail_fixed_plane(SRC src, int nframes, int sw, int sh, const double* __restrict__ M,
+                                                           int inverse_map, const int32_t* __restrict__ rect, uint8_t* canvas,
+                                                           int64_t canvas_stride, uint8_t* out, int64_t out_stride,
+                                                           int64_t out_img_stride, int dw, int ox, int oy, int runs_per_row,
+                                                           unsigned nruns, int vec) {
+  __shared__ int32_t tab[512];
+  tab[threadIdx.x] = g_trail_tab[threadIdx.x];
+  tab[256 + threadIdx.x] = g_trail_tab[256 + threadIdx.x];
+  __syncthreads();
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nruns) return;
+  const int y = (int)(t / (unsigned)runs_per_row), x0 = ((int)t - y * runs_per_row) * WARP_RUN;
+  const int n = min(WARP_RUN, dw - x0);
+  const bool full = n == WARP_RUN;
+  const double Y = (double)((int64_t)y + oy);
+  double X[WARP_RUN];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) X[p] = (double)((int64_t)x0 + p + ox);
+  // the two pictures that need no pixel: show of a colour with V < 2, and show of the white outline
+  int dark[3] = {0, 0, 0}, white[3] = {0, 0, 0};
+  if (out) {
+    const int w255[3] = {255, 255, 255};
+    int h, s, v;
+    trail_to_hsv(tab, w255, h, s, v);
+    trail_from_hsv(h, s, v - 2, white);
+    trail_from_hsv(222, 12, 31, dark);
+  }
+  uint8_t* const crow = canvas + (int64_t)y * canvas_stride + (int64_t)x0 * 3;
+  int c[WARP_RUN][3];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) c[p][0] = c[p][1] = c[p][2] = 0;
+  warp_run_load<3>(crow, n, full && (vec & 2), c);
+  for (int k = 0; k < nframes; k++) {
+    const WarpMap A = warp_map(M + 9 * (int64_t)k, inverse_map);
+    int rx0 = 0, ry0 = 0, rx1 = -1, ry1 = -1;
+    if (rect) { rx0 = rect[4 * k]; ry0 = rect[4 * k + 1]; rx1 = rect[4 * k + 2]; ry1 = rect[4 * k + 3]; }
+    const bool yin = y >= ry0 && y <= ry1, yedge = y == ry0 || y == ry1;
+    int q[WARP_RUN][3];
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      q[p][0] = q[p][1] = q[p][2] = 0;
+      if (p >= n) continue;
+      warp_sample(src, k, A, X[p], Y, sw, sh, c[p]);
+      const int x = x0 + p;
+      const bool outline = yin && x >= rx0 && x <= rx1 && (yedge || x == rx0 || x == rx1);
+      // keep(c); where V >= 2 it is show(c) too, where V < 2 it is black and the picture is the constant
+      const bool lit = max(c[p][0], max(c[p][1], c[p][2])) >= 2;
+      q[p][0] = dark[0]; q[p][1] = dark[1]; q[p][2] = dark[2];
+      if (lit) {
+        int h, s, v;
+        trail_to_hsv(tab, c[p], h, s, v);
+        trail_from_hsv(h, s, v - 2, c[p]);
+        q[p][0] = c[p][0]; q[p][1] = c[p][1]; q[p][2] = c[p][2];
+      } else {
+        c[p][0] = c[p][1] = c[p][2] = 0;
+      }
+      if (outline) { q[p][0] = white[0]; q[p][1] = white[1]; q[p][2] = white[2]; }
+    }
+    if (out) warp_run_store<3>(out + (int64_t)k * out_img_stride + (int64_t)y * out_stride + (int64_t)x0 * 3, n, full && (vec & 1), q);
+  }
+  warp_run_store<3>(crow, n, full && (vec & 2), c);
+}
+
 // Heat-map pictures (processing_visualization.py:336-344 without part_line): k_fixed_plane's field taken to a colour index,
 // looked up in a 256-entry BGR table and laid over the frame, in the arithmetic include/evhip.h states for evh_heatmap_render.
 // grid.y = frame; a thread owns WARP_RUN adjacent pixels of a row and moves their 12 bytes as three words where the pointers and
@@ -812,6 +913,47 @@ int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, i
   if (src.channels == 3)
     return launch_warp<3>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
   return launch_warp<1>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
+}
+
+// the tables of evh_trail_fixed_plane's colour step, in double on the host: S[i] = rint((255 << 12) / i),
+// H[i] = rint((180 << 12) / (6 i)), halves to even; entry 0 of both is 0
+static const int32_t* trail_tables() {
+  static int32_t T[512];
+  static const bool built = [] {
+    T[0] = T[256] = 0;
+    for (int i = 1; i < 256; i++) {
+      T[i] = (int32_t)std::rint(1044480.0 / i);
+      T[256 + i] = (int32_t)std::rint(737280.0 / (6.0 * i));
+    }
+    return true;
+  }();
+  (void)built;
+  return T;
+}
+
+// k_trail_fixed_plane over the canvas (the entry has checked dw * dh <= INT_MAX); d_out may be NULL
+int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride,
+                                 uint8_t* d_out, int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy) {
+  if (!c->trail_tab_ready) {          // once per context, stream-ordered in front of the first launch that reads it
+    EVH_HIP(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_trail_tab), trail_tables(), 512 * sizeof(int32_t), 0, hipMemcpyHostToDevice,
+                                      c->stream));
+    c->trail_tab_ready = true;
+  }
+  const int runs_per_row = (dw + WARP_RUN - 1) / WARP_RUN;
+  const unsigned nruns = (unsigned)runs_per_row * (unsigned)dh;
+  // the picture stride is only used between the pictures of a call
+  const uintptr_t ois = nframes > 1 ? (uintptr_t)out_img_stride : 0;
+  const int vec = (d_out && (((uintptr_t)d_out | (uintptr_t)out_stride | ois) & 3) == 0 ? 1 : 0) |
+                  ((((uintptr_t)d_canvas | (uintptr_t)canvas_stride) & 3) == 0 ? 2 : 0);
+  auto go = [&](auto kernel, const auto& S) {
+    hipLaunchKernelGGL(kernel, dim3((nruns + 255) / 256), dim3(256), 0, c->stream, S, nframes, sw, sh, d_M, inverse_map, d_rect,
+                       d_canvas, canvas_stride, d_out, out_stride, out_img_stride, dw, ox, oy, runs_per_row, nruns, vec);
+  };
+  if (src.yuv) go(k_trail_fixed_plane<Yuv420Src>, yuv420_src(*src.yuv));
+  else go(k_trail_fixed_plane<PackedSrc>, PackedSrc{src.packed, 3, src.row_stride, src.frame_stride});
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
 }
 
 // k_heatmap_render over n frames of w x h (the entry has checked w * h <= INT_MAX and n <= 65535)

@@ -160,6 +160,7 @@ struct evh_ctx {
   hipEvent_t ev_segs[EVH_SEG_TURNS] = {};
   unsigned seg_turn = 0;
   uint8_t* d_yuv_bgr = nullptr; size_t yuv_bgr_bytes = 0;   // BGR frames of evh_stream_homography_batch_types_yuv420's chunk
+  bool trail_tab_ready = false;   // evh_trail_fixed_plane's colour tables are on the device (uploaded by its first launch)
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv
   int order_mode = 1;             // EVH_ORDER_OPENCV
@@ -315,6 +316,9 @@ int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w,
 int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
                                 int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh,
                                 int64_t out_stride, int64_t out_img_stride, int ox, int oy);
+int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride,
+                                 uint8_t* d_out, int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);

@@ -8,8 +8,12 @@ evh_warp_fixed_plane (include/evhip.h), either way:
                             reference's canvas (get_reference_system / initialize_background, :100-126, :241-249);
     placement="warp"        the projective warp of the full-size frame through diag(s,s,1) . H_sup . diag(kx,ky,1).
 
-Drawing -- the white frame border, the text, the HSV dimming of earlier frames, the side-by-side picture and its PNG -- is
-not done here: stabilized_frames yields the canvases as arrays.
+stabilized_frames yields the canvases as arrays.  With trail=True they are the reference's picture of the fixed plane:
+earlier frames fade out behind the current one (the HSV dimming of decrease_brightness) and the current frame sits in its
+white rectangle (change_frame_location), both by evh_trail_fixed_plane; comparison_frames sets the original beside it inside
+the red canvas border, as create_video_comparison does.  The two words of text ("Original",
+"EvenVizion") are not drawn: no Hershey glyph table is at hand.  The colour conversions are restated arithmetic, not
+cv2.cvtColor compared byte for byte (include/evhip.h says what is claimed).
 """
 import math
 
@@ -118,22 +122,33 @@ def _placement(superposition_homography_dict, resize_info, placement, scale, fra
     return ox, oy, dw, dh, matrix_of
 
 
-def stabilized_frames(capture, superposition_homography_dict, resize_info, mode="history", placement="warp", scale=1.0,
-                      chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS):
-    """Generator of (frame_no, uint8 ndarray [dh,dw,3]): the frames of `capture` (frame_no counts from 1, as the
-    dictionary's keys do) placed in the fixed plane on the device.
+def _check_trail(mode, placement, trail, border):
+    """The refusals of the trail arguments -> whether the frames get their white outline."""
+    if not (isinstance(border, bool) or (isinstance(border, str) and border == "auto")):
+        raise ValueError("border must be 'auto', True or False")
+    if not trail:
+        if border is True:
+            raise ValueError("border=True needs trail=True: only the trail pictures carry the frame's outline")
+        return False
+    if mode != "history":
+        raise ValueError("trail=True needs mode='history': the trail is the canvas after every frame")
+    if border is True and placement == "warp":
+        raise ValueError("border=True with placement='warp': a projective outline is not built")
+    return placement == "translate" and border is not False
 
-    mode "history": per frame, the canvas after this frame -- the picture create_video_comparison shows (without its
-    drawing); "each": per frame, this frame alone on black; "mosaic": yields once, the last frame_no and the canvas of all
-    frames.  placement, scale: see the module text and fixed_plane_bounds.  Frames are read and uploaded chunk_frames at a
-    time (as 4:2:0 planes where ingest allows, see video_processing.get_homography_dict) and the canvas stays on the device
-    between chunks.  A frame whose matrix is missing, None or not finite leaves the canvas as it was."""
+
+def _chunks(capture, superposition_homography_dict, resize_info, mode, placement, scale, chunk_frames, ingest, max_pixels,
+            trail, border, originals=False):
+    """The loop behind stabilized_frames and comparison_frames: reads and uploads chunk_frames frames at a time and yields
+    (number of the chunk's first frame, n, the canvases of the chunk on the device or None for "mosaic", the chunk's
+    full-size BGR frames on the device when `originals`, the carried canvas).  What it yields is valid until the next step."""
     import torch
     from .processing.video_processing import _open_capture, _read_frame
     if mode not in WARP_MODES:
         raise ValueError("mode must be 'each', 'history' or 'mosaic'")
     if ingest not in ("auto", "bgr", "yuv420"):
         raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    outline = _check_trail(mode, placement, trail, border)
     first, planes, w0, h0 = _open_capture(capture, ingest)
     ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
     w, h = int(resize_info["w"]), int(resize_info["h"])
@@ -147,7 +162,7 @@ def stabilized_frames(capture, superposition_homography_dict, resize_info, mode=
     canvas = torch.zeros((dh, dw, 3), dtype=torch.uint8, device=dev)
     out = torch.empty((chunk, dh, dw, 3), dtype=torch.uint8, device=dev) if per_frame else None
     resize = placement == "translate" and (w, h) != (w0, h0)
-    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and resize else None
+    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and (resize or originals) else None
     small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
     host[0] = first
     n, frame_no, exhausted = 1, 0, False
@@ -157,34 +172,128 @@ def stabilized_frames(capture, superposition_homography_dict, resize_info, mode=
                 n += 1
             else:
                 exhausted = True
-        src = torch.from_numpy(host[:n]).to(dev)
-        mats = torch.from_numpy(np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])).to(dev)
+        full = src = torch.from_numpy(host[:n]).to(dev)
+        host_mats = np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])
+        mats = torch.from_numpy(host_mats).to(dev)
         size = (w0, h0) if planes else None
+        if bgr is not None:
+            ctx.yuv420_to_bgr(src, bgr[:n], size=size)
+            full = src = bgr[:n]
+            size = None
         if resize:
-            if planes:
-                ctx.yuv420_to_bgr(src, bgr[:n], size=size)
-                src = bgr[:n]
             ctx.resize_area(src, small[:n])
-            src, size = small[:n], None
-        if per_frame:
+            src = small[:n]
+        if trail:
+            if frame_no == 0 and placement == "translate":
+                # initialize_background (stabilization.py:245-249): frame 1 at (|min_x|, |min_y|), the plane's origin, undimmed
+                eye = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1], dtype=torch.float64, device=dev)
+                ctx.warp_fixed_plane(src[:1], eye, canvas, "mosaic", (ox, oy), background=canvas, size=size)
+            rects = None
+            if outline:                           # change_frame_location's corners (stabilization.py:76-94)
+                rects = np.tile(np.array([0, 0, -1, -1], np.int32), (n, 1))
+                for k, m in enumerate(host_mats):
+                    if np.isfinite(m[2]) and np.isfinite(m[5]):
+                        rects[k] = frame_outline(-ox, -oy, int(m[2]), int(m[5]), w, h)
+                rects = torch.from_numpy(rects).to(dev)
+            ctx.trail_fixed_plane(src, mats, canvas, (ox, oy), out=out[:n], rects=rects, size=size)
+            ctx.order_torch_after()
+        elif per_frame:
             ctx.warp_fixed_plane(src, mats, out[:n], mode, (ox, oy), background=canvas if mode == "history" else None, size=size)
             ctx.order_torch_after()
             if mode == "history":
                 canvas.copy_(out[n - 1])
-            pictures = out[:n].cpu().numpy()
-            for k in range(n):
-                yield frame_no + 1 + k, pictures[k]
         else:
             ctx.warp_fixed_plane(src, mats, canvas, mode, (ox, oy), background=canvas, size=size)
             ctx.order_torch_after()
+        yield frame_no + 1, n, (out[:n] if per_frame else None), (full if originals else None), canvas
         frame_no += n
         n = 0
         if not exhausted and _read_frame(capture, planes, host[0], w0, h0, frame_no + 1):
             n = 1
         else:
             exhausted = True
-    if not per_frame:
+
+
+def frame_outline(abs_min_x, abs_min_y, x_offset, y_offset, w, h):
+    """(x0, y0, x1, y1) of the white rectangle change_frame_location draws around a w x h frame (stabilization.py:76-94):
+    from (|min_x| + x_offset, |min_y| + y_offset) to that plus (w, h), both ends inclusive."""
+    x0, y0 = int(abs_min_x) + int(x_offset), int(abs_min_y) + int(y_offset)
+    return x0, y0, x0 + int(w), y0 + int(h)
+
+
+def stabilized_frames(capture, superposition_homography_dict, resize_info, mode="history", placement="warp", scale=1.0,
+                      chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS, trail=False, border="auto"):
+    """Generator of (frame_no, uint8 ndarray [dh,dw,3]): the frames of `capture` (frame_no counts from 1, as the
+    dictionary's keys do) placed in the fixed plane on the device.
+
+    mode "history": per frame, the canvas after this frame -- the picture create_video_comparison shows (without its
+    drawing); "each": per frame, this frame alone on black; "mosaic": yields once, the last frame_no and the canvas of all
+    frames.  placement, scale: see the module text and fixed_plane_bounds.  Frames are read and uploaded chunk_frames at a
+    time (as 4:2:0 planes where ingest allows, see video_processing.get_homography_dict) and the canvas stays on the device
+    between chunks.  A frame whose matrix is missing, None or not finite leaves the canvas as it was.
+
+    trail=True (mode "history" only): the reference's picture -- earlier frames fade out behind the current one
+    (evh_trail_fixed_plane), and with placement "translate" the canvas starts from initialize_background's.  border: "auto" =
+    the white rectangle of change_frame_location for "translate", none for "warp"; True = the rectangle ("warp": ValueError,
+    a projective outline is not built); False = none.  A frame without a usable matrix gets no rectangle and still dims."""
+    frame_no = 0                                  # _chunks refuses bad arguments before it opens anything
+    for first, n, pictures, _, canvas in _chunks(capture, superposition_homography_dict, resize_info, mode, placement, scale,
+                                                 chunk_frames, ingest, max_pixels, trail, border):
+        frame_no = first + n - 1
+        if pictures is not None:
+            pictures = pictures.cpu().numpy()
+            for k in range(n):
+                yield first + k, pictures[k]
+    if WARP_MODES[mode] == WARP_MOSAIC:
         yield frame_no, canvas.cpu().numpy()
+
+
+def comparison_size(w0, h0, dw, dh, height=300):
+    """((width of the original, width of the fixed plane), height) of the two halves of a comparison picture:
+    imutils.resize(image, height=height) gives (int(w * (height / float(h))), height)."""
+    return (int(w0 * (height / float(h0))), int(dw * (height / float(dh)))), int(height)
+
+
+def comparison_frames(capture, superposition_homography_dict, resize_info, placement="translate", height=300,
+                      canvas_border=(0, 0, 248), scale=1.0, chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS, border="auto"):
+    """Generator of (frame_no, uint8 ndarray [height, wa + wb, 3]): create_video_comparison's picture (stabilization.py:252-290)
+    without its two words of text.  Left the original frame, right the trail picture of stabilized_frames(trail=True), both
+    taken to `height` rows by evh_resize_area_u8 (imutils.resize(height=) is INTER_AREA; enlarging is its bilinear emulation),
+    the right one then inside the one-pixel rectangle (0, 0)-(W-1, H-1) of colour canvas_border (b, g, r) that create_border
+    draws.  Everything stays on the device; the pictures come back a chunk at a time."""
+    import torch
+    _check_trail("history", placement, True, border)
+    height = int(height)
+    if height < 1:
+        raise ValueError("height must be at least 1")
+    colour = [int(v) for v in canvas_border]
+    if len(colour) != 3 or min(colour) < 0 or max(colour) > 255:
+        raise ValueError("canvas_border is (b, g, r) with bytes")
+    ctx = dev = a = b = both = None
+    for first, n, pictures, full, _ in _chunks(capture, superposition_homography_dict, resize_info, "history", placement, scale,
+                                               chunk_frames, ingest, max_pixels, True, border, originals=True):
+        if both is None:
+            ctx, dev = runtime.get_context(64, 64), runtime.device()
+            (wa, wb), _ = comparison_size(full.shape[2], full.shape[1], pictures.shape[2], pictures.shape[1], height)
+            if wa < 1 or wb < 1:
+                raise ValueError("height = %d leaves a half of the picture without columns" % height)
+            cap = max(1, int(chunk_frames))
+            a = torch.empty((cap, height, wa, 3), dtype=torch.uint8, device=dev)
+            b = torch.empty((cap, height, wb, 3), dtype=torch.uint8, device=dev)
+            both = torch.empty((cap, height, wa + wb, 3), dtype=torch.uint8, device=dev)
+            edge = torch.tensor(colour, dtype=torch.uint8, device=dev)
+        ctx.resize_area(full.contiguous(), a[:n])
+        ctx.resize_area(pictures, b[:n])
+        ctx.order_torch_after()
+        b[:n, 0, :] = edge
+        b[:n, -1, :] = edge
+        b[:n, :, 0] = edge
+        b[:n, :, -1] = edge
+        both[:n, :, :wa] = a[:n]
+        both[:n, :, wa:] = b[:n]
+        host = both[:n].cpu().numpy()
+        for k in range(n):
+            yield first + k, host[k]
 
 
 def write_ppm(path, image):

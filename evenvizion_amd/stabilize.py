@@ -1,13 +1,21 @@
 """Command-line driver of the stabilised view, with the arguments of the reference's
-evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement and --scale:
+evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail and --comparison:
 
     python -m evenvizion_amd.stabilize --path_to_homography_dict run1/video/dict_with_homography_matrix.json \
-           --path_to_video video.mp4 --experiment_name run1 --mode history --placement warp
+           --path_to_video video.mp4 --experiment_name run1 --comparison 1
 
-writes  <cwd>/<experiment_name>/<video stem>/visualize_camera_stabilization/NNNNNN.ppm : per frame (one file for --mode
-mosaic) the canvas of the fixed coordinate system as binary P6, produced on the MI355X by evenvizion_amd.stabilization.
-Only the geometry of the reference's pictures is reproduced: no "Original" / "EvenVizion" text, no frame or canvas border,
-no dimming of earlier frames and no side-by-side original are drawn, and the files are PPM, not PNG.
+writes into  <cwd>/<experiment_name>/<video stem>/visualize_camera_stabilization/ , produced on the MI355X by
+evenvizion_amd.stabilization:
+
+    --comparison 1   NNNNNN.png per frame, the reference's picture: the original frame beside the fixed plane, both 300 rows
+                     high; in the plane earlier frames fade out behind the current one, which sits in its white rectangle
+                     (--placement translate), and the plane sits in the red canvas border;
+    --trail 1        NNNNNN.ppm per frame: that fixed-plane picture alone, at the canvas's own size, as binary P6;
+    neither          NNNNNN.ppm per frame (one file for --mode mosaic): the canvas of the fixed coordinate system, geometry
+                     only -- no dimming, no border.
+
+What is still missing from the reference's picture is its text ("Original", "EvenVizion").  The dimming is the arithmetic
+include/evhip.h states for evh_trail_fixed_plane, not cv2.cvtColor compared byte for byte.
 """
 import argparse
 import os
@@ -15,8 +23,11 @@ import os
 
 def main(argv=None):
     ap = argparse.ArgumentParser(
-        description="Stabilised view on MI355X (argument surface of compare_evenvizion_with_original_video.py).  Writes the "
-                    "fixed-plane canvas per frame as binary PPM; draws no text, no border and no dimming of earlier frames.")
+        description="Stabilised view on MI355X (argument surface of compare_evenvizion_with_original_video.py).  By default "
+                    "writes the fixed-plane canvas per frame as binary PPM, geometry only: no text, no border and no dimming "
+                    "of earlier frames.  With --trail 1 earlier frames fade out and the frame is outlined; with "
+                    "--comparison 1 the original is set beside that picture inside the canvas border, as PNG.  The "
+                    "reference's text is never drawn.")
     ap.add_argument("--path_to_homography_dict", help="path to homography dict",
                     default="test_video_processing/test_video/dict_with_homography_matrix.json")
     ap.add_argument("--path_to_video", default="test_video/test_video.mp4")
@@ -27,17 +38,29 @@ def main(argv=None):
     ap.add_argument("--placement", choices=("warp", "translate"), default="translate",
                     help="translate: the reference's paste of the resized frame; warp: the projective warp of the full-size frame")
     ap.add_argument("--scale", type=float, default=1.0, help="warp only: canvas pixels per fixed-plane unit")
+    ap.add_argument("--trail", type=int, choices=(0, 1), default=0,
+                    help="1: earlier frames fade out behind the current one and (translate) the frame gets its white rectangle; "
+                         "needs --mode history")
+    ap.add_argument("--comparison", type=int, choices=(0, 1), default=0,
+                    help="1: the reference's side-by-side picture (original | trail inside the canvas border) as NNNNNN.png")
     args = ap.parse_args(argv)
+    if (args.trail or args.comparison) and args.mode != "history":
+        ap.error("--trail and --comparison need --mode history")
     from .component import open_capture
     from .processing.utils import read_homography_dict, superposition_dict
-    from .stabilization import stabilized_frames, write_ppm
+    from .stabilization import comparison_frames, stabilized_frames, write_ppm
     cap, _, stem = open_capture(args.path_to_video)
     save_folder = os.path.join(os.getcwd(), args.experiment_name, stem, "visualize_camera_stabilization")
     os.makedirs(save_folder, exist_ok=True)
     homography_dict, resize_info = read_homography_dict(args.path_to_homography_dict)
     sup = superposition_dict(homography_dict)
+    if args.comparison:
+        from .matching_pictures import write_png
+        for frame_no, picture in comparison_frames(cap, sup, resize_info, placement=args.placement, scale=args.scale):
+            write_png(os.path.join(save_folder, "%06d.png" % frame_no), picture)
+        return save_folder
     for frame_no, picture in stabilized_frames(cap, sup, resize_info, mode=args.mode, placement=args.placement,
-                                               scale=args.scale):
+                                               scale=args.scale, trail=bool(args.trail)):
         write_ppm(os.path.join(save_folder, "%06d.ppm" % frame_no), picture)
     return save_folder
 

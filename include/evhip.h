@@ -23,6 +23,8 @@
  *   evh_*_yuv420                  capture.read() + imutils.resize + the entry of the same name without the suffix
  *   evh_warp_fixed_plane[_yuv420] stabilize_view / initialize_background: a frame placed on the fixed plane
  *                                 visualization/stabilization.py:129-172, 220-249
+ *   evh_trail_fixed_plane[_yuv420] stabilize_view with decrease_brightness and change_frame_location: earlier frames dimmed,
+ *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
  *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
  *                                 visualization/processing_visualization.py:336-344
  *   evh_batch_static_info         the length of the static point lists that reach draw_matches   video_processing.py:69
@@ -466,6 +468,55 @@ int evh_warp_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int
 int evh_warp_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
                                 int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
                                 int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy);
+
+/* ---- the trail: earlier frames fade out behind the current one (stabilization.py:21-97, 129-172) -------------------------- */
+/* What stabilize_view does to its canvas per frame -- paste, white outline on a copy, both through 8-bit BGR -> HSV -> BGR with
+ * V lowered by 2 -- for nframes BGR frames of sw x sh and their matrices d_M f64[nframes,9] (DEVICE), over a BGR canvas of
+ * dw x dh at d_canvas (rows of 3*dw bytes at canvas_row_stride), which is read, carried through the frames and written back:
+ * hand the same canvas to the next call and the trail goes on.  Only BGR is supported.  Frames are taken in order,
+ * k = 0 .. nframes-1; a canvas pixel carries its value c, starting from d_canvas:
+ *   1. Paste.  If frame k covers the pixel, c becomes the sampled value; coverage and sampling are exactly
+ *      evh_warp_fixed_plane's (d_M, inverse_map, ox, oy as there).  A NaN, singular or horizon-crossing matrix covers nothing;
+ *      the dimming still goes on.
+ *   2. Picture.  q = c.  If d_rect i32[nframes,4] (DEVICE; may be NULL) is given and the pixel lies on the outline of rectangle
+ *      k = (x0, y0, x1, y1) in canvas pixels, q becomes (255, 255, 255).  The outline is x0 <= x <= x1 && y0 <= y <= y1 &&
+ *      (x == x0 || x == x1 || y == y0 || y == y1); x1 < x0 or y1 < y0: no rectangle for this frame; parts outside the canvas
+ *      do not exist.  These are the pixels of the four cv2.line calls of change_frame_location (axis-aligned, both ends
+ *      inclusive).  If d_out is given (it may be NULL: the call then only advances the canvas), out[k] = show(q), picture k at
+ *      d_out + k*out_frame_stride, rows of 3*dw bytes at out_row_stride.
+ *   3. Carry.  c = keep(c): the pasted value, not the one with the outline (the reference draws the outline on a copy).
+ * After the last frame c is stored to d_canvas.
+ * Colour arithmetic.  Tables, built on the host in double: S[0] = H[0] = 0 and for i = 1..255 S[i] = rint(1044480.0 / i)
+ * (255 << 12), H[i] = rint(737280.0 / (6.0 * i)) (180 << 12), halves to even.
+ *   to_hsv(b, g, r), int32: v = max, m = min, d = v - m; s = (d*S[v] + 2048) >> 12; t = g - b if v == r, else b - r + 2d if
+ *     v == g, else r - g + 4d; h = (t*H[d] + 2048) >> 12 with an arithmetic shift (a floor); h += 180 if h < 0.  h is in [0, 179].
+ *   from_hsv(h, s, v), IEEE float32, one rounding per operation, no fma: hf = (float)h * C6 with C6 the float32 0x3D088889
+ *     (6.f/180.f); while hf >= 6: hf -= 6.f; k = floor(hf), f = hf - k; sf = (float)s * K, vf = (float)v * K with K the float32
+ *     0x3B808081 (1.f/255.f).  If s == 0: b = g = r = vf.  Otherwise tab = {vf, vf*(1 - sf), vf*(1 - sf*f),
+ *     vf*(1 - sf*(1 - f))} and (b, g, r) = tab[.] by sector k: 0: {1,3,0}  1: {1,0,2}  2: {3,0,1}  3: {0,2,1}  4: {0,1,3}
+ *     5: {2,1,0}.  Each output byte is clamp(rint(x * 255.f), 0, 255), halves to even.
+ *   keep(p) = from_hsv(h, s, max(v - 2, 0)) with (h, s, v) = to_hsv(p): np.where((v - 2) >= 254, 0, v - 2) on uint8.
+ *   show(p) = from_hsv(h, s, v - 2) if v >= 2, else from_hsv(222, 12, 31): the reference stores [222, 12.35, 31.76] into a
+ *     uint8 array, which truncates; the result is the constant BGR (30, 31, 30).
+ * The two conversions are OpenCV 3.4.2's scalar 8-bit BGR2HSV and HSV2BGR restated from its source; no OpenCV binary or source
+ * was at hand to compare with, so byte identity with cv2.cvtColor is NOT claimed -- the claim is the arithmetic above.
+ * Every byte of every picture and canvas row inside 3*dw is written, bytes between rows are not; a thread reads only the canvas
+ * bytes it later writes.  Only caller buffers are used: nothing depends on the sizes given to evh_create.  Refused before
+ * anything is launched, outputs untouched -- EVH_ERR_INVALID: d_M, d_canvas or the frames NULL, nframes < 0, sw, sh, dw or
+ * dh < 1, a stride shorter than its row / frame (frame strides count when nframes > 1, the picture strides when d_out is
+ * given), d_out overlapping d_canvas or the frames, d_canvas overlapping the frames; EVH_ERR_CAPACITY: sw or sh >= 2^26,
+ * dw*dh > INT_MAX, nframes > 65535.  nframes == 0 succeeds and does nothing.  The plane form converts every tap as
+ * evh_yuv420_to_bgr does: it equals evh_yuv420_to_bgr followed by the BGR form.  Speed, not results, depends on alignment:
+ * d_out and its strides multiples of 4 let a thread store its four pixels as words, d_canvas and canvas_row_stride alike.
+ * Neither entry synchronises.                                                                                              */
+int evh_trail_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int64_t row_stride,
+                          int64_t frame_stride, const double* d_M, int inverse_map, const int32_t* d_rect /* may be NULL */,
+                          uint8_t* d_canvas /* in and out */, int64_t canvas_row_stride, uint8_t* d_out /* may be NULL */,
+                          int64_t out_row_stride, int64_t out_frame_stride, int dw, int dh, int ox, int oy);
+int evh_trail_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, const int32_t* d_rect /* may be NULL */, uint8_t* d_canvas /* in and out */,
+                                 int64_t canvas_row_stride, uint8_t* d_out /* may be NULL */, int64_t out_row_stride,
+                                 int64_t out_frame_stride, int dw, int dh, int ox, int oy);
 
 /* ---- heat-map pictures: the colouring of heatmap_frame_processing (processing_visualization.py:336-344) ------------------------ */
 /* What heatmap_frame_processing does with the field of evh_fixed_plane_field and the resized frame, without part_line's grid,

@@ -24,6 +24,9 @@ WARP_EACH, WARP_HISTORY, WARP_MOSAIC = 0, 1, 2
 WARP_MODES = {"each": WARP_EACH, "history": WARP_HISTORY, "mosaic": WARP_MOSAIC}
 DRAW_REFERENCE, DRAW_OWN_FRAME = 0, 1
 DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
+RESIDUAL_ABS, RESIDUAL_MASK = 0, 1
+RESIDUAL_KINDS = {"abs": RESIDUAL_ABS, "mask": RESIDUAL_MASK}
+RES_COVERED, RES_SAD, RES_SSD, RES_SAD0, RES_SSD0, RES_MOVING, RES_NSTATS = range(7)
 
 # every symbol include/evhip.h declares, with its ctypes signature
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -112,6 +115,9 @@ SIGNATURES = {
     "evh_batch_static_info": (_i, [_vp, _pi, _pi]),
     "evh_batch_static_rows": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "evh_draw_matches": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i, C.c_uint32, _vp, _i64, _i64]),
+    # the score of a homography: the motion-compensated residual of a pair
+    "evh_pair_residual": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i, _i64, _i64]),
+    "evh_pair_residual_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i64, _i64]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -707,6 +713,60 @@ class Context:
             raise ValueError("color is (b, g, r) with bytes")
         self._check(self.lib.evh_draw_matches(self.h, fp, npairs, int(frame_step), w, h, frs, ffs, rows.data_ptr(), rows.shape[1],
                                               counts.data_ptr(), _ptr(status), points, b | g << 8 | r << 16, op, ors, ofs))
+
+    # ---- the score of a homography ----
+    def _pair_residual(self, planes, frames, mats, stats, out, threshold, kind, frame_step, size):
+        import torch
+        self._enter()
+        kind = RESIDUAL_KINDS[kind] if isinstance(kind, str) else int(kind)
+        frame_step = int(frame_step)
+        if frame_step not in (1, 2):
+            raise ValueError("frame_step must be 1 or 2")
+        if planes:
+            d, n, w, h = self._yuv420(frames, size, self.device)
+        else:
+            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
+            fp, w, h, frs, ffs = self._image_rows(frames, cn, 1, "frames")
+            n = frames.shape[0]
+        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
+                or mats.numel() % 9:
+            raise ValueError("mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        npairs = mats.numel() // 9
+        if npairs and n < (npairs - 1) * frame_step + 2:
+            raise ValueError("frames holds fewer frames than the pairs take")
+        if stats is None:
+            stats = torch.empty((npairs, RES_NSTATS), dtype=torch.int64, device="cuda:%d" % self.device)
+        if stats.dtype != torch.int64 or not stats.is_cuda or stats.device.index != self.device or not stats.is_contiguous() \
+                or tuple(stats.shape) != (npairs, RES_NSTATS):
+            raise ValueError("stats must be a contiguous CUDA int64 tensor [npairs,%d]" % RES_NSTATS)
+        op, ors, ofs = None, 0, 0
+        if out is not None:
+            op, ow, oh, ors, ofs = self._image_rows(out, 1, 1, "out")
+            if (out.shape[0], ow, oh) != (npairs, w, h):
+                raise ValueError("out must be [npairs,h,w] for frames of h x w")
+        if npairs == 0:                      # empty tensors have no address to hand over
+            return stats
+        tail = (mats.data_ptr(), int(threshold), stats.data_ptr(), op, kind, ors, ofs)
+        if planes:
+            self._check(self.lib.evh_pair_residual_yuv420(self.h, C.byref(d), npairs, frame_step, w, h, *tail))
+        else:
+            self._check(self.lib.evh_pair_residual(self.h, fp, npairs, frame_step, w, h, cn, frs, ffs, *tail))
+        return stats
+
+    def pair_residual(self, frames, mats, stats=None, out=None, threshold=16, kind="abs", frame_step=1):
+        """The motion-compensated residual of pairs of frames (evh_pair_residual, the arithmetic is stated in include/evhip.h).
+        frames: CUDA uint8 [n,h,w] (gray) or [n,h,w,3] (BGR), rows and frames may be strided; pair p is (frame p*frame_step,
+        frame p*frame_step + 1).  mats: CUDA float64, npairs*9 contiguous elements, pixel of the current frame -> pixel of the
+        previous frame.  stats: CUDA int64 [npairs,6] contiguous or None = a new tensor; it is returned: (covered, sad, ssd,
+        sad of the unregistered pair, ssd of the unregistered pair, moving) per pair, the library's u64 values viewed as int64
+        (all below 2^47).  out: CUDA uint8 [npairs,h,w], rows and pictures may be strided, or None; kind "abs": the
+        difference, "mask": 255 where it exceeds threshold.  Does not synchronise."""
+        return self._pair_residual(False, frames, mats, stats, out, threshold, kind, frame_step, None)
+
+    def pair_residual_yuv420(self, planes, mats, stats=None, out=None, threshold=16, kind="abs", frame_step=1, size=None):
+        """pair_residual on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel and tap converted as
+        yuv420_to_bgr converts it (evh_pair_residual_yuv420)."""
+        return self._pair_residual(True, planes, mats, stats, out, threshold, kind, frame_step, size)
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

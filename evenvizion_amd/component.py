@@ -17,6 +17,13 @@ with --matching_pictures 1 (extension, default off) also the reference's matchin
                                        pair whose matching succeeded (get_homography_dict(matching_sink=): evh_draw_matches,
                                        drawn in the same pass; --path_to_video only).
 
+with --registration_report 1 (extension, default off) also a score for every matrix,
+    registration_report.json           per pair of consecutive frames the motion-compensated residual under the pair's matrix and
+                                       without it (covered pixels, sums of |difference| and difference^2 in gray, PSNR), their means
+                                       over the video (itf, itf_unregistered) and the frames in order of least gain
+                                       (registration.registration_report: evh_pair_residual; inf is written as Infinity).
+with --residual_pictures 1 (extension, default off) also the difference pictures behind those figures,
+    registration_visualization/res%06d.ppm   |current frame - registered previous frame| in gray, in all three channels.
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
@@ -87,6 +94,12 @@ def main(argv=None):
     ap.add_argument("--heatmap_pictures", default=False,
                     help="also write heatmap_visualization/img%%06d.ppm: the heat-map colours over every resized frame, "
                          "without grid, arrows or text (extension; the video is read a second time)")
+    ap.add_argument("--registration_report", default=False,
+                    help="also write registration_report.json: the motion-compensated residual and PSNR of every pair of frames "
+                         "under its matrix (extension; the video is read a second time)")
+    ap.add_argument("--residual_pictures", default=False,
+                    help="also write registration_visualization/res%%06d.ppm: the registered difference of every pair in gray "
+                         "(extension; the video is read a second time)")
     ap.add_argument("--show_matching_visualization", default=False, help="not taken: use --matching_pictures")
     ap.add_argument("--matching_pictures", default=False,
                     help="also write matching_visualization/matching_vis_{i}.png: the resized frames i-1 | i with a green line "
@@ -138,7 +151,7 @@ def output_folder(args, stem):
 
 def write_outputs(args, result, original_shape, stem, spec=None):
     """One video's files under <cwd>/<experiment_name>/<stem>/ (evenvizion_component.py:62-65,139-140) -> the folder.
-    spec: what the video was opened from, to read it again for --heatmap_pictures."""
+    spec: what the video was opened from, to read it again for --heatmap_pictures, --registration_report and --residual_pictures."""
     from .processing.utils import read_homography_dict, superposition_dict, read_json_with_coordinates, \
         are_infinity_coordinates
     from .processing.fixed_coordinate_system import from_original_to_fix
@@ -166,6 +179,18 @@ def write_outputs(args, result, original_shape, stem, spec=None):
         cap = open_capture(spec)[0]                              # visualize_heatmap opens the video again too (:52)
         for frame_no, picture in heatmap.heatmap_frames(cap, reformat, resize_info, ingest=args.ingest):
             write_ppm(os.path.join(pictures, "img%06d.ppm" % int(frame_no)), picture)
+    if _bool(args.registration_report):
+        from . import registration
+        report = registration.registration_report(open_capture(spec)[0], reformat, resize_info, ingest=args.ingest)
+        with open(os.path.join(save_folder, "registration_report.json"), "w") as json_:
+            json.dump(report, json_)
+    if _bool(args.residual_pictures):
+        from . import registration
+        from .stabilization import write_ppm
+        pictures = os.path.join(save_folder, "registration_visualization")
+        os.makedirs(pictures, exist_ok=True)
+        for frame_no, picture in registration.residual_frames(open_capture(spec)[0], reformat, resize_info, ingest=args.ingest):
+            write_ppm(os.path.join(pictures, "res%06d.ppm" % int(frame_no)), np.repeat(picture[:, :, None], 3, axis=2))
     if args.path_to_original_coordinate:
         original_coordinates = read_json_with_coordinates(args.path_to_original_coordinate)
         fixed = from_original_to_fix(original_coordinates, reformat, original_shape, [resize_info["h"], resize_info["w"]])

@@ -1036,6 +1036,72 @@ int evh_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_
                                  points, color_bgr, d_out, out_row_stride, out_frame_stride);
 }
 
+// ---- the score of a homography: the motion-compensated residual of a pair -----------------------------------------------------------
+// the argument checks of both forms; every refusal comes before the memset and the launch
+static int pair_residual(evh_ctx* c, const char* who, const EvhFrames& F, int npairs, int frame_step, int w, int h, const double* d_M,
+                         int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_stride, int64_t out_img_stride) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = std::string(who) + ": ";
+  const int cn = F.channels;
+  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
+  if (!d_M || !d_stats) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
+  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
+  if (npairs < 0 || w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or negative npairs");
+  if (threshold < 0 || threshold > 255) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
+  if (kind != EVH_RESIDUAL_ABS && kind != EVH_RESIDUAL_MASK) return evh_fail(c, EVH_ERR_INVALID, W + "unknown kind");
+  if (w >= (1 << 26) || h >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "frame sizes stay below 2^26 (positions are held in 1/32 pixels)");
+  if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "w * h above INT_MAX");
+  if (npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
+  const int64_t row = (int64_t)w * cn, frame = F.planes ? 0 : (h - 1) * F.row_stride + row;
+  if (!F.planes && (F.row_stride < row || F.frame_stride < frame))
+    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
+  const int64_t picture = (h - 1) * out_stride + w;
+  if (d_out && (out_stride < w || (npairs > 1 && out_img_stride < picture)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "output stride smaller than a row / picture");
+  if (npairs == 0) return EVH_SUCCESS;
+  const int64_t nframes = (int64_t)(npairs - 1) * frame_step + 2;
+  if (F.yuv) {
+    if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+    if (int rc = evh_check_yuv420(c, who, F.yuv, (int)nframes, w, h)) return rc;
+  }
+  if (d_out) {      // the byte ranges the launch reads and writes: the pictures apart from the frames and from the statistics
+    struct Span { const uint8_t* p; int64_t n; };
+    const auto meet = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
+    const Span pic{d_out, picture + (npairs - 1) * out_img_stride};
+    const Span st{reinterpret_cast<const uint8_t*>(d_stats), (int64_t)npairs * EVH_RES_NSTATS * (int64_t)sizeof(uint64_t)};
+    Span srcs[3]; int nsrc = 1;
+    if (F.yuv) {
+      const evh_yuv420& s = *F.yuv;
+      const int64_t cw = (w + 1) / 2, ch = (h + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
+      const int64_t yb = (h - 1) * s.y_stride + w + (nframes - 1) * s.y_frame_stride;
+      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
+      srcs[0] = {s.d_y, yb}; srcs[1] = {s.d_cb, cb}; srcs[2] = {s.d_cr, cb}; nsrc = 3;
+    } else {
+      srcs[0] = {F.packed, frame + (nframes - 1) * F.frame_stride};
+    }
+    if (meet(pic, st)) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps d_stats");
+    for (int i = 0; i < nsrc; i++)
+      if (meet(pic, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps the frames");
+  }
+  return evh_launch_pair_residual(c, F, npairs, frame_step, w, h, d_M, threshold, d_stats, d_out, kind, out_stride, out_img_stride);
+}
+
+int evh_pair_residual(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int channels,
+                      int64_t row_stride, int64_t frame_stride, const double* d_M, int threshold, uint64_t* d_stats, uint8_t* d_out,
+                      int kind, int64_t out_row_stride, int64_t out_frame_stride) {
+  return pair_residual(c, "evh_pair_residual", packed_frames(d_frames, channels, row_stride, frame_stride), npairs, frame_step, w, h,
+                       d_M, threshold, d_stats, d_out, kind, out_row_stride, out_frame_stride);
+}
+
+int evh_pair_residual_yuv420(evh_ctx* c, const evh_yuv420* src, int npairs, int frame_step, int w, int h, const double* d_M,
+                             int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_row_stride,
+                             int64_t out_frame_stride) {
+  return pair_residual(c, "evh_pair_residual_yuv420", yuv420_frames(src), npairs, frame_step, w, h, d_M, threshold, d_stats, d_out,
+                       kind, out_row_stride, out_frame_stride);
+}
+
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);

@@ -510,6 +510,78 @@ __global__ __launch_bounds__(256) void k_warp_fixed_plane(SRC src, int nframes, 
   }
 }
 
+// The motion-compensated residual of a pair (include/evhip.h states the contract for evh_pair_residual): grid.y = pair, previous
+// frame p * frame_step, current frame p * frame_step + 1.  A thread owns WARP_RUN adjacent pixels of a row of the current frame:
+// it loads them and the previous frame's pixels at the same place (as words where vec bit 1 allows; planes are converted pixel by
+// pixel), forms the pair's matrix once, samples the previous frame through warp_sample and keeps six partial sums.  No warped
+// frame is ever written.  Bounds of the sums, all unsigned: a thread holds at most WARP_RUN * 255^2 = 260 100 per statistic, a
+// workgroup 256 * 4 * 65025 = 66 585 600 < 2^32, so the registers, the __shfl_xor steps across the wave and the LDS sums across
+// the four waves are 32-bit; a pair holds at most INT_MAX * 65025 < 2^47 (w * h <= INT_MAX), so d_stats is 64-bit and takes one
+// integer atomicAdd per statistic per workgroup.  Integer sums do not depend on the order of the atomics; there is no
+// floating-point accumulation.  The 256 threads of a block all reach the barrier; those past the last run add zeros.
+template <int CN, class SRC>
+__global__ __launch_bounds__(256) void k_pair_residual(SRC src, int frame_step, int w, int h, const double* __restrict__ M,
+                                                       int threshold, unsigned long long* __restrict__ stats,
+                                                       uint8_t* __restrict__ out, int kind, int64_t out_stride,
+                                                       int64_t out_img_stride, int runs_per_row, unsigned nruns, int vec) {
+  __shared__ uint32_t part[4][EVH_RES_NSTATS];
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int pair = blockIdx.y;
+  uint32_t s[EVH_RES_NSTATS];
+#pragma unroll
+  for (int k = 0; k < EVH_RES_NSTATS; k++) s[k] = 0;
+  if (t < nruns) {
+    const int prev = pair * frame_step, cur = prev + 1;
+    const int y = (int)(t / (unsigned)runs_per_row), x0 = ((int)t - y * runs_per_row) * WARP_RUN;
+    const int n = min(WARP_RUN, w - x0);
+    const bool full = n == WARP_RUN;
+    int a[WARP_RUN][3], b[WARP_RUN][3];                   // the current and the previous frame's pixels of the run
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) a[p][0] = a[p][1] = a[p][2] = b[p][0] = b[p][1] = b[p][2] = 0;
+    if constexpr (std::is_same_v<SRC, PackedSrc>) {
+      const int64_t at = (int64_t)y * src.stride + (int64_t)x0 * CN;
+      warp_run_load<CN>(src.p + (int64_t)cur * src.img_stride + at, n, full && (vec & 2), a);
+      warp_run_load<CN>(src.p + (int64_t)prev * src.img_stride + at, n, full && (vec & 2), b);
+    } else {
+      const typename SRC::Row ra = src.row(cur, y), rb = src.row(prev, y);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) if (p < n) { ra.px(x0 + p, a[p]); rb.px(x0 + p, b[p]); }
+    }
+    const WarpMap A = warp_map(M + 9 * (int64_t)pair, 1);
+    const double Y = (double)y;
+    int q[WARP_RUN][3];
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      q[p][0] = q[p][1] = q[p][2] = 0;
+      int r[3] = {0, 0, 0};
+      if (p < n && warp_sample(src, prev, A, (double)(x0 + p), Y, w, h, r)) {
+        const int g_cur = CN == 3 ? gray_of(a[p][0], a[p][1], a[p][2]) : a[p][0];
+        const int g_prev = CN == 3 ? gray_of(b[p][0], b[p][1], b[p][2]) : b[p][0];
+        const int g_reg = CN == 3 ? gray_of(r[0], r[1], r[2]) : r[0];
+        const uint32_t d = (uint32_t)abs(g_cur - g_reg), d0 = (uint32_t)abs(g_cur - g_prev);
+        s[EVH_RES_COVERED] += 1;
+        s[EVH_RES_SAD] += d; s[EVH_RES_SSD] += d * d;
+        s[EVH_RES_SAD0] += d0; s[EVH_RES_SSD0] += d0 * d0;
+        s[EVH_RES_MOVING] += d > (uint32_t)threshold ? 1 : 0;
+        q[p][0] = kind == EVH_RESIDUAL_MASK ? (d > (uint32_t)threshold ? 255 : 0) : (int)d;
+      }
+    }
+    if (out) warp_run_store<1>(out + (int64_t)pair * out_img_stride + (int64_t)y * out_stride + x0, n, full && (vec & 1), q);
+  }
+#pragma unroll
+  for (int k = 0; k < EVH_RES_NSTATS; k++)
+    for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < EVH_RES_NSTATS; k++) part[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < EVH_RES_NSTATS) {
+    const uint32_t sum = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (sum) atomicAdd(&stats[(int64_t)pair * EVH_RES_NSTATS + threadIdx.x], (unsigned long long)sum);
+  }
+}
+
 // The trail (stabilization.py:21-44, 129-172, 252-290): EVH_WARP_HISTORY with the colour step include/evhip.h states for
 // evh_trail_fixed_plane between the frames.  g_trail_tab holds S[256] | H[256], built by the launcher on the host in double
 // and uploaded once per context; a workgroup stages it in LDS, two entries per thread (the look-ups are per lane).
@@ -913,6 +985,31 @@ int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, i
   if (src.channels == 3)
     return launch_warp<3>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
   return launch_warp<1>(c, P, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride, out_img_stride, ox, oy);
+}
+
+// d_stats zeroed, then k_pair_residual over npairs >= 1 pairs of w x h (the entry has checked w * h <= INT_MAX and
+// npairs <= 65535); d_out may be NULL
+int evh_launch_pair_residual(evh_ctx* c, const EvhFrames& src, int npairs, int frame_step, int w, int h, const double* d_M,
+                             int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_stride,
+                             int64_t out_img_stride) {
+  EVH_HIP(c, hipMemsetAsync(d_stats, 0, (size_t)npairs * EVH_RES_NSTATS * sizeof(uint64_t), c->stream));
+  const int runs_per_row = (w + WARP_RUN - 1) / WARP_RUN;
+  const unsigned nruns = (unsigned)runs_per_row * (unsigned)h;
+  // the pictures' stride is only used between the pictures of a call; the frames' always (a pair takes two frames)
+  const uintptr_t ois = npairs > 1 ? (uintptr_t)out_img_stride : 0;
+  const int vec = (d_out && (((uintptr_t)d_out | (uintptr_t)out_stride | ois) & 3) == 0 ? 1 : 0) |
+                  (!src.yuv && (((uintptr_t)src.packed | (uintptr_t)src.row_stride | (uintptr_t)src.frame_stride) & 3) == 0 ? 2 : 0);
+  const dim3 grid((nruns + 255) / 256, npairs);
+  auto go = [&](auto kernel, const auto& S) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, S, frame_step, w, h, d_M, threshold,
+                       reinterpret_cast<unsigned long long*>(d_stats), d_out, kind, out_stride, out_img_stride, runs_per_row, nruns, vec);
+  };
+  const PackedSrc P{src.packed, src.channels, src.row_stride, src.frame_stride};
+  if (src.yuv) go(k_pair_residual<3, Yuv420Src>, yuv420_src(*src.yuv));
+  else if (src.channels == 3) go(k_pair_residual<3, PackedSrc>, P);
+  else go(k_pair_residual<1, PackedSrc>, P);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
 }
 
 // the tables of evh_trail_fixed_plane's colour step, in double on the host: S[i] = rint((255 << 12) / i),

@@ -316,6 +316,9 @@ int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w,
 int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
                                 int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh,
                                 int64_t out_stride, int64_t out_img_stride, int ox, int oy);
+int evh_launch_pair_residual(evh_ctx* c, const EvhFrames& src, int npairs, int frame_step, int w, int h, const double* d_M,
+                             int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_stride,
+                             int64_t out_img_stride);
 int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
                                  int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride,
                                  uint8_t* d_out, int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy);

@@ -1,0 +1,180 @@
+"""How good is each homography?  The motion-compensated residual of every pair of consecutive frames, computed on the GPU.
+
+The library returns one matrix per frame; the reference's known-issues.md names a poorly obtained homography as its open problem
+("Error": it distorts every recalculated coordinate; "N/A coordinates": matches clinging to moving objects cause it, and the
+authors "consider applying video motion segmentation").  The stabilisation literature measures exactly this: warp frame k-1 onto
+frame k through the estimated motion, difference the two, report the PSNR and its mean over the video (the inter-frame
+transformation fidelity, ITF); the same difference, thresholded, is the moving-object mask.
+
+`pair_maps` forms the matrix that registers a pair, `registration_report` the per-pair figures and the two means,
+`residual_frames` the difference pictures or masks.  The sampling, differencing and summing is one fused operator,
+evh_pair_residual (include/evhip.h states its arithmetic): no warped frame is ever stored.
+"""
+import math
+
+import numpy as np
+
+from . import runtime
+
+STAT_NAMES = ("covered", "sad", "ssd", "sad_unregistered", "ssd_unregistered", "moving")
+
+
+def _matrix33(S):
+    """A dictionary entry as f64[3,3]; None or a wrong size gives NaN."""
+    if S is not None:
+        m = np.asarray(S, np.float64)
+        if m.size == 9:
+            return m.reshape(3, 3)
+    return np.full((3, 3), np.nan)
+
+
+def _pair_map(S_prev, S_cur):
+    nan = np.full((3, 3), np.nan)
+    if not (np.isfinite(S_prev).all() and np.isfinite(S_cur).all()):
+        return nan
+    with np.errstate(all="ignore"):
+        if np.linalg.det(S_prev) == 0 or np.linalg.det(S_cur) == 0:
+            return nan
+        try:
+            M = np.linalg.solve(S_prev, S_cur)
+        except np.linalg.LinAlgError:
+            return nan
+    return M if np.isfinite(M).all() else nan
+
+
+def pair_maps(superposition_homography_dict):
+    """{frame_no: superposed S} -> {frame_no: f64[3,3] M_k}, M_k = S_{k-1}^-1 . S_k, for every entry but the first, taking
+    consecutive entries in the dictionary's order; float64 on the host, np.linalg.solve(S_{k-1}, S_k).  NaN where either
+    matrix is None, not finite or singular (such a pair then covers nothing and scores nothing).
+
+    M_k takes pixels of frame k to pixels of frame k-1, which is what evh_pair_residual samples through.  It is NOT the
+    per-frame H_k of dict_with_homography_matrix.json: the reference composes S_k = H_k . S_{k-1} (normalised by [2][2]) and
+    S_k takes frame k's pixels to the fixed plane, so the pixel-to-pixel map of a pair is S_{k-1}^-1 . S_k.  On the reference's
+    test_video.mp4 with its recorded dictionary (frames subsampled to 400x224), the registered sum of squared differences lies
+    below the unregistered one on 120 of 120 pairs with M_k, on 56 of 120 with H_k itself and on 2 of 120 with H_k^-1."""
+    entries = [(k, _matrix33(v)) for k, v in superposition_homography_dict.items() if k != "resize_info"]
+    return {k1: _pair_map(S0, S1) for (_, S0), (k1, S1) in zip(entries, entries[1:])}
+
+
+def psnr(covered, ssd):
+    """10 log10(255^2 covered / ssd): inf for ssd == 0, None for a pair without a covered pixel."""
+    if covered <= 0:
+        return None
+    if ssd == 0:
+        return math.inf
+    return 10.0 * math.log10(65025.0 * covered / ssd)
+
+
+def report_from_stats(stats_by_frame):
+    """{frame_no: (covered, sad, ssd, sad0, ssd0, moving)} (evh_pair_residual's six sums) -> the report registration_report
+    returns.  worst: the frame numbers in ascending order of psnr - psnr_unregistered, pairs without a covered pixel (no
+    score at all) first; a pair whose two PSNRs are both inf counts as a gain of 0; equal gains keep the dictionary's order."""
+    frames, finite, finite0, order = {}, [], [], []
+    for pos, (no, s) in enumerate(stats_by_frame.items()):
+        s = [int(v) for v in s]
+        e = dict(zip(STAT_NAMES, s))
+        e["psnr"], e["psnr_unregistered"] = psnr(s[0], s[2]), psnr(s[0], s[4])
+        frames[no] = e
+        if e["psnr"] is None:
+            gain = -math.inf
+        else:
+            if math.isfinite(e["psnr"]):
+                finite.append(e["psnr"])
+            if math.isfinite(e["psnr_unregistered"]):
+                finite0.append(e["psnr_unregistered"])
+            both_inf = math.isinf(e["psnr"]) and math.isinf(e["psnr_unregistered"])
+            gain = 0.0 if both_inf else e["psnr"] - e["psnr_unregistered"]
+        order.append((gain, pos, no))
+    mean = lambda v: float(np.mean(v)) if v else None
+    return {"frames": frames, "itf": mean(finite), "itf_unregistered": mean(finite0), "worst": [no for _, _, no in sorted(order)]}
+
+
+def _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, kind):
+    """The refusals of both drivers, before the capture is opened or the device touched -> (entries, maps, w, h, threshold, chunk)"""
+    from ._lib import RESIDUAL_KINDS
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    if kind not in RESIDUAL_KINDS:
+        raise ValueError("kind must be 'abs' or 'mask'")
+    if isinstance(threshold, bool) or int(threshold) != threshold or not 0 <= int(threshold) <= 255:
+        raise ValueError("threshold must be an integer in 0..255")
+    if isinstance(chunk_frames, bool) or int(chunk_frames) != chunk_frames or int(chunk_frames) < 1:
+        raise ValueError("chunk_frames must be an integer of at least 1")
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    if w < 1 or h < 1:
+        raise ValueError("resize_info must hold a positive w and h")
+    keys = [k for k in superposition_homography_dict if k != "resize_info"]
+    return keys, pair_maps(superposition_homography_dict), w, h, int(threshold), max(2, int(chunk_frames))
+
+
+def _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, kind, pictures):
+    """Generator of (frame_no, six ints, picture or None) per pair.  The i-th frame read from `capture` goes with the i-th entry
+    of the dictionary; frames are read, uploaded, converted and resized as heatmap._heatmap_frames does, `chunk` at a time, and a
+    chunk's last frame is kept as the next chunk's first, so that every pair of consecutive frames lies inside one chunk."""
+    import torch
+    from .processing.video_processing import _open_capture, _read_frame
+    if len(keys) < 2:
+        return
+    first, planes, w0, h0 = _open_capture(capture, ingest)
+    if not planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
+        raise ValueError("frames must be BGR [h,w,3] or gray [h,w]")
+    ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
+    dev = runtime.device()
+    chunk = max(2, min(chunk, len(keys), runtime.STAGING_BYTES_PER_BUFFER // max(first.nbytes, 1)))      # the host chunk stays bounded
+    host = np.empty((chunk,) + first.shape, np.uint8)
+    resize = (w, h) != (w0, h0)
+    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes else None
+    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    stats = torch.empty((chunk - 1, 6), dtype=torch.int64, device=dev)
+    out = torch.empty((chunk - 1, h, w), dtype=torch.uint8, device=dev) if pictures else None
+    host[0] = first
+    done, n, more = 0, 1, True                     # host[0] is frame `done` of the dictionary's order
+    while more:
+        while n < chunk and done + n < len(keys):
+            if not _read_frame(capture, planes, host[n], w0, h0, done + n + 1):
+                more = False
+                break
+            n += 1
+        more = more and done + n < len(keys)
+        if n < 2:
+            break
+        src = torch.from_numpy(host[:n]).to(dev)
+        if planes:
+            ctx.yuv420_to_bgr(src, bgr[:n], size=(w0, h0))
+            src = bgr[:n]
+        elif src.dim() == 3:
+            src = src[..., None].expand(-1, -1, -1, 3).contiguous()          # gray frames: B = G = R
+        if resize:
+            ctx.resize_area(src, small[:n])
+            src = small[:n]
+        nos = keys[done + 1:done + n]
+        mats = torch.from_numpy(np.stack([maps[k] for k in nos]).reshape(n - 1, 9)).to(dev)
+        ctx.pair_residual(src, mats, stats=stats[:n - 1], out=out[:n - 1] if pictures else None, threshold=threshold, kind=kind)
+        ctx.order_torch_after()
+        sums = stats[:n - 1].cpu().numpy()
+        pics = out[:n - 1].cpu().numpy() if pictures else None
+        for k, no in enumerate(nos):
+            yield no, tuple(int(v) for v in sums[k]), (pics[k] if pictures else None)
+        host[0] = host[n - 1]
+        done += n - 1
+        n = 1
+
+
+def registration_report(capture, superposition_homography_dict, resize_info, threshold=16, chunk_frames=32, ingest="auto"):
+    """-> {"frames": {frame_no: {covered, sad, ssd, sad_unregistered, ssd_unregistered, moving, psnr, psnr_unregistered}},
+    "itf": mean of the finite psnr, "itf_unregistered": mean of the finite psnr_unregistered, "worst": frame numbers, the least
+    gain first}.  Entry frame_no scores the pair (frame before it in the dictionary's order, frame_no) under pair_maps' matrix:
+    over the pixels of the resized frame the matrix keeps inside the previous frame (covered), the sums of |difference| and
+    difference^2 in gray with the previous frame registered (sad, ssd) and as it is (*_unregistered), and the pixels whose
+    registered difference exceeds threshold (moving).  psnr = 10 log10(65025 covered / ssd), inf for ssd == 0, None for
+    covered == 0.  The i-th frame read from `capture` goes with the i-th entry of the dictionary, as in heatmap.heatmap_frames;
+    it ends when either runs out.  chunk_frames (at least 2 are taken) frames are on the device at a time."""
+    keys, maps, w, h, threshold, chunk = _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, "abs")
+    return report_from_stats({no: s for no, s, _ in _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, "abs", False)})
+
+
+def residual_frames(capture, superposition_homography_dict, resize_info, threshold=16, chunk_frames=32, ingest="auto", kind="abs"):
+    """Generator of (frame_no, uint8 ndarray [h,w]) per pair of registration_report: kind "abs": the registered difference in
+    gray, "mask": 255 where it exceeds threshold (the moving objects), 0 elsewhere and where the pair is not covered."""
+    keys, maps, w, h, threshold, chunk = _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, kind)
+    return ((no, pic) for no, _, pic in _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, kind, True))

@@ -31,6 +31,8 @@
  *   evh_batch_static_rows         concatenate_all_features_types' two point lists as draw_matches gets them   video_processing.py:69,78-80
  *   evh_draw_matches              draw_matches + imwrite: matching_vis_{i}.png   video_processing.py:78-81,
  *                                 visualization/processing_visualization.py:22-57
+ *   evh_pair_residual[_yuv420]    no counterpart: the measure of a matrix the reference's known-issues.md lacks ("Error",
+ *                                 "N/A coordinates"): the motion-compensated residual of a pair of frames
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -611,6 +613,51 @@ int evh_draw_matches(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int fram
                      int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts,
                      const int32_t* d_status /* may be NULL */, int points, uint32_t color_bgr, uint8_t* d_out,
                      int64_t out_row_stride, int64_t out_frame_stride);
+
+/* ---- the score of a homography: the motion-compensated residual of a pair of frames ---------------------------------------------- */
+/* How well a matrix registers two consecutive frames: the previous frame is sampled where the matrix sends each pixel of the current
+ * frame, the two are differenced in gray, and the differences are summed per pair -- the sums behind the PSNR / ITF figures of the
+ * stabilisation literature -- with, optionally, the difference picture or its thresholded mask (the moving objects the reference's
+ * known-issues.md names as the cause of bad matrices).  No warped frame is stored.
+ * d_frames: frames of w x h with `channels` bytes per pixel (BGR or gray), rows at row_stride, frames at frame_stride.  Pair p has
+ * the PREVIOUS frame p*frame_step and the CURRENT frame p*frame_step + 1, as in evh_draw_matches (frame_step 1 for streams, 2 for
+ * independent pairs): (npairs - 1)*frame_step + 2 frames are read.  d_M f64[npairs,9] (DEVICE): d_M[p] maps pixels of the current
+ * frame to pixels of the previous frame and is used as it is, the inverse_map != 0 form of evh_warp_fixed_plane.
+ * Per pixel (x, y) of the current frame, in this order:
+ *   1. X = (double)x, Y = (double)y; tx, ty, tw, U, V, coverage and, for a covered pixel, the sampled value of the previous frame per
+ *      channel are exactly evh_warp_fixed_plane's with A = d_M[p], sw = w, sh = h: positions in 1/32 pixels, the comparison in
+ *      double, the four taps with >> 10, a tap of weight 0 not read.
+ *   2. gray(b, g, r) = (b*1868 + g*9617 + r*4899 + 8192) >> 14 (the weights of the ingest); with 3 channels the sample is
+ *      interpolated per channel first and converted afterwards; with channels == 1 the byte is the gray value.
+ *   3. g_cur = gray of the current frame's pixel, g_reg = gray of the sample, g_prev = gray of the previous frame's pixel at the same
+ *      (x, y); d = |g_cur - g_reg|, d0 = |g_cur - g_prev|.
+ * d_stats u64[npairs,EVH_RES_NSTATS] (DEVICE), over the COVERED pixels of pair p only, exact unsigned integers:
+ *   [EVH_RES_COVERED] += 1; [EVH_RES_SAD] += d; [EVH_RES_SSD] += d*d; [EVH_RES_SAD0] += d0; [EVH_RES_SSD0] += d0*d0;
+ *   [EVH_RES_MOVING] += (d > threshold).
+ * The entry zeroes d_stats itself, stream-ordered, whatever it held.  Every value stays below 2^47 (w*h <= INT_MAX times 255^2).  A
+ * NaN, zero, singular or horizon-crossing matrix covers nothing or only part, exactly as in evh_warp_fixed_plane; a pair without a
+ * covered pixel has six zeros.  The sums are integers, so they do not depend on the order in which the device adds them.
+ * d_out (may be NULL): pair p's picture at d_out + p*out_frame_stride, gray, h rows of w bytes at out_row_stride.  A covered pixel
+ * holds d (EVH_RESIDUAL_ABS) or 255 if d > threshold, else 0 (EVH_RESIDUAL_MASK); an uncovered pixel holds 0 in both kinds.  Every
+ * byte of every row inside w is written, bytes between rows are not.
+ * Only caller buffers are used: nothing depends on the sizes given to evh_create.  Refused before anything is launched, outputs
+ * untouched -- EVH_ERR_INVALID: NULL d_frames (a NULL plane), d_M or d_stats, channels not 1 or 3, frame_step not 1 or 2, w or h < 1,
+ * npairs < 0, threshold outside 0..255, an unknown kind, a stride shorter than its row / frame (the frames' always: a pair takes two
+ * frames; the pictures' when d_out is given, out_frame_stride when npairs > 1), d_out overlapping the frames or d_stats;
+ * EVH_ERR_CAPACITY: w or h >= 2^26, w*h > INT_MAX, npairs > 65535.  npairs == 0 succeeds and does nothing.  The plane form converts
+ * every tap and every pixel as evh_yuv420_to_bgr does: it equals evh_yuv420_to_bgr followed by the BGR form.  Speed, not results,
+ * depends on alignment: d_frames and its strides multiples of 4 let a thread load its four pixels as words, d_out and its strides
+ * store them so.  One memset and one launch on the context's stream; neither entry synchronises.                                */
+enum { EVH_RESIDUAL_ABS = 0, EVH_RESIDUAL_MASK = 1 };
+enum { EVH_RES_COVERED = 0, EVH_RES_SAD, EVH_RES_SSD, EVH_RES_SAD0, EVH_RES_SSD0, EVH_RES_MOVING, EVH_RES_NSTATS };  /* 6 */
+int evh_pair_residual(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int frame_step /* 1 | 2 */, int w, int h,
+                      int channels /* 1 | 3 */, int64_t row_stride, int64_t frame_stride,
+                      const double* d_M /* f64[npairs,9] DEVICE */, int threshold /* 0..255 */,
+                      uint64_t* d_stats /* u64[npairs,6] DEVICE */,
+                      uint8_t* d_out /* may be NULL */, int kind, int64_t out_row_stride, int64_t out_frame_stride);
+int evh_pair_residual_yuv420(evh_ctx* ctx, const evh_yuv420* src, int npairs, int frame_step, int w, int h,
+                             const double* d_M, int threshold, uint64_t* d_stats,
+                             uint8_t* d_out, int kind, int64_t out_row_stride, int64_t out_frame_stride);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

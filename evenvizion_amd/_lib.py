@@ -22,6 +22,7 @@ MAX_FEATURES = 5984   # EVH_MAX_FEATURES (include/evhip.h): largest max_features
 MODE_INDEPENDENT_PAIRS, MODE_STREAM = 0, 1
 WARP_EACH, WARP_HISTORY, WARP_MOSAIC = 0, 1, 2
 WARP_MODES = {"each": WARP_EACH, "history": WARP_HISTORY, "mosaic": WARP_MOSAIC}
+PLATE_MAX_FRAMES = 255   # EVH_PLATE_MAX_FRAMES (include/evhip.h): frames one plate_fixed_plane call takes
 DRAW_REFERENCE, DRAW_OWN_FRAME = 0, 1
 DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
 RESIDUAL_ABS, RESIDUAL_MASK = 0, 1
@@ -109,6 +110,10 @@ SIGNATURES = {
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_trail_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     "evh_trail_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
+    "evh_plate_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i64,
+                                   _i, _i, _i, _i]),
+    "evh_plate_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i64,
+                                          _i, _i, _i, _i]),
     # heat-map pictures: colour index, table, blend over the frame
     "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
     # matching pictures: the rows a batch handed to its final solve, and the two frames side by side with a line per row
@@ -627,6 +632,51 @@ class Context:
             self._check(self.lib.evh_trail_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
         else:
             self._check(self.lib.evh_trail_fixed_plane(self.h, fp, n, sw, sh, frs, ffs, *tail))
+
+    def plate_fixed_plane(self, frames, mats, plate, origin, background=None, count=None, masks=None, threshold=16, min_cover=1,
+                          inverse_map=False, size=None):
+        """The background plate of frames on the fixed plane (evh_plate_fixed_plane[_yuv420], the contract is stated in
+        include/evhip.h): per canvas pixel and channel the lower median of the frames that cover it, where at least min_cover
+        (1..255) do; elsewhere the background.  frames, mats, origin, inverse_map, size: as for warp_fixed_plane, at most
+        PLATE_MAX_FRAMES frames.  plate: CUDA uint8 [dh,dw] (gray frames) or [dh,dw,3], rows may be strided.  background:
+        [dh,dw(,3)] with plate's row stride, or None = zeros.  count: [dh,dw], the number of covering frames, or None.  masks:
+        [n,dh,dw], 255 where frame k covers the pixel and its gray differs from the plate's by more than threshold (0..255), or
+        None; rows (and masks) may be strided.  Does not synchronise."""
+        import torch
+        self._enter()
+        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
+        if planes:
+            d, n, sw, sh = self._yuv420(frames, size, self.device)
+            cn = 3
+        else:
+            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
+            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
+            n = frames.shape[0]
+        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
+                or mats.numel() != 9 * n:
+            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        pp, dw, dh, prs, _ = self._image_rows(plate, cn, 0, "plate")
+        bp = None
+        if background is not None:
+            bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
+            if (bw, bh) != (dw, dh) or (dh > 1 and brs != prs):
+                raise ValueError("background must be [dh,dw(,3)] with plate's row stride")
+        cp, crs = None, 0
+        if count is not None:
+            cp, cw, ch, crs, _ = self._image_rows(count, 1, 0, "count")
+            if (cw, ch) != (dw, dh):
+                raise ValueError("count must be [dh,dw] for a plate [dh,dw(,3)]")
+        mp, mrs, mfs = None, 0, 0
+        if masks is not None:
+            mp, mw, mh, mrs, mfs = self._image_rows(masks, 1, 1, "masks")
+            if (masks.shape[0], mw, mh) != (n, dw, dh):
+                raise ValueError("masks must be [n,dh,dw] for a plate [dh,dw(,3)]")
+        tail = (mats.data_ptr(), int(bool(inverse_map)), int(min_cover), bp, pp, prs, cp, crs, mp, int(threshold), mrs, mfs, dw, dh,
+                int(origin[0]), int(origin[1]))
+        if planes:
+            self._check(self.lib.evh_plate_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
+        else:
+            self._check(self.lib.evh_plate_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
 
     def heatmap_render(self, Hsup, out, lut, frames=None, heatmap_constant=1000.0, alpha=0.8, saturate=False):
         """The heat-map pictures of n superposed matrices (evh_heatmap_render, the arithmetic is stated in include/evhip.h).

@@ -982,6 +982,80 @@ int evh_trail_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes,
                            d_canvas, canvas_row_stride, d_out, out_row_stride, out_frame_stride, dw, dh, ox, oy);
 }
 
+// ---- the background plate: the temporal median of the frames on the fixed plane, and what moves against it -------------------
+// the argument checks of both forms; every refusal comes before the launch
+static int plate_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
+                             int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
+                             uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
+                             int64_t mask_img_stride, int dw, int dh, int ox, int oy) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = std::string(who) + ": ";
+  const int cn = F.channels;
+  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
+  if (!d_M || !d_plate) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
+  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (min_cover < 1 || min_cover > 255) return evh_fail(c, EVH_ERR_INVALID, W + "min_cover must lie in 1..255");
+  if (d_mask && (threshold < 0 || threshold > 255)) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
+  if (nframes > EVH_PLATE_MAX_FRAMES) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most EVH_PLATE_MAX_FRAMES = 255 frames per call");
+  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
+  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
+  const int64_t row = (int64_t)dw * cn, srow = (int64_t)sw * cn;
+  const int64_t canvas = (dh - 1) * plate_stride + row, gray = (dh - 1) * count_stride + dw, picture = (dh - 1) * mask_stride + dw;
+  if (plate_stride < row) return evh_fail(c, EVH_ERR_INVALID, W + "plate stride smaller than a row");
+  if (d_count && count_stride < dw) return evh_fail(c, EVH_ERR_INVALID, W + "count stride smaller than a row");
+  if (d_mask && (mask_stride < dw || (nframes > 1 && mask_img_stride < picture)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "mask stride smaller than a row / picture");
+  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
+  if (F.yuv && nframes > 0)
+    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  // the byte ranges the launch reads and writes: the outputs apart from each other, from the frames and from the background
+  struct Span { const uint8_t* p; int64_t n; const char* name; };
+  const auto meet = [](const Span& a, const Span& b) { return a.p && b.p && a.n > 0 && b.n > 0 && a.p < b.p + b.n && b.p < a.p + a.n; };
+  const Span outs[3] = {{d_plate, canvas, "d_plate"}, {d_count, gray, "d_count"},
+                        {d_mask, nframes > 0 ? picture + (nframes - 1) * mask_img_stride : 0, "d_mask"}};
+  Span ins[4] = {{d_bg, canvas, "d_background"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}};
+  if (nframes > 0) {
+    if (F.yuv) {
+      const evh_yuv420& s = *F.yuv;
+      const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
+      const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
+      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
+      ins[1] = {s.d_y, yb, "the frames"}; ins[2] = {s.d_cb, cb, "the frames"}; ins[3] = {s.d_cr, cb, "the frames"};
+    } else {
+      ins[1] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride, "the frames"};
+    }
+  }
+  for (int i = 0; i < 3; i++) {
+    for (int j = i + 1; j < 3; j++)
+      if (meet(outs[i], outs[j])) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + outs[j].name);
+    for (const Span& in : ins)
+      if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + in.name);
+  }
+  return evh_launch_plate_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, min_cover, d_bg, d_plate, plate_stride, d_count,
+                                      count_stride, d_mask, threshold, mask_stride, mask_img_stride, dw, dh, ox, oy);
+}
+
+int evh_plate_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                          int64_t frame_stride, const double* d_M, int inverse_map, int min_cover, const uint8_t* d_background,
+                          uint8_t* d_plate, int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask,
+                          int threshold, int64_t mask_row_stride, int64_t mask_frame_stride, int dw, int dh, int ox, int oy) {
+  return plate_fixed_plane(c, "evh_plate_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
+                           d_M, inverse_map, min_cover, d_background, d_plate, plate_row_stride, d_count, count_row_stride, d_mask,
+                           threshold, mask_row_stride, mask_frame_stride, dw, dh, ox, oy);
+}
+
+int evh_plate_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, int min_cover, const uint8_t* d_background, uint8_t* d_plate,
+                                 int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask, int threshold,
+                                 int64_t mask_row_stride, int64_t mask_frame_stride, int dw, int dh, int ox, int oy) {
+  return plate_fixed_plane(c, "evh_plate_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, min_cover,
+                           d_background, d_plate, plate_row_stride, d_count, count_row_stride, d_mask, threshold, mask_row_stride,
+                           mask_frame_stride, dw, dh, ox, oy);
+}
+
 // ---- heat-map pictures (processing_visualization.py:336-344) -----------------------------------------------------------------------
 int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
                        int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,

@@ -683,6 +683,90 @@ __global__ __launch_bounds__(256) void k_trail_fixed_plane(SRC src, int nframes,
   warp_run_store<3>(crow, n, full && (vec & 2), c);
 }
 
+// The background plate (include/evhip.h states the contract for evh_plate_fixed_plane): the per-pixel, per-channel lower
+// median of the frames that cover a canvas pixel, the number of those frames, and per frame the mask of the pixels that
+// differ from the plate.  One canvas pixel per thread, one wave per workgroup; dynamic LDS u32[nframes][64], the column
+// lds[.][lane] is this thread's alone (bank = lane: every access is conflict-free, and no barrier is needed, so threads past
+// the last pixel leave at once).
+//   pass 1  every frame sampled once through warp_sample; the samples of the n covering frames are kept, in frame order, at
+//           the head of the column as b | g << 8 | r << 16 | k << 24 (gray: the byte | k << 24; k <= 254);
+//   pass 2  the element of rank (n - 1) >> 1 by an MSB-first radix select, 8 rounds over the n kept words, the three channels
+//           side by side in the word: with P the packed prefixes found so far, a sample's byte of (word ^ P) & HI (HI = the
+//           bits from `bit` upward in each of the three bytes) is zero iff it agrees with the prefix above `bit` and has a 0
+//           there; ((t & 0x7f7f7f) + 0x7f7f7f | t) >> 7 & 0x010101 is 1 in each byte that is NOT zero, and the three counts
+//           (<= 255 each, no carry) add up in one register;
+//   pass 3  only with masks: frame by frame along the kept words, one byte per frame (64 adjacent pixels of a row: one
+//           64-byte store a wave).
+// The samples never sit in a private array: indexed at run time it would go to scratch.
+template <int CN, class SRC>
+__global__ __launch_bounds__(64) void k_plate_fixed_plane(SRC src, int nframes, int sw, int sh, const double* __restrict__ M,
+                                                          int inverse_map, int min_cover, const uint8_t* __restrict__ bg,
+                                                          uint8_t* __restrict__ plate, int64_t plate_stride,
+                                                          uint8_t* __restrict__ count, int64_t count_stride,
+                                                          uint8_t* __restrict__ mask, int threshold, int64_t mask_stride,
+                                                          int64_t mask_img_stride, int dw, int ox, int oy, unsigned npix) {
+  extern __shared__ uint32_t plate_col[];
+  const unsigned t = blockIdx.x * 64u + threadIdx.x;
+  if (t >= npix) return;
+  const int y = (int)(t / (unsigned)dw), x = (int)t - y * dw;
+  const double X = (double)((int64_t)x + ox), Y = (double)((int64_t)y + oy);
+  uint32_t* const col = plate_col + threadIdx.x;
+  int n = 0;
+  for (int k = 0; k < nframes; k++) {
+    const WarpMap A = warp_map(M + 9 * (int64_t)k, inverse_map);
+    int v[3] = {0, 0, 0};
+    if (warp_sample(src, k, A, X, Y, sw, sh, v)) {
+      col[64 * n] = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)k << 24;
+      n++;
+    }
+  }
+  const bool settled = n >= min_cover;                  // min_cover >= 1: a settled pixel has a sample
+  int p[3] = {0, 0, 0};
+  if (settled) {
+    uint32_t P = 0;
+    int rank[3];
+    rank[0] = rank[1] = rank[2] = (n - 1) >> 1;
+    for (int bit = 7; bit >= 0; bit--) {
+      const uint32_t HI = ((0xffu << bit) & 0xffu) * 0x010101u;
+      uint32_t differ = 0;
+      for (int j = 0; j < n; j++) {
+        const uint32_t d = (col[64 * j] ^ P) & HI;
+        differ += ((((d & 0x7f7f7fu) + 0x7f7f7fu) | d) >> 7) & 0x010101u;
+      }
+#pragma unroll
+      for (int c = 0; c < CN; c++) {
+        const int zeros = n - (int)((differ >> (8 * c)) & 255u);
+        if (rank[c] >= zeros) { rank[c] -= zeros; P |= 1u << (bit + 8 * c); }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CN; c++) p[c] = (int)((P >> (8 * c)) & 255u);
+  } else if (bg) {
+#pragma unroll
+    for (int c = 0; c < CN; c++) p[c] = bg[(int64_t)y * plate_stride + (int64_t)x * CN + c];
+  }
+#pragma unroll
+  for (int c = 0; c < CN; c++) plate[(int64_t)y * plate_stride + (int64_t)x * CN + c] = (uint8_t)p[c];
+  if (count) count[(int64_t)y * count_stride + x] = (uint8_t)n;
+  if (mask) {
+    const int gp = CN == 3 ? gray_of(p[0], p[1], p[2]) : p[0];
+    const uint32_t none = 0xffffffffu;                  // frame 255: no frame has that number
+    uint8_t* m = mask + (int64_t)y * mask_stride + x;
+    int j = 0;
+    uint32_t word = settled ? col[0] : none;
+    for (int k = 0; k < nframes; k++, m += mask_img_stride) {
+      int moving = 0;
+      if ((int)(word >> 24) == k) {
+        const int g = CN == 3 ? gray_of(word & 255u, (word >> 8) & 255u, (word >> 16) & 255u) : (int)(word & 255u);
+        moving = abs(g - gp) > threshold ? 255 : 0;
+        j++;
+        word = j < n ? col[64 * j] : none;
+      }
+      *m = (uint8_t)moving;
+    }
+  }
+}
+
 // Heat-map pictures (processing_visualization.py:336-344 without part_line): k_fixed_plane's field taken to a colour index,
 // looked up in a 256-entry BGR table and laid over the frame, in the arithmetic include/evhip.h states for evh_heatmap_render.
 // grid.y = frame; a thread owns WARP_RUN adjacent pixels of a row and moves their 12 bytes as three words where the pointers and
@@ -1049,6 +1133,28 @@ int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, 
   };
   if (src.yuv) go(k_trail_fixed_plane<Yuv420Src>, yuv420_src(*src.yuv));
   else go(k_trail_fixed_plane<PackedSrc>, PackedSrc{src.packed, 3, src.row_stride, src.frame_stride});
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+// k_plate_fixed_plane over the canvas (the entry has checked dw * dh <= INT_MAX and nframes <= EVH_PLATE_MAX_FRAMES, so the
+// column of samples, 256 bytes per frame, stays below the 64 KiB a workgroup gets without asking); nframes may be 0, d_bg,
+// d_count and d_mask may be NULL
+int evh_launch_plate_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
+                                 uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
+                                 int64_t mask_img_stride, int dw, int dh, int ox, int oy) {
+  const unsigned npix = (unsigned)dw * (unsigned)dh;
+  const size_t lds = (size_t)nframes * 64 * sizeof(uint32_t);
+  auto go = [&](auto kernel, const auto& S) {
+    hipLaunchKernelGGL(kernel, dim3((npix + 63) / 64), dim3(64), lds, c->stream, S, nframes, sw, sh, d_M, inverse_map, min_cover,
+                       d_bg, d_plate, plate_stride, d_count, count_stride, d_mask, threshold, mask_stride, mask_img_stride, dw,
+                       ox, oy, npix);
+  };
+  const PackedSrc P{src.packed, src.channels, src.row_stride, src.frame_stride};
+  if (src.yuv) go(k_plate_fixed_plane<3, Yuv420Src>, yuv420_src(*src.yuv));
+  else if (src.channels == 3) go(k_plate_fixed_plane<3, PackedSrc>, P);
+  else go(k_plate_fixed_plane<1, PackedSrc>, P);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;
 }

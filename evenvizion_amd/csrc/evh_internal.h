@@ -322,6 +322,10 @@ int evh_launch_pair_residual(evh_ctx* c, const EvhFrames& src, int npairs, int f
 int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
                                  int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride,
                                  uint8_t* d_out, int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy);
+int evh_launch_plate_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
+                                 uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
+                                 int64_t mask_img_stride, int dw, int dh, int ox, int oy);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);

@@ -45,15 +45,19 @@ def _chunk(tag, data):
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def write_png(path, bgr, level=1):
-    """A uint8 BGR picture [h,w,3] as an 8-bit RGB PNG (one IDAT chunk, filter 0 on every row), written with zlib alone.  The
-    decoded pixels are the picture's; the file's bytes are not those cv2.imwrite would write."""
+def write_png(path, bgr, level=1, gray=False):
+    """A uint8 BGR picture [h,w,3] as an 8-bit RGB PNG or, with gray=True, a gray picture [h,w] as an 8-bit grayscale PNG (one
+    IDAT chunk, filter 0 on every row), written with zlib alone.  The decoded pixels are the picture's; the file's bytes are
+    not those cv2.imwrite would write."""
     bgr = np.asarray(bgr)
-    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3 or bgr.shape[0] < 1 or bgr.shape[1] < 1:
-        raise ValueError("write_png takes a uint8 BGR picture [h,w,3]")
+    gray = bool(gray)
+    if bgr.dtype != np.uint8 or bgr.ndim != (2 if gray else 3) or (not gray and bgr.shape[2] != 3) or bgr.shape[0] < 1 \
+            or bgr.shape[1] < 1:
+        raise ValueError("write_png takes a uint8 BGR picture [h,w,3], or with gray=True a gray picture [h,w]")
     h, w = bgr.shape[:2]
-    raw = np.zeros((h, 1 + 3 * w), np.uint8)                                  # a filter byte (0: none) before every row
-    raw[:, 1:] = bgr[:, :, ::-1].reshape(h, 3 * w)
+    cn = 1 if gray else 3
+    raw = np.zeros((h, 1 + cn * w), np.uint8)                                 # a filter byte (0: none) before every row
+    raw[:, 1:] = bgr if gray else bgr[:, :, ::-1].reshape(h, 3 * w)
     with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+        f.write(b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0 if gray else 2, 0, 0, 0)) +
                 _chunk(b"IDAT", zlib.compress(raw.tobytes(), int(level))) + _chunk(b"IEND", b""))

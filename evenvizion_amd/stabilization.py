@@ -14,13 +14,18 @@ white rectangle (change_frame_location), both by evh_trail_fixed_plane; comparis
 the red canvas border, as create_video_comparison does.  The two words of text ("Original",
 "EvenVizion") are not drawn: no Hershey glyph table is at hand.  The colour conversions are restated arithmetic, not
 cv2.cvtColor compared byte for byte (include/evhip.h says what is claimed).
+
+background_plate takes the registered frames one step further than the reference goes: their per-pixel temporal median is the
+scene without what moves through it, and each frame's difference from it a moving-object mask (evh_plate_fixed_plane,
+DESIGN.md section 16).
 """
+import collections
 import math
 
 import numpy as np
 
 from . import runtime
-from ._lib import WARP_MODES, WARP_MOSAIC
+from ._lib import PLATE_MAX_FRAMES, WARP_MODES, WARP_MOSAIC
 
 MAX_PIXELS = 1 << 26          # canvas pixels fixed_plane_bounds accepts by default (201 MB of BGR)
 CHUNK_BYTES = 512 << 20       # cap of the canvases of one "each" / "history" chunk on the device
@@ -294,6 +299,87 @@ def comparison_frames(capture, superposition_homography_dict, resize_info, place
         host = both[:n].cpu().numpy()
         for k in range(n):
             yield first + k, host[k]
+
+
+BackgroundPlate = collections.namedtuple("BackgroundPlate", "plate count origin frame_nos masks")
+
+
+def plate_frame_numbers(n_frames, max_frames):
+    """The frames a plate is taken over: 1, 1 + s, 1 + 2s, ... <= n_frames with s = max(1, ceil(n_frames / max_frames)), at most
+    max_frames of them, spread over the whole video."""
+    n_frames, max_frames = int(n_frames), int(max_frames)
+    if n_frames < 1 or max_frames < 1:
+        raise ValueError("n_frames and max_frames must be at least 1")
+    return list(range(1, n_frames + 1, max(1, -(-n_frames // max_frames))))
+
+
+def background_plate(capture, superposition_homography_dict, resize_info, placement="warp", scale=1.0, max_frames=64, min_cover=1,
+                     masks=False, threshold=16, ingest="auto", max_pixels=MAX_PIXELS, max_bytes=2 << 30):
+    """The scene without its moving objects -> BackgroundPlate(plate u8[dh,dw,3], count u8[dh,dw], origin (ox, oy), frame_nos,
+    masks u8[n,dh,dw] or None).
+
+    Canvas and matrices are those of stabilized_frames (placement, scale, max_pixels as there).  Of the frames 1 .. the largest
+    key of the dictionary, plate_frame_numbers(., max_frames) are kept (max_frames in 1..255) while the capture is read once,
+    uploaded (as 4:2:0 planes where ingest allows) and handed to evh_plate_fixed_plane in one call: plate = per pixel and channel
+    the lower median of the frames that cover it where count >= min_cover (1..255), black elsewhere; count = how many of the
+    kept frames cover the pixel; masks=True: per kept frame, 255 where it covers the pixel and its gray differs from the plate's
+    by more than threshold (0..255) -- what moves, in fixed-plane coordinates.  A kept frame without a usable matrix covers
+    nothing; frame_nos lists the frames that were kept (fewer when the capture ends early).  ValueError when frames, plate, count
+    and masks together would take more than max_bytes on the device."""
+    import torch
+    from .processing.video_processing import _open_capture, _read_frame
+    if not 1 <= int(max_frames) <= PLATE_MAX_FRAMES:
+        raise ValueError("max_frames must lie in 1..%d" % PLATE_MAX_FRAMES)
+    if not 1 <= int(min_cover) <= 255:
+        raise ValueError("min_cover must lie in 1..255")
+    if not 0 <= int(threshold) <= 255:
+        raise ValueError("threshold must lie in 0..255")
+    if placement not in ("warp", "translate"):
+        raise ValueError("placement must be 'warp' or 'translate'")
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    first, planes, w0, h0 = _open_capture(capture, ingest)
+    ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    frame_nos = plate_frame_numbers(max(int(k) for k in _frames_of(superposition_homography_dict)), max_frames)
+    n = len(frame_nos)
+    resize = placement == "translate" and (w, h) != (w0, h0)
+    device_bytes = n * first.size + (n * h0 * w0 * 3 if planes and resize else 0) + (n * h * w * 3 if resize else 0) \
+        + dw * dh * (4 + (n if masks else 0))
+    if device_bytes > int(max_bytes):
+        raise ValueError("%d frames, plate, count and masks take %d bytes on the device, more than max_bytes = %d"
+                         % (n, device_bytes, int(max_bytes)))
+    host = np.empty((n,) + first.shape, np.uint8)
+    host[0] = first
+    kept, number = 1, 1
+    while kept < n:                                # the capture read once; only the selected frames stay
+        number += 1
+        if not _read_frame(capture, planes, host[kept], w0, h0, number):
+            break
+        if number == frame_nos[kept]:
+            kept += 1
+    n, frame_nos = kept, frame_nos[:kept]
+    ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
+    dev = runtime.device()
+    src = torch.from_numpy(host[:n]).to(dev)
+    mats = torch.from_numpy(np.stack([matrix_of(k) for k in frame_nos])).to(dev)
+    size = (w0, h0) if planes else None
+    if resize:
+        if planes:
+            bgr = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=dev)
+            ctx.yuv420_to_bgr(src, bgr, size=size)
+            src, size = bgr, None
+        small = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        ctx.resize_area(src, small)
+        src = small
+    plate = torch.empty((dh, dw, 3), dtype=torch.uint8, device=dev)
+    count = torch.empty((dh, dw), dtype=torch.uint8, device=dev)
+    pictures = torch.empty((n, dh, dw), dtype=torch.uint8, device=dev) if masks else None
+    ctx.plate_fixed_plane(src, mats, plate, (ox, oy), count=count, masks=pictures, threshold=int(threshold),
+                          min_cover=int(min_cover), size=size)
+    ctx.order_torch_after()
+    return BackgroundPlate(plate.cpu().numpy(), count.cpu().numpy(), (ox, oy), frame_nos,
+                           pictures.cpu().numpy() if masks else None)
 
 
 def write_ppm(path, image):

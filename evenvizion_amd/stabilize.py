@@ -1,5 +1,5 @@
 """Command-line driver of the stabilised view, with the arguments of the reference's
-evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail and --comparison:
+evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison and --plate:
 
     python -m evenvizion_amd.stabilize --path_to_homography_dict run1/video/dict_with_homography_matrix.json \
            --path_to_video video.mp4 --experiment_name run1 --comparison 1
@@ -12,7 +12,11 @@ evenvizion_amd.stabilization:
                      (--placement translate), and the plane sits in the red canvas border;
     --trail 1        NNNNNN.ppm per frame: that fixed-plane picture alone, at the canvas's own size, as binary P6;
     neither          NNNNNN.ppm per frame (one file for --mode mosaic): the canvas of the fixed coordinate system, geometry
-                     only -- no dimming, no border.
+                     only -- no dimming, no border;
+    --plate 1        plate.ppm, the scene without its moving objects (the per-pixel median of up to --plate_frames frames spread
+                     over the video, where at least --plate_min_cover of them cover the pixel), plate_count.png, how many frames
+                     cover each pixel, and with --plate_masks 1 mask_NNNNNN.png per frame taken: white where that frame differs
+                     from the plate by more than --plate_threshold gray levels.
 
 What is still missing from the reference's picture is its text ("Original", "EvenVizion").  The dimming is the arithmetic
 include/evhip.h states for evh_trail_fixed_plane, not cv2.cvtColor compared byte for byte.
@@ -21,7 +25,7 @@ import argparse
 import os
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(
         description="Stabilised view on MI355X (argument surface of compare_evenvizion_with_original_video.py).  By default "
                     "writes the fixed-plane canvas per frame as binary PPM, geometry only: no text, no border and no dimming "
@@ -43,9 +47,27 @@ def main(argv=None):
                          "needs --mode history")
     ap.add_argument("--comparison", type=int, choices=(0, 1), default=0,
                     help="1: the reference's side-by-side picture (original | trail inside the canvas border) as NNNNNN.png")
+    ap.add_argument("--plate", type=int, choices=(0, 1), default=0,
+                    help="1: instead of the pictures per frame, plate.ppm (the median of the registered frames: the scene without "
+                         "its moving objects) and plate_count.png (frames covering each pixel)")
+    ap.add_argument("--plate_frames", type=int, default=64, help="plate: frames taken, spread over the video (1..255)")
+    ap.add_argument("--plate_min_cover", type=int, default=1,
+                    help="plate: a pixel fewer frames cover stays black (1..255)")
+    ap.add_argument("--plate_masks", type=int, choices=(0, 1), default=0,
+                    help="plate: 1 writes mask_NNNNNN.png per frame taken, white where the frame differs from the plate")
+    ap.add_argument("--plate_threshold", type=int, default=16, help="plate: gray levels a mask pixel must differ by (0..255)")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     args = ap.parse_args(argv)
     if (args.trail or args.comparison) and args.mode != "history":
         ap.error("--trail and --comparison need --mode history")
+    if args.plate and (args.trail or args.comparison):
+        ap.error("--plate writes the plate only: not with --trail or --comparison")
+    if not (1 <= args.plate_frames <= 255 and 1 <= args.plate_min_cover <= 255 and 0 <= args.plate_threshold <= 255):
+        ap.error("--plate_frames and --plate_min_cover lie in 1..255, --plate_threshold in 0..255")
     from .component import open_capture
     from .processing.utils import read_homography_dict, superposition_dict
     from .stabilization import comparison_frames, stabilized_frames, write_ppm
@@ -54,6 +76,16 @@ def main(argv=None):
     os.makedirs(save_folder, exist_ok=True)
     homography_dict, resize_info = read_homography_dict(args.path_to_homography_dict)
     sup = superposition_dict(homography_dict)
+    if args.plate:
+        from .matching_pictures import write_png
+        from .stabilization import background_plate
+        got = background_plate(cap, sup, resize_info, placement=args.placement, scale=args.scale, max_frames=args.plate_frames,
+                               min_cover=args.plate_min_cover, masks=bool(args.plate_masks), threshold=args.plate_threshold)
+        write_ppm(os.path.join(save_folder, "plate.ppm"), got.plate)
+        write_png(os.path.join(save_folder, "plate_count.png"), got.count, gray=True)
+        for k, frame_no in enumerate(got.frame_nos if args.plate_masks else ()):
+            write_png(os.path.join(save_folder, "mask_%06d.png" % frame_no), got.masks[k], gray=True)
+        return save_folder
     if args.comparison:
         from .matching_pictures import write_png
         for frame_no, picture in comparison_frames(cap, sup, resize_info, placement=args.placement, scale=args.scale):

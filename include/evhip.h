@@ -25,6 +25,8 @@
  *                                 visualization/stabilization.py:129-172, 220-249
  *   evh_trail_fixed_plane[_yuv420] stabilize_view with decrease_brightness and change_frame_location: earlier frames dimmed,
  *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
+ *   evh_plate_fixed_plane[_yuv420] no counterpart: the "video motion segmentation" the reference's known-issues.md considers --
+ *                                 the temporal median of the registered frames (a background plate) and a moving-object mask per frame
  *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
  *                                 visualization/processing_visualization.py:336-344
  *   evh_batch_static_info         the length of the static point lists that reach draw_matches   video_processing.py:69
@@ -519,6 +521,50 @@ int evh_trail_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframe
                                  int inverse_map, const int32_t* d_rect /* may be NULL */, uint8_t* d_canvas /* in and out */,
                                  int64_t canvas_row_stride, uint8_t* d_out /* may be NULL */, int64_t out_row_stride,
                                  int64_t out_frame_stride, int dw, int dh, int ox, int oy);
+
+/* ---- the background plate: the scene without its moving objects, and the moving objects --------------------------------------- */
+/* The per-pixel temporal median of nframes frames of sw x sh registered on the fixed plane -- the scene without whatever crosses
+ * it (a background plate) -- and, by differencing each frame against that plate, a moving-object mask per frame in fixed-plane
+ * coordinates: the "video motion segmentation" the reference's known-issues.md asks for.  The frames (BGR or gray), their
+ * matrices d_M f64[nframes,9] (DEVICE), inverse_map, the canvas of dw x dh pixels and its origin (ox, oy) are
+ * evh_warp_fixed_plane's.  Per canvas pixel (x, y), the plane point (x + ox, y + oy):
+ *   1. Samples.  For k = 0 .. nframes-1, whether frame k covers the pixel and the sampled value s_k[c] per channel are exactly
+ *      evh_warp_fixed_plane's: the adjugate or inverse_map, U and V in 1/32 pixels rounded half to even, the comparison in double
+ *      (a NaN, zero, singular, huge or horizon-crossing matrix covers nothing and reads nothing), the four taps with >> 10, a tap
+ *      of weight 0 not read.  C is the set of covering frames, n = |C|.
+ *   2. Plate.  If n >= min_cover (1..255), channel c of the plate is the element of 0-based rank (n - 1) >> 1 of the samples
+ *      {s_k[c] : k in C} sorted ascending: the lower median, per channel independently, so the three channels may come from
+ *      different frames; the value always occurred, nothing is averaged or rounded.  Otherwise the pixel takes d_background's
+ *      bytes (dh rows of dw*channels bytes at plate_row_stride), or zeros when d_background is NULL.
+ *   3. Count.  If d_count is given (it may be NULL), d_count[y][x] = n as a byte, rows of dw bytes at count_row_stride, whatever
+ *      min_cover is.
+ *   4. Masks.  If d_mask is given (it may be NULL), mask k is gray, dh rows of dw bytes at mask_row_stride, at
+ *      d_mask + k*mask_frame_stride.  Its pixel is 255 iff k is in C and n >= min_cover and |gray(s_k) - gray(plate)| > threshold
+ *      (0..255), else 0, with gray(b, g, r) = (b*1868 + g*9617 + r*4899 + 8192) >> 14 as in evh_pair_residual; with
+ *      channels == 1 the byte is the gray value.
+ * Every byte of every plate row inside dw*channels is written, count and mask rows inside dw; bytes between rows are not.  Only
+ * caller buffers are used (the kernel keeps a pixel's samples in LDS, 256 bytes per frame and workgroup, which is where
+ * EVH_PLATE_MAX_FRAMES comes from): nothing depends on the sizes given to evh_create.  One launch on the context's stream; neither
+ * entry synchronises.  Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: a NULL d_frames (a NULL plane),
+ * d_M or d_plate, channels not 1 or 3, sw, sh, dw or dh < 1, nframes < 0, min_cover outside 1..255, threshold outside 0..255 when
+ * d_mask is given, a stride shorter than its row / frame (frame strides count when nframes > 1, the count and mask strides when
+ * those outputs are given), any output overlapping another output, the frames or d_background; EVH_ERR_CAPACITY:
+ * nframes > EVH_PLATE_MAX_FRAMES, sw or sh >= 2^26, dw*dh > INT_MAX.  nframes == 0 succeeds: every pixel takes the background, the
+ * count is 0, no mask is written.  The plane form (BGR plate) converts every tap as evh_yuv420_to_bgr does: it equals
+ * evh_yuv420_to_bgr followed by the BGR form.                                                                               */
+enum { EVH_PLATE_MAX_FRAMES = 255 };
+int evh_plate_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                          int64_t row_stride, int64_t frame_stride, const double* d_M, int inverse_map,
+                          int min_cover /* 1..255 */, const uint8_t* d_background /* may be NULL */,
+                          uint8_t* d_plate, int64_t plate_row_stride,
+                          uint8_t* d_count /* may be NULL */, int64_t count_row_stride,
+                          uint8_t* d_mask /* may be NULL */, int threshold /* 0..255 */, int64_t mask_row_stride,
+                          int64_t mask_frame_stride, int dw, int dh, int ox, int oy);
+int evh_plate_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, int min_cover, const uint8_t* d_background, uint8_t* d_plate,
+                                 int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask,
+                                 int threshold, int64_t mask_row_stride, int64_t mask_frame_stride,
+                                 int dw, int dh, int ox, int oy);
 
 /* ---- heat-map pictures: the colouring of heatmap_frame_processing (processing_visualization.py:336-344) ------------------------ */
 /* What heatmap_frame_processing does with the field of evh_fixed_plane_field and the resized frame, without part_line's grid,

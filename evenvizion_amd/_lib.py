@@ -114,6 +114,11 @@ SIGNATURES = {
                                    _i, _i, _i, _i]),
     "evh_plate_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i64,
                                           _i, _i, _i, _i]),
+    # match rows judged against a plate: rows on what moves are dropped, the survivors compacted in order
+    "evh_rows_moving_filter": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i,
+                                    _d, _d, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "evh_rows_moving_filter_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i,
+                                           _d, _d, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # heat-map pictures: colour index, table, blend over the frame
     "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
     # matching pictures: the rows a batch handed to its final solve, and the two frames side by side with a line per row
@@ -677,6 +682,57 @@ class Context:
             self._check(self.lib.evh_plate_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
         else:
             self._check(self.lib.evh_plate_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+
+    def rows_moving_filter(self, frames, mats, plate, count, origin, rows, counts, status1, out_rows, out_counts, moving=None,
+                           flags=None, *, threshold=16, min_cover=1, radius=1, min_hits=1, row_scale=(1.0, 1.0), frame_step=1,
+                           min_keep=8, size=None):
+        """Match rows judged against a plate (evh_rows_moving_filter[_yuv420], the contract is stated in include/evhip.h): a row
+        one of whose points sits, in its frame, on something that differs from the plate is dropped, the others move up in
+        order.  frames, mats (frame pixel -> plane point, n*9), origin, size: as for plate_fixed_plane; plate [dh,dw(,3)] and count
+        [dh,dw] as plate_fixed_plane wrote them (rows may be strided).  rows f32[npairs,cap,4] as (ax, ay, bx, by) with a on frame
+        p*frame_step + 1 and b on frame p*frame_step, counts and status1 i32[npairs]: what batch_static_rows hands out.  out_rows
+        like rows, out_counts i32[npairs], moving i32[npairs] or None, flags u8[npairs,cap] or None; all contiguous.  A point is
+        moving when at least min_hits of the (2*radius+1)^2 canvas pixels around it (row_scale takes row coordinates to frame
+        pixels) differ by more than threshold where count >= min_cover; a pair left with fewer than min_keep rows keeps all of
+        them.  Does not synchronise."""
+        import torch
+        self._enter()
+        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
+        if planes:
+            d, n, sw, sh = self._yuv420(frames, size, self.device)
+            cn = 3
+        else:
+            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
+            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
+            n = frames.shape[0]
+        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
+                or mats.numel() != 9 * n:
+            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        pp, dw, dh, prs, _ = self._image_rows(plate, cn, 0, "plate")
+        cp, cw, ch, crs, _ = self._image_rows(count, 1, 0, "count")
+        if (cw, ch) != (dw, dh):
+            raise ValueError("count must be [dh,dw] for a plate [dh,dw(,3)]")
+        if rows.dim() != 3 or rows.shape[2] != 4 or tuple(out_rows.shape) != tuple(rows.shape):
+            raise ValueError("rows and out_rows must be [npairs,cap,4]")
+        npairs, cap = int(rows.shape[0]), int(rows.shape[1])
+        for t, dt, numel, what in ((rows, torch.float32, npairs * cap * 4, "rows"), (out_rows, torch.float32, npairs * cap * 4, "out_rows"),
+                                   (counts, torch.int32, npairs, "counts"), (status1, torch.int32, npairs, "status1"),
+                                   (out_counts, torch.int32, npairs, "out_counts"), (moving, torch.int32, npairs, "moving"),
+                                   (flags, torch.uint8, npairs * cap, "flags")):
+            if t is None and what in ("moving", "flags"):
+                continue
+            if t.dtype != dt or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.numel() != numel:
+                raise ValueError("%s must be a contiguous CUDA %s tensor of %d elements" % (what, dt, numel))
+        if npairs == 0:                      # empty tensors have no address to hand over
+            return
+        tail = (mats.data_ptr(), pp, prs, cp, crs, dw, dh, int(origin[0]), int(origin[1]), int(min_cover), int(threshold),
+                int(radius), int(min_hits), float(row_scale[0]), float(row_scale[1]), rows.data_ptr(), cap, counts.data_ptr(),
+                status1.data_ptr(), npairs, int(frame_step), int(min_keep), out_rows.data_ptr(), out_counts.data_ptr(),
+                _ptr(moving), _ptr(flags))
+        if planes:
+            self._check(self.lib.evh_rows_moving_filter_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
+        else:
+            self._check(self.lib.evh_rows_moving_filter(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
 
     def heatmap_render(self, Hsup, out, lut, frames=None, heatmap_constant=1000.0, alpha=0.8, saturate=False):
         """The heat-map pictures of n superposed matrices (evh_heatmap_render, the arithmetic is stated in include/evhip.h).

@@ -24,6 +24,13 @@ with --registration_report 1 (extension, default off) also a score for every mat
                                        (registration.registration_report: evh_pair_residual; inf is written as Infinity).
 with --residual_pictures 1 (extension, default off) also the difference pictures behind those figures,
     registration_visualization/res%06d.ppm   |current frame - registered previous frame| in gray, in all three channels.
+with --reject_moving 1 (extension, default off; --path_to_video and --features ORB only) also a second pass that drops the matches on moving objects,
+    dict_with_homography_matrix_refined.json   the dictionary of moving.refine_homography_dict: the first pass's background plate
+                                       (stabilization.background_plate over --plate_frames frames), then every chunk's match rows
+                                       judged against it (evh_rows_moving_filter: --moving_threshold, --moving_radius,
+                                       --moving_min_cover) before the final solve; the first dictionary stays as it is
+    moving_rows.json                   {frame_no: {"rows", "moving", "rows_out"}} per pair
+    registration_report_refined.json   with --registration_report 1: the refined dictionary scored like the first one.
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
@@ -79,7 +86,19 @@ def load_frames(spec):
     return list(arr), os.path.split(spec)[-1].split(".")[0]
 
 
-def main(argv=None):
+def _int_in(lo, hi):
+    def parse(text):
+        try:
+            v = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError("%r is not an integer" % text)
+        if not lo <= v <= hi:
+            raise argparse.ArgumentTypeError("%d is outside %d..%d" % (v, lo, hi))
+        return v
+    return parse
+
+
+def parser():
     ap = argparse.ArgumentParser(description="EvenVizion hot path on MI355X (argument surface of evenvizion_component.py)")
     ap.add_argument("--path_to_video", type=str, default="synthetic:16:400x224:1")
     ap.add_argument("--path_to_videos", type=str, nargs="+", default=None,
@@ -109,16 +128,36 @@ def main(argv=None):
     ap.add_argument("--ingest", type=str, default="bgr", choices=("auto", "bgr", "yuv420"),
                     help="how frames reach the GPU: BGR frames (default), the decoder's 4:2:0 planes when the capture offers them "
                          "(auto), or planes only (extension; results do not depend on it)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--reject_moving", type=int, choices=(0, 1), default=0,
+                    help="1: a second pass that drops the matches on moving objects (extension; --path_to_video and --features ORB only): the "
+                         "background plate of the first pass, then moving.refine_homography_dict; writes "
+                         "dict_with_homography_matrix_refined.json and moving_rows.json beside the first dictionary, which "
+                         "stays as it is (the video is read twice more)")
+    ap.add_argument("--moving_threshold", type=_int_in(0, 255), default=16,
+                    help="--reject_moving: gray levels a point's surroundings must differ from the plate by")
+    ap.add_argument("--moving_radius", type=_int_in(0, 7), default=1,
+                    help="--reject_moving: the window around a point is (2*radius + 1)^2 canvas pixels")
+    ap.add_argument("--moving_min_cover", type=_int_in(1, 255), default=2,
+                    help="--reject_moving: frames of the plate that must cover a canvas pixel for it to be judged")
+    ap.add_argument("--plate_frames", type=_int_in(1, 255), default=64, help="--reject_moving: frames the plate is taken over")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     if _bool(args.show_matching_visualization):
         raise NotImplementedError("--show_matching_visualization is not taken: leave it off and ask for the matching pictures "
                                   "with --matching_pictures 1")
 
     from .processing.video_processing import get_homography_dict, get_homography_dicts
     features = [f for f in args.features.split(",") if f]
+    if args.reject_moving and features != ["ORB"]:
+        raise ValueError("--reject_moving takes --features ORB: the second pass is built on the fused ORB path only")
     if args.path_to_videos:
         if _bool(args.matching_pictures):
             raise ValueError("--matching_pictures takes one video (--path_to_video)")
+        if args.reject_moving:
+            raise ValueError("--reject_moving takes one video (--path_to_video)")
         opened = [open_capture(spec) for spec in args.path_to_videos]
         kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
         results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
@@ -142,7 +181,37 @@ def main(argv=None):
     result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
                                  none_H_processing=_bool(args.none_H_processing),
                                  features_type_list=features, ingest=args.ingest, matching_sink=sink)
-    return write_outputs(args, result, original_shape, stem, args.path_to_video)
+    save_folder = write_outputs(args, result, original_shape, stem, args.path_to_video)
+    if args.reject_moving:
+        write_refined(args, save_folder, features)
+    return save_folder
+
+
+def write_refined(args, save_folder, features):
+    """--reject_moving 1: the background plate of the first pass's dictionary, the second pass against it, and its files beside
+    the first pass's, which are left as they are.  The capture is opened again for each pass."""
+    from .processing.utils import read_homography_dict, superposition_dict
+    from .stabilization import background_plate
+    from .moving import refine_homography_dict
+    spec = args.path_to_video
+    first_pass, resize_info = read_homography_dict(os.path.join(save_folder, "dict_with_homography_matrix.json"))
+    plate = background_plate(open_capture(spec)[0], superposition_dict(first_pass), resize_info, placement="warp",
+                             max_frames=args.plate_frames, min_cover=args.moving_min_cover, ingest=args.ingest)
+    refined, stats = refine_homography_dict(open_capture(spec)[0], dict(first_pass, resize_info=resize_info), plate,
+                                            placement="warp", threshold=args.moving_threshold, min_cover=args.moving_min_cover,
+                                            radius=args.moving_radius, features_type_list=features, ingest=args.ingest,
+                                            none_H_processing=_bool(args.none_H_processing))
+    path = os.path.join(save_folder, "dict_with_homography_matrix_refined.json")
+    with open(path, "w") as json_:
+        json.dump(refined, json_)
+    with open(os.path.join(save_folder, "moving_rows.json"), "w") as json_:
+        json.dump({str(k): {"rows": v[0], "moving": v[1], "rows_out": v[2]} for k, v in stats.items()}, json_)
+    if _bool(args.registration_report):
+        from . import registration
+        matrices, resize_info = read_homography_dict(path)
+        report = registration.registration_report(open_capture(spec)[0], superposition_dict(matrices), resize_info, ingest=args.ingest)
+        with open(os.path.join(save_folder, "registration_report_refined.json"), "w") as json_:
+            json.dump(report, json_)
 
 
 def output_folder(args, stem):

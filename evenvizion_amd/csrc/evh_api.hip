@@ -1056,6 +1056,106 @@ int evh_plate_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes,
                            mask_frame_stride, dw, dh, ox, oy);
 }
 
+// ---- match rows against the plate: rows whose points sit on what moves are dropped ------------------------------------------------
+// the argument checks of both forms; every refusal comes before the launch
+static int rows_moving_filter(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
+                              const uint8_t* d_plate, int64_t plate_stride, const uint8_t* d_count, int64_t count_stride, int dw,
+                              int dh, int ox, int oy, int min_cover, int threshold, int radius, int min_hits, double row_sx,
+                              double row_sy, const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1,
+                              int npairs, int frame_step, int min_keep, float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving,
+                              uint8_t* d_flags) {
+  if (!c) return EVH_ERR_INVALID;
+  const std::string W = std::string(who) + ": ";
+  const int cn = F.channels;
+  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
+  if (!d_M || !d_plate || !d_count || !d_rows || !d_counts || !d_status1 || !d_out_rows || !d_out_counts)
+    return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
+  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || row_cap < 1 || npairs < 0)
+    return evh_fail(c, EVH_ERR_INVALID, W + "empty frame, canvas or row block");
+  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
+  if (min_cover < 1 || min_cover > 255) return evh_fail(c, EVH_ERR_INVALID, W + "min_cover must lie in 1..255");
+  if (threshold < 0 || threshold > 255) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
+  if (radius < 0 || radius > 7) return evh_fail(c, EVH_ERR_INVALID, W + "radius must lie in 0..7");
+  if (min_hits < 1 || min_hits > (2 * radius + 1) * (2 * radius + 1))
+    return evh_fail(c, EVH_ERR_INVALID, W + "min_hits must lie in 1..(2*radius+1)^2");
+  if (min_keep < 0) return evh_fail(c, EVH_ERR_INVALID, W + "min_keep must not be negative");
+  if (!(std::isfinite(row_sx) && std::isfinite(row_sy) && row_sx > 0.0 && row_sy > 0.0))
+    return evh_fail(c, EVH_ERR_INVALID, W + "row_sx and row_sy must be finite and positive");
+  if (npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
+  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
+  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
+  if (npairs > 0 && (int64_t)(npairs - 1) * frame_step + 2 > nframes)
+    return evh_fail(c, EVH_ERR_INVALID, W + "nframes does not reach the last pair's frames");
+  const int64_t row = (int64_t)dw * cn, srow = (int64_t)sw * cn;
+  if (plate_stride < row) return evh_fail(c, EVH_ERR_INVALID, W + "plate stride smaller than a row");
+  if (count_stride < dw) return evh_fail(c, EVH_ERR_INVALID, W + "count stride smaller than a row");
+  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
+    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
+  if (F.yuv && nframes > 0)
+    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
+  if (((uintptr_t)d_rows | (uintptr_t)d_out_rows) & 15) return evh_fail(c, EVH_ERR_INVALID, W + "d_rows and d_out_rows must be 16-byte aligned");
+  // the byte ranges the launch reads and writes: every output apart from every input and from the other outputs
+  struct Span { const void* p; int64_t n; const char* name; };
+  const auto meet = [](const Span& a, const Span& b) {
+    const uint8_t* x = (const uint8_t*)a.p; const uint8_t* y = (const uint8_t*)b.p;
+    return x && y && a.n > 0 && b.n > 0 && x < y + b.n && y < x + a.n;
+  };
+  const int64_t block = (int64_t)npairs * row_cap;
+  const Span outs[4] = {{d_out_rows, block * 16, "d_out_rows"}, {d_out_counts, (int64_t)npairs * 4, "d_out_counts"},
+                        {d_moving, (int64_t)npairs * 4, "d_moving"}, {d_flags, block, "d_flags"}};
+  Span ins[9] = {{d_M, (int64_t)nframes * 72, "d_M"}, {d_plate, (dh - 1) * plate_stride + row, "d_plate"},
+                 {d_count, (dh - 1) * count_stride + dw, "d_count"}, {d_rows, block * 16, "d_rows"},
+                 {d_counts, (int64_t)npairs * 4, "d_counts"}, {d_status1, (int64_t)npairs * 4, "d_status1"},
+                 {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}};
+  if (nframes > 0) {
+    if (F.yuv) {
+      const evh_yuv420& s = *F.yuv;
+      const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
+      const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
+      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
+      ins[6] = {s.d_y, yb, "the frames"}; ins[7] = {s.d_cb, cb, "the frames"}; ins[8] = {s.d_cr, cb, "the frames"};
+    } else {
+      ins[6] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride, "the frames"};
+    }
+  }
+  for (int i = 0; i < 4; i++) {
+    for (int j = i + 1; j < 4; j++)
+      if (meet(outs[i], outs[j])) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + outs[j].name);
+    for (const Span& in : ins)
+      if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + in.name);
+  }
+  if (npairs == 0) return EVH_SUCCESS;
+  return evh_launch_rows_moving_filter(c, F, sw, sh, d_M, d_plate, plate_stride, d_count, count_stride, dw, dh, ox, oy, min_cover,
+                                       threshold, radius, min_hits, row_sx, row_sy, d_rows, row_cap, d_counts, d_status1, npairs,
+                                       frame_step, min_keep, d_out_rows, d_out_counts, d_moving, d_flags);
+}
+
+int evh_rows_moving_filter(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                           int64_t frame_stride, const double* d_M, const uint8_t* d_plate, int64_t plate_row_stride,
+                           const uint8_t* d_count, int64_t count_row_stride, int dw, int dh, int ox, int oy, int min_cover,
+                           int threshold, int radius, int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
+                           const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
+                           float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags) {
+  return rows_moving_filter(c, "evh_rows_moving_filter", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw,
+                            sh, d_M, d_plate, plate_row_stride, d_count, count_row_stride, dw, dh, ox, oy, min_cover, threshold,
+                            radius, min_hits, row_sx, row_sy, d_rows, row_cap, d_counts, d_status1, npairs, frame_step, min_keep,
+                            d_out_rows, d_out_counts, d_moving, d_flags);
+}
+
+int evh_rows_moving_filter_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                  const uint8_t* d_plate, int64_t plate_row_stride, const uint8_t* d_count,
+                                  int64_t count_row_stride, int dw, int dh, int ox, int oy, int min_cover, int threshold, int radius,
+                                  int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
+                                  const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
+                                  float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags) {
+  return rows_moving_filter(c, "evh_rows_moving_filter_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, d_plate, plate_row_stride,
+                            d_count, count_row_stride, dw, dh, ox, oy, min_cover, threshold, radius, min_hits, row_sx, row_sy,
+                            d_rows, row_cap, d_counts, d_status1, npairs, frame_step, min_keep, d_out_rows, d_out_counts, d_moving,
+                            d_flags);
+}
+
 // ---- heat-map pictures (processing_visualization.py:336-344) -----------------------------------------------------------------------
 int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
                        int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,

@@ -767,6 +767,124 @@ __global__ __launch_bounds__(64) void k_plate_fixed_plane(SRC src, int nframes, 
   }
 }
 
+// Match rows whose points sit on something that differs from the plate are dropped (include/evhip.h states the contract for
+// evh_rows_moving_filter).  One workgroup of four waves per pair, walking the pair's rows in tiles of MOVING_TILE:
+//   phase A  one (row, end point) per thread: the end point through its frame's matrix to the canvas pixel (cx, cy), kept in LDS
+//            (cx == INT_MIN: the end point cannot be moving);
+//   phase B  the lanes spread over (end point, window pixel), window pixels of an end point on adjacent lanes: the count byte
+//            first (a pixel below min_cover costs no division), then warp_sample and the gray difference from the plate.  The
+//            hits of a wave are one ballot; the first lane of every end point's run inside the wave adds the popcount of the
+//            run to the end point's LDS counter (runs of one end point meet only across waves and tiles of 256 items);
+//   phase C  one row per thread: its flags, and the survivors compacted in order -- ballot and popcount inside the wave, the
+//            four wave totals through LDS, a running offset across the tiles.
+// A pair left with fewer than min_keep rows is then copied whole by the same workgroup (the barrier that ends every tile
+// orders the two writes of a slot).  The two frames' matrices and adjugates sit in LDS, formed once by warp_map.
+#define MOVING_TILE 256
+template <int CN, class SRC>
+__global__ __launch_bounds__(MOVING_TILE) void k_rows_moving_filter(
+    SRC src, int sw, int sh, const double* __restrict__ M, const uint8_t* __restrict__ plate, int64_t plate_stride,
+    const uint8_t* __restrict__ count, int64_t count_stride, int dw, int dh, int ox, int oy, int min_cover, int threshold,
+    int radius, int min_hits, double row_sx, double row_sy, const float* __restrict__ rows, int row_cap,
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ status1, int frame_step, int min_keep,
+    float* __restrict__ out_rows, int32_t* __restrict__ out_counts, int32_t* __restrict__ moving_out, uint8_t* __restrict__ flags) {
+  __shared__ double s_fwd[2][9], s_adj[2][9];          // [0]: the current frame (point a), [1]: the previous frame (point b)
+  __shared__ int s_cx[2 * MOVING_TILE], s_cy[2 * MOVING_TILE], s_hits[2 * MOVING_TILE];
+  __shared__ int s_wtot[MOVING_TILE / 64];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int given = counts[p];
+  const int n = min(max(given, 0), row_cap);
+  if (status1[p] != EVH_PAIR_OK || n == 0) {
+    if (tid == 0) {
+      out_counts[p] = given;
+      if (moving_out) moving_out[p] = 0;
+    }
+    return;
+  }
+  const int fprev = p * frame_step;
+  if (tid < 2) {
+    const double* m = M + 9 * (int64_t)(fprev + 1 - tid);
+    const WarpMap A = warp_map(m, 0);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { s_fwd[tid][k] = m[k]; s_adj[tid][k] = A.a[k]; }
+  }
+  const uint4* const in4 = reinterpret_cast<const uint4*>(rows) + (int64_t)p * row_cap;
+  uint4* const out4 = reinterpret_cast<uint4*>(out_rows) + (int64_t)p * row_cap;
+  const unsigned W = 2u * (unsigned)radius + 1u, W2 = W * W;
+  int kept = 0;                                        // the running offset: rows kept in the tiles before this one
+  for (int base = 0; base < n; base += MOVING_TILE) {
+    const int tn = min(n - base, MOVING_TILE);
+    __syncthreads();                                   // the matrices are there; the tile before is done with LDS
+    for (int e = tid; e < 2 * tn; e += MOVING_TILE) {
+      const int s = e & 1;
+      const float* q = rows + ((int64_t)p * row_cap + base + (e >> 1)) * 4 + 2 * s;
+      const double px = (double)q[0] * row_sx, py = (double)q[1] * row_sy;
+      const double tx = (s_fwd[s][0] * px + s_fwd[s][1] * py) + s_fwd[s][2];
+      const double ty = (s_fwd[s][3] * px + s_fwd[s][4] * py) + s_fwd[s][5];
+      const double tw = (s_fwd[s][6] * px + s_fwd[s][7] * py) + s_fwd[s][8];
+      const double cx = __builtin_rint(tx / tw), cy = __builtin_rint(ty / tw);
+      const bool on = __builtin_fabs(cx) <= 1073741824.0 && __builtin_fabs(cy) <= 1073741824.0;      // NaN fails
+      s_cx[e] = on ? (int)cx : INT_MIN;
+      s_cy[e] = on ? (int)cy : 0;
+      s_hits[e] = 0;
+    }
+    __syncthreads();
+    const unsigned items = 2u * (unsigned)tn * W2;      // <= 512 * 225
+    for (unsigned first = 0; first < items; first += MOVING_TILE) {
+      const unsigned idx = first + (unsigned)tid;
+      const bool active = idx < items;
+      const unsigned e = active ? idx / W2 : 0u, wp = active ? idx - e * W2 : 0u;
+      bool hit = false;
+      const int cx = s_cx[e];
+      if (active && cx != INT_MIN) {
+        const int s = (int)(e & 1u);
+        const int wj = (int)(wp / W), wi = (int)wp - wj * (int)W;
+        const int64_t PX = (int64_t)cx + (wi - radius), PY = (int64_t)s_cy[e] + (wj - radius);      // the plane point
+        const int64_t X = PX - ox, Y = PY - oy;                                                    // the canvas pixel
+        if (X >= 0 && X < dw && Y >= 0 && Y < dh && (int)count[Y * count_stride + X] >= min_cover) {
+          WarpMap A;
+#pragma unroll
+          for (int k = 0; k < 9; k++) A.a[k] = s_adj[s][k];
+          int v[3] = {0, 0, 0};
+          if (warp_sample(src, fprev + 1 - s, A, (double)PX, (double)PY, sw, sh, v)) {
+            const uint8_t* pl = plate + Y * plate_stride + X * CN;
+            const int g = CN == 3 ? gray_of(v[0], v[1], v[2]) : v[0];
+            const int gp = CN == 3 ? gray_of(pl[0], pl[1], pl[2]) : pl[0];
+            hit = abs(g - gp) > threshold;
+          }
+        }
+      }
+      const unsigned long long m = __ballot(hit);
+      if (active && (lane == 0 || wp == 0)) {           // the first lane of this end point's run inside the wave
+        const unsigned run = min(64u - (unsigned)lane, W2 - wp);
+        const unsigned long long span = (run >= 64u ? ~0ull : ((1ull << run) - 1ull)) << lane;
+        const int c = __popcll(m & span);
+        if (c) atomicAdd(&s_hits[e], c);
+      }
+    }
+    __syncthreads();
+    const bool mine = tid < tn;
+    const int fa = mine && s_hits[2 * tid] >= min_hits, fb = mine && s_hits[2 * tid + 1] >= min_hits;
+    const bool keep = mine && !(fa | fb);
+    const unsigned long long km = __ballot(keep);
+    if (lane == 0) s_wtot[wv] = __popcll(km);
+    if (mine && flags) flags[(int64_t)p * row_cap + base + tid] = (uint8_t)(fa | fb << 1);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < MOVING_TILE / 64; k++) { const int t = s_wtot[k]; before += k < wv ? t : 0; total += t; }
+    if (keep) out4[kept + before + __popcll(km & ((1ull << lane) - 1ull))] = in4[base + tid];
+    kept += total;
+  }
+  __syncthreads();                                     // every slot written above is visible to whoever writes it again
+  const bool starved = kept < min_keep;
+  if (starved)
+    for (int i = tid; i < n; i += MOVING_TILE) out4[i] = in4[i];
+  if (tid == 0) {
+    out_counts[p] = starved ? n : kept;
+    if (moving_out) moving_out[p] = n - kept;
+  }
+}
+
 // Heat-map pictures (processing_visualization.py:336-344 without part_line): k_fixed_plane's field taken to a colour index,
 // looked up in a 256-entry BGR table and laid over the frame, in the arithmetic include/evhip.h states for evh_heatmap_render.
 // grid.y = frame; a thread owns WARP_RUN adjacent pixels of a row and moves their 12 bytes as three words where the pointers and
@@ -1155,6 +1273,27 @@ int evh_launch_plate_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, 
   if (src.yuv) go(k_plate_fixed_plane<3, Yuv420Src>, yuv420_src(*src.yuv));
   else if (src.channels == 3) go(k_plate_fixed_plane<3, PackedSrc>, P);
   else go(k_plate_fixed_plane<1, PackedSrc>, P);
+  EVH_HIP(c, hipGetLastError());
+  return EVH_SUCCESS;
+}
+
+// k_rows_moving_filter, one workgroup per pair (the entry has checked 1 <= npairs <= 65535, that the frames reach the last pair and
+// that every output lies apart from every input); d_moving and d_flags may be NULL
+int evh_launch_rows_moving_filter(evh_ctx* c, const EvhFrames& src, int sw, int sh, const double* d_M, const uint8_t* d_plate,
+                                  int64_t plate_stride, const uint8_t* d_count, int64_t count_stride, int dw, int dh, int ox, int oy,
+                                  int min_cover, int threshold, int radius, int min_hits, double row_sx, double row_sy,
+                                  const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1, int npairs,
+                                  int frame_step, int min_keep, float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving,
+                                  uint8_t* d_flags) {
+  auto go = [&](auto kernel, const auto& S) {
+    hipLaunchKernelGGL(kernel, dim3(npairs), dim3(MOVING_TILE), 0, c->stream, S, sw, sh, d_M, d_plate, plate_stride, d_count,
+                       count_stride, dw, dh, ox, oy, min_cover, threshold, radius, min_hits, row_sx, row_sy, d_rows, row_cap,
+                       d_counts, d_status1, frame_step, min_keep, d_out_rows, d_out_counts, d_moving, d_flags);
+  };
+  const PackedSrc P{src.packed, src.channels, src.row_stride, src.frame_stride};
+  if (src.yuv) go(k_rows_moving_filter<3, Yuv420Src>, yuv420_src(*src.yuv));
+  else if (src.channels == 3) go(k_rows_moving_filter<3, PackedSrc>, P);
+  else go(k_rows_moving_filter<1, PackedSrc>, P);
   EVH_HIP(c, hipGetLastError());
   return EVH_SUCCESS;
 }

@@ -326,6 +326,12 @@ int evh_launch_plate_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, 
                                  int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
                                  uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
                                  int64_t mask_img_stride, int dw, int dh, int ox, int oy);
+int evh_launch_rows_moving_filter(evh_ctx* c, const EvhFrames& src, int sw, int sh, const double* d_M, const uint8_t* d_plate,
+                                  int64_t plate_stride, const uint8_t* d_count, int64_t count_stride, int dw, int dh, int ox, int oy,
+                                  int min_cover, int threshold, int radius, int min_hits, double row_sx, double row_sy,
+                                  const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1, int npairs,
+                                  int frame_step, int min_keep, float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving,
+                                  uint8_t* d_flags);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);

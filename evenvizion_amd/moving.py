@@ -1,0 +1,169 @@
+"""The second pass over a video: matches on moving objects are dropped before the final solve.
+
+The reference's known-issues.md names moving objects as the open problem of the method: key points cling to what moves, and the
+homography follows the object instead of the camera.  With a first pass (get_homography_dict) and the background plate taken from
+it (stabilization.background_plate) at hand, refine_homography_dict reads the video again and, per chunk, runs the same batch
+entry, fetches the rows that entered its final solve (evh_batch_static_rows), drops the rows one of whose points sits on
+something that differs from the plate (evh_rows_moving_filter) and solves the remaining rows with the reference's running
+superposition (evh_stream_scan).  Rows, flags and counts never leave the device; only the matrices, the statuses and three counts
+per pair come back.
+"""
+import numpy as np
+
+from . import runtime
+from ._lib import PAIR_CAPACITY, PAIR_OK
+from .processing.utils import superposition_dict
+from .processing.video_processing import CHUNK_FRAMES
+
+MAX_RADIUS = 7      # evh_rows_moving_filter: the window is (2*radius + 1)^2 canvas pixels
+
+
+def _integer(name, value, lo, hi=None):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
+        raise ValueError("%s must be an integer %s" % (name, ("in %d..%d" % (lo, hi)) if hi is not None else "of at least %d" % lo))
+    return int(value)
+
+
+def _arguments(homography_dict, plate, placement, scale, threshold, min_cover, radius, min_hits, min_keep, nfeatures, chunk_frames,
+               features_type_list, ingest):
+    """The refusals of refine_homography_dict, before the capture is opened or the device touched
+    -> (per-frame dictionary with int keys, resize_info)"""
+    from .processing.video_processing import _feature_list
+    if placement not in ("warp", "translate"):
+        raise ValueError("placement must be 'warp' or 'translate'")
+    if ingest not in ("auto", "bgr", "yuv420"):
+        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or scale <= 0:
+        raise ValueError("scale must be a finite positive number")
+    if placement == "translate" and float(scale) != 1.0:
+        raise ValueError("placement='translate' is the reference's paste: scale must be 1")
+    _integer("threshold", threshold, 0, 255)
+    _integer("min_cover", min_cover, 1, 255)
+    radius = _integer("radius", radius, 0, MAX_RADIUS)
+    _integer("min_hits", min_hits, 1, (2 * radius + 1) ** 2)
+    _integer("min_keep", min_keep, 0)
+    _integer("nfeatures", nfeatures, 1)
+    _integer("chunk_frames", chunk_frames, 2)
+    if _feature_list(features_type_list) != ["ORB"]:
+        raise ValueError('features_type_list must be ["ORB"]: the second pass is built on the fused ORB path only')
+    if not isinstance(homography_dict, dict) or "resize_info" not in homography_dict:
+        raise ValueError("homography_dict must be the first pass's dictionary, with its resize_info")
+    resize_info = homography_dict["resize_info"]
+    per_frame = {int(k): v for k, v in homography_dict.items() if k != "resize_info"}
+    if not per_frame:
+        raise ValueError("homography_dict holds no pair")
+    for name in ("plate", "count", "origin"):
+        if not hasattr(plate, name):
+            raise ValueError("plate must be the BackgroundPlate that background_plate returned")
+    p, c = np.asarray(plate.plate), np.asarray(plate.count)
+    if p.dtype != np.uint8 or p.ndim != 3 or p.shape[2] != 3 or c.dtype != np.uint8 or c.shape != p.shape[:2]:
+        raise ValueError("plate.plate must be u8[dh,dw,3] and plate.count u8[dh,dw]")
+    return per_frame, resize_info
+
+
+def refine_homography_dict(capture, homography_dict, plate, placement="warp", scale=1.0, threshold=16, min_cover=2, radius=1,
+                           min_hits=1, min_keep=8, nfeatures=runtime.NFEATURES, chunk_frames=CHUNK_FRAMES,
+                           features_type_list=("ORB",), ingest="auto", none_H_processing=True):
+    """-> (refined_dict, stats).  capture: the video of the first pass, opened again.  homography_dict: the first pass's result
+    ({frame_no: {"H": 3x3}, ..., "resize_info"}, keys int or str).  plate: the BackgroundPlate background_plate returned for the
+    same video with the same placement and scale (its superposition must be superposition_dict of homography_dict).
+
+    The superposition and the canvas are formed as background_plate forms them; a canvas whose shape or origin differs from
+    the plate's is a ValueError (wrong placement or scale).  Plate and count are uploaded once.  The capture is then read chunk
+    by chunk (chunk_frames frames, consecutive chunks overlapping by one frame); per chunk the batch entry get_homography_dict
+    runs for ["ORB"] and this ingest, batch_static_rows, rows_moving_filter -- for "warp" on the frames as uploaded, with
+    row_scale = (w0 / w, h0 / h) from resized to original pixels; for "translate" on the device-resized frames with (1, 1) --
+    and stream_scan with the carried {H_sup, H_prev}.  The matrices that place a frame on the plate are the FIRST pass's: the
+    plate was built from them.  threshold, min_cover, radius, min_hits, min_keep: see Context.rows_moving_filter; the default
+    min_cover = 2 judges a point only where at least two of the plate's frames met.
+
+    This is a plain synchronous chunk loop: every chunk is read, uploaded, solved and downloaded before the next is read.  The
+    double-buffered pipeline of get_homography_dict is not built here.  A chunk in which a pair reports EVH_PAIR_CAPACITY (more
+    tied key points than a frame slot holds) raises RuntimeError naming the frames: the re-run on larger slots of the first
+    pass is not built either.  Only features_type_list=["ORB"] is taken (ValueError otherwise): evh_stream_scan solves the
+    row blocks of the fused ORB path; on the wider blocks of a multi-type batch it did not reproduce that batch's own solve
+    when it was tried (the first pair came back EVH_PAIR_LOW_INLIER_RATIO), so the second pass over such a list is not built.
+
+    refined_dict has the format and the none_H_processing rule of get_homography_dict.  stats[frame_no] = (rows, moving,
+    rows_out) for the pair ending at frame_no: the rows that reached the filter, those it found moving, those handed to the
+    solve (rows - moving, or rows when fewer than min_keep would have been left); (0, 0, 0) for a pair without rows."""
+    import torch
+    from .processing.video_processing import _open_capture, _pairs_into, _read_frame, resized_shape
+    from .stabilization import MAX_PIXELS, _placement
+    per_frame, resize_info = _arguments(homography_dict, plate, placement, scale, threshold, min_cover, radius, min_hits,
+                                                  min_keep, nfeatures, chunk_frames, features_type_list, ingest)
+    sup = superposition_dict(per_frame)
+    first, planes, w0, h0 = _open_capture(capture, ingest)
+    if not planes and (first.ndim != 3 or first.shape[2] != 3):
+        raise ValueError("frames must be BGR [h,w,3] or decoded planes: the plate is a BGR picture")
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    if (w, h) != resized_shape((h0, w0), w):
+        raise ValueError("resize_info %dx%d is not what frames of %dx%d resize to" % (w, h, w0, h0))
+    ox, oy, dw, dh, matrix_of = _placement(sup, resize_info, placement, scale, w0, h0, max(MAX_PIXELS, int(np.asarray(plate.plate).size)))
+    if (dh, dw) != tuple(np.asarray(plate.plate).shape[:2]) or (ox, oy) != (int(plate.origin[0]), int(plate.origin[1])):
+        raise ValueError("the canvas of this dictionary is %d x %d at (%d, %d), the plate %d x %d at (%d, %d): another placement or scale"
+                         % (dw, dh, ox, oy, plate.plate.shape[1], plate.plate.shape[0], plate.origin[0], plate.origin[1]))
+    method, size = ("stream_homography_batch_yuv420", ((w0, h0),)) if planes else ("stream_homography_batch", ())
+    chunk = runtime.chunk_frames_for(first.nbytes, max(2, int(chunk_frames)))
+    ctx = runtime.get_context(w, h, chunk, nfeatures)
+    dev = runtime.device()
+    plate_dev = torch.from_numpy(np.ascontiguousarray(plate.plate)).to(dev)
+    count_dev = torch.from_numpy(np.ascontiguousarray(plate.count)).to(dev)
+    translate = placement == "translate"
+    resize = translate and (w, h) != (w0, h0)
+    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and resize else None
+    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    row_scale = (1.0, 1.0) if translate else (w0 / w, h0 / h)
+    H_dev = torch.zeros((chunk - 1, 9), dtype=torch.float64, device=dev)
+    st_dev = torch.zeros(chunk - 1, dtype=torch.int32, device=dev)
+    first_state = torch.zeros(18, dtype=torch.float64, device=dev)      # {H_sup, H_prev} of the first pass's solve, as it ran
+    state = torch.zeros(18, dtype=torch.float64, device=dev)            # and of the refined one
+    host = np.empty((chunk,) + first.shape, np.uint8)
+    host[0] = first
+    refined, stats = {}, {}
+    frame_no, n, have_state, more = 1, 1, False, True        # host[0] is frame `frame_no`, the newest frame already paired
+    buffers = {}                                             # row capacity -> the filter's outputs
+    while more:
+        while n < chunk:
+            if not _read_frame(capture, planes, host[n], w0, h0, frame_no + n):
+                more = False
+                break
+            n += 1
+        if n < 2:
+            break
+        npairs = n - 1
+        src = torch.from_numpy(host[:n]).to(dev)
+        getattr(ctx, method)(src, *size, H_dev, st_dev, state_in=first_state if have_state else None,
+                             state_out=first_state, nfeatures=nfeatures, resize_to=(w, h))
+        rows, counts, st1 = ctx.batch_static_rows(0, npairs)
+        cap = rows.shape[1]
+        if cap not in buffers:
+            buffers[cap] = (torch.empty((chunk - 1, cap, 4), dtype=torch.float32, device=dev),
+                            torch.empty(chunk - 1, dtype=torch.int32, device=dev), torch.empty(chunk - 1, dtype=torch.int32, device=dev))
+        out_rows, out_counts, moving = (t[:npairs] for t in buffers[cap])
+        judged, judged_size = src, (w0, h0) if planes else None
+        if resize:
+            if planes:
+                ctx.yuv420_to_bgr(src, bgr[:n], size=(w0, h0))
+                judged, judged_size = bgr[:n], None
+            ctx.resize_area(judged, small[:n])
+            judged = small[:n]
+        mats = torch.from_numpy(np.stack([matrix_of(k) for k in range(frame_no, frame_no + n)])).to(dev)
+        ctx.rows_moving_filter(judged, mats, plate_dev, count_dev, (ox, oy), rows, counts, st1, out_rows, out_counts, moving,
+                               threshold=int(threshold), min_cover=int(min_cover), radius=int(radius), min_hits=int(min_hits),
+                               row_scale=row_scale, frame_step=1, min_keep=int(min_keep), size=judged_size)
+        Hs, sts = ctx.stream_scan(out_rows, out_counts, st1, state_in=state if have_state else None, state_out=state)
+        have_state = True
+        sts_h, st1_h = sts.cpu().numpy(), st1.cpu().numpy()
+        if (sts_h == PAIR_CAPACITY).any() or (st1_h == PAIR_CAPACITY).any() or (st_dev[:npairs].cpu().numpy() == PAIR_CAPACITY).any():
+            raise RuntimeError("frames %d..%d: more tied key points than a frame slot holds (EVH_PAIR_CAPACITY); the re-run on "
+                               "larger slots is not built for the second pass" % (frame_no, frame_no + npairs))
+        n_in, n_out, mov = (np.clip(t.cpu().numpy(), 0, cap) for t in (counts, out_counts, moving))
+        for k in range(npairs):
+            ok = st1_h[k] == PAIR_OK and n_in[k] > 0
+            stats[frame_no + 1 + k] = (int(n_in[k]), int(mov[k]), int(n_out[k])) if ok else (0, 0, 0)
+        frame_no = _pairs_into(refined, frame_no, Hs.cpu().numpy().reshape(-1, 3, 3), sts_h, none_H_processing)
+        host[0] = host[n - 1]                               # consecutive chunks overlap by one frame
+        n = 1
+    refined["resize_info"] = {"h": h, "w": w}
+    return refined, stats

@@ -27,6 +27,8 @@
  *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
  *   evh_plate_fixed_plane[_yuv420] no counterpart: the "video motion segmentation" the reference's known-issues.md considers --
  *                                 the temporal median of the registered frames (a background plate) and a moving-object mask per frame
+ *   evh_rows_moving_filter[_yuv420] no counterpart: match rows whose points differ from that plate are dropped before the final
+ *                                 solve (known-issues.md: key points cling to what moves)
  *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
  *                                 visualization/processing_visualization.py:336-344
  *   evh_batch_static_info         the length of the static point lists that reach draw_matches   video_processing.py:69
@@ -565,6 +567,57 @@ int evh_plate_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframe
                                  int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask,
                                  int threshold, int64_t mask_row_stride, int64_t mask_frame_stride,
                                  int dw, int dh, int ox, int oy);
+/* Match rows judged against a plate: the rows of a batch (evh_batch_static_rows) whose points sit on something that differs from
+ * the plate are dropped before the final solve, so that the homography follows the camera and not what moves -- the step between
+ * evh_plate_fixed_plane and evh_stream_scan.  It judges ANY frame against a given plate (the masks above exist only for the plate's
+ * own frames) and reads only the canvas pixels around each key point.  The frames, d_M f64[nframes,9] (DEVICE; frame pixels ->
+ * plane, the inverse_map == 0 form only), the canvas of dw x dh pixels and its origin (ox, oy) are evh_plate_fixed_plane's; d_plate
+ * has the frames' channels (the plane form: BGR), d_count one byte per pixel.  d_rows f32[npairs][row_cap][4] holds rows
+ * (ax, ay, bx, by), a on the current and b on the previous frame; pair p has its previous frame at index fp = p*frame_step and its
+ * current frame at fc = fp + 1, as in evh_draw_matches and evh_pair_residual; nframes must reach the last index used.  All
+ * arithmetic is IEEE float64 with one rounding per operation (no fma).
+ *   1. Rows of a pair.  n = min(max(d_counts[p], 0), row_cap).  If d_status1[p] != EVH_PAIR_OK or n == 0: d_out_counts[p] =
+ *      d_counts[p], d_moving[p] = 0, and no row and no flag of the pair is written.
+ *   2. An end point's place.  End point (x, y) lies in frame f (fc for a, fp for b): px = (double)x * row_sx, py = (double)y * row_sy;
+ *      with m = d_M[f]: tx = (m0*px + m1*py) + m2, ty = (m3*px + m4*py) + m5, tw = (m6*px + m7*py) + m8; cx = rint(tx / tw),
+ *      cy = rint(ty / tw), halves to even.  Unless |cx| <= 2^30 and |cy| <= 2^30, compared in double (NaN fails), the end point is
+ *      not moving.
+ *   3. Window and hits.  The window pixels are (X, Y) = (cx - ox + i, cy - oy + j) for |i|, |j| <= radius (0..7), formed in int64.
+ *      A window pixel is a HIT iff 0 <= X < dw and 0 <= Y < dh, and d_count[Y][X] >= min_cover (1..255), and frame f covers (X, Y)
+ *      exactly as evh_warp_fixed_plane defines coverage (the adjugate of m, U and V in 1/32 pixels), and
+ *      |gray(s_f) - gray(plate[Y][X])| > threshold (0..255), s_f being that entry's four-tap sample and gray the integer gray of
+ *      evh_pair_residual; with channels == 1 the byte is the gray value.  A hit is precisely the byte evh_plate_fixed_plane would have
+ *      written into frame f's mask, had f been one of the plate's frames.  The end point is moving iff hits >= min_hits
+ *      (1..(2*radius+1)^2).
+ *   4. A row is moving iff a is moving in fc or b is moving in fp; moving = the number of such rows among the n.  If d_flags is
+ *      given (u8[npairs][row_cap]; it may be NULL), row i < n gets (a moving) | (b moving) << 1; flags past n are untouched.
+ *   5. Output.  If n - moving >= min_keep (>= 0): the rows that are not moving go to the head of pair p's block of d_out_rows
+ *      f32[npairs][row_cap][4] in their original order, each copied as 16 bytes (bit patterns: -0.0 and NaN payloads survive), and
+ *      d_out_counts[p] = n - moving.  Otherwise all n rows are copied unfiltered and d_out_counts[p] = n: a filter must never starve
+ *      a pair that had a solution.  d_moving[p] = moving in both cases (d_moving may be NULL).  Rows past the out count are untouched.
+ * Only caller buffers are used; one launch on the context's stream (one workgroup per pair; the survivors are compacted by a prefix
+ * scan, so their order is stable), neither entry synchronises, and the record of the last batch is left alone.  Refused before
+ * anything is launched, outputs untouched -- EVH_ERR_INVALID: a NULL source (a NULL plane), d_M, d_plate, d_count, d_rows, d_counts,
+ * d_status1, d_out_rows or d_out_counts, channels not 1 or 3, sw, sh, dw, dh or row_cap < 1, nframes or npairs < 0, frame_step not 1
+ * or 2, nframes < (npairs - 1)*frame_step + 2 when npairs >= 1, min_cover outside 1..255, threshold outside 0..255, radius outside
+ * 0..7, min_hits outside 1..(2*radius+1)^2, min_keep < 0, row_sx or row_sy not finite or <= 0, a stride shorter than its row / frame
+ * (frame strides count when nframes > 1), d_rows or d_out_rows not 16-byte aligned, any output overlapping any input or another
+ * output; EVH_ERR_CAPACITY: npairs > 65535, sw or sh >= 2^26, dw*dh > INT_MAX.  npairs == 0 succeeds and does nothing.  The plane
+ * form converts every tap as evh_yuv420_to_bgr does: it equals evh_yuv420_to_bgr followed by the BGR form.                       */
+int evh_rows_moving_filter(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                           int64_t row_stride, int64_t frame_stride, const double* d_M /* f64[nframes,9] DEVICE */,
+                           const uint8_t* d_plate, int64_t plate_row_stride, const uint8_t* d_count, int64_t count_row_stride,
+                           int dw, int dh, int ox, int oy, int min_cover /* 1..255 */, int threshold /* 0..255 */,
+                           int radius /* 0..7 */, int min_hits /* 1..(2r+1)^2 */, double row_sx, double row_sy,
+                           const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1, int npairs,
+                           int frame_step /* 1 | 2 */, int min_keep /* >= 0 */, float* d_out_rows, int32_t* d_out_counts,
+                           int32_t* d_moving /* may be NULL */, uint8_t* d_flags /* may be NULL */);
+int evh_rows_moving_filter_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                  const uint8_t* d_plate, int64_t plate_row_stride, const uint8_t* d_count,
+                                  int64_t count_row_stride, int dw, int dh, int ox, int oy, int min_cover, int threshold, int radius,
+                                  int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
+                                  const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
+                                  float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags);
 
 /* ---- heat-map pictures: the colouring of heatmap_frame_processing (processing_visualization.py:336-344) ------------------------ */
 /* What heatmap_frame_processing does with the field of evh_fixed_plane_field and the resized frame, without part_line's grid,

@@ -54,7 +54,8 @@ void compute_geometry(int w, int h, int nfeatures, EvhGeom& g) {
     L.h = round_f((float)h / L.scale);
     L.stride = align_up(L.w, 64);
     L.off = off;
-    off += align_up64((int64_t)L.stride * L.h, 256);
+    // two rows at the least: the pyramid kernels stage the row below a tap's (weight 0 under a source of one row)
+    off += align_up64((int64_t)L.stride * std::max(L.h, 2), 256);
     L.cand_cap = (L.w / 2 + 1) * (L.h / 2 + 1) + 64;  // NMS admits at most one corner per 2x2 block
     L.cand_off = coff;
     coff += L.cand_cap;
@@ -115,6 +116,9 @@ int configure(evh_ctx* c, int w, int h, int nfeatures) {
   if (w >= 4096 || h >= 4096) return evh_fail(c, EVH_ERR_UNSUPPORTED, "frames must be smaller than 4096 in each dimension");
   EvhGeom g;
   compute_geometry(w, h, nfeatures, g);
+  // a side of 1 rounds to 0 from level 6 on (1 / 2.99): a level without pixels is a launch with an empty grid
+  if (g.lv[EVH_NLEVELS - 1].w < 1 || g.lv[EVH_NLEVELS - 1].h < 1)
+    return evh_fail(c, EVH_ERR_UNSUPPORTED, "frames must be at least 2 pixels in each dimension: a pyramid level would be empty");
   EvhGeom gmax;
   compute_geometry(c->max_w, c->max_h, c->max_features, gmax);
   if (g.pyr_frame_bytes > gmax.pyr_frame_bytes || g.cand_frame_entries > gmax.cand_frame_entries)

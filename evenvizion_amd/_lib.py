@@ -567,6 +567,32 @@ class Context:
             raise ValueError("%s must have packed pixels" % what)
         return t.data_ptr(), int(w), int(h), (t.stride(lead) if h > 1 else w * cn), t.stride(0)
 
+    def _frame_source(self, frames, size, bgr_only=False, planes=None):
+        """The frames of an entry that has a packed and a _yuv420 form: a uint8 CUDA tensor [n,h,w] (gray) or [n,h,w,3] (BGR;
+        bgr_only: nothing else), or decoded planes (see _yuv420; planes=None: a tuple or a 2-D tensor is taken for planes).
+        -> (planes?, head, n, w, h, cn); head is what follows the context in the call: (description, n, w, h) for planes,
+        (pointer, n, w, h, cn, row stride, frame stride) for packed frames, without cn where bgr_only."""
+        if planes is None:
+            planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
+        if planes:
+            d, n, w, h = self._yuv420(frames, size, self.device)
+            return True, (C.byref(d), n, w, h), n, w, h, 3
+        cn = 3 if bgr_only else 1 if frames.dim() == 3 else int(frames.shape[-1])
+        fp, w, h, frs, ffs = self._image_rows(frames, cn, 1, "frames")
+        n = frames.shape[0]
+        return False, (fp, n, w, h) + (() if bgr_only else (cn,)) + (frs, ffs), n, w, h, cn
+
+    def _dev_tensor(self, t, dtype, size, message, *args):
+        """ValueError(message % args) unless t is a contiguous CUDA tensor of `dtype` on the context's device with `size`
+        elements (an int) or of that shape (a tuple).  The message is only put together when it is needed."""
+        if t.dtype != dtype or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or \
+                (t.numel() != size if isinstance(size, int) else tuple(t.shape) != tuple(size)):
+            raise ValueError(message % args if args else message)
+
+    def _form(self, name, planes):
+        """The entry `name`, or its _yuv420 form for planes."""
+        return getattr(self.lib, name + "_yuv420" if planes else name)
+
     def warp_fixed_plane(self, frames, mats, out, mode, origin, background=None, inverse_map=False, size=None):
         """Frames warped into the fixed plane (evh_warp_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h).
         frames: CUDA uint8 [n,h,w] (gray) or [n,h,w,3] (BGR), rows and frames may be strided, or decoded planes (see _yuv420;
@@ -578,17 +604,8 @@ class Context:
         import torch
         self._enter()
         mode = WARP_MODES[mode] if isinstance(mode, str) else int(mode)
-        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
-        if planes:
-            d, n, sw, sh = self._yuv420(frames, size, self.device)
-            cn = 3
-        else:
-            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
-            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
-            n = frames.shape[0]
-        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
-                or mats.numel() != 9 * n:
-            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
         lead = 0 if mode == WARP_MOSAIC else 1
         op, dw, dh, ors, ofs = self._image_rows(out, cn, lead, "out")
         if lead and out.shape[0] != n:
@@ -599,10 +616,7 @@ class Context:
             if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
                 raise ValueError("background must be [dh,dw(,3)] with out's row stride")
         tail = (mats.data_ptr(), int(bool(inverse_map)), mode, bp, op, dw, dh, ors, ofs if lead else 0, int(origin[0]), int(origin[1]))
-        if planes:
-            self._check(self.lib.evh_warp_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
-        else:
-            self._check(self.lib.evh_warp_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+        self._check(self._form("evh_warp_fixed_plane", planes)(self.h, *head, *tail))
 
     def trail_fixed_plane(self, frames, mats, canvas, origin, out=None, rects=None, inverse_map=False, size=None):
         """The trail of the stabilised view (evh_trail_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h): per
@@ -614,18 +628,10 @@ class Context:
         (x0, y0, x1, y1) in canvas pixels, or None.  origin=(ox, oy) as for warp_fixed_plane.  Does not synchronise."""
         import torch
         self._enter()
-        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
-        if planes:
-            d, n, sw, sh = self._yuv420(frames, size, self.device)
-        else:
-            fp, sw, sh, frs, ffs = self._image_rows(frames, 3, 1, "frames")
-            n = frames.shape[0]
-        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
-                or mats.numel() != 9 * n:
-            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
-        if rects is not None and (rects.dtype != torch.int32 or not rects.is_cuda or rects.device.index != self.device or
-                                  not rects.is_contiguous() or rects.numel() != 4 * n):
-            raise ValueError("rects must be a contiguous CUDA int32 tensor of n*4 elements")
+        planes, head, n, sw, sh, _ = self._frame_source(frames, size, bgr_only=True)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        if rects is not None:
+            self._dev_tensor(rects, torch.int32, 4 * n, "rects must be a contiguous CUDA int32 tensor of n*4 elements")
         cp, dw, dh, crs, _ = self._image_rows(canvas, 3, 0, "canvas")
         op, ors, ofs = None, 0, 0
         if out is not None:
@@ -633,10 +639,7 @@ class Context:
             if (out.shape[0], ow, oh) != (n, dw, dh):
                 raise ValueError("out must be [n,dh,dw,3] for a canvas [dh,dw,3]")
         tail = (mats.data_ptr(), int(bool(inverse_map)), _ptr(rects), cp, crs, op, ors, ofs, dw, dh, int(origin[0]), int(origin[1]))
-        if planes:
-            self._check(self.lib.evh_trail_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
-        else:
-            self._check(self.lib.evh_trail_fixed_plane(self.h, fp, n, sw, sh, frs, ffs, *tail))
+        self._check(self._form("evh_trail_fixed_plane", planes)(self.h, *head, *tail))
 
     def plate_fixed_plane(self, frames, mats, plate, origin, background=None, count=None, masks=None, threshold=16, min_cover=1,
                           inverse_map=False, size=None):
@@ -649,17 +652,8 @@ class Context:
         None; rows (and masks) may be strided.  Does not synchronise."""
         import torch
         self._enter()
-        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
-        if planes:
-            d, n, sw, sh = self._yuv420(frames, size, self.device)
-            cn = 3
-        else:
-            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
-            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
-            n = frames.shape[0]
-        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
-                or mats.numel() != 9 * n:
-            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
         pp, dw, dh, prs, _ = self._image_rows(plate, cn, 0, "plate")
         bp = None
         if background is not None:
@@ -678,10 +672,7 @@ class Context:
                 raise ValueError("masks must be [n,dh,dw] for a plate [dh,dw(,3)]")
         tail = (mats.data_ptr(), int(bool(inverse_map)), int(min_cover), bp, pp, prs, cp, crs, mp, int(threshold), mrs, mfs, dw, dh,
                 int(origin[0]), int(origin[1]))
-        if planes:
-            self._check(self.lib.evh_plate_fixed_plane_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
-        else:
-            self._check(self.lib.evh_plate_fixed_plane(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+        self._check(self._form("evh_plate_fixed_plane", planes)(self.h, *head, *tail))
 
     def rows_moving_filter(self, frames, mats, plate, count, origin, rows, counts, status1, out_rows, out_counts, moving=None,
                            flags=None, *, threshold=16, min_cover=1, radius=1, min_hits=1, row_scale=(1.0, 1.0), frame_step=1,
@@ -697,17 +688,8 @@ class Context:
         them.  Does not synchronise."""
         import torch
         self._enter()
-        planes = isinstance(frames, (tuple, list)) or frames.dim() == 2
-        if planes:
-            d, n, sw, sh = self._yuv420(frames, size, self.device)
-            cn = 3
-        else:
-            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
-            fp, sw, sh, frs, ffs = self._image_rows(frames, cn, 1, "frames")
-            n = frames.shape[0]
-        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
-                or mats.numel() != 9 * n:
-            raise ValueError("mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
         pp, dw, dh, prs, _ = self._image_rows(plate, cn, 0, "plate")
         cp, cw, ch, crs, _ = self._image_rows(count, 1, 0, "count")
         if (cw, ch) != (dw, dh):
@@ -721,18 +703,14 @@ class Context:
                                    (flags, torch.uint8, npairs * cap, "flags")):
             if t is None and what in ("moving", "flags"):
                 continue
-            if t.dtype != dt or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.numel() != numel:
-                raise ValueError("%s must be a contiguous CUDA %s tensor of %d elements" % (what, dt, numel))
+            self._dev_tensor(t, dt, numel, "%s must be a contiguous CUDA %s tensor of %d elements", what, dt, numel)
         if npairs == 0:                      # empty tensors have no address to hand over
             return
         tail = (mats.data_ptr(), pp, prs, cp, crs, dw, dh, int(origin[0]), int(origin[1]), int(min_cover), int(threshold),
                 int(radius), int(min_hits), float(row_scale[0]), float(row_scale[1]), rows.data_ptr(), cap, counts.data_ptr(),
                 status1.data_ptr(), npairs, int(frame_step), int(min_keep), out_rows.data_ptr(), out_counts.data_ptr(),
                 _ptr(moving), _ptr(flags))
-        if planes:
-            self._check(self.lib.evh_rows_moving_filter_yuv420(self.h, C.byref(d), n, sw, sh, *tail))
-        else:
-            self._check(self.lib.evh_rows_moving_filter(self.h, fp, n, sw, sh, cn, frs, ffs, *tail))
+        self._check(self._form("evh_rows_moving_filter", planes)(self.h, *head, *tail))
 
     def heatmap_render(self, Hsup, out, lut, frames=None, heatmap_constant=1000.0, alpha=0.8, saturate=False):
         """The heat-map pictures of n superposed matrices (evh_heatmap_render, the arithmetic is stated in include/evhip.h).
@@ -743,12 +721,8 @@ class Context:
         self._enter()
         op, w, h, ors, ofs = self._image_rows(out, 3, 1, "out")
         n = out.shape[0]
-        if Hsup.dtype != torch.float64 or not Hsup.is_cuda or Hsup.device.index != self.device or not Hsup.is_contiguous() \
-                or Hsup.numel() != 9 * n:
-            raise ValueError("Hsup must be a contiguous CUDA float64 tensor of n*9 elements")
-        if lut.dtype != torch.uint8 or not lut.is_cuda or lut.device.index != self.device or not lut.is_contiguous() \
-                or tuple(lut.shape) != (256, 3):
-            raise ValueError("lut must be a contiguous CUDA uint8 tensor [256,3]")
+        self._dev_tensor(Hsup, torch.float64, 9 * n, "Hsup must be a contiguous CUDA float64 tensor of n*9 elements")
+        self._dev_tensor(lut, torch.uint8, (256, 3), "lut must be a contiguous CUDA uint8 tensor [256,3]")
         fp, frs, ffs = None, 0, 0
         if frames is not None:
             fp, fw, fh, frs, ffs = self._image_rows(frames, 3, 1, "frames")
@@ -828,23 +802,14 @@ class Context:
         frame_step = int(frame_step)
         if frame_step not in (1, 2):
             raise ValueError("frame_step must be 1 or 2")
-        if planes:
-            d, n, w, h = self._yuv420(frames, size, self.device)
-        else:
-            cn = 1 if frames.dim() == 3 else int(frames.shape[-1])
-            fp, w, h, frs, ffs = self._image_rows(frames, cn, 1, "frames")
-            n = frames.shape[0]
-        if mats.dtype != torch.float64 or not mats.is_cuda or mats.device.index != self.device or not mats.is_contiguous() \
-                or mats.numel() % 9:
-            raise ValueError("mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        planes, head, n, w, h, _ = self._frame_source(frames, size, planes=planes)
         npairs = mats.numel() // 9
+        self._dev_tensor(mats, torch.float64, 9 * npairs, "mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
         if npairs and n < (npairs - 1) * frame_step + 2:
             raise ValueError("frames holds fewer frames than the pairs take")
         if stats is None:
             stats = torch.empty((npairs, RES_NSTATS), dtype=torch.int64, device="cuda:%d" % self.device)
-        if stats.dtype != torch.int64 or not stats.is_cuda or stats.device.index != self.device or not stats.is_contiguous() \
-                or tuple(stats.shape) != (npairs, RES_NSTATS):
-            raise ValueError("stats must be a contiguous CUDA int64 tensor [npairs,%d]" % RES_NSTATS)
+        self._dev_tensor(stats, torch.int64, (npairs, RES_NSTATS), "stats must be a contiguous CUDA int64 tensor [npairs,%d]", RES_NSTATS)
         op, ors, ofs = None, 0, 0
         if out is not None:
             op, ow, oh, ors, ofs = self._image_rows(out, 1, 1, "out")
@@ -853,10 +818,8 @@ class Context:
         if npairs == 0:                      # empty tensors have no address to hand over
             return stats
         tail = (mats.data_ptr(), int(threshold), stats.data_ptr(), op, kind, ors, ofs)
-        if planes:
-            self._check(self.lib.evh_pair_residual_yuv420(self.h, C.byref(d), npairs, frame_step, w, h, *tail))
-        else:
-            self._check(self.lib.evh_pair_residual(self.h, fp, npairs, frame_step, w, h, cn, frs, ffs, *tail))
+        # the head with (npairs, frame_step) in the place of the frame count
+        self._check(self._form("evh_pair_residual", planes)(self.h, head[0], npairs, frame_step, w, h, *head[4:], *tail))
         return stats
 
     def pair_residual(self, frames, mats, stats=None, out=None, threshold=16, kind="abs", frame_step=1):

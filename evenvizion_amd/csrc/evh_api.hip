@@ -877,409 +877,6 @@ int evh_yuv420_to_bgr(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int
   return evh_launch_yuv420_to_bgr(c, *src, nframes, w, h, d_bgr, row_stride, frame_stride);
 }
 
-// ---- stabilised output: frames warped into the fixed plane (stabilization.py:129-172, 220-249) -------------------------------
-// the argument checks of both forms; every refusal comes before the launch
-static int warp_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
-                            int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh, int64_t out_stride,
-                            int64_t out_img_stride, int ox, int oy) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = std::string(who) + ": ";
-  const int cn = F.channels;
-  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
-  if (!d_M || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
-  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
-  if (mode != EVH_WARP_EACH && mode != EVH_WARP_HISTORY && mode != EVH_WARP_MOSAIC) return evh_fail(c, EVH_ERR_INVALID, W + "unknown mode");
-  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
-  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
-  if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
-  const bool many = mode != EVH_WARP_MOSAIC && nframes > 1;       // the canvases of out[0 .. nframes)
-  const int64_t canvas = (int64_t)(dh - 1) * out_stride + (int64_t)dw * cn;
-  if (out_stride < (int64_t)dw * cn || (many && out_img_stride < canvas))
-    return evh_fail(c, EVH_ERR_INVALID, W + "output stride smaller than a row / canvas");
-  if (!F.planes && (F.row_stride < (int64_t)sw * cn || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + (int64_t)sw * cn)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
-  if (d_bg && !(mode == EVH_WARP_MOSAIC && d_bg == d_out)) {      // only a mosaic may be carried in place
-    const int64_t out_bytes = canvas + (many ? (nframes - 1) * out_img_stride : 0);
-    if (d_bg < d_out + out_bytes && d_out < d_bg + canvas) return evh_fail(c, EVH_ERR_INVALID, W + "d_background overlaps d_out");
-  }
-  if (nframes == 0) return EVH_SUCCESS;
-  if (F.yuv)
-    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
-  return evh_launch_warp_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, mode, d_bg, d_out, dw, dh, out_stride,
-                                     out_img_stride, ox, oy);
-}
-
-int evh_warp_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
-                         int64_t frame_stride, const double* d_M, int inverse_map, int mode, const uint8_t* d_background,
-                         uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy) {
-  return warp_fixed_plane(c, "evh_warp_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
-                          d_M, inverse_map, mode, d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
-}
-
-int evh_warp_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
-                                int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
-                                int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy) {
-  return warp_fixed_plane(c, "evh_warp_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, mode,
-                          d_background, d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy);
-}
-
-// ---- the trail: the fixed plane with earlier frames dimmed and the frame outlined (stabilization.py:21-97, 129-172) ----------
-// the argument checks of both forms; every refusal comes before the launch
-static int trail_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
-                             int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride, uint8_t* d_out,
-                             int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = std::string(who) + ": ";
-  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
-  if (!d_M || !d_canvas) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
-  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
-  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
-  if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
-  const int64_t row = (int64_t)dw * 3, srow = (int64_t)sw * 3;
-  const int64_t canvas = (dh - 1) * canvas_stride + row, picture = (dh - 1) * out_stride + row;
-  if (canvas_stride < row || (d_out && (out_stride < row || (nframes > 1 && out_img_stride < picture))))
-    return evh_fail(c, EVH_ERR_INVALID, W + "canvas or output stride smaller than a row / picture");
-  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
-  if (nframes == 0) return EVH_SUCCESS;
-  if (F.yuv)
-    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
-  // the byte ranges the launch reads and writes: canvas and pictures apart from each other and from the frames
-  struct Span { const uint8_t* p; int64_t n; };
-  const auto meet = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
-  const Span cv{d_canvas, canvas}, pic{d_out, d_out ? picture + (nframes - 1) * out_img_stride : 0};
-  Span srcs[3]; int nsrc = 1;
-  if (F.yuv) {
-    const evh_yuv420& s = *F.yuv;
-    const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
-    const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
-    const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
-    srcs[0] = {s.d_y, yb}; srcs[1] = {s.d_cb, cb}; srcs[2] = {s.d_cr, cb}; nsrc = 3;
-  } else {
-    srcs[0] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride};
-  }
-  if (d_out && meet(pic, cv)) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps d_canvas");
-  for (int i = 0; i < nsrc; i++) {
-    if (d_out && meet(pic, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps the frames");
-    if (meet(cv, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_canvas overlaps the frames");
-  }
-  return evh_launch_trail_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, d_rect, d_canvas, canvas_stride, d_out, out_stride,
-                                      out_img_stride, dw, dh, ox, oy);
-}
-
-int evh_trail_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int64_t row_stride,
-                          int64_t frame_stride, const double* d_M, int inverse_map, const int32_t* d_rect, uint8_t* d_canvas,
-                          int64_t canvas_row_stride, uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride, int dw,
-                          int dh, int ox, int oy) {
-  return trail_fixed_plane(c, "evh_trail_fixed_plane", packed_frames(d_frames, 3, row_stride, frame_stride), nframes, sw, sh, d_M,
-                           inverse_map, d_rect, d_canvas, canvas_row_stride, d_out, out_row_stride, out_frame_stride, dw, dh, ox, oy);
-}
-
-int evh_trail_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
-                                 int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_row_stride,
-                                 uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride, int dw, int dh, int ox, int oy) {
-  return trail_fixed_plane(c, "evh_trail_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, d_rect,
-                           d_canvas, canvas_row_stride, d_out, out_row_stride, out_frame_stride, dw, dh, ox, oy);
-}
-
-// ---- the background plate: the temporal median of the frames on the fixed plane, and what moves against it -------------------
-// the argument checks of both forms; every refusal comes before the launch
-static int plate_fixed_plane(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
-                             int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
-                             uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
-                             int64_t mask_img_stride, int dw, int dh, int ox, int oy) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = std::string(who) + ": ";
-  const int cn = F.channels;
-  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
-  if (!d_M || !d_plate) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
-  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
-  if (min_cover < 1 || min_cover > 255) return evh_fail(c, EVH_ERR_INVALID, W + "min_cover must lie in 1..255");
-  if (d_mask && (threshold < 0 || threshold > 255)) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
-  if (nframes > EVH_PLATE_MAX_FRAMES) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most EVH_PLATE_MAX_FRAMES = 255 frames per call");
-  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
-  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
-  const int64_t row = (int64_t)dw * cn, srow = (int64_t)sw * cn;
-  const int64_t canvas = (dh - 1) * plate_stride + row, gray = (dh - 1) * count_stride + dw, picture = (dh - 1) * mask_stride + dw;
-  if (plate_stride < row) return evh_fail(c, EVH_ERR_INVALID, W + "plate stride smaller than a row");
-  if (d_count && count_stride < dw) return evh_fail(c, EVH_ERR_INVALID, W + "count stride smaller than a row");
-  if (d_mask && (mask_stride < dw || (nframes > 1 && mask_img_stride < picture)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "mask stride smaller than a row / picture");
-  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
-  if (F.yuv && nframes > 0)
-    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
-  // the byte ranges the launch reads and writes: the outputs apart from each other, from the frames and from the background
-  struct Span { const uint8_t* p; int64_t n; const char* name; };
-  const auto meet = [](const Span& a, const Span& b) { return a.p && b.p && a.n > 0 && b.n > 0 && a.p < b.p + b.n && b.p < a.p + a.n; };
-  const Span outs[3] = {{d_plate, canvas, "d_plate"}, {d_count, gray, "d_count"},
-                        {d_mask, nframes > 0 ? picture + (nframes - 1) * mask_img_stride : 0, "d_mask"}};
-  Span ins[4] = {{d_bg, canvas, "d_background"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}};
-  if (nframes > 0) {
-    if (F.yuv) {
-      const evh_yuv420& s = *F.yuv;
-      const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
-      const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
-      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
-      ins[1] = {s.d_y, yb, "the frames"}; ins[2] = {s.d_cb, cb, "the frames"}; ins[3] = {s.d_cr, cb, "the frames"};
-    } else {
-      ins[1] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride, "the frames"};
-    }
-  }
-  for (int i = 0; i < 3; i++) {
-    for (int j = i + 1; j < 3; j++)
-      if (meet(outs[i], outs[j])) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + outs[j].name);
-    for (const Span& in : ins)
-      if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + in.name);
-  }
-  return evh_launch_plate_fixed_plane(c, F, nframes, sw, sh, d_M, inverse_map, min_cover, d_bg, d_plate, plate_stride, d_count,
-                                      count_stride, d_mask, threshold, mask_stride, mask_img_stride, dw, dh, ox, oy);
-}
-
-int evh_plate_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
-                          int64_t frame_stride, const double* d_M, int inverse_map, int min_cover, const uint8_t* d_background,
-                          uint8_t* d_plate, int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask,
-                          int threshold, int64_t mask_row_stride, int64_t mask_frame_stride, int dw, int dh, int ox, int oy) {
-  return plate_fixed_plane(c, "evh_plate_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
-                           d_M, inverse_map, min_cover, d_background, d_plate, plate_row_stride, d_count, count_row_stride, d_mask,
-                           threshold, mask_row_stride, mask_frame_stride, dw, dh, ox, oy);
-}
-
-int evh_plate_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
-                                 int inverse_map, int min_cover, const uint8_t* d_background, uint8_t* d_plate,
-                                 int64_t plate_row_stride, uint8_t* d_count, int64_t count_row_stride, uint8_t* d_mask, int threshold,
-                                 int64_t mask_row_stride, int64_t mask_frame_stride, int dw, int dh, int ox, int oy) {
-  return plate_fixed_plane(c, "evh_plate_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, min_cover,
-                           d_background, d_plate, plate_row_stride, d_count, count_row_stride, d_mask, threshold, mask_row_stride,
-                           mask_frame_stride, dw, dh, ox, oy);
-}
-
-// ---- match rows against the plate: rows whose points sit on what moves are dropped ------------------------------------------------
-// the argument checks of both forms; every refusal comes before the launch
-static int rows_moving_filter(evh_ctx* c, const char* who, const EvhFrames& F, int nframes, int sw, int sh, const double* d_M,
-                              const uint8_t* d_plate, int64_t plate_stride, const uint8_t* d_count, int64_t count_stride, int dw,
-                              int dh, int ox, int oy, int min_cover, int threshold, int radius, int min_hits, double row_sx,
-                              double row_sy, const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1,
-                              int npairs, int frame_step, int min_keep, float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving,
-                              uint8_t* d_flags) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = std::string(who) + ": ";
-  const int cn = F.channels;
-  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
-  if (!d_M || !d_plate || !d_count || !d_rows || !d_counts || !d_status1 || !d_out_rows || !d_out_counts)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
-  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || row_cap < 1 || npairs < 0)
-    return evh_fail(c, EVH_ERR_INVALID, W + "empty frame, canvas or row block");
-  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
-  if (min_cover < 1 || min_cover > 255) return evh_fail(c, EVH_ERR_INVALID, W + "min_cover must lie in 1..255");
-  if (threshold < 0 || threshold > 255) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
-  if (radius < 0 || radius > 7) return evh_fail(c, EVH_ERR_INVALID, W + "radius must lie in 0..7");
-  if (min_hits < 1 || min_hits > (2 * radius + 1) * (2 * radius + 1))
-    return evh_fail(c, EVH_ERR_INVALID, W + "min_hits must lie in 1..(2*radius+1)^2");
-  if (min_keep < 0) return evh_fail(c, EVH_ERR_INVALID, W + "min_keep must not be negative");
-  if (!(std::isfinite(row_sx) && std::isfinite(row_sy) && row_sx > 0.0 && row_sy > 0.0))
-    return evh_fail(c, EVH_ERR_INVALID, W + "row_sx and row_sy must be finite and positive");
-  if (npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
-  if (sw >= (1 << 26) || sh >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "source sizes stay below 2^26 (positions are held in 1/32 pixels)");
-  if ((int64_t)dw * dh > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "dw * dh above INT_MAX");
-  if (npairs > 0 && (int64_t)(npairs - 1) * frame_step + 2 > nframes)
-    return evh_fail(c, EVH_ERR_INVALID, W + "nframes does not reach the last pair's frames");
-  const int64_t row = (int64_t)dw * cn, srow = (int64_t)sw * cn;
-  if (plate_stride < row) return evh_fail(c, EVH_ERR_INVALID, W + "plate stride smaller than a row");
-  if (count_stride < dw) return evh_fail(c, EVH_ERR_INVALID, W + "count stride smaller than a row");
-  if (!F.planes && (F.row_stride < srow || (nframes > 1 && F.frame_stride < (sh - 1) * F.row_stride + srow)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
-  if (F.yuv && nframes > 0)
-    if (int rc = evh_check_yuv420(c, who, F.yuv, nframes, sw, sh)) return rc;
-  if (((uintptr_t)d_rows | (uintptr_t)d_out_rows) & 15) return evh_fail(c, EVH_ERR_INVALID, W + "d_rows and d_out_rows must be 16-byte aligned");
-  // the byte ranges the launch reads and writes: every output apart from every input and from the other outputs
-  struct Span { const void* p; int64_t n; const char* name; };
-  const auto meet = [](const Span& a, const Span& b) {
-    const uint8_t* x = (const uint8_t*)a.p; const uint8_t* y = (const uint8_t*)b.p;
-    return x && y && a.n > 0 && b.n > 0 && x < y + b.n && y < x + a.n;
-  };
-  const int64_t block = (int64_t)npairs * row_cap;
-  const Span outs[4] = {{d_out_rows, block * 16, "d_out_rows"}, {d_out_counts, (int64_t)npairs * 4, "d_out_counts"},
-                        {d_moving, (int64_t)npairs * 4, "d_moving"}, {d_flags, block, "d_flags"}};
-  Span ins[9] = {{d_M, (int64_t)nframes * 72, "d_M"}, {d_plate, (dh - 1) * plate_stride + row, "d_plate"},
-                 {d_count, (dh - 1) * count_stride + dw, "d_count"}, {d_rows, block * 16, "d_rows"},
-                 {d_counts, (int64_t)npairs * 4, "d_counts"}, {d_status1, (int64_t)npairs * 4, "d_status1"},
-                 {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}, {nullptr, 0, "the frames"}};
-  if (nframes > 0) {
-    if (F.yuv) {
-      const evh_yuv420& s = *F.yuv;
-      const int64_t cw = (sw + 1) / 2, ch = (sh + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
-      const int64_t yb = (sh - 1) * s.y_stride + sw + (nframes - 1) * s.y_frame_stride;
-      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
-      ins[6] = {s.d_y, yb, "the frames"}; ins[7] = {s.d_cb, cb, "the frames"}; ins[8] = {s.d_cr, cb, "the frames"};
-    } else {
-      ins[6] = {F.packed, (sh - 1) * F.row_stride + srow + (nframes - 1) * F.frame_stride, "the frames"};
-    }
-  }
-  for (int i = 0; i < 4; i++) {
-    for (int j = i + 1; j < 4; j++)
-      if (meet(outs[i], outs[j])) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + outs[j].name);
-    for (const Span& in : ins)
-      if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps " + in.name);
-  }
-  if (npairs == 0) return EVH_SUCCESS;
-  return evh_launch_rows_moving_filter(c, F, sw, sh, d_M, d_plate, plate_stride, d_count, count_stride, dw, dh, ox, oy, min_cover,
-                                       threshold, radius, min_hits, row_sx, row_sy, d_rows, row_cap, d_counts, d_status1, npairs,
-                                       frame_step, min_keep, d_out_rows, d_out_counts, d_moving, d_flags);
-}
-
-int evh_rows_moving_filter(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
-                           int64_t frame_stride, const double* d_M, const uint8_t* d_plate, int64_t plate_row_stride,
-                           const uint8_t* d_count, int64_t count_row_stride, int dw, int dh, int ox, int oy, int min_cover,
-                           int threshold, int radius, int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
-                           const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
-                           float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags) {
-  return rows_moving_filter(c, "evh_rows_moving_filter", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw,
-                            sh, d_M, d_plate, plate_row_stride, d_count, count_row_stride, dw, dh, ox, oy, min_cover, threshold,
-                            radius, min_hits, row_sx, row_sy, d_rows, row_cap, d_counts, d_status1, npairs, frame_step, min_keep,
-                            d_out_rows, d_out_counts, d_moving, d_flags);
-}
-
-int evh_rows_moving_filter_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
-                                  const uint8_t* d_plate, int64_t plate_row_stride, const uint8_t* d_count,
-                                  int64_t count_row_stride, int dw, int dh, int ox, int oy, int min_cover, int threshold, int radius,
-                                  int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
-                                  const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
-                                  float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags) {
-  return rows_moving_filter(c, "evh_rows_moving_filter_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, d_plate, plate_row_stride,
-                            d_count, count_row_stride, dw, dh, ox, oy, min_cover, threshold, radius, min_hits, row_sx, row_sy,
-                            d_rows, row_cap, d_counts, d_status1, npairs, frame_step, min_keep, d_out_rows, d_out_counts, d_moving,
-                            d_flags);
-}
-
-// ---- heat-map pictures (processing_visualization.py:336-344) -----------------------------------------------------------------------
-int evh_heatmap_render(evh_ctx* c, const double* d_Hsup, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
-                       int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
-                       uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = "evh_heatmap_render: ";
-  if (!d_Hsup || !d_lut || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (n < 0 || w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty grid or negative n");
-  if (!std::isfinite(heatmap_constant) || heatmap_constant <= 0) return evh_fail(c, EVH_ERR_INVALID, W + "heatmap_constant must be finite and positive");
-  if (!std::isfinite(alpha) || alpha < 0) return evh_fail(c, EVH_ERR_INVALID, W + "alpha must be finite and not negative");
-  if (n > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 matrices per call");
-  if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "w * h above INT_MAX");
-  const int64_t row = (int64_t)w * 3;
-  if (out_row_stride < row || (d_frames && row_stride < row)) return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a row");
-  const int64_t picture = (h - 1) * out_row_stride + row, frame = d_frames ? (h - 1) * row_stride + row : 0;
-  if (n > 1 && (out_frame_stride < picture || (d_frames && frame_stride < frame)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a frame");
-  if (d_frames && n > 0) {
-    const int64_t out_bytes = picture + (n - 1) * out_frame_stride, frames_bytes = frame + (n - 1) * frame_stride;
-    if (d_frames < d_out + out_bytes && d_out < d_frames + frames_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_frames overlaps d_out");
-  }
-  if (n == 0) return EVH_SUCCESS;
-  return evh_launch_heatmap_render(c, d_Hsup, n, w, h, d_frames, row_stride, frame_stride, d_lut, heatmap_constant, alpha, saturate,
-                                   d_out, out_row_stride, out_frame_stride);
-}
-
-// ---- matching pictures (processing_visualization.py:22-57) -------------------------------------------------------------------------
-int evh_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
-                     int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status,
-                     int points, uint32_t color_bgr, uint8_t* d_out, int64_t out_row_stride, int64_t out_frame_stride) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = "evh_draw_matches: ";
-  if (!d_frames || !d_rows || !d_counts || !d_out) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (npairs < 0 || w < 1 || h < 1 || row_cap < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame, no row capacity or negative npairs");
-  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
-  if (points != EVH_DRAW_REFERENCE && points != EVH_DRAW_OWN_FRAME) return evh_fail(c, EVH_ERR_INVALID, W + "unknown points value");
-  if (color_bgr >> 24) return evh_fail(c, EVH_ERR_INVALID, W + "color_bgr has bits above 24 set");
-  if (w > 16383) return evh_fail(c, EVH_ERR_CAPACITY, W + "w above 16383 (a picture's columns are held in 16 bits)");
-  const int64_t row = (int64_t)w * 3;
-  if (row_stride < row || out_row_stride < 2 * row) return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a row");
-  const int64_t frame = (h - 1) * row_stride + row, picture = (h - 1) * out_row_stride + 2 * row;
-  if ((npairs >= 1 && frame_stride < frame) || (npairs > 1 && out_frame_stride < picture))
-    return evh_fail(c, EVH_ERR_INVALID, W + "stride smaller than a frame");
-  if (npairs == 0) return EVH_SUCCESS;
-  const int64_t out_bytes = picture + (npairs - 1) * out_frame_stride;
-  const int64_t frames_bytes = frame + ((int64_t)(npairs - 1) * frame_step + 1) * frame_stride;
-  const int64_t rows_bytes = (int64_t)npairs * row_cap * 4 * (int64_t)sizeof(float);
-  const uint8_t* rows8 = reinterpret_cast<const uint8_t*>(d_rows);
-  if (d_frames < d_out + out_bytes && d_out < d_frames + frames_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_frames overlaps d_out");
-  if (rows8 < d_out + out_bytes && d_out < rows8 + rows_bytes) return evh_fail(c, EVH_ERR_INVALID, W + "d_rows overlaps d_out");
-  return evh_launch_draw_matches(c, d_frames, npairs, frame_step, w, h, row_stride, frame_stride, d_rows, row_cap, d_counts, d_status,
-                                 points, color_bgr, d_out, out_row_stride, out_frame_stride);
-}
-
-// ---- the score of a homography: the motion-compensated residual of a pair -----------------------------------------------------------
-// the argument checks of both forms; every refusal comes before the memset and the launch
-static int pair_residual(evh_ctx* c, const char* who, const EvhFrames& F, int npairs, int frame_step, int w, int h, const double* d_M,
-                         int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_stride, int64_t out_img_stride) {
-  if (!c) return EVH_ERR_INVALID;
-  const std::string W = std::string(who) + ": ";
-  const int cn = F.channels;
-  if (F.planes ? (!F.yuv || !F.yuv->d_y || !F.yuv->d_cb || !F.yuv->d_cr) : !F.packed)
-    return evh_fail(c, EVH_ERR_INVALID, W + "NULL source");
-  if (!d_M || !d_stats) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (cn != 1 && cn != 3) return evh_fail(c, EVH_ERR_INVALID, W + "channels must be 1 or 3");
-  if (frame_step != 1 && frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
-  if (npairs < 0 || w < 1 || h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or negative npairs");
-  if (threshold < 0 || threshold > 255) return evh_fail(c, EVH_ERR_INVALID, W + "threshold must lie in 0..255");
-  if (kind != EVH_RESIDUAL_ABS && kind != EVH_RESIDUAL_MASK) return evh_fail(c, EVH_ERR_INVALID, W + "unknown kind");
-  if (w >= (1 << 26) || h >= (1 << 26)) return evh_fail(c, EVH_ERR_CAPACITY, W + "frame sizes stay below 2^26 (positions are held in 1/32 pixels)");
-  if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + "w * h above INT_MAX");
-  if (npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
-  const int64_t row = (int64_t)w * cn, frame = F.planes ? 0 : (h - 1) * F.row_stride + row;
-  if (!F.planes && (F.row_stride < row || F.frame_stride < frame))
-    return evh_fail(c, EVH_ERR_INVALID, W + "source stride smaller than a row / frame");
-  const int64_t picture = (h - 1) * out_stride + w;
-  if (d_out && (out_stride < w || (npairs > 1 && out_img_stride < picture)))
-    return evh_fail(c, EVH_ERR_INVALID, W + "output stride smaller than a row / picture");
-  if (npairs == 0) return EVH_SUCCESS;
-  const int64_t nframes = (int64_t)(npairs - 1) * frame_step + 2;
-  if (F.yuv) {
-    if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
-    if (int rc = evh_check_yuv420(c, who, F.yuv, (int)nframes, w, h)) return rc;
-  }
-  if (d_out) {      // the byte ranges the launch reads and writes: the pictures apart from the frames and from the statistics
-    struct Span { const uint8_t* p; int64_t n; };
-    const auto meet = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
-    const Span pic{d_out, picture + (npairs - 1) * out_img_stride};
-    const Span st{reinterpret_cast<const uint8_t*>(d_stats), (int64_t)npairs * EVH_RES_NSTATS * (int64_t)sizeof(uint64_t)};
-    Span srcs[3]; int nsrc = 1;
-    if (F.yuv) {
-      const evh_yuv420& s = *F.yuv;
-      const int64_t cw = (w + 1) / 2, ch = (h + 1) / 2, crow = (cw - 1) * s.c_pixel_stride + 1;
-      const int64_t yb = (h - 1) * s.y_stride + w + (nframes - 1) * s.y_frame_stride;
-      const int64_t cb = (ch - 1) * s.c_stride + crow + (nframes - 1) * s.c_frame_stride;
-      srcs[0] = {s.d_y, yb}; srcs[1] = {s.d_cb, cb}; srcs[2] = {s.d_cr, cb}; nsrc = 3;
-    } else {
-      srcs[0] = {F.packed, frame + (nframes - 1) * F.frame_stride};
-    }
-    if (meet(pic, st)) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps d_stats");
-    for (int i = 0; i < nsrc; i++)
-      if (meet(pic, srcs[i])) return evh_fail(c, EVH_ERR_INVALID, W + "d_out overlaps the frames");
-  }
-  return evh_launch_pair_residual(c, F, npairs, frame_step, w, h, d_M, threshold, d_stats, d_out, kind, out_stride, out_img_stride);
-}
-
-int evh_pair_residual(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int channels,
-                      int64_t row_stride, int64_t frame_stride, const double* d_M, int threshold, uint64_t* d_stats, uint8_t* d_out,
-                      int kind, int64_t out_row_stride, int64_t out_frame_stride) {
-  return pair_residual(c, "evh_pair_residual", packed_frames(d_frames, channels, row_stride, frame_stride), npairs, frame_step, w, h,
-                       d_M, threshold, d_stats, d_out, kind, out_row_stride, out_frame_stride);
-}
-
-int evh_pair_residual_yuv420(evh_ctx* c, const evh_yuv420* src, int npairs, int frame_step, int w, int h, const double* d_M,
-                             int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_row_stride,
-                             int64_t out_frame_stride) {
-  return pair_residual(c, "evh_pair_residual_yuv420", yuv420_frames(src), npairs, frame_step, w, h, d_M, threshold, d_stats, d_out,
-                       kind, out_row_stride, out_frame_stride);
-}
-
 int evh_orb_detect_batch_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int src_w, int src_h, int w, int h,
                                 int nfeatures) {
   return detect_batch(c, yuv420_frames(src), nframes, src_w, src_h, w, h, nfeatures);

@@ -313,25 +313,6 @@ int evh_launch_gray_level0(evh_ctx* c, const uint8_t* d_frames, int nframes, int
 int evh_launch_ingest_level0(evh_ctx* c, const EvhFrames& src, int nimg, int sw, int sh, int dw, int dh);
 int evh_launch_yuv420_to_bgr(evh_ctx* c, const evh_yuv420& src, int nimg, int w, int h, uint8_t* d_dst, int64_t dst_stride,
                              int64_t dst_img_stride);
-int evh_launch_warp_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
-                                int inverse_map, int mode, const uint8_t* d_bg, uint8_t* d_out, int dw, int dh,
-                                int64_t out_stride, int64_t out_img_stride, int ox, int oy);
-int evh_launch_pair_residual(evh_ctx* c, const EvhFrames& src, int npairs, int frame_step, int w, int h, const double* d_M,
-                             int threshold, uint64_t* d_stats, uint8_t* d_out, int kind, int64_t out_stride,
-                             int64_t out_img_stride);
-int evh_launch_trail_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
-                                 int inverse_map, const int32_t* d_rect, uint8_t* d_canvas, int64_t canvas_stride,
-                                 uint8_t* d_out, int64_t out_stride, int64_t out_img_stride, int dw, int dh, int ox, int oy);
-int evh_launch_plate_fixed_plane(evh_ctx* c, const EvhFrames& src, int nframes, int sw, int sh, const double* d_M,
-                                 int inverse_map, int min_cover, const uint8_t* d_bg, uint8_t* d_plate, int64_t plate_stride,
-                                 uint8_t* d_count, int64_t count_stride, uint8_t* d_mask, int threshold, int64_t mask_stride,
-                                 int64_t mask_img_stride, int dw, int dh, int ox, int oy);
-int evh_launch_rows_moving_filter(evh_ctx* c, const EvhFrames& src, int sw, int sh, const double* d_M, const uint8_t* d_plate,
-                                  int64_t plate_stride, const uint8_t* d_count, int64_t count_stride, int dw, int dh, int ox, int oy,
-                                  int min_cover, int threshold, int radius, int min_hits, double row_sx, double row_sy,
-                                  const float* d_rows, int row_cap, const int32_t* d_counts, const int32_t* d_status1, int npairs,
-                                  int frame_step, int min_keep, float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving,
-                                  uint8_t* d_flags);
 int evh_launch_pyramid(evh_ctx* c, int nframes);
 int evh_launch_fast(evh_ctx* c, int nframes, int share_group);
 int evh_launch_select(evh_ctx* c, int nframes);
@@ -340,13 +321,6 @@ int evh_launch_superposition_scan(evh_ctx* c, const double* d_H, int n, double* 
 int evh_launch_transform_points(evh_ctx* c, const double* d_M, const int* d_idx, const double* d_pts, int n, double kx,
                                 double ky, int decimals, double* d_out);
 int evh_launch_fixed_plane(evh_ctx* c, const double* d_H, int n, int w, int h, double* d_field, unsigned long long* d_max);
-int evh_launch_heatmap_render(evh_ctx* c, const double* d_H, int n, int w, int h, const uint8_t* d_frames, int64_t row_stride,
-                              int64_t frame_stride, const uint8_t* d_lut, double heatmap_constant, double alpha, int saturate,
-                              uint8_t* d_out, int64_t out_stride, int64_t out_img_stride);
-int evh_launch_draw_matches(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int64_t row_stride,
-                            int64_t frame_stride, const float* d_rows, int row_cap, const int32_t* d_counts,
-                            const int32_t* d_status, int points, uint32_t color_bgr, uint8_t* d_out, int64_t out_stride,
-                            int64_t out_img_stride);
 // N4: SIFT (evh_sift.hip)
 int evh_sift_allocate(evh_ctx* c, int max_sift_features);
 int evh_launch_sift(evh_ctx* c, int nframes, int w, int h);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import draw_checks as DC
+from refusal_arena import Arena
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -193,10 +194,11 @@ def test_results_do_not_depend_on_alignment(ctx, w, h):
 def test_refusals_leave_the_outputs_untouched(ctx):
     w, h, cap, npairs = 8, 4, 6, 2
     rng = np.random.default_rng(3)
-    frames = dev(rng.integers(0, 256, (3, h, w, 3), dtype=np.uint8))
-    rows = dev(random_rows(rng, npairs * cap, w, h).reshape(npairs, cap, 4))
-    counts = dev(np.int32([cap, cap]))
-    out = torch.full((npairs * h * 6 * w + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
+    A = Arena(4)            # every buffer a fixed distance from the others: which ranges meet is the test's to say
+    frames = A.put(rng.integers(0, 256, (3, h, w, 3), dtype=np.uint8))
+    rows = A.put(random_rows(rng, npairs * cap, w, h).reshape(npairs, cap, 4))
+    counts = A.put(np.int32([cap, cap]))
+    out = A.take((npairs * h * 6 * w + 64,), fill=SENTINEL)
     good = dict(frames=frames.data_ptr(), npairs=npairs, step=1, w=w, h=h, rs=3 * w, fs=3 * w * h, rows=rows.data_ptr(), cap=cap,
                 counts=counts.data_ptr(), status=None, points=0, color=0x00FF00, out=out.data_ptr(), ors=6 * w, ofs=6 * w * h)
 
@@ -207,18 +209,27 @@ def test_refusals_leave_the_outputs_untouched(ctx):
         ctx.synchronize()
         return rc
 
-    bad = [(dict(frames=None), INVALID), (dict(rows=None), INVALID), (dict(counts=None), INVALID), (dict(out=None), INVALID),
-           (dict(w=0), INVALID), (dict(h=0), INVALID), (dict(cap=0), INVALID), (dict(npairs=-1), INVALID),
-           (dict(step=0), INVALID), (dict(step=3), INVALID), (dict(points=2), INVALID), (dict(points=-1), INVALID),
-           (dict(color=0x01000000), INVALID), (dict(rs=3 * w - 1), INVALID), (dict(ors=6 * w - 1), INVALID),
-           (dict(fs=3 * w * h - 1), INVALID), (dict(ofs=6 * w * h - 1), INVALID),
-           (dict(out=frames.data_ptr()), INVALID), (dict(out=frames.data_ptr() + 3 * w * h * 3 - 1), INVALID),
-           (dict(out=rows.data_ptr()), INVALID), (dict(out=rows.data_ptr() + npairs * cap * 16 - 1), INVALID),
-           (dict(w=16384, rs=3 * 16384, ors=6 * 16384, fs=3 * 16384 * h, ofs=6 * 16384 * h), CAPACITY)]
+    NA, EM, STEP = "NULL argument", "empty frame, no row capacity or negative npairs", "frame_step must be 1 or 2"
+    PTS, COL = "unknown points value", "color_bgr has bits above 24 set"
+    WCAP, SR, SF = "w above 16383 (a picture's columns are held in 16 bits)", "stride smaller than a row", "stride smaller than a frame"
+    OVF, OVR = "d_frames overlaps d_out", "d_rows overlaps d_out"
+    wide = dict(w=16384, rs=3 * 16384, ors=6 * 16384, fs=3 * 16384 * h, ofs=6 * 16384 * h)
+    bad = [(dict(frames=None), INVALID, NA), (dict(rows=None), INVALID, NA), (dict(counts=None), INVALID, NA), (dict(out=None), INVALID, NA),
+           (dict(w=0), INVALID, EM), (dict(h=0), INVALID, EM), (dict(cap=0), INVALID, EM), (dict(npairs=-1), INVALID, EM),
+           (dict(step=0), INVALID, STEP), (dict(step=3), INVALID, STEP), (dict(points=2), INVALID, PTS), (dict(points=-1), INVALID, PTS),
+           (dict(color=0x01000000), INVALID, COL), (dict(rs=3 * w - 1), INVALID, SR), (dict(ors=6 * w - 1), INVALID, SR),
+           (dict(fs=3 * w * h - 1), INVALID, SF), (dict(ofs=6 * w * h - 1), INVALID, SF),
+           (dict(out=frames.data_ptr()), INVALID, OVF), (dict(out=frames.data_ptr() + 3 * w * h * 3 - 1), INVALID, OVF),
+           (dict(out=rows.data_ptr()), INVALID, OVR), (dict(out=rows.data_ptr() + npairs * cap * 16 - 1), INVALID, OVR),
+           (wide, CAPACITY, WCAP),
+           # two faults: the earlier check of the entry names the refusal
+           (dict(frames=None, w=0), INVALID, NA), (dict(step=0, w=0), INVALID, EM), (dict(wide, color=0x01000000), INVALID, COL),
+           (dict(wide, rs=3 * 16384 - 1), CAPACITY, WCAP), (dict(rs=3 * w - 1, fs=3 * w * h - 1), INVALID, SR),
+           (dict(out=frames.data_ptr(), ofs=6 * w * h - 1), INVALID, SF), (dict(out=frames.data_ptr(), rows=frames.data_ptr()), INVALID, OVF)]
     keep_frames, keep_rows = frames.clone(), rows.clone()
-    for kw, code in bad:
+    for kw, code, text in bad:
         assert call(**kw) == code, kw
-        assert ctx.lib.evh_last_error_string(ctx.h).decode().startswith("evh_draw_matches: ")
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == "evh_draw_matches: " + text, kw
     assert bool((out == SENTINEL).all()) and torch.equal(frames, keep_frames) and torch.equal(rows, keep_rows)
     assert call(npairs=0) == 0 and call(npairs=0, fs=0, ofs=0) == 0 and bool((out == SENTINEL).all())       # no pictures: nothing to do
     assert call(npairs=1, ofs=0) == 0                                 # one picture: its stride is not used

@@ -248,16 +248,33 @@ def test_refusals_leave_the_output_alone(ctx, jet):
                                           a["alpha"], a["sat"], a["out"], a["ors"], a["ofs"])
 
     nan, inf = float("nan"), float("inf")
-    invalid = [dict(ctx=None), dict(H=None), dict(lut=None), dict(out=None), dict(w=0), dict(h=0), dict(w=-3), dict(n=-1),
-               dict(rs=rs - 1), dict(fs=fs - 1), dict(ors=rs - 1), dict(ofs=fs - 1), dict(frames=None, ors=rs - 1),
-               dict(const=0.0), dict(const=-1.0), dict(const=nan), dict(const=inf), dict(const=-inf),
-               dict(alpha=-0.5), dict(alpha=nan), dict(alpha=inf), dict(alpha=-inf),
-               dict(frames=o), dict(frames=o + fs), dict(frames=o + 2 * fs - 1), dict(frames=o - 2 * fs + 1), dict(n=1, frames=o + fs - 1)]
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
-    for kw in (dict(n=65536), dict(w=65536, h=32768, rs=65536 * 3, ors=65536 * 3, fs=1 << 40, ofs=1 << 40)):
-        assert call(**kw) == CAPACITY, kw
+    who = "evh_heatmap_render: "
+    NA, EM, SR, SF = "NULL argument", "empty grid or negative n", "stride smaller than a row", "stride smaller than a frame"
+    HCON, AL = "heatmap_constant must be finite and positive", "alpha must be finite and not negative"
+    NM, AREA, OV = "at most 65535 matrices per call", "w * h above INT_MAX", "d_frames overlaps d_out"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(H=None), NA), (dict(lut=None), NA), (dict(out=None), NA), (dict(w=0), EM), (dict(h=0), EM), (dict(w=-3), EM),
+               (dict(n=-1), EM), (dict(rs=rs - 1), SR), (dict(fs=fs - 1), SF), (dict(ors=rs - 1), SR), (dict(ofs=fs - 1), SF),
+               (dict(frames=None, ors=rs - 1), SR), (dict(const=0.0), HCON), (dict(const=-1.0), HCON), (dict(const=nan), HCON),
+               (dict(const=inf), HCON), (dict(const=-inf), HCON), (dict(alpha=-0.5), AL), (dict(alpha=nan), AL), (dict(alpha=inf), AL),
+               (dict(alpha=-inf), AL), (dict(frames=o), OV), (dict(frames=o + fs), OV), (dict(frames=o + 2 * fs - 1), OV),
+               (dict(frames=o - 2 * fs + 1), OV), (dict(n=1, frames=o + fs - 1), OV),
+               # two faults: the earlier check of the entry names the refusal
+               (dict(H=None, w=0), NA), (dict(w=-3, alpha=nan), EM), (dict(const=0.0, n=65536), HCON), (dict(rs=rs - 1, fs=fs - 1), SR),
+               (dict(frames=o, ofs=fs - 1), SF), (dict(frames=o, ors=rs - 1), SR)]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
+    capacity = [(dict(n=65536), NM), (dict(w=65536, h=32768, rs=65536 * 3, ors=65536 * 3, fs=1 << 40, ofs=1 << 40), AREA),
+                # two faults: a capacity refusal precedes the strides and the overlap, the matrices come before the grid
+                (dict(n=65536, rs=rs - 1), NM), (dict(n=65536, frames=o), NM), (dict(n=65536, w=65536, h=32768), NM),
+                (dict(w=65536, h=32768), AREA)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
     assert call(n=0) == 0 and call(n=0, frames=None) == 0                    # no matrices: success, and nothing is done
     ctx.synchronize()
     assert (out == SENTINEL).all()

@@ -11,6 +11,7 @@ import pytest
 import moving_checks as MC
 import plate_checks as P
 import warp_checks as W
+from refusal_arena import Arena
 from test_gpu_warp import NOTHING, rot_zoom_persp
 
 pytestmark = pytest.mark.gpu
@@ -339,17 +340,18 @@ def test_refusals_leave_the_outputs_alone(ctx):
     from evenvizion_amd._lib import Yuv420
     INVALID, CAPACITY = -1, -3
     n, sw, sh, dw, dh, npairs, cap = 3, 23, 17, 31, 22, 2, 12
-    src = dev(np.random.default_rng(78).integers(0, 256, (n, sh, sw, 3), dtype=np.uint8))
-    mats = dev(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
-    plate = torch.zeros((dh, dw, 3), dtype=torch.uint8, device="cuda")
-    count = torch.ones((dh, dw), dtype=torch.uint8, device="cuda")
-    rows = torch.ones((npairs, cap, 4), dtype=torch.float32, device="cuda")
-    counts = torch.full((npairs,), cap, dtype=torch.int32, device="cuda")
-    status = torch.zeros(npairs, dtype=torch.int32, device="cuda")
-    out_rows = torch.full((npairs, cap, 4), -7.0, dtype=torch.float32, device="cuda")
-    out_counts = torch.full((npairs,), -7, dtype=torch.int32, device="cuda")
-    moving = torch.full((npairs,), -7, dtype=torch.int32, device="cuda")
-    flags = torch.full((npairs, cap), SENTINEL, dtype=torch.uint8, device="cuda")
+    A = Arena(13)           # every buffer a fixed distance from the others: which ranges meet is the test's to say
+    src = A.put(np.random.default_rng(78).integers(0, 256, (n, sh, sw, 3), dtype=np.uint8))
+    mats = A.put(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
+    plate = A.take((dh, dw, 3))
+    count = A.take((dh, dw), fill=1)
+    rows = A.take((npairs, cap, 4), torch.float32, 1.0)
+    counts = A.take((npairs,), torch.int32, cap)
+    status = A.take((npairs,), torch.int32)
+    out_rows = A.take((npairs, cap, 4), torch.float32, -7.0)
+    out_counts = A.take((npairs,), torch.int32, -7)
+    moving = A.take((npairs,), torch.int32, -7)
+    flags = A.take((npairs, cap), fill=SENTINEL)
     f, m, p, c, r, k, s, o, oc, mv, fl = (t.data_ptr() for t in (src, mats, plate, count, rows, counts, status, out_rows, out_counts,
                                                                    moving, flags))
     rs, fs, prs = sw * 3, sw * sh * 3, dw * 3
@@ -365,27 +367,53 @@ def test_refusals_leave_the_outputs_alone(ctx):
                                               *[a[t] for t in tail])
 
     nan, inf = float("nan"), float("inf")
-    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(plate=None), dict(count=None), dict(rows=None), dict(counts=None),
-               dict(st=None), dict(orows=None), dict(ocounts=None), dict(cn=2), dict(cn=0), dict(cn=4), dict(sw=0), dict(sh=0),
-               dict(dw=0), dict(dh=-1), dict(cap=0), dict(n=-1), dict(np=-1), dict(step=0), dict(step=3), dict(n=2), dict(n=0),
-               dict(step=2), dict(mc=0), dict(mc=256), dict(thr=-1), dict(thr=256), dict(rad=-1), dict(rad=8), dict(hits=0),
-               dict(hits=10), dict(rad=0, hits=2), dict(rad=7, hits=226), dict(keep=-1), dict(sx=0.0), dict(sy=-1.0), dict(sx=nan),
-               dict(sy=inf), dict(sx=-inf), dict(rs=rs - 1), dict(fs=fs - 1), dict(prs=prs - 1), dict(crs=dw - 1),
-               dict(rows=r + 4), dict(orows=o + 8),
-               # an output over an input or another output
-               dict(orows=r), dict(orows=r + 16 * (npairs * cap - 1)), dict(orows=f), dict(ocounts=k), dict(ocounts=s), dict(moving=oc),
-               dict(moving=m), dict(flags=p), dict(flags=c + dw * dh - 1), dict(flags=o), dict(flags=mv), dict(ocounts=mv + 4),
-               dict(moving=r + 16), dict(flags=f + n * fs - 1)]
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+    who, who_yuv = "evh_rows_moving_filter: ", "evh_rows_moving_filter_yuv420: "
+    NS, NA, CH, EM = "NULL source", "NULL argument", "channels must be 1 or 3", "empty frame, canvas or row block"
+    STEP, MC, TH, RAD = "frame_step must be 1 or 2", "min_cover must lie in 1..255", "threshold must lie in 0..255", "radius must lie in 0..7"
+    HITS, KEEP = "min_hits must lie in 1..(2*radius+1)^2", "min_keep must not be negative"
+    SXY, NP = "row_sx and row_sy must be finite and positive", "at most 65535 pairs per call"
+    BIG, AREA = "source sizes stay below 2^26 (positions are held in 1/32 pixels)", "dw * dh above INT_MAX"
+    REACH, SS = "nframes does not reach the last pair's frames", "source stride smaller than a row / frame"
+    PS, CTS, AL = "plate stride smaller than a row", "count stride smaller than a row", "d_rows and d_out_rows must be 16-byte aligned"
+
+    def over(a, b):
+        return "%s overlaps %s" % (a, b)
+    OR, OC, MV, FL, FR = "d_out_rows", "d_out_counts", "d_moving", "d_flags", "the frames"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(frames=None), NS)] + [(dict([(a, None)]), NA) for a in ("M", "plate", "count", "rows", "counts", "st", "orows", "ocounts")]
+    invalid += [(dict(cn=2), CH), (dict(cn=0), CH), (dict(cn=4), CH), (dict(sw=0), EM), (dict(sh=0), EM), (dict(dw=0), EM), (dict(dh=-1), EM),
+                (dict(cap=0), EM), (dict(n=-1), EM), (dict(np=-1), EM), (dict(step=0), STEP), (dict(step=3), STEP), (dict(n=2), REACH),
+                (dict(n=0), REACH), (dict(step=2), REACH), (dict(mc=0), MC), (dict(mc=256), MC), (dict(thr=-1), TH), (dict(thr=256), TH),
+                (dict(rad=-1), RAD), (dict(rad=8), RAD), (dict(hits=0), HITS), (dict(hits=10), HITS), (dict(rad=0, hits=2), HITS),
+                (dict(rad=7, hits=226), HITS), (dict(keep=-1), KEEP), (dict(sx=0.0), SXY), (dict(sy=-1.0), SXY), (dict(sx=nan), SXY),
+                (dict(sy=inf), SXY), (dict(sx=-inf), SXY), (dict(rs=rs - 1), SS), (dict(fs=fs - 1), SS), (dict(prs=prs - 1), PS),
+                (dict(crs=dw - 1), CTS), (dict(rows=r + 4), AL), (dict(orows=o + 8), AL),
+                # an output over an input or another output
+                (dict(orows=r), over(OR, "d_rows")), (dict(orows=r + 16 * (npairs * cap - 1)), over(OR, "d_rows")), (dict(orows=f), over(OR, FR)),
+                (dict(ocounts=k), over(OC, "d_counts")), (dict(ocounts=s), over(OC, "d_status1")), (dict(moving=oc), over(OC, MV)),
+                (dict(moving=m), over(MV, "d_M")), (dict(flags=p), over(FL, "d_plate")), (dict(flags=c + dw * dh - 1), over(FL, "d_count")),
+                (dict(flags=o), over(OR, FL)), (dict(flags=mv), over(MV, FL)), (dict(ocounts=mv + 4), over(OC, MV)),
+                (dict(moving=r + 16), over(MV, "d_rows")), (dict(flags=f + n * fs - 1), over(FL, FR)),
+                # two faults: the earlier check of the entry names the refusal
+                (dict(frames=None, rows=None), NS), (dict(M=None, cn=2), NA), (dict(np=65536, n=65537, mc=0), MC), (dict(prs=prs - 1, rs=rs - 1), PS),
+                (dict(orows=r, prs=prs - 1), PS), (dict(rows=r + 4, flags=p), AL), (dict(orows=r, ocounts=k), over(OR, "d_rows")),
+                (dict(moving=m, flags=o), over(OR, FL))]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
     big = 1 << 26
-    capacity = [dict(np=65536, n=65537), dict(sw=big, rs=big * 3, fs=big * 3 * sh), dict(sh=big, fs=sw * 3 * big),
-                dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536)]
-    for kw in capacity:
-        assert call(**kw) == CAPACITY, kw
-    y = torch.zeros((n, sh, sw), dtype=torch.uint8, device="cuda")
-    cc = torch.zeros((2, n, 9, 12), dtype=torch.uint8, device="cuda")
+    capacity = [(dict(np=65536, n=65537), NP), (dict(sw=big, rs=big * 3, fs=big * 3 * sh), BIG), (dict(sh=big, fs=sw * 3 * big), BIG),
+                (dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536), AREA),
+                # two faults: a capacity refusal precedes the reach of the frames, the strides and the overlaps
+                (dict(sw=big, rs=big * 3 - 1, fs=big * 3 * sh), BIG), (dict(n=2, sw=big), BIG), (dict(np=65536, n=3), NP), (dict(sh=big, orows=r), BIG)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
+    y = A.take((n, sh, sw))
+    cc = A.take((2, n, 9, 12))
     yuv = dict(d_y=y.data_ptr(), d_cb=cc[0].data_ptr(), d_cr=cc[1].data_ptr(), y_stride=sw, c_stride=12, y_frame_stride=sw * sh,
                c_frame_stride=12 * 9, c_pixel_stride=1)
 
@@ -394,15 +422,24 @@ def test_refusals_leave_the_outputs_alone(ctx):
         d = None if desc is None else ctypes.byref(Yuv420(**desc))
         return ctx.lib.evh_rows_moving_filter_yuv420(a["ctx"], d, a["n"], a["sw"], a["sh"], *[a[t] for t in tail])
 
-    assert call_yuv(None) == INVALID
-    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=sw - 1), dict(c_stride=11),
-                dict(y_frame_stride=sw * sh - 1), dict(c_frame_stride=12 * 9 - 1)):
-        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
-    for kw in (dict(M=None), dict(count=None), dict(dw=0), dict(mc=0), dict(thr=256), dict(rad=8), dict(prs=prs - 1), dict(n=2),
-               dict(orows=r), dict(flags=y.data_ptr()), dict(moving=cc[1].data_ptr())):
-        assert call_yuv(yuv, **kw) == INVALID, kw
-    for kw in (dict(np=65536, n=65537), dict(sw=big), dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536)):
-        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    refused(call_yuv(None), INVALID, who_yuv + NS, "no description")
+    CPS, PLANE = "chroma pixel stride must be 1 or 2", "frame stride smaller than a plane"
+    for bad, text in ((dict(d_y=None), NS), (dict(d_cb=None), NS), (dict(d_cr=None), NS), (dict(c_pixel_stride=3), CPS),
+                      (dict(y_stride=sw - 1), "luma row stride smaller than the width"),
+                      (dict(c_stride=11), "chroma row stride smaller than a chroma row"),
+                      (dict(y_frame_stride=sw * sh - 1), PLANE), (dict(c_frame_stride=12 * 9 - 1), PLANE)):
+        refused(call_yuv(dict(yuv, **bad)), INVALID, who_yuv + text, bad)
+    for kw, text in ((dict(M=None), NA), (dict(count=None), NA), (dict(dw=0), EM), (dict(mc=0), MC), (dict(thr=256), TH), (dict(rad=8), RAD),
+                     (dict(prs=prs - 1), PS), (dict(n=2), REACH), (dict(orows=r), over(OR, "d_rows")), (dict(flags=y.data_ptr()), over(FL, FR)),
+                     (dict(moving=cc[1].data_ptr()), over(MV, FR)), (dict(ocounts=cc[0].data_ptr()), over(OC, FR))):   # the last: over the Cb plane
+        refused(call_yuv(yuv, **kw), INVALID, who_yuv + text, kw)
+    # two faults, one of them in the description: a NULL plane first, the strides before the planes, the planes before the overlaps
+    refused(call_yuv(dict(yuv, d_y=None), M=None), INVALID, who_yuv + NS, "NULL plane before NULL argument")
+    refused(call_yuv(dict(yuv, y_stride=sw - 1), prs=prs - 1), INVALID, who_yuv + PS, "strides before the description")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), orows=r), INVALID, who_yuv + CPS, "the description before the overlaps")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), np=65536, n=65537), CAPACITY, who_yuv + NP, "capacity before the description")
+    for kw, text in ((dict(np=65536, n=65537), NP), (dict(sw=big), BIG), (dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536), AREA)):
+        refused(call_yuv(yuv, **kw), CAPACITY, who_yuv + text, kw)
     assert call(np=0) == 0 and call(np=0, n=0) == 0 and call_yuv(yuv, np=0) == 0           # no pairs: nothing is done
     ctx.synchronize()
     assert (out_rows == -7.0).all() and (out_counts == -7).all() and (moving == -7).all() and (flags == SENTINEL).all()

@@ -9,6 +9,7 @@ import pytest
 
 import plate_checks as P
 import warp_checks as W
+from refusal_arena import Arena
 from test_gpu_warp import NOTHING, rot_zoom_persp
 
 pytestmark = pytest.mark.gpu
@@ -265,12 +266,13 @@ def test_refusals_leave_the_outputs_alone(ctx):
     from evenvizion_amd._lib import Yuv420
     INVALID, CAPACITY = -1, -3
     n, sw, sh, dw, dh = 2, 23, 17, 31, 22
-    src = dev(frames_of(69, n, sw, sh))
-    mats = dev(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
-    plate = torch.full((dh, dw, 3), SENTINEL, dtype=torch.uint8, device="cuda")
-    count = torch.full((dh, dw), SENTINEL, dtype=torch.uint8, device="cuda")
-    masks = torch.full((n, dh, dw), SENTINEL, dtype=torch.uint8, device="cuda")
-    elsewhere = torch.full((dh, dw, 3), 7, dtype=torch.uint8, device="cuda")
+    A = Arena(8)            # every buffer a fixed distance from the others: which ranges meet is the test's to say
+    src = A.put(frames_of(69, n, sw, sh))
+    mats = A.put(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
+    plate = A.take((dh, dw, 3), fill=SENTINEL)
+    count = A.take((dh, dw), fill=SENTINEL)
+    masks = A.take((n, dh, dw), fill=SENTINEL)
+    elsewhere = A.take((dh, dw, 3), fill=7)
     f, m, p, c, k, b = (t.data_ptr() for t in (src, mats, plate, count, masks, elsewhere))
     rs, fs, prs, mfs = sw * 3, sw * sh * 3, dw * 3, dw * dh
     good = dict(ctx=ctx.h, frames=f, n=n, sw=sw, sh=sh, cn=3, rs=rs, fs=fs, M=m, inv=0, mc=1, bg=b, plate=p, prs=prs, count=c,
@@ -282,25 +284,50 @@ def test_refusals_leave_the_outputs_alone(ctx):
         return ctx.lib.evh_plate_fixed_plane(a["ctx"], a["frames"], a["n"], a["sw"], a["sh"], a["cn"], a["rs"], a["fs"],
                                              *[a[t] for t in tail])
 
-    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(plate=None), dict(cn=2), dict(cn=0), dict(cn=4), dict(sw=0),
-               dict(sh=0), dict(dw=0), dict(dh=-1), dict(n=-1), dict(mc=0), dict(mc=256), dict(mc=-1), dict(thr=-1), dict(thr=256),
-               dict(rs=rs - 1), dict(fs=fs - 1), dict(prs=prs - 1), dict(crs=dw - 1), dict(mrs=dw - 1), dict(mfs=mfs - 1),
+    who, who_yuv = "evh_plate_fixed_plane: ", "evh_plate_fixed_plane_yuv420: "
+    NS, NA, CH, EM = "NULL source", "NULL argument", "channels must be 1 or 3", "empty frame or canvas"
+    MC, TH = "min_cover must lie in 1..255", "threshold must lie in 0..255"
+    PLN, BIG = "at most EVH_PLATE_MAX_FRAMES = 255 frames per call", "source sizes stay below 2^26 (positions are held in 1/32 pixels)"
+    AREA, SS = "dw * dh above INT_MAX", "source stride smaller than a row / frame"
+    PS, CTS, MS = "plate stride smaller than a row", "count stride smaller than a row", "mask stride smaller than a row / picture"
+
+    def over(a, b):
+        return "%s overlaps %s" % (a, b)
+    PL, CO, MA, BG, FR = "d_plate", "d_count", "d_mask", "d_background", "the frames"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(frames=None), NS), (dict(M=None), NA), (dict(plate=None), NA), (dict(cn=2), CH), (dict(cn=0), CH), (dict(cn=4), CH),
+               (dict(sw=0), EM), (dict(sh=0), EM), (dict(dw=0), EM), (dict(dh=-1), EM), (dict(n=-1), EM), (dict(mc=0), MC),
+               (dict(mc=256), MC), (dict(mc=-1), MC), (dict(thr=-1), TH), (dict(thr=256), TH), (dict(rs=rs - 1), SS), (dict(fs=fs - 1), SS),
+               (dict(prs=prs - 1), PS), (dict(crs=dw - 1), CTS), (dict(mrs=dw - 1), MS), (dict(mfs=mfs - 1), MS),
                # an output over another output, the frames or the background
-               dict(count=p), dict(count=p + prs * dh - 1), dict(mask=p), dict(mask=c), dict(mask=c - mfs), dict(count=k + mfs),
-               dict(plate=f), dict(plate=f + 2 * fs - 1), dict(count=f), dict(mask=f + fs), dict(bg=p), dict(bg=p + prs),
-               dict(bg=p - prs), dict(bg=c), dict(bg=k + mfs)]
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+               (dict(count=p), over(PL, CO)), (dict(count=p + prs * dh - 1), over(PL, CO)), (dict(mask=p), over(PL, MA)),
+               (dict(mask=c), over(CO, MA)), (dict(mask=c - mfs), over(CO, MA)), (dict(count=k + mfs), over(CO, MA)),
+               (dict(plate=f), over(PL, FR)), (dict(plate=f + 2 * fs - 1), over(PL, FR)), (dict(count=f), over(CO, FR)),
+               (dict(mask=f + fs), over(MA, FR)), (dict(bg=p), over(PL, BG)), (dict(bg=p + prs), over(PL, BG)),
+               (dict(bg=p - prs), over(PL, BG)), (dict(bg=c), over(CO, BG)), (dict(bg=k + mfs), over(MA, BG)),
+               # two faults: the earlier check of the entry names the refusal
+               (dict(frames=None, plate=None), NS), (dict(M=None, cn=2), NA), (dict(n=256, mc=0), MC), (dict(prs=prs - 1, rs=rs - 1), PS),
+               (dict(count=p, crs=dw - 1), CTS), (dict(count=p, mask=p), over(PL, CO)), (dict(mask=f, bg=c), over(CO, BG))]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
     big = 1 << 26
-    capacity = [dict(n=256), dict(n=65536), dict(sw=big, rs=big * 3, fs=big * 3 * sh), dict(sh=big, fs=sw * 3 * big),
-                dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536, mrs=65536, mfs=1 << 40)]
-    for kw in capacity:
-        assert call(**kw) == CAPACITY, kw
-    assert call(n=255, fs=fs - 1) == INVALID and call(sw=big - 1, rs=(big - 1) * 3 - 1) == INVALID    # at the limits the ordinary checks apply
+    capacity = [(dict(n=256), PLN), (dict(n=65536), PLN), (dict(sw=big, rs=big * 3, fs=big * 3 * sh), BIG), (dict(sh=big, fs=sw * 3 * big), BIG),
+                (dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536, mrs=65536, mfs=1 << 40), AREA),
+                # two faults: a capacity refusal precedes the strides and the overlaps
+                (dict(sw=big, rs=big * 3 - 1, fs=big * 3 * sh), BIG), (dict(n=256, sw=big), PLN), (dict(sh=big, count=p), BIG),
+                (dict(n=256, prs=prs - 1), PLN)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
+    refused(call(n=255, fs=fs - 1), INVALID, who + SS, "at the limit")                                # there the ordinary checks apply
+    refused(call(sw=big - 1, rs=(big - 1) * 3 - 1), INVALID, who + SS, "below the limit")
     # the plane form: its own description, then the same checks
-    y = torch.zeros((n, sh, sw), dtype=torch.uint8, device="cuda")
-    cc = torch.zeros((2, n, 9, 12), dtype=torch.uint8, device="cuda")
+    y = A.take((n, sh, sw))
+    cc = A.take((2, n, 9, 12))
     yuv = dict(d_y=y.data_ptr(), d_cb=cc[0].data_ptr(), d_cr=cc[1].data_ptr(), y_stride=sw, c_stride=12, y_frame_stride=sw * sh,
                c_frame_stride=12 * 9, c_pixel_stride=1)
 
@@ -309,15 +336,25 @@ def test_refusals_leave_the_outputs_alone(ctx):
         d = None if desc is None else ctypes.byref(Yuv420(**desc))
         return ctx.lib.evh_plate_fixed_plane_yuv420(a["ctx"], d, a["n"], a["sw"], a["sh"], *[a[t] for t in tail])
 
-    assert call_yuv(None) == INVALID
-    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=sw - 1), dict(c_stride=11),
-                dict(y_frame_stride=sw * sh - 1), dict(c_frame_stride=12 * 9 - 1)):
-        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
-    for kw in (dict(M=None), dict(plate=None), dict(dw=0), dict(mc=0), dict(thr=256), dict(prs=prs - 1), dict(bg=p), dict(count=p),
-               dict(plate=y.data_ptr()), dict(mask=cc[1].data_ptr())):
-        assert call_yuv(yuv, **kw) == INVALID, kw
-    for kw in (dict(n=256), dict(sw=big), dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536, mrs=65536, mfs=1 << 40)):
-        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    refused(call_yuv(None), INVALID, who_yuv + NS, "no description")
+    CPS, PLANE = "chroma pixel stride must be 1 or 2", "frame stride smaller than a plane"
+    for bad, text in ((dict(d_y=None), NS), (dict(d_cb=None), NS), (dict(d_cr=None), NS), (dict(c_pixel_stride=3), CPS),
+                      (dict(y_stride=sw - 1), "luma row stride smaller than the width"),
+                      (dict(c_stride=11), "chroma row stride smaller than a chroma row"),
+                      (dict(y_frame_stride=sw * sh - 1), PLANE), (dict(c_frame_stride=12 * 9 - 1), PLANE)):
+        refused(call_yuv(dict(yuv, **bad)), INVALID, who_yuv + text, bad)
+    for kw, text in ((dict(M=None), NA), (dict(plate=None), NA), (dict(dw=0), EM), (dict(mc=0), MC), (dict(thr=256), TH),
+                     (dict(prs=prs - 1), PS), (dict(bg=p), over(PL, BG)), (dict(count=p), over(PL, CO)),
+                     (dict(plate=y.data_ptr()), over(PL, FR)), (dict(mask=cc[1].data_ptr()), over(MA, FR)),
+                     (dict(count=cc[0].data_ptr()), over(CO, FR))):                                    # the last: over the Cb plane
+        refused(call_yuv(yuv, **kw), INVALID, who_yuv + text, kw)
+    # two faults, one of them in the description: a NULL plane first, the strides before the planes, the planes before the overlaps
+    refused(call_yuv(dict(yuv, d_cr=None), plate=None), INVALID, who_yuv + NS, "NULL plane before NULL argument")
+    refused(call_yuv(dict(yuv, y_stride=sw - 1), prs=prs - 1), INVALID, who_yuv + PS, "strides before the description")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), count=p), INVALID, who_yuv + CPS, "the description before the overlaps")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), n=256), CAPACITY, who_yuv + PLN, "capacity before the description")
+    for kw, text in ((dict(n=256), PLN), (dict(sw=big), BIG), (dict(dw=65536, dh=32768, prs=65536 * 3, crs=65536, mrs=65536, mfs=1 << 40), AREA)):
+        refused(call_yuv(yuv, **kw), CAPACITY, who_yuv + text, kw)
     ctx.synchronize()
     assert (plate == SENTINEL).all() and (count == SENTINEL).all() and (masks == SENTINEL).all() and (elsewhere == 7).all()
     # no frames: every pixel takes the background, the count is 0, no mask is written

@@ -10,6 +10,7 @@ import pytest
 
 import residual_checks as R
 import warp_checks as W
+from refusal_arena import Arena
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -326,10 +327,11 @@ def test_refusals_leave_the_outputs_alone(ctx):
     from evenvizion_amd._lib import Yuv420
     INVALID, CAPACITY = -1, -3
     n, w, h = 3, 23, 17
-    src = dev(frames_of(80, n + 1, w, h))
-    mats = dev(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
-    stats = torch.full((n + 1, 6), -1, dtype=torch.int64, device="cuda")
-    out = torch.full((n + 1, h, w), SENTINEL, dtype=torch.uint8, device="cuda")
+    A = Arena(6)            # every buffer a fixed distance from the others: which ranges meet is the test's to say
+    src = A.put(frames_of(80, n + 1, w, h))
+    mats = A.put(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
+    stats = A.take((n + 1, 6), torch.int64, -1)
+    out = A.take((n + 1, h, w), fill=SENTINEL)
     f, m, s, o = src.data_ptr(), mats.data_ptr(), stats.data_ptr(), out.data_ptr()
     rs, fs, ors, ofs = w * 3, w * h * 3, w, w * h
     good = dict(ctx=ctx.h, frames=f, n=n, step=1, w=w, h=h, cn=3, rs=rs, fs=fs, M=m, thr=16, stats=s, out=o, kind=0, ors=ors, ofs=ofs)
@@ -339,24 +341,43 @@ def test_refusals_leave_the_outputs_alone(ctx):
         return ctx.lib.evh_pair_residual(a["ctx"], a["frames"], a["n"], a["step"], a["w"], a["h"], a["cn"], a["rs"], a["fs"], a["M"],
                                          a["thr"], a["stats"], a["out"], a["kind"], a["ors"], a["ofs"])
 
-    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(stats=None), dict(cn=2), dict(cn=0), dict(cn=4), dict(step=0),
-               dict(step=3), dict(w=0), dict(h=0), dict(h=-1), dict(n=-1), dict(thr=-1), dict(thr=256), dict(kind=2), dict(kind=-1),
-               dict(rs=rs - 1), dict(fs=fs - 1), dict(n=1, fs=fs - 1), dict(ors=ors - 1), dict(ofs=ofs - 1),
-               dict(out=f), dict(out=f + (n + 1) * fs - 1), dict(out=f - n * ofs + 1), dict(frames=o + 5),       # the frames
-               dict(out=s), dict(out=s + n * 48 - 1), dict(stats=o + n * ofs - 8), dict(stats=o)]                # the statistics
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+    who, who_yuv = "evh_pair_residual: ", "evh_pair_residual_yuv420: "
+    NS, NA, CH, STEP = "NULL source", "NULL argument", "channels must be 1 or 3", "frame_step must be 1 or 2"
+    EM, TH, KIND = "empty frame or negative npairs", "threshold must lie in 0..255", "unknown kind"
+    BIG, AREA = "frame sizes stay below 2^26 (positions are held in 1/32 pixels)", "w * h above INT_MAX"
+    NP, NF = "at most 65535 pairs per call", "at most 65535 frames per call"
+    SS, OS = "source stride smaller than a row / frame", "output stride smaller than a row / picture"
+    OST, OFR = "d_out overlaps d_stats", "d_out overlaps the frames"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(frames=None), NS), (dict(M=None), NA), (dict(stats=None), NA), (dict(cn=2), CH), (dict(cn=0), CH), (dict(cn=4), CH),
+               (dict(step=0), STEP), (dict(step=3), STEP), (dict(w=0), EM), (dict(h=0), EM), (dict(h=-1), EM), (dict(n=-1), EM),
+               (dict(thr=-1), TH), (dict(thr=256), TH), (dict(kind=2), KIND), (dict(kind=-1), KIND), (dict(rs=rs - 1), SS),
+               (dict(fs=fs - 1), SS), (dict(n=1, fs=fs - 1), SS), (dict(ors=ors - 1), OS), (dict(ofs=ofs - 1), OS),
+               (dict(out=f), OFR), (dict(out=f + (n + 1) * fs - 1), OFR), (dict(out=f - n * ofs + 1), OFR), (dict(frames=o + 5), OFR),
+               (dict(out=s), OST), (dict(out=s + n * 48 - 1), OST), (dict(stats=o + n * ofs - 8), OST), (dict(stats=o), OST),
+               # two faults: the earlier check of the entry names the refusal
+               (dict(frames=None, stats=None), NS), (dict(M=None, cn=2), NA), (dict(step=0, n=-1), STEP), (dict(rs=rs - 1, ors=ors - 1), SS),
+               (dict(out=s, ors=ors - 1), OS), (dict(out=f, stats=f), OST)]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
     big = 1 << 26
-    capacity = [dict(w=big, rs=big * 3, fs=big * 3 * h), dict(h=big, fs=rs * big), dict(w=65536, h=32768, rs=65536 * 3, fs=1 << 40, ors=65536, ofs=1 << 40),
-                dict(n=65536)]
-    for kw in capacity:
-        assert call(**kw) == CAPACITY, kw
-    assert call(w=big - 1, rs=(big - 1) * 3 - 1) == INVALID              # just below the limit the ordinary checks apply
+    capacity = [(dict(w=big, rs=big * 3, fs=big * 3 * h), BIG), (dict(h=big, fs=rs * big), BIG),
+                (dict(w=65536, h=32768, rs=65536 * 3, fs=1 << 40, ors=65536, ofs=1 << 40), AREA), (dict(n=65536), NP),
+                # two faults: a capacity refusal precedes the strides and the overlaps
+                (dict(w=big, rs=big * 3 - 1, fs=big * 3 * h), BIG), (dict(n=65536, fs=fs - 1), NP), (dict(h=big, out=s), BIG),
+                (dict(w=big, n=65536), BIG)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
+    refused(call(w=big - 1, rs=(big - 1) * 3 - 1), INVALID, who + SS, "below the limit")      # there the ordinary checks apply
     # the plane form: its own description, then the same checks
     cw, ch = 12, 9
-    y = torch.zeros((n + 1, h, w), dtype=torch.uint8, device="cuda")
-    c = torch.zeros((2, n + 1, ch, cw), dtype=torch.uint8, device="cuda")
+    y = A.take((n + 1, h, w))
+    c = A.take((2, n + 1, ch, cw))
     torch.cuda.synchronize()
     yuv = dict(d_y=y.data_ptr(), d_cb=c[0].data_ptr(), d_cr=c[1].data_ptr(), y_stride=w, c_stride=cw, y_frame_stride=w * h,
                c_frame_stride=cw * ch, c_pixel_stride=1)
@@ -367,15 +388,24 @@ def test_refusals_leave_the_outputs_alone(ctx):
         return ctx.lib.evh_pair_residual_yuv420(a["ctx"], d, a["n"], a["step"], a["w"], a["h"], a["M"], a["thr"], a["stats"], a["out"],
                                                 a["kind"], a["ors"], a["ofs"])
 
-    assert call_yuv(None) == INVALID
-    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=w - 1), dict(c_stride=cw - 1),
-                dict(y_frame_stride=w * h - 1), dict(c_frame_stride=cw * ch - 1)):
-        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
-    for kw in (dict(M=None), dict(stats=None), dict(w=0), dict(step=3), dict(thr=256), dict(kind=5), dict(ors=ors - 1),
-               dict(out=y.data_ptr() + 7), dict(out=c[1].data_ptr()), dict(out=s)):
-        assert call_yuv(yuv, **kw) == INVALID, kw
-    for kw in (dict(w=big), dict(n=65536), dict(w=65536, h=32768, ors=65536, ofs=1 << 40)):
-        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    refused(call_yuv(None), INVALID, who_yuv + NS, "no description")
+    CPS, PLANE = "chroma pixel stride must be 1 or 2", "frame stride smaller than a plane"
+    for bad, text in ((dict(d_y=None), NS), (dict(d_cb=None), NS), (dict(d_cr=None), NS), (dict(c_pixel_stride=3), CPS),
+                      (dict(y_stride=w - 1), "luma row stride smaller than the width"),
+                      (dict(c_stride=cw - 1), "chroma row stride smaller than a chroma row"),
+                      (dict(y_frame_stride=w * h - 1), PLANE), (dict(c_frame_stride=cw * ch - 1), PLANE)):
+        refused(call_yuv(dict(yuv, **bad)), INVALID, who_yuv + text, bad)
+    for kw, text in ((dict(M=None), NA), (dict(stats=None), NA), (dict(w=0), EM), (dict(step=3), STEP), (dict(thr=256), TH), (dict(kind=5), KIND),
+                     (dict(ors=ors - 1), OS), (dict(out=y.data_ptr() + 7), OFR), (dict(out=c[1].data_ptr()), OFR), (dict(out=s), OST),
+                     (dict(out=c[0].data_ptr()), OFR)):                                                # the last: over the Cb plane
+        refused(call_yuv(yuv, **kw), INVALID, who_yuv + text, kw)
+    # two faults, one of them in the description: a NULL plane first, the strides before the planes, the planes before the overlaps
+    refused(call_yuv(dict(yuv, d_y=None), stats=None), INVALID, who_yuv + NS, "NULL plane before NULL argument")
+    refused(call_yuv(dict(yuv, y_stride=w - 1), ors=ors - 1), INVALID, who_yuv + OS, "strides before the description")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), out=s), INVALID, who_yuv + CPS, "the description before the overlaps")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), n=65535, step=2), CAPACITY, who_yuv + NF, "the frames' capacity before the description")
+    for kw, text in ((dict(w=big), BIG), (dict(n=65536), NP), (dict(w=65536, h=32768, ors=65536, ofs=1 << 40), AREA), (dict(n=65535), NF)):
+        refused(call_yuv(yuv, **kw), CAPACITY, who_yuv + text, kw)
     # no pairs: success, and nothing is done, not even the zeroing
     assert call(n=0) == 0 and call_yuv(yuv, n=0) == 0
     ctx.synchronize()

@@ -11,6 +11,7 @@ import pytest
 
 import trail_checks as T
 import warp_checks as W
+from refusal_arena import Arena
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0xCD
@@ -241,10 +242,11 @@ def test_refusals_leave_the_outputs_alone(ctx):
     INVALID, CAPACITY = -1, -3
     n, sw, sh, dw, dh = 2, 10, 8, 31, 22
     rng = np.random.default_rng(47)
-    src = dev(rng.integers(1, 256, (n + 1, sh, sw, 3), dtype=np.uint8))
-    mats = dev(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
-    out = torch.full((n + 1, dh, dw, 3), SENTINEL, dtype=torch.uint8, device="cuda")
-    canvas = torch.full((dh + 1, dw, 3), 7, dtype=torch.uint8, device="cuda")
+    A = Arena(6)            # every buffer a fixed distance from the others: which ranges meet is the test's to say
+    src = A.put(rng.integers(1, 256, (n + 1, sh, sw, 3), dtype=np.uint8))
+    mats = A.put(np.tile(np.eye(3).reshape(1, 9), (n, 1)))
+    out = A.take((n + 1, dh, dw, 3), fill=SENTINEL)
+    canvas = A.take((dh + 1, dw, 3), fill=7)
     f, m, o, cv = src.data_ptr(), mats.data_ptr(), out.data_ptr(), canvas.data_ptr()
     rs, fs, ors, ofs = sw * 3, sw * sh * 3, dw * 3, dw * dh * 3
     good = dict(ctx=ctx.h, frames=f, n=n, sw=sw, sh=sh, rs=rs, fs=fs, M=m, inv=0, rect=None, canvas=cv, crs=ors, out=o, ors=ors,
@@ -256,26 +258,44 @@ def test_refusals_leave_the_outputs_alone(ctx):
                                              a["rect"], a["canvas"], a["crs"], a["out"], a["ors"], a["ofs"], a["dw"], a["dh"],
                                              a["ox"], a["oy"])
 
-    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(canvas=None), dict(sw=0), dict(sh=0), dict(dw=0), dict(dh=-1),
-               dict(n=-1), dict(rs=rs - 1), dict(fs=fs - 1), dict(crs=ors - 1), dict(ors=ors - 1), dict(ofs=ofs - 1),
-               dict(out=cv), dict(out=cv + ors), dict(out=cv - ofs), dict(canvas=o + ofs + ors),          # d_out and d_canvas
-               dict(out=f), dict(out=f + fs + rs), dict(out=f - ofs - ors),                               # d_out and the frames
-               dict(canvas=f), dict(canvas=f + 2 * fs - 1), dict(canvas=f - ofs + 1),                     # d_canvas and the frames
-               dict(out=None, canvas=f + fs)]
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+    who, who_yuv = "evh_trail_fixed_plane: ", "evh_trail_fixed_plane_yuv420: "
+    NS, NA, EM = "NULL source", "NULL argument", "empty frame or canvas"
+    BIG, AREA = "source sizes stay below 2^26 (positions are held in 1/32 pixels)", "dw * dh above INT_MAX"
+    NF, SS = "at most 65535 frames per call", "source stride smaller than a row / frame"
+    CS = "canvas or output stride smaller than a row / picture"
+    OC, OF, CF = "d_out overlaps d_canvas", "d_out overlaps the frames", "d_canvas overlaps the frames"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(frames=None), NS), (dict(M=None), NA), (dict(canvas=None), NA), (dict(sw=0), EM), (dict(sh=0), EM), (dict(dw=0), EM),
+               (dict(dh=-1), EM), (dict(n=-1), EM), (dict(rs=rs - 1), SS), (dict(fs=fs - 1), SS), (dict(crs=ors - 1), CS),
+               (dict(ors=ors - 1), CS), (dict(ofs=ofs - 1), CS),
+               (dict(out=cv), OC), (dict(out=cv + ors), OC), (dict(out=cv - ofs), OC), (dict(canvas=o + ofs + ors), OC),
+               (dict(out=f), OF), (dict(out=f + fs + rs), OF), (dict(out=f - ofs - ors), OF),
+               (dict(canvas=f), CF), (dict(canvas=f + 2 * fs - 1), CF), (dict(canvas=f - ofs + 1), CF),
+               (dict(out=None, canvas=f + fs), CF),
+               # two faults: the earlier check of the entry names the refusal
+               (dict(frames=None, canvas=None), NS), (dict(M=None, sw=0), NA), (dict(out=cv, crs=ors - 1), CS),
+               (dict(ors=ors - 1, rs=rs - 1), CS), (dict(rs=rs - 1, out=cv), SS), (dict(out=f, canvas=f), OC)]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
     big = 1 << 26
-    capacity = [dict(sw=big, rs=big * 3, fs=big * 3 * sh), dict(sh=big, fs=sw * 3 * big),
-                dict(dw=65536, dh=32768, crs=65536 * 3, ors=65536 * 3, ofs=1 << 40), dict(n=65536)]
-    for kw in capacity:
-        assert call(**kw) == CAPACITY, kw
-    assert call(sw=big - 1, rs=(big - 1) * 3 - 1) == INVALID           # just below the limit the ordinary checks apply
+    capacity = [(dict(sw=big, rs=big * 3, fs=big * 3 * sh), BIG), (dict(sh=big, fs=sw * 3 * big), BIG),
+                (dict(dw=65536, dh=32768, crs=65536 * 3, ors=65536 * 3, ofs=1 << 40), AREA), (dict(n=65536), NF),
+                # two faults: a capacity refusal precedes the strides and the overlaps
+                (dict(sw=big, rs=big * 3 - 1, fs=big * 3 * sh), BIG), (dict(n=65536, crs=ors - 1), NF), (dict(sh=big, out=cv), BIG),
+                (dict(sw=big, n=65536), BIG)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
+    refused(call(sw=big - 1, rs=(big - 1) * 3 - 1), INVALID, who + SS, "below the limit")     # there the ordinary checks apply
     # what touches nothing is accepted: the buffers may lie side by side, and without pictures their strides do not count
     assert call(n=0) == 0 and call(n=0, out=None, ors=0, ofs=0) == 0
     # the plane form: its own description, then the same checks
-    y = torch.full((n, sh, sw), 200, dtype=torch.uint8, device="cuda")
-    c = torch.full((2, n, 4, 5), 128, dtype=torch.uint8, device="cuda")
+    y = A.take((n, sh, sw), fill=200)
+    c = A.take((2, n, 4, 5), fill=128)
     yuv = dict(d_y=y.data_ptr(), d_cb=c[0].data_ptr(), d_cr=c[1].data_ptr(), y_stride=sw, c_stride=5, y_frame_stride=sw * sh,
                c_frame_stride=20, c_pixel_stride=1)
 
@@ -285,15 +305,24 @@ def test_refusals_leave_the_outputs_alone(ctx):
         return ctx.lib.evh_trail_fixed_plane_yuv420(a["ctx"], d, a["n"], a["sw"], a["sh"], a["M"], a["inv"], a["rect"], a["canvas"],
                                                     a["crs"], a["out"], a["ors"], a["ofs"], a["dw"], a["dh"], a["ox"], a["oy"])
 
-    assert call_yuv(None) == INVALID
-    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=sw - 1), dict(c_stride=4),
-                dict(y_frame_stride=sw * sh - 1), dict(c_frame_stride=19)):
-        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
-    for kw in (dict(M=None), dict(canvas=None), dict(dw=0), dict(crs=ors - 1), dict(ors=ors - 1), dict(out=cv),
-               dict(out=y.data_ptr()), dict(canvas=c[1].data_ptr() + 39), dict(out=c[0].data_ptr() - ofs - ors + 1)):
-        assert call_yuv(yuv, **kw) == INVALID, kw
-    for kw in (dict(sw=big), dict(n=65536), dict(dw=65536, dh=32768, crs=65536 * 3, ors=65536 * 3, ofs=1 << 40)):
-        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    refused(call_yuv(None), INVALID, who_yuv + NS, "no description")
+    CPS, PLANE = "chroma pixel stride must be 1 or 2", "frame stride smaller than a plane"
+    for bad, text in ((dict(d_y=None), NS), (dict(d_cb=None), NS), (dict(d_cr=None), NS), (dict(c_pixel_stride=3), CPS),
+                      (dict(y_stride=sw - 1), "luma row stride smaller than the width"),
+                      (dict(c_stride=4), "chroma row stride smaller than a chroma row"),
+                      (dict(y_frame_stride=sw * sh - 1), PLANE), (dict(c_frame_stride=19), PLANE)):
+        refused(call_yuv(dict(yuv, **bad)), INVALID, who_yuv + text, bad)
+    for kw, text in ((dict(M=None), NA), (dict(canvas=None), NA), (dict(dw=0), EM), (dict(crs=ors - 1), CS), (dict(ors=ors - 1), CS),
+                     (dict(out=cv), OC), (dict(out=y.data_ptr()), OF), (dict(canvas=c[1].data_ptr() + 39), CF),
+                     (dict(out=c[0].data_ptr() - ofs - ors + 1), OF), (dict(out=c[0].data_ptr()), OF)):       # the last: over the Cb plane
+        refused(call_yuv(yuv, **kw), INVALID, who_yuv + text, kw)
+    # two faults, one of them in the description: a NULL plane first, the strides before the planes, the planes before the overlaps
+    refused(call_yuv(dict(yuv, d_cb=None), M=None), INVALID, who_yuv + NS, "NULL plane before NULL argument")
+    refused(call_yuv(dict(yuv, y_stride=sw - 1), crs=ors - 1), INVALID, who_yuv + CS, "strides before the description")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), out=cv), INVALID, who_yuv + CPS, "the description before the overlaps")
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), n=65536), CAPACITY, who_yuv + NF, "capacity before the description")
+    for kw, text in ((dict(sw=big), BIG), (dict(n=65536), NF), (dict(dw=65536, dh=32768, crs=65536 * 3, ors=65536 * 3, ofs=1 << 40), AREA)):
+        refused(call_yuv(yuv, **kw), CAPACITY, who_yuv + text, kw)
     assert call_yuv(yuv, n=0) == 0
     ctx.synchronize()
     assert (out == SENTINEL).all() and (canvas == 7).all() and (y == 200).all() and (c == 128).all()

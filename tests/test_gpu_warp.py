@@ -280,20 +280,37 @@ def test_refusals_leave_the_output_alone(ctx):
                                             a["inv"], a["mode"], a["bg"], a["out"], a["dw"], a["dh"], a["ors"], a["ofs"],
                                             a["ox"], a["oy"])
 
-    invalid = [dict(ctx=None), dict(frames=None), dict(M=None), dict(out=None), dict(cn=2), dict(cn=0), dict(cn=4), dict(sw=0),
-               dict(sh=0), dict(dw=0), dict(dh=-1), dict(n=-1), dict(rs=sw * 3 - 1), dict(fs=sw * sh * 3 - 1), dict(ors=ors - 1),
-               dict(ofs=ofs - 1), dict(mode=1, ofs=ofs - 1), dict(mode=3), dict(mode=-1),
-               dict(bg=o), dict(mode=1, bg=o), dict(bg=o + ofs), dict(bg=o + ofs + ors), dict(bg=o - ors),      # overlaps
-               dict(mode=2, bg=o + 3), dict(mode=2, bg=o + ors), dict(mode=2, bg=o - ors)]                         # mosaic: only bg == out
-    for kw in invalid:
-        assert call(**kw) == INVALID, kw
-        assert kw == dict(ctx=None) or ctx.lib.evh_last_error_string(ctx.h)
+    who, who_yuv = "evh_warp_fixed_plane: ", "evh_warp_fixed_plane_yuv420: "
+    NS, NA, CH, EM, MODE = "NULL source", "NULL argument", "channels must be 1 or 3", "empty frame or canvas", "unknown mode"
+    BIG, AREA = "source sizes stay below 2^26 (positions are held in 1/32 pixels)", "dw * dh above INT_MAX"
+    NF, OS, SS = "at most 65535 frames per call", "output stride smaller than a row / canvas", "source stride smaller than a row / frame"
+    OV = "d_background overlaps d_out"
+
+    def refused(rc, code, text, what):
+        assert rc == code, what
+        assert ctx.lib.evh_last_error_string(ctx.h).decode() == text, what
+
+    assert call(ctx=None) == INVALID
+    invalid = [(dict(frames=None), NS), (dict(M=None), NA), (dict(out=None), NA), (dict(cn=2), CH), (dict(cn=0), CH), (dict(cn=4), CH),
+               (dict(sw=0), EM), (dict(sh=0), EM), (dict(dw=0), EM), (dict(dh=-1), EM), (dict(n=-1), EM), (dict(rs=sw * 3 - 1), SS),
+               (dict(fs=sw * sh * 3 - 1), SS), (dict(ors=ors - 1), OS), (dict(ofs=ofs - 1), OS), (dict(mode=1, ofs=ofs - 1), OS),
+               (dict(mode=3), MODE), (dict(mode=-1), MODE),
+               (dict(bg=o), OV), (dict(mode=1, bg=o), OV), (dict(bg=o + ofs), OV), (dict(bg=o + ofs + ors), OV), (dict(bg=o - ors), OV),    # overlaps
+               (dict(mode=2, bg=o + 3), OV), (dict(mode=2, bg=o + ors), OV), (dict(mode=2, bg=o - ors), OV),      # mosaic: only bg == out
+               # two faults: the earlier check of the entry names the refusal
+               (dict(frames=None, M=None), NS), (dict(M=None, cn=2), NA), (dict(cn=2, sw=0), CH), (dict(bg=o, ors=ors - 1), OS),
+               (dict(rs=sw * 3 - 1, bg=o), SS), (dict(mode=3, n=65536), MODE)]
+    for kw, text in invalid:
+        refused(call(**kw), INVALID, who + text, kw)
     big = 1 << 26
-    capacity = [dict(sw=big, rs=big * 3, fs=big * 3 * sh), dict(sh=big, fs=sw * 3 * big), dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40),
-                dict(n=65536)]
-    for kw in capacity:
-        assert call(**kw) == CAPACITY, kw
-    assert call(sw=big - 1, rs=(big - 1) * 3 - 1) == INVALID            # just below the limit the ordinary checks apply
+    capacity = [(dict(sw=big, rs=big * 3, fs=big * 3 * sh), BIG), (dict(sh=big, fs=sw * 3 * big), BIG),
+                (dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40), AREA), (dict(n=65536), NF),
+                # two faults: a capacity refusal precedes the strides and the overlap
+                (dict(sw=big, rs=big * 3 - 1, fs=big * 3 * sh), BIG), (dict(n=65536, ors=ors - 1), NF), (dict(sh=big, bg=o), BIG),
+                (dict(sw=big, dw=65536, dh=32768), BIG)]
+    for kw, text in capacity:
+        refused(call(**kw), CAPACITY, who + text, kw)
+    refused(call(sw=big - 1, rs=(big - 1) * 3 - 1), INVALID, who + SS, "below the limit")      # there the ordinary checks apply
     # the plane form: its own description, then the same checks
     y = torch.zeros((n, sh, sw), dtype=torch.uint8, device="cuda")
     c = torch.zeros((2, n, 9, 12), dtype=torch.uint8, device="cuda")
@@ -306,14 +323,24 @@ def test_refusals_leave_the_output_alone(ctx):
         return ctx.lib.evh_warp_fixed_plane_yuv420(a["ctx"], d, a["n"], a["sw"], a["sh"], a["M"], a["inv"], a["mode"], a["bg"],
                                                    a["out"], a["dw"], a["dh"], a["ors"], a["ofs"], a["ox"], a["oy"])
 
-    assert call_yuv(None) == INVALID
-    for bad in (dict(d_y=None), dict(d_cb=None), dict(d_cr=None), dict(c_pixel_stride=3), dict(y_stride=sw - 1), dict(c_stride=11),
-                dict(y_frame_stride=sw * sh - 1), dict(c_frame_stride=12 * 9 - 1)):
-        assert call_yuv(dict(yuv, **bad)) == INVALID, bad
-    for kw in (dict(M=None), dict(out=None), dict(dw=0), dict(mode=7), dict(ors=ors - 1), dict(bg=o)):
-        assert call_yuv(yuv, **kw) == INVALID, kw
-    for kw in (dict(sw=big), dict(n=65536), dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40)):
-        assert call_yuv(yuv, **kw) == CAPACITY, kw
+    refused(call_yuv(None), INVALID, who_yuv + NS, "no description")
+    PLANE = "frame stride smaller than a plane"
+    for bad, text in ((dict(d_y=None), NS), (dict(d_cb=None), NS), (dict(d_cr=None), NS),
+                      (dict(c_pixel_stride=3), "chroma pixel stride must be 1 or 2"),
+                      (dict(y_stride=sw - 1), "luma row stride smaller than the width"),
+                      (dict(c_stride=11), "chroma row stride smaller than a chroma row"),
+                      (dict(y_frame_stride=sw * sh - 1), PLANE), (dict(c_frame_stride=12 * 9 - 1), PLANE)):
+        refused(call_yuv(dict(yuv, **bad)), INVALID, who_yuv + text, bad)
+    # (the entry does not compare d_out with the planes, so there is no refusal of an output laid over one to pin)
+    for kw, text in ((dict(M=None), NA), (dict(out=None), NA), (dict(dw=0), EM), (dict(mode=7), MODE), (dict(ors=ors - 1), OS),
+                     (dict(bg=o), OV)):
+        refused(call_yuv(yuv, **kw), INVALID, who_yuv + text, kw)
+    # two faults, one of them in the description: the planes are examined last, a NULL plane first
+    refused(call_yuv(dict(yuv, c_pixel_stride=3), bg=o), INVALID, who_yuv + OV, "overlap before the description")
+    refused(call_yuv(dict(yuv, d_cb=None), M=None), INVALID, who_yuv + NS, "NULL plane before NULL argument")
+    refused(call_yuv(dict(yuv, y_stride=sw - 1), n=65536), CAPACITY, who_yuv + NF, "capacity before the description")
+    for kw, text in ((dict(sw=big), BIG), (dict(n=65536), NF), (dict(dw=65536, dh=32768, ors=65536 * 3, ofs=1 << 40), AREA)):
+        refused(call_yuv(yuv, **kw), CAPACITY, who_yuv + text, kw)
     # no frames: success, and nothing is done
     assert call(n=0) == 0 and call(n=0, mode=2, bg=o) == 0 and call_yuv(yuv, n=0) == 0
     ctx.synchronize()

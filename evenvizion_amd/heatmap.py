@@ -16,6 +16,7 @@ and are not done here.
 import numpy as np
 
 from . import runtime
+from .frames import DeviceLadder, FrameReader, check_ingest, entry_matrix
 from .processing.constants import HEATMAP_CONSTANT
 
 
@@ -51,27 +52,17 @@ def jet_lut():
     return (half + ((v2 & 1) & (half & 1))).astype(np.uint8)          # an odd v2 is a half: up only onto an even value
 
 
-def _matrix9(H):
-    """A frame's matrix as f64[9]; None or a wrong size gives NaN (index 0 at every pixel, as a non-finite matrix does)."""
-    if H is not None:
-        m = np.asarray(H, np.float64)
-        if m.size == 9:
-            return m.reshape(9)
-    return np.full(9, np.nan)
-
-
 def heatmap_frames(capture, superposition_homography_dict, resize_info, heatmap_constant=HEATMAP_CONSTANT, alpha=0.8, lut=None,
                    saturate=False, chunk_frames=32, ingest="auto"):
     """Generator of (frame_no, uint8 ndarray [h,w,3] BGR): the heat-map picture of every frame, coloured on the device.
 
     The i-th frame read from `capture` is paired with the i-th entry of the dictionary in the dictionary's order, as
-    heatmap_video_processing pairs them; it ends when either runs out.  Frames are read, uploaded, converted and resized as
-    stabilization.stabilized_frames does (4:2:0 planes where ingest allows, evh_yuv420_to_bgr, evh_resize_area_u8 to
+    heatmap_video_processing pairs them; it ends when either runs out.  Frames are read by frames.FrameReader and taken to the working size by
+    frames.DeviceLadder (4:2:0 planes where ingest allows, evh_yuv420_to_bgr, evh_resize_area_u8 to
     resize_info's w x h), chunk_frames at a time.  lut: u8[256,3] in BGR order, default jet_lut() (see there for what it is and
     is not).  saturate=False wraps the colour index as the reference's np.uint8 cast does; True holds it at 255.  An entry
     that is None or not finite gives colour index 0 everywhere: the frame plus alpha * lut[0]."""
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    check_ingest(ingest)
     if not (np.isfinite(heatmap_constant) and heatmap_constant > 0):
         raise ValueError("heatmap_constant must be finite and positive")
     if not (np.isfinite(alpha) and alpha >= 0):
@@ -84,49 +75,31 @@ def heatmap_frames(capture, superposition_homography_dict, resize_info, heatmap_
     w, h = int(resize_info["w"]), int(resize_info["h"])
     if w < 1 or h < 1:
         raise ValueError("resize_info must hold a positive w and h")
-    entries = [(k, _matrix9(v)) for k, v in superposition_homography_dict.items() if k != "resize_info"]
+    entries = [(k, entry_matrix(v).reshape(9)) for k, v in superposition_homography_dict.items() if k != "resize_info"]
     return _heatmap_frames(capture, entries, w, h, float(heatmap_constant), float(alpha), table, bool(saturate), int(chunk_frames),
                            ingest)
 
 
 def _heatmap_frames(capture, entries, w, h, heatmap_constant, alpha, table, saturate, chunk, ingest):
     import torch
-    from .processing.video_processing import _open_capture, _read_frame
     if not entries:
         return
-    first, planes, w0, h0 = _open_capture(capture, ingest)
-    if not planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
+    reader = FrameReader(capture, ingest)
+    first = reader.first
+    if not reader.planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
         raise ValueError("frames must be BGR [h,w,3] or gray [h,w]")
     ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
     dev = runtime.device()
     chunk = max(1, min(chunk, len(entries), runtime.STAGING_BYTES_PER_BUFFER // max(first.nbytes, 1)))      # the host chunk stays bounded
-    host = np.empty((chunk,) + first.shape, np.uint8)
     d_lut = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
-    resize = (w, h) != (w0, h0)
-    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes else None
-    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    ladder = DeviceLadder(dev, chunk, reader.planes, (reader.w0, reader.h0), (w, h), bgr=True, gray3=True)
     out = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev)
-    host[0] = first
-    done, n = 0, 1
-    while n:
-        while n < chunk and done + n < len(entries) and _read_frame(capture, planes, host[n], w0, h0, done + n + 1):
-            n += 1
-        src = torch.from_numpy(host[:n]).to(dev)
-        if planes:
-            ctx.yuv420_to_bgr(src, bgr[:n], size=(w0, h0))
-            src = bgr[:n]
-        elif src.dim() == 3:
-            src = src[..., None].expand(-1, -1, -1, 3).contiguous()          # gray frames: B = G = R
-        if resize:
-            ctx.resize_area(src, small[:n])
-            src = small[:n]
+    for done, frames in reader.chunks(chunk, 0, len(entries)):
+        n = len(frames)
+        _, src, _ = ladder(ctx, torch.from_numpy(frames).to(dev))
         mats = torch.from_numpy(np.stack([m for _, m in entries[done:done + n]])).to(dev)
         ctx.heatmap_render(mats, out[:n], d_lut, frames=src, heatmap_constant=heatmap_constant, alpha=alpha, saturate=saturate)
         ctx.order_torch_after()
         pictures = out[:n].cpu().numpy()
         for k in range(n):
             yield entries[done + k][0], pictures[k]
-        done += n
-        n = 0
-        if done < len(entries) and _read_frame(capture, planes, host[0], w0, h0, done + 1):
-            n = 1

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import runtime
 from ._lib import PAIR_CAPACITY, PAIR_OK
+from .frames import DeviceLadder, FrameReader, check_ingest
 from .processing.utils import superposition_dict
 from .processing.video_processing import CHUNK_FRAMES
 
@@ -29,10 +30,9 @@ def _arguments(homography_dict, plate, placement, scale, threshold, min_cover, r
     """The refusals of refine_homography_dict, before the capture is opened or the device touched
     -> (per-frame dictionary with int keys, resize_info)"""
     from .processing.video_processing import _feature_list
-    if placement not in ("warp", "translate"):
-        raise ValueError("placement must be 'warp' or 'translate'")
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    from .stabilization import check_placement
+    check_placement(placement)
+    check_ingest(ingest)
     if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or scale <= 0:
         raise ValueError("scale must be a finite positive number")
     if placement == "translate" and float(scale) != 1.0:
@@ -77,7 +77,7 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
     plate was built from them.  threshold, min_cover, radius, min_hits, min_keep: see Context.rows_moving_filter; the default
     min_cover = 2 judges a point only where at least two of the plate's frames met.
 
-    This is a plain synchronous chunk loop: every chunk is read, uploaded, solved and downloaded before the next is read.  The
+    The chunk loop (frames.FrameReader) is synchronous: every chunk is read, uploaded, solved and downloaded before the next is read.  The
     double-buffered pipeline of get_homography_dict is not built here.  A chunk in which a pair reports EVH_PAIR_CAPACITY (more
     tied key points than a frame slot holds) raises RuntimeError naming the frames: the re-run on larger slots of the first
     pass is not built either.  Only features_type_list=["ORB"] is taken (ValueError otherwise): evh_stream_scan solves the
@@ -88,12 +88,13 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
     rows_out) for the pair ending at frame_no: the rows that reached the filter, those it found moving, those handed to the
     solve (rows - moving, or rows when fewer than min_keep would have been left); (0, 0, 0) for a pair without rows."""
     import torch
-    from .processing.video_processing import _open_capture, _pairs_into, _read_frame, resized_shape
+    from .processing.video_processing import _pairs_into, resized_shape
     from .stabilization import MAX_PIXELS, _placement
     per_frame, resize_info = _arguments(homography_dict, plate, placement, scale, threshold, min_cover, radius, min_hits,
                                                   min_keep, nfeatures, chunk_frames, features_type_list, ingest)
     sup = superposition_dict(per_frame)
-    first, planes, w0, h0 = _open_capture(capture, ingest)
+    reader = FrameReader(capture, ingest)
+    first, planes, w0, h0 = reader.first, reader.planes, reader.w0, reader.h0
     if not planes and (first.ndim != 3 or first.shape[2] != 3):
         raise ValueError("frames must be BGR [h,w,3] or decoded planes: the plate is a BGR picture")
     w, h = int(resize_info["w"]), int(resize_info["h"])
@@ -110,29 +111,19 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
     plate_dev = torch.from_numpy(np.ascontiguousarray(plate.plate)).to(dev)
     count_dev = torch.from_numpy(np.ascontiguousarray(plate.count)).to(dev)
     translate = placement == "translate"
-    resize = translate and (w, h) != (w0, h0)
-    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and resize else None
-    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    ladder = DeviceLadder(dev, chunk, planes, (w0, h0), (w, h) if translate else None)
     row_scale = (1.0, 1.0) if translate else (w0 / w, h0 / h)
     H_dev = torch.zeros((chunk - 1, 9), dtype=torch.float64, device=dev)
     st_dev = torch.zeros(chunk - 1, dtype=torch.int32, device=dev)
     first_state = torch.zeros(18, dtype=torch.float64, device=dev)      # {H_sup, H_prev} of the first pass's solve, as it ran
     state = torch.zeros(18, dtype=torch.float64, device=dev)            # and of the refined one
-    host = np.empty((chunk,) + first.shape, np.uint8)
-    host[0] = first
     refined, stats = {}, {}
-    frame_no, n, have_state, more = 1, 1, False, True        # host[0] is frame `frame_no`, the newest frame already paired
+    have_state = False
     buffers = {}                                             # row capacity -> the filter's outputs
-    while more:
-        while n < chunk:
-            if not _read_frame(capture, planes, host[n], w0, h0, frame_no + n):
-                more = False
-                break
-            n += 1
-        if n < 2:
-            break
+    for start, frames in reader.chunks(chunk, 1):            # consecutive chunks overlap by one frame
+        frame_no, n = start + 1, len(frames)                 # frames[0] is frame `frame_no`, the newest frame already paired
         npairs = n - 1
-        src = torch.from_numpy(host[:n]).to(dev)
+        src = torch.from_numpy(frames).to(dev)
         getattr(ctx, method)(src, *size, H_dev, st_dev, state_in=first_state if have_state else None,
                              state_out=first_state, nfeatures=nfeatures, resize_to=(w, h))
         rows, counts, st1 = ctx.batch_static_rows(0, npairs)
@@ -141,13 +132,7 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
             buffers[cap] = (torch.empty((chunk - 1, cap, 4), dtype=torch.float32, device=dev),
                             torch.empty(chunk - 1, dtype=torch.int32, device=dev), torch.empty(chunk - 1, dtype=torch.int32, device=dev))
         out_rows, out_counts, moving = (t[:npairs] for t in buffers[cap])
-        judged, judged_size = src, (w0, h0) if planes else None
-        if resize:
-            if planes:
-                ctx.yuv420_to_bgr(src, bgr[:n], size=(w0, h0))
-                judged, judged_size = bgr[:n], None
-            ctx.resize_area(judged, small[:n])
-            judged = small[:n]
+        _, judged, judged_size = ladder(ctx, src)
         mats = torch.from_numpy(np.stack([matrix_of(k) for k in range(frame_no, frame_no + n)])).to(dev)
         ctx.rows_moving_filter(judged, mats, plate_dev, count_dev, (ox, oy), rows, counts, st1, out_rows, out_counts, moving,
                                threshold=int(threshold), min_cover=int(min_cover), radius=int(radius), min_hits=int(min_hits),
@@ -162,8 +147,6 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
         for k in range(npairs):
             ok = st1_h[k] == PAIR_OK and n_in[k] > 0
             stats[frame_no + 1 + k] = (int(n_in[k]), int(mov[k]), int(n_out[k])) if ok else (0, 0, 0)
-        frame_no = _pairs_into(refined, frame_no, Hs.cpu().numpy().reshape(-1, 3, 3), sts_h, none_H_processing)
-        host[0] = host[n - 1]                               # consecutive chunks overlap by one frame
-        n = 1
+        _pairs_into(refined, frame_no, Hs.cpu().numpy().reshape(-1, 3, 3), sts_h, none_H_processing)
     refined["resize_info"] = {"h": h, "w": w}
     return refined, stats

@@ -19,6 +19,7 @@ import numpy as np
 
 from .. import runtime
 from .._lib import PAIR_OK, PAIR_CAPACITY, EvhError
+from ..frames import DeviceLadder, check_ingest, open_capture, read_frame
 
 CHUNK_FRAMES = 64   # frames uploaded per GPU call (pairs per call = CHUNK_FRAMES - 1)
 
@@ -30,33 +31,6 @@ def resized_shape(frame_shape, resize_width):
     return int(resize_width), int(h0 * r)
 
 
-def _first_planes(capture, ingest):
-    """The first frame of `capture` as packed I420 bytes, or None when the frames are to be read as BGR.  Planes are taken
-    when the capture offers read_yuv420_into(y, cb, cr), declares the conversion the device implements (bgr_mode ==
-    BGR_SWSCALE_X86) and its first plane read succeeds -- a capture refuses, by raising capture.CaptureError, BEFORE it consumes a frame (libevcap: odd crop
-    offset), so the BGR path then starts from the same first frame.  -> (packed uint8 array or None, w, h)."""
-    from ..capture import BGR_SWSCALE_X86, CaptureError
-    from .._lib import yuv420_size, yuv420_views
-    able = callable(getattr(capture, "read_yuv420_into", None)) and getattr(capture, "bgr_mode", None) == BGR_SWSCALE_X86
-    if ingest == "bgr" or not able:
-        if ingest == "yuv420":
-            raise ValueError("ingest='yuv420': the capture does not deliver 4:2:0 planes in the swscale-x86 conversion")
-        return None, 0, 0
-    w, h = int(capture.width), int(capture.height)
-    packed = np.empty((1, yuv420_size(w, h)[0]), np.uint8)
-    y, cb, cr = yuv420_views(packed, w, h)
-    try:
-        ok = capture.read_yuv420_into(y[0], cb[0], cr[0])
-    except CaptureError as e:               # the capture's refusal: nothing was consumed; anything else is a bug and propagates
-        if ingest == "yuv420":
-            raise ValueError("ingest='yuv420': the capture refused to deliver planes (%s)" % e)
-        logging.info("capture refused 4:2:0 planes (%s): reading BGR frames", e)
-        return None, 0, 0
-    if not ok:
-        raise ValueError("Problem with video! Can't read first frame")
-    return packed[0], w, h
-
-
 def _feature_list(features_type_list):
     """-> the feature list a driver runs with (None: the reference's default); ValueError as the reference raises it."""
     from .frame_processing import DEFAULT_FEATURES
@@ -65,37 +39,6 @@ def _feature_list(features_type_list):
         if name not in ("ORB", "SIFT", "SURF"):
             raise ValueError("You need to choose descriptors type")
     return features
-
-
-def _open_capture(capture, ingest):
-    """The first frame of `capture`: planes where _first_planes takes them, else read().
-    -> (first frame: packed I420 bytes or a BGR array, planes?, w0, h0)"""
-    first, w0, h0 = _first_planes(capture, ingest)
-    if first is not None:
-        return first, True, w0, h0
-    success, first = capture.read()
-    if not success:
-        raise ValueError("Problem with video! Can't read first frame")
-    first = np.ascontiguousarray(first, np.uint8)
-    h0, w0 = first.shape[:2]
-    return first, False, w0, h0
-
-
-def _read_frame(capture, planes, slot, w0, h0, number):
-    """The capture's next frame (its `number`, 1-based, for the error) into `slot`, a frame of the pinned staging buffer: the
-    one host copy.  -> False when the capture has no further frame."""
-    if planes:
-        from .._lib import yuv420_views
-        y, cb, cr = yuv420_views(slot[None], w0, h0)
-        return bool(capture.read_yuv420_into(y[0], cb[0], cr[0]))
-    ok, frame = capture.read()
-    if not ok:
-        return False
-    frame = np.asarray(frame, np.uint8)
-    if frame.shape != slot.shape:
-        raise ValueError("frame %d has shape %s, the first frame %s" % (number, frame.shape, slot.shape))
-    slot[...] = frame
-    return True
 
 
 def _upload(B, j, spans, cur):
@@ -201,10 +144,9 @@ class _MatchingPictures:
         from .._lib import DRAW_POINTS
         if points not in DRAW_POINTS:
             raise ValueError("matching_points must be one of %s" % sorted(DRAW_POINTS))
-        self.points, self.planes, self.size, self.dev = points, planes, (w0, h0), dev
+        self.points, self.dev = points, dev
         npairs = chunk_frames - 1
-        self.bgr = torch.empty((chunk_frames, h0, w0, 3), dtype=torch.uint8, device=dev) if planes else None
-        self.small = torch.empty((chunk_frames, dh, dw, 3), dtype=torch.uint8, device=dev) if (dw, dh) != (w0, h0) else None
+        self.ladder = DeviceLadder(dev, chunk_frames, planes, (w0, h0), (dw, dh), bgr=True)
         # the picture and front-status buffers live with the staging set B (runtime.staging: pinning is slow, a service
         # processes many videos of one size) and go when it goes
         key = ("pictures", dw, dh)
@@ -222,13 +164,7 @@ class _MatchingPictures:
         pic_dev[j], their front statuses into st1_dev[j].  -> what _results_to_host brings back besides H and status."""
         import torch
         nb = frames.shape[0]
-        src = frames
-        if self.planes:
-            c.yuv420_to_bgr(src, self.bgr[:nb], size=self.size)
-            src = self.bgr[:nb]
-        if self.small is not None:
-            c.resize_area(src, self.small[:nb])
-            src = self.small[:nb]
+        _, src, _ = self.ladder(c, frames)
         cap = c.batch_static_info()[1]
         if cap not in self.rows:
             self.rows[cap] = (torch.empty((self.pic_dev[0].shape[0], cap, 4), dtype=torch.float32, device=self.dev),
@@ -244,7 +180,7 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
                         matching_sink=None, matching_points="reference"):
     """capture: anything with read() -> (bool, BGR uint8 frame) (cv2.VideoCapture duck type).
     ingest: "bgr" (always read(); the default until the plane path's end-to-end rates have been measured against it, see
-    DESIGN.md 3a), "auto" (planes when the capture can deliver them, see _first_planes), "yuv420" (planes or ValueError).
+    DESIGN.md 3a), "auto" (planes when the capture can deliver them, see frames.first_planes), "yuv420" (planes or ValueError).
     features_type_list: the list the reference hands to FrameProcessing (frame_processing.py:37-40), e.g. ["SIFT", "ORB"];
     None = frame_processing.DEFAULT_FEATURES = the reference's own default ["SURF", "SIFT", "ORB"]; the north-star hot path
     is features_type_list=["ORB"] (one fused ORB pipeline, evh_stream_homography_batch_resized).
@@ -261,9 +197,8 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
         raise NotImplementedError("matching_path (draw_matches + imwrite into a directory) is not taken: pass "
                                   "matching_sink=callable(frame_no, picture) -- matching_pictures.write_png stores a picture; "
                                   "the command line has --matching_pictures")
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
-    first, planes, w0, h0 = _open_capture(capture, ingest)
+    check_ingest(ingest)
+    first, planes, w0, h0 = open_capture(capture, ingest)
     if matching_sink is not None and not planes and first.ndim != 3:
         raise ValueError("matching_sink takes BGR frames [h,w,3] or decoded planes: the picture is a BGR picture, and the "
                          "reference's capture delivers no gray frames")
@@ -353,7 +288,7 @@ def get_homography_dict(capture, resize_width=400, matching_path=None, none_H_pr
     try:
         while True:
             while n < chunk_frames and not exhausted:
-                if not _read_frame(capture, planes, host_np[j][n], w0, h0, frame_no[0] + n):
+                if not read_frame(capture, planes, host_np[j][n], w0, h0, frame_no[0] + n):
                     exhausted = True
                     break
                 n += 1
@@ -405,7 +340,7 @@ def _read_frames(st, region):
     n = 1
     try:
         while n < len(region):
-            if not _read_frame(st.capture, st.planes, region[n], st.w0, st.h0, st.read + 1):
+            if not read_frame(st.capture, st.planes, region[n], st.w0, st.h0, st.read + 1):
                 st.exhausted = True
                 break
             st.read += 1
@@ -429,7 +364,7 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
     capture that ended gives its place to the next waiting one.  Frames are read by `decode_threads` host threads, one
     capture per task, straight into the pinned staging buffer (libevcap releases the GIL); the reads of round r + 1 overlap
     the GPU work of round r, and one GPU round is in flight.  Captures are grouped by the geometry of their frames and by
-    whether they deliver planes (the rule of _first_planes, per capture); the groups run one after another.  A capture is
+    whether they deliver planes (the rule of frames.first_planes, per capture); the groups run one after another.  A capture is
     opened -- its first frame read, which decides its group -- only when a place is free for it, so what is held scales with
     max_streams, not with the list; one that turns out to belong to another group waits, opened, for that group's turn.
 
@@ -440,8 +375,7 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from types import SimpleNamespace
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    check_ingest(ingest)
     features = _feature_list(features_type_list)
     captures = list(captures)
     results = [None] * len(captures)
@@ -471,7 +405,7 @@ def get_homography_dicts(captures, resize_width=400, none_H_processing=True, nfe
             if i > stop_after[0]:
                 continue
             try:
-                first, planes, w0, h0 = _open_capture(capture, ingest)
+                first, planes, w0, h0 = open_capture(capture, ingest)
             except Exception as e:
                 fail(i, e)
                 continue

@@ -15,17 +15,9 @@ import math
 import numpy as np
 
 from . import runtime
+from .frames import DeviceLadder, FrameReader, check_ingest, entry_matrix
 
 STAT_NAMES = ("covered", "sad", "ssd", "sad_unregistered", "ssd_unregistered", "moving")
-
-
-def _matrix33(S):
-    """A dictionary entry as f64[3,3]; None or a wrong size gives NaN."""
-    if S is not None:
-        m = np.asarray(S, np.float64)
-        if m.size == 9:
-            return m.reshape(3, 3)
-    return np.full((3, 3), np.nan)
 
 
 def _pair_map(S_prev, S_cur):
@@ -52,7 +44,7 @@ def pair_maps(superposition_homography_dict):
     S_k takes frame k's pixels to the fixed plane, so the pixel-to-pixel map of a pair is S_{k-1}^-1 . S_k.  On the reference's
     test_video.mp4 with its recorded dictionary (frames subsampled to 400x224), the registered sum of squared differences lies
     below the unregistered one on 120 of 120 pairs with M_k, on 56 of 120 with H_k itself and on 2 of 120 with H_k^-1."""
-    entries = [(k, _matrix33(v)) for k, v in superposition_homography_dict.items() if k != "resize_info"]
+    entries = [(k, entry_matrix(v)) for k, v in superposition_homography_dict.items() if k != "resize_info"]
     return {k1: _pair_map(S0, S1) for (_, S0), (k1, S1) in zip(entries, entries[1:])}
 
 
@@ -92,8 +84,7 @@ def report_from_stats(stats_by_frame):
 def _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, kind):
     """The refusals of both drivers, before the capture is opened or the device touched -> (entries, maps, w, h, threshold, chunk)"""
     from ._lib import RESIDUAL_KINDS
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    check_ingest(ingest)
     if kind not in RESIDUAL_KINDS:
         raise ValueError("kind must be 'abs' or 'mask'")
     if isinstance(threshold, bool) or int(threshold) != threshold or not 0 <= int(threshold) <= 255:
@@ -109,44 +100,24 @@ def _arguments(superposition_homography_dict, resize_info, threshold, chunk_fram
 
 def _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, kind, pictures):
     """Generator of (frame_no, six ints, picture or None) per pair.  The i-th frame read from `capture` goes with the i-th entry
-    of the dictionary; frames are read, uploaded, converted and resized as heatmap._heatmap_frames does, `chunk` at a time, and a
-    chunk's last frame is kept as the next chunk's first, so that every pair of consecutive frames lies inside one chunk."""
+    of the dictionary; frames are read `chunk` at a time (frames.FrameReader) and taken to w x h as the heat-map pictures' are
+    (frames.DeviceLadder); a chunk's last frame is the next chunk's first, so that every pair of consecutive frames lies inside one chunk."""
     import torch
-    from .processing.video_processing import _open_capture, _read_frame
     if len(keys) < 2:
         return
-    first, planes, w0, h0 = _open_capture(capture, ingest)
-    if not planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
+    reader = FrameReader(capture, ingest)
+    first = reader.first
+    if not reader.planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
         raise ValueError("frames must be BGR [h,w,3] or gray [h,w]")
     ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
     dev = runtime.device()
     chunk = max(2, min(chunk, len(keys), runtime.STAGING_BYTES_PER_BUFFER // max(first.nbytes, 1)))      # the host chunk stays bounded
-    host = np.empty((chunk,) + first.shape, np.uint8)
-    resize = (w, h) != (w0, h0)
-    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes else None
-    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
+    ladder = DeviceLadder(dev, chunk, reader.planes, (reader.w0, reader.h0), (w, h), bgr=True, gray3=True)
     stats = torch.empty((chunk - 1, 6), dtype=torch.int64, device=dev)
     out = torch.empty((chunk - 1, h, w), dtype=torch.uint8, device=dev) if pictures else None
-    host[0] = first
-    done, n, more = 0, 1, True                     # host[0] is frame `done` of the dictionary's order
-    while more:
-        while n < chunk and done + n < len(keys):
-            if not _read_frame(capture, planes, host[n], w0, h0, done + n + 1):
-                more = False
-                break
-            n += 1
-        more = more and done + n < len(keys)
-        if n < 2:
-            break
-        src = torch.from_numpy(host[:n]).to(dev)
-        if planes:
-            ctx.yuv420_to_bgr(src, bgr[:n], size=(w0, h0))
-            src = bgr[:n]
-        elif src.dim() == 3:
-            src = src[..., None].expand(-1, -1, -1, 3).contiguous()          # gray frames: B = G = R
-        if resize:
-            ctx.resize_area(src, small[:n])
-            src = small[:n]
+    for done, frames in reader.chunks(chunk, 1, len(keys)):        # frames[0] is frame `done` of the dictionary's order
+        n = len(frames)
+        _, src, _ = ladder(ctx, torch.from_numpy(frames).to(dev))
         nos = keys[done + 1:done + n]
         mats = torch.from_numpy(np.stack([maps[k] for k in nos]).reshape(n - 1, 9)).to(dev)
         ctx.pair_residual(src, mats, stats=stats[:n - 1], out=out[:n - 1] if pictures else None, threshold=threshold, kind=kind)
@@ -155,9 +126,6 @@ def _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, kind, pictur
         pics = out[:n - 1].cpu().numpy() if pictures else None
         for k, no in enumerate(nos):
             yield no, tuple(int(v) for v in sums[k]), (pics[k] if pictures else None)
-        host[0] = host[n - 1]
-        done += n - 1
-        n = 1
 
 
 def registration_report(capture, superposition_homography_dict, resize_info, threshold=16, chunk_frames=32, ingest="auto"):

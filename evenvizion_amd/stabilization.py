@@ -26,6 +26,7 @@ import numpy as np
 
 from . import runtime
 from ._lib import PLATE_MAX_FRAMES, WARP_MODES, WARP_MOSAIC
+from .frames import DeviceLadder, FrameReader, check_ingest, entry_matrix
 
 MAX_PIXELS = 1 << 26          # canvas pixels fixed_plane_bounds accepts by default (201 MB of BGR)
 CHUNK_BYTES = 512 << 20       # cap of the canvases of one "each" / "history" chunk on the device
@@ -37,10 +38,8 @@ def _frames_of(superposition_homography_dict):
 
 def _matrix(H):
     """A frame's matrix as f64[3,3], or None when it has none or it is not finite."""
-    if H is None:
-        return None
-    m = np.asarray(H, np.float64)
-    return m.reshape(3, 3) if m.size == 9 and np.all(np.isfinite(m)) else None
+    m = entry_matrix(H)
+    return m if np.all(np.isfinite(m)) else None
 
 
 def get_reference_system(superposition_homography_dict):
@@ -95,10 +94,16 @@ def fixed_plane_bounds(superposition_homography_dict, resize_info, scale=1.0, ma
     return ox, oy, dw, dh
 
 
+def check_placement(placement):
+    if placement not in ("warp", "translate"):
+        raise ValueError("placement must be 'warp' or 'translate'")
+
+
 def _placement(superposition_homography_dict, resize_info, placement, scale, frame_w, frame_h, max_pixels):
     """-> (ox, oy, dw, dh, matrix_of(frame_no) -> f64[9], NaN for a frame that leaves the canvas alone)"""
     w, h = int(resize_info["w"]), int(resize_info["h"])
     nan = np.full(9, np.nan)
+    check_placement(placement)
     if placement == "translate":
         if float(scale) != 1.0:
             raise ValueError("placement='translate' is the reference's paste: scale must be 1")
@@ -112,7 +117,7 @@ def _placement(superposition_homography_dict, resize_info, placement, scale, fra
                 return nan
             dx, dy = translate_offset(m)
             return np.array([1, 0, dx, 0, 1, dy, 0, 0, 1], np.float64)
-    elif placement == "warp":
+    else:
         ox, oy, dw, dh = fixed_plane_bounds(superposition_homography_dict, resize_info, scale, max_pixels)
         S = np.diag([float(scale), float(scale), 1.0])
         K = np.diag([w / frame_w, h / frame_h, 1.0])          # from_original_to_fix: original pixels -> resized pixels
@@ -120,8 +125,6 @@ def _placement(superposition_homography_dict, resize_info, placement, scale, fra
         def matrix_of(frame_no):
             m = _matrix(superposition_homography_dict.get(frame_no))
             return nan if m is None else np.dot(np.dot(S, m), K).reshape(9)
-    else:
-        raise ValueError("placement must be 'warp' or 'translate'")
     if dw * dh > int(max_pixels):
         raise ValueError("the canvas is %d x %d pixels, more than max_pixels = %d" % (dw, dh, int(max_pixels)))
     return ox, oy, dw, dh, matrix_of
@@ -148,13 +151,12 @@ def _chunks(capture, superposition_homography_dict, resize_info, mode, placement
     (number of the chunk's first frame, n, the canvases of the chunk on the device or None for "mosaic", the chunk's
     full-size BGR frames on the device when `originals`, the carried canvas).  What it yields is valid until the next step."""
     import torch
-    from .processing.video_processing import _open_capture, _read_frame
     if mode not in WARP_MODES:
         raise ValueError("mode must be 'each', 'history' or 'mosaic'")
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
+    check_ingest(ingest)
     outline = _check_trail(mode, placement, trail, border)
-    first, planes, w0, h0 = _open_capture(capture, ingest)
+    reader = FrameReader(capture, ingest)
+    w0, h0 = reader.w0, reader.h0
     ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
     w, h = int(resize_info["w"]), int(resize_info["h"])
     ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
@@ -163,31 +165,14 @@ def _chunks(capture, superposition_homography_dict, resize_info, mode, placement
     chunk = max(1, int(chunk_frames))
     if per_frame:
         chunk = max(1, min(chunk, CHUNK_BYTES // (dw * dh * 3)))
-    host = np.empty((chunk,) + first.shape, np.uint8)
     canvas = torch.zeros((dh, dw, 3), dtype=torch.uint8, device=dev)
     out = torch.empty((chunk, dh, dw, 3), dtype=torch.uint8, device=dev) if per_frame else None
-    resize = placement == "translate" and (w, h) != (w0, h0)
-    bgr = torch.empty((chunk, h0, w0, 3), dtype=torch.uint8, device=dev) if planes and (resize or originals) else None
-    small = torch.empty((chunk, h, w, 3), dtype=torch.uint8, device=dev) if resize else None
-    host[0] = first
-    n, frame_no, exhausted = 1, 0, False
-    while n:
-        while n < chunk and not exhausted:
-            if _read_frame(capture, planes, host[n], w0, h0, frame_no + n + 1):
-                n += 1
-            else:
-                exhausted = True
-        full = src = torch.from_numpy(host[:n]).to(dev)
+    ladder = DeviceLadder(dev, chunk, reader.planes, (w0, h0), (w, h) if placement == "translate" else None, bgr=originals)
+    for frame_no, frames in reader.chunks(chunk, 0):
+        n = len(frames)
+        full, src, size = ladder(ctx, torch.from_numpy(frames).to(dev))
         host_mats = np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])
         mats = torch.from_numpy(host_mats).to(dev)
-        size = (w0, h0) if planes else None
-        if bgr is not None:
-            ctx.yuv420_to_bgr(src, bgr[:n], size=size)
-            full = src = bgr[:n]
-            size = None
-        if resize:
-            ctx.resize_area(src, small[:n])
-            src = small[:n]
         if trail:
             if frame_no == 0 and placement == "translate":
                 # initialize_background (stabilization.py:245-249): frame 1 at (|min_x|, |min_y|), the plane's origin, undimmed
@@ -211,12 +196,6 @@ def _chunks(capture, superposition_homography_dict, resize_info, mode, placement
             ctx.warp_fixed_plane(src, mats, canvas, mode, (ox, oy), background=canvas, size=size)
             ctx.order_torch_after()
         yield frame_no + 1, n, (out[:n] if per_frame else None), (full if originals else None), canvas
-        frame_no += n
-        n = 0
-        if not exhausted and _read_frame(capture, planes, host[0], w0, h0, frame_no + 1):
-            n = 1
-        else:
-            exhausted = True
 
 
 def frame_outline(abs_min_x, abs_min_y, x_offset, y_offset, w, h):
@@ -327,51 +306,37 @@ def background_plate(capture, superposition_homography_dict, resize_info, placem
     nothing; frame_nos lists the frames that were kept (fewer when the capture ends early).  ValueError when frames, plate, count
     and masks together would take more than max_bytes on the device."""
     import torch
-    from .processing.video_processing import _open_capture, _read_frame
     if not 1 <= int(max_frames) <= PLATE_MAX_FRAMES:
         raise ValueError("max_frames must lie in 1..%d" % PLATE_MAX_FRAMES)
     if not 1 <= int(min_cover) <= 255:
         raise ValueError("min_cover must lie in 1..255")
     if not 0 <= int(threshold) <= 255:
         raise ValueError("threshold must lie in 0..255")
-    if placement not in ("warp", "translate"):
-        raise ValueError("placement must be 'warp' or 'translate'")
-    if ingest not in ("auto", "bgr", "yuv420"):
-        raise ValueError("ingest must be 'auto', 'bgr' or 'yuv420'")
-    first, planes, w0, h0 = _open_capture(capture, ingest)
+    check_placement(placement)
+    check_ingest(ingest)
+    reader = FrameReader(capture, ingest)
+    planes, w0, h0 = reader.planes, reader.w0, reader.h0
     ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
     w, h = int(resize_info["w"]), int(resize_info["h"])
     frame_nos = plate_frame_numbers(max(int(k) for k in _frames_of(superposition_homography_dict)), max_frames)
     n = len(frame_nos)
     resize = placement == "translate" and (w, h) != (w0, h0)
-    device_bytes = n * first.size + (n * h0 * w0 * 3 if planes and resize else 0) + (n * h * w * 3 if resize else 0) \
+    device_bytes = n * reader.first.size + (n * h0 * w0 * 3 if planes and resize else 0) + (n * h * w * 3 if resize else 0) \
         + dw * dh * (4 + (n if masks else 0))
     if device_bytes > int(max_bytes):
         raise ValueError("%d frames, plate, count and masks take %d bytes on the device, more than max_bytes = %d"
                          % (n, device_bytes, int(max_bytes)))
-    host = np.empty((n,) + first.shape, np.uint8)
-    host[0] = first
-    kept, number = 1, 1
-    while kept < n:                                # the capture read once; only the selected frames stay
-        number += 1
-        if not _read_frame(capture, planes, host[kept], w0, h0, number):
-            break
-        if number == frame_nos[kept]:
+    host = reader.buffer(n)
+    kept = 1
+    while kept < n and reader.read_into(host[kept]):       # the capture read once; only the selected frames stay
+        if reader.consumed == frame_nos[kept]:
             kept += 1
     n, frame_nos = kept, frame_nos[:kept]
     ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
     dev = runtime.device()
-    src = torch.from_numpy(host[:n]).to(dev)
     mats = torch.from_numpy(np.stack([matrix_of(k) for k in frame_nos])).to(dev)
-    size = (w0, h0) if planes else None
-    if resize:
-        if planes:
-            bgr = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=dev)
-            ctx.yuv420_to_bgr(src, bgr, size=size)
-            src, size = bgr, None
-        small = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-        ctx.resize_area(src, small)
-        src = small
+    ladder = DeviceLadder(dev, n, planes, (w0, h0), (w, h) if placement == "translate" else None)
+    _, src, size = ladder(ctx, torch.from_numpy(host[:n]).to(dev))
     plate = torch.empty((dh, dw, 3), dtype=torch.uint8, device=dev)
     count = torch.empty((dh, dw), dtype=torch.uint8, device=dev)
     pictures = torch.empty((n, dh, dw), dtype=torch.uint8, device=dev) if masks else None

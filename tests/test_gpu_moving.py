@@ -532,6 +532,43 @@ def test_refine_translate_placement(passes):
         moving.refine_homography_dict(capture.VideoCapture(MP4), first, plate, placement="warp", chunk_frames=16, ingest="bgr")
 
 
+class FirstFrames:
+    """The first n frames of the reference's video, as BGR frames or as planes."""
+
+    def __init__(self, n):
+        from evenvizion_amd import capture
+        self.cap, self.left = capture.VideoCapture(MP4), n
+        self.width, self.height, self.bgr_mode = self.cap.width, self.cap.height, self.cap.bgr_mode
+
+    def read(self):
+        self.left -= 1
+        return self.cap.read() if self.left >= 0 else (False, None)
+
+    def read_yuv420_into(self, y, cb, cr):
+        self.left -= 1
+        return self.left >= 0 and self.cap.read_yuv420_into(y, cb, cr)
+
+
+def test_refine_does_not_depend_on_the_chunks():
+    """12 frames in chunks of 2 (eleven chunks of one pair, every {H_sup, H_prev} carried) and in one chunk, from BGR frames and
+    from planes: the same dictionary and the same counts."""
+    from evenvizion_amd import moving
+    from evenvizion_amd import stabilization as S
+    from evenvizion_amd.processing.utils import superposition_dict
+    from evenvizion_amd.processing.video_processing import get_homography_dict
+    first = get_homography_dict(FirstFrames(12), resize_width=400, ingest="bgr", chunk_frames=16, features_type_list=["ORB"])
+    sup = superposition_dict({k: v for k, v in first.items() if k != "resize_info"})
+    plate = S.background_plate(FirstFrames(12), sup, first["resize_info"], placement="warp", max_frames=12, ingest="bgr")
+    assert plate.frame_nos == list(range(1, 13))
+    got = {(chunk, ingest): moving.refine_homography_dict(FirstFrames(12), first, plate, threshold=16, chunk_frames=chunk, ingest=ingest)
+           for chunk in (2, 16) for ingest in ("bgr", "auto")}
+    refined, stats = got[(16, "bgr")]
+    assert list(refined) == list(range(2, 13)) + ["resize_info"] and sorted(stats) == list(range(2, 13))
+    assert sum(s[0] for s in stats.values()) > 0
+    for key, (again, again_stats) in got.items():
+        assert again == refined and again_stats == stats, key
+
+
 def test_component_reject_moving_writes_its_files(tmp_path, monkeypatch):
     from evenvizion_amd import component
     monkeypatch.chdir(tmp_path)

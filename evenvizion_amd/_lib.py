@@ -28,6 +28,9 @@ DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
 RESIDUAL_ABS, RESIDUAL_MASK = 0, 1
 RESIDUAL_KINDS = {"abs": RESIDUAL_ABS, "mask": RESIDUAL_MASK}
 RES_COVERED, RES_SAD, RES_SSD, RES_SAD0, RES_SSD0, RES_MOVING, RES_NSTATS = range(7)
+REFINE_REFINED, REFINE_UNCHANGED, REFINE_NOTHING_COVERED, REFINE_TOO_FEW, REFINE_DEGENERATE = range(5)
+REFINE_INFO = ("status", "evals", "accepted", "covered_in", "ssd_in", "covered_out", "ssd_out", "n_in")
+REFINE_NINFO, REFINE_NSUMS, REFINE_MAX_ITERS, REFINE_MAX_SIZE = 8, 45, 64, 4096
 
 # every symbol include/evhip.h declares, with its ctypes signature
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -128,6 +131,8 @@ SIGNATURES = {
     # the score of a homography: the motion-compensated residual of a pair
     "evh_pair_residual": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i, _i64, _i64]),
     "evh_pair_residual_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i64, _i64]),
+    "evh_pair_refine": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    "evh_pair_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -836,6 +841,47 @@ class Context:
         """pair_residual on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel and tap converted as
         yuv420_to_bgr converts it (evh_pair_residual_yuv420)."""
         return self._pair_residual(True, planes, mats, stats, out, threshold, kind, frame_step, size)
+
+    # ---- direct alignment ----
+    def _pair_refine(self, planes, frames, mats, iters, clip, out, info, normal, frame_step, size):
+        import torch
+        self._enter()
+        frame_step = int(frame_step)
+        if frame_step not in (1, 2):
+            raise ValueError("frame_step must be 1 or 2")
+        planes, head, n, w, h, _ = self._frame_source(frames, size, planes=planes)
+        npairs = mats.numel() // 9
+        self._dev_tensor(mats, torch.float64, 9 * npairs, "mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        if npairs and n < (npairs - 1) * frame_step + 2:
+            raise ValueError("frames holds fewer frames than the pairs take")
+        dev = "cuda:%d" % self.device
+        if out is None:
+            out = torch.empty((npairs, 9), dtype=torch.float64, device=dev)
+        if info is None:
+            info = torch.empty((npairs, REFINE_NINFO), dtype=torch.int64, device=dev)
+        self._dev_tensor(out, torch.float64, 9 * npairs, "out must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        self._dev_tensor(info, torch.int64, (npairs, REFINE_NINFO), "info must be a contiguous CUDA int64 tensor [npairs,%d]", REFINE_NINFO)
+        if normal is not None:
+            self._dev_tensor(normal, torch.float64, (npairs, REFINE_NSUMS), "normal must be a contiguous CUDA float64 tensor [npairs,%d]",
+                             REFINE_NSUMS)
+        if npairs == 0:                      # empty tensors have no address to hand over
+            return out, info
+        tail = (mats.data_ptr(), int(iters), int(clip), out.data_ptr(), info.data_ptr(), _ptr(normal))
+        self._check(self._form("evh_pair_refine", planes)(self.h, head[0], npairs, frame_step, w, h, *head[4:], *tail))
+        return out, info
+
+    def pair_refine(self, frames, mats, iters=8, clip=255, out=None, info=None, normal=None, frame_step=1):
+        """Direct alignment of pairs of frames (evh_pair_refine, the method is stated in include/evhip.h): each matrix improved
+        by damped Gauss-Newton steps on the photometric residual, never made worse.  frames, mats and frame_step as in
+        pair_residual.  out: CUDA float64 npairs*9 contiguous (it may be `mats`) or None = a new tensor; info: CUDA int64
+        [npairs,8] contiguous (REFINE_INFO names the columns) or None; both are returned.  normal: CUDA float64 [npairs,45] or
+        None: the normal sums at `mats`.  Does not synchronise."""
+        return self._pair_refine(False, frames, mats, iters, clip, out, info, normal, frame_step, None)
+
+    def pair_refine_yuv420(self, planes, mats, iters=8, clip=255, out=None, info=None, normal=None, frame_step=1, size=None):
+        """pair_refine on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel and tap converted as
+        yuv420_to_bgr converts it (evh_pair_refine_yuv420)."""
+        return self._pair_refine(True, planes, mats, iters, clip, out, info, normal, frame_step, size)
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

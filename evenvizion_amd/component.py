@@ -140,6 +140,13 @@ def parser():
     ap.add_argument("--moving_min_cover", type=_int_in(1, 255), default=2,
                     help="--reject_moving: frames of the plate that must cover a canvas pixel for it to be judged")
     ap.add_argument("--plate_frames", type=_int_in(1, 255), default=64, help="--reject_moving: frames the plate is taken over")
+    ap.add_argument("--refine_direct", type=int, choices=(0, 1), default=0,
+                    help="1: direct alignment of every pair on the pixels, starting from the dictionary's matrices (extension; "
+                         "--path_to_video only): registration.refined_homography_dict; writes "
+                         "dict_with_homography_matrix_direct.json and direct_report.json beside the first dictionary, which "
+                         "stays as it is (the video is read three times more)")
+    ap.add_argument("--refine_levels", type=_int_in(1, 4), default=1, help="--refine_direct: pyramid levels, coarse to fine")
+    ap.add_argument("--refine_iters", type=_int_in(0, 64), default=8, help="--refine_direct: steps tried per level")
     return ap
 
 
@@ -158,6 +165,8 @@ def main(argv=None):
             raise ValueError("--matching_pictures takes one video (--path_to_video)")
         if args.reject_moving:
             raise ValueError("--reject_moving takes one video (--path_to_video)")
+        if args.refine_direct:
+            raise ValueError("--refine_direct takes one video (--path_to_video)")
         opened = [open_capture(spec) for spec in args.path_to_videos]
         kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
         results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
@@ -184,7 +193,25 @@ def main(argv=None):
     save_folder = write_outputs(args, result, original_shape, stem, args.path_to_video)
     if args.reject_moving:
         write_refined(args, save_folder, features)
+    if args.refine_direct:
+        write_direct(args, save_folder)
     return save_folder
+
+
+def write_direct(args, save_folder):
+    """--refine_direct 1: the first pass's matrices refined on the pixels, the refined dictionary and the score of both beside the
+    first pass's files, which are left as they are.  The capture is opened again for each pass."""
+    from .processing.utils import read_homography_dict, superposition_dict
+    from . import registration
+    spec = args.path_to_video
+    first_pass, resize_info = read_homography_dict(os.path.join(save_folder, "dict_with_homography_matrix.json"))
+    got = registration.refined_homography_dict(lambda: open_capture(spec)[0], superposition_dict(first_pass), resize_info,
+                                               iters=args.refine_iters, levels=args.refine_levels, ingest=args.ingest)
+    with open(os.path.join(save_folder, "dict_with_homography_matrix_direct.json"), "w") as json_:
+        json.dump(dict(got["homography"], resize_info=resize_info), json_)
+    with open(os.path.join(save_folder, "direct_report.json"), "w") as json_:
+        json.dump({"before": got["report_before"], "after": got["report_after"],
+                   "info": {str(k): v for k, v in got["info"].items()}}, json_)
 
 
 def write_refined(args, save_folder, features):

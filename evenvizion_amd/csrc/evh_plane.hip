@@ -1,6 +1,6 @@
 // evh_plane.hip -- the products on the fixed plane and the pictures drawn from a batch's results: evh_warp_fixed_plane,
-// evh_pair_residual, evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded 4:2:0 planes),
-// evh_heatmap_render and evh_draw_matches.  Kernels first, then the host side: what the entries share (checks, launch
+// evh_pair_residual, evh_pair_refine, evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded
+// 4:2:0 planes), evh_heatmap_render and evh_draw_matches.  Kernels first, then the host side: what the entries share (checks, launch
 // plumbing), then per product its arguments, check() -- every refusal comes before anything is enqueued -- and launch().
 #include "evh_devmath.h"
 #include "evh_internal.h"
@@ -214,6 +214,223 @@ __global__ __launch_bounds__(256) void k_pair_residual(SRC src, int frame_step, 
   if (threadIdx.x < EVH_RES_NSTATS) {
     const uint32_t sum = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
     if (sum) atomicAdd(&stats[(int64_t)pair * EVH_RES_NSTATS + threadIdx.x], (unsigned long long)sum);
+  }
+}
+
+// Direct alignment of a pair (include/evhip.h states the contract for evh_pair_refine): k_pair_refine_eval evaluates one matrix
+// per pair -- the cost and the 45 normal sums -- and k_pair_refine_step, launched behind it, adds the workgroups' partial sums,
+// judges the trial and forms the next one.  Per pair the state below lives in the context's workspace, followed by the partial
+// sums: REFINE_SLOTS doubles per workgroup, [0..44] the normal sums, [45] and [46] covered and ssd as 64-bit integers.
+// The evaluation: grid.y = pair, grid.x = REFINE_GROUPS(w, h) workgroups whose threads stride over the runs of WARP_RUN pixels,
+// run t of thread (g, i) being i + 256 * g, then + 256 * groups: the assignment depends on w and h only.  A thread keeps the 45
+// sums in registers over all of its runs (pixels in ascending order), the wave adds them by __shfl_xor (every lane forms the same
+// commutative tree), the four waves go through LDS and are added in wave order.  Nothing is accumulated by atomics.
+#define REFINE_SLOTS 48
+struct RefineState {
+  double M[9], Mtry[9], N[EVH_REFINE_NSUMS], lambda;
+  unsigned long long cov, ssd, cov_in, ssd_in, n_in;
+  int done, stop, evals, accepted;
+};
+// (the row by value: taken by reference, the packed instances of every other kernel of the unit compile differently)
+template <int CN, class ROW> __device__ __forceinline__ int gray_at(const ROW r, int x) {
+  int v[3] = {0, 0, 0};
+  r.px(x, v);
+  return gray_px<CN>(v);
+}
+template <int CN, class SRC>
+__global__ __launch_bounds__(256) void k_pair_refine_eval(SRC src, int frame_step, int w, int h, const double* __restrict__ M_in,
+                                                          const RefineState* __restrict__ state, double* __restrict__ part,
+                                                          int clip, int runs_per_row, unsigned nruns) {
+  __shared__ double wsum[4][REFINE_SLOTS];
+  const int pair = blockIdx.y;
+  if (!M_in && state[pair].done) return;                  // the whole workgroup: nobody waits at the barrier below
+  const double* M = M_in ? M_in + 9 * (int64_t)pair : state[pair].Mtry;
+  const WarpMap A = warp_map(M, 1);
+  const int prev = pair * frame_step, cur = prev + 1;
+  double acc[EVH_REFINE_NSUMS];
+#pragma unroll
+  for (int k = 0; k < EVH_REFINE_NSUMS; k++) acc[k] = 0.0;
+  unsigned long long cov = 0, ssd = 0;
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < nruns; t += gridDim.x * 256u) {
+    const RunPos rp = run_pos(t, runs_per_row, w);
+    const int y = rp.y, x0 = rp.x0, n = rp.n;
+    const typename SRC::Row rc = src.row(cur, y);
+    const bool yin = y >= 1 && y <= h - 2;
+    const double Y = (double)y, Yc = (double)(2 * y - (h - 1));
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      int s[3] = {0, 0, 0};
+      const int x = x0 + p;
+      if (p >= n || !warp_sample(src, prev, A, (double)x, Y, w, h, s)) continue;
+      const int r = gray_at<CN>(rc, x) - gray_px<CN>(s);
+      cov += 1; ssd += (unsigned)(r * r);
+      if (!yin || x < 1 || x > w - 2 || abs(r) > clip) continue;
+      const int gxi = gray_at<CN>(rc, x + 1) - gray_at<CN>(rc, x - 1);
+      const int gyi = gray_at<CN>(src.row(cur, y + 1), x) - gray_at<CN>(src.row(cur, y - 1), x);
+      const double gx = (double)gxi, gy = (double)gyi, Xc = (double)(2 * x - (w - 1)), rd = (double)r;
+      const double sxy = gx * Xc + gy * Yc;                 // integers below 2^53: every operation here is exact
+      const double J[8] = {gx * Xc, gx * Yc, gx, gy * Xc, gy * Yc, gy, -Xc * sxy, -Yc * sxy};
+      int k = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int j = i; j < 8; j++) acc[k++] += J[i] * J[j];
+#pragma unroll
+      for (int i = 0; i < 8; i++) acc[36 + i] += J[i] * rd;
+      acc[44] += 1.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < EVH_REFINE_NSUMS; k++)
+    for (int m = 32; m > 0; m >>= 1) acc[k] += __shfl_xor(acc[k], m);
+  for (int m = 32; m > 0; m >>= 1) { cov += __shfl_xor(cov, m); ssd += __shfl_xor(ssd, m); }
+  if ((threadIdx.x & 63) == 0) {
+    double* o = wsum[threadIdx.x >> 6];
+#pragma unroll
+    for (int k = 0; k < EVH_REFINE_NSUMS; k++) o[k] = acc[k];
+    o[45] = __longlong_as_double((long long)cov); o[46] = __longlong_as_double((long long)ssd);
+  }
+  __syncthreads();
+  if (threadIdx.x < REFINE_SLOTS - 1) {
+    const int k = threadIdx.x;
+    double* o = part + ((int64_t)pair * gridDim.x + blockIdx.x) * REFINE_SLOTS + k;
+    if (k < EVH_REFINE_NSUMS) {
+      *o = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    } else {
+      unsigned long long u = 0;
+      for (int v = 0; v < 4; v++) u += (unsigned long long)__double_as_longlong(wsum[v][k]);
+      *o = __longlong_as_double((long long)u);
+    }
+  }
+}
+// A < B for the costs (ssd, covered): ssd_a * cov_b < ssd_b * cov_a in 128 bits
+__device__ __forceinline__ bool refine_better(unsigned long long ssd_a, unsigned long long cov_a, unsigned long long ssd_b,
+                                              unsigned long long cov_b) {
+  const unsigned long long lh = __umul64hi(ssd_a, cov_b), ll = ssd_a * cov_b, rh = __umul64hi(ssd_b, cov_a), rl = ssd_b * cov_a;
+  return lh < rh || (lh == rh && ll < rl);
+}
+__device__ __forceinline__ bool refine_finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }      // NaN fails
+// The step from the sums N and lambda, onto Mtry -> 0, or the reason the pair stops.  One thread; the 8x8 system sits in LDS
+// (`a`, 64 doubles, and `y`, 8), where it may be indexed at run time.
+__device__ int refine_step(const double* N, double lambda, const double* M, int w, int h, double* a, double* y, double* Mtry) {
+  if (N[44] < (double)EVH_REFINE_MIN_PIXELS) return EVH_REFINE_TOO_FEW;
+  double d[8];
+  int k = 0;
+  for (int i = 0; i < 8; i++)
+    for (int j = i; j < 8; j++, k++) {
+      a[8 * i + j] = a[8 * j + i] = N[k];
+      if (i == j) d[i] = __builtin_sqrt(N[k]);
+    }
+  for (int i = 0; i < 8; i++) if (!(d[i] > 0.0)) return EVH_REFINE_DEGENERATE;
+  for (int i = 0; i < 8; i++) {
+    for (int j = 0; j < 8; j++) a[8 * i + j] = a[8 * i + j] / (d[i] * d[j]) + (i == j ? lambda : 0.0);
+    y[i] = N[36 + i] / d[i];
+  }
+  // LDL': the lower triangle of a becomes L (unit diagonal) below D
+  for (int j = 0; j < 8; j++) {
+    double dj = a[8 * j + j];
+    for (int q = 0; q < j; q++) dj -= a[8 * j + q] * a[8 * j + q] * a[8 * q + q];
+    a[8 * j + j] = dj;
+    for (int i = j + 1; i < 8; i++) {
+      double v = a[8 * i + j];
+      for (int q = 0; q < j; q++) v -= a[8 * i + q] * a[8 * j + q] * a[8 * q + q];
+      a[8 * i + j] = v / dj;
+    }
+  }
+  for (int i = 0; i < 8; i++) for (int q = 0; q < i; q++) y[i] -= a[8 * i + q] * y[q];
+  for (int i = 0; i < 8; i++) y[i] /= a[8 * i + i];
+  for (int i = 7; i >= 0; i--) for (int q = i + 1; q < 8; q++) y[i] -= a[8 * q + i] * y[q];
+  double D[8];
+  for (int i = 0; i < 8; i++) {
+    D[i] = -4.0 * y[i] / d[i];
+    if (!refine_finite(D[i])) return EVH_REFINE_DEGENERATE;
+  }
+  // Q = (C^-1 P) C, left to right
+  const double cx = (double)(w - 1), cy = (double)(h - 1);
+  const double P[9] = {1.0 + D[0], D[1], D[2], D[3], 1.0 + D[4], D[5], D[6], D[7], 1.0};
+  double T[9], Q[9];
+  for (int j = 0; j < 3; j++) {
+    T[j] = 0.5 * P[j] + (cx / 2.0) * P[6 + j];
+    T[3 + j] = 0.5 * P[3 + j] + (cy / 2.0) * P[6 + j];
+    T[6 + j] = P[6 + j];
+  }
+  for (int i = 0; i < 3; i++) {
+    Q[3 * i] = 2.0 * T[3 * i];
+    Q[3 * i + 1] = 2.0 * T[3 * i + 1];
+    Q[3 * i + 2] = (T[3 * i + 2] - T[3 * i] * cx) - T[3 * i + 1] * cy;
+  }
+  const WarpMap R = warp_map(Q, 0);
+  double O[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) O[3 * i + j] = (M[3 * i] * R.a[j] + M[3 * i + 1] * R.a[3 + j]) + M[3 * i + 2] * R.a[6 + j];
+  for (int i = 0; i < 9; i++) {
+    Mtry[i] = O[i] / O[8];
+    if (!refine_finite(Mtry[i])) return EVH_REFINE_DEGENERATE;
+  }
+  return 0;
+}
+// Launch k of the solving kernel (k = 0: behind the evaluation at M_in; last: behind the final one), one workgroup of 64 threads
+// per pair: thread j adds slot j of the pair's `groups` partial sums in index order, thread 0 then judges and steps.
+__global__ __launch_bounds__(64) void k_pair_refine_step(RefineState* __restrict__ state, const double* __restrict__ part, int groups,
+                                                         int first, int last, int w, int h, const double* M_in, double* M_out,
+                                                         unsigned long long* __restrict__ info, double* __restrict__ normal) {
+  __shared__ double S[REFINE_SLOTS], a[64], y[8];
+  const int pair = blockIdx.x, j = threadIdx.x;
+  RefineState& st = state[pair];
+  const bool active = first || !st.done;                  // the same for the whole workgroup
+  if (active && j < REFINE_SLOTS - 1) {
+    const double* p = part + (int64_t)pair * groups * REFINE_SLOTS + j;
+    if (j < EVH_REFINE_NSUMS) {
+      double v = 0.0;
+      for (int g = 0; g < groups; g++) v += p[(int64_t)g * REFINE_SLOTS];
+      S[j] = v;
+    } else {
+      unsigned long long u = 0;
+      for (int g = 0; g < groups; g++) u += (unsigned long long)__double_as_longlong(p[(int64_t)g * REFINE_SLOTS]);
+      S[j] = __longlong_as_double((long long)u);
+    }
+  }
+  __syncthreads();
+  if (j != 0) return;
+  if (active) {
+    const unsigned long long cov = (unsigned long long)__double_as_longlong(S[45]), ssd = (unsigned long long)__double_as_longlong(S[46]);
+    bool take = false;
+    if (first) {
+      for (int i = 0; i < 9; i++) st.M[i] = M_in[9 * (int64_t)pair + i];
+      st.lambda = 1e-3; st.done = 0; st.stop = 0; st.evals = 1; st.accepted = 0;
+      st.cov_in = cov; st.ssd_in = ssd; st.n_in = (unsigned long long)S[44];
+      if (normal) for (int i = 0; i < EVH_REFINE_NSUMS; i++) normal[(int64_t)pair * EVH_REFINE_NSUMS + i] = S[i];
+      take = true;
+      if (cov == 0) { st.done = 1; st.stop = EVH_REFINE_NOTHING_COVERED; }
+    } else {
+      st.evals += 1;
+      take = cov > 0 && 10 * cov >= 9 * st.cov_in && refine_better(ssd, cov, st.ssd, st.cov);
+      if (take) {
+        for (int i = 0; i < 9; i++) st.M[i] = st.Mtry[i];
+        st.lambda = fmax(st.lambda / 10.0, 1e-9);
+        st.accepted += 1;
+      } else {
+        st.lambda = 10.0 * st.lambda;
+      }
+    }
+    if (take) {
+      st.cov = cov; st.ssd = ssd;
+      for (int i = 0; i < EVH_REFINE_NSUMS; i++) st.N[i] = S[i];
+    }
+    if (!st.done && !last) {
+      const int stop = refine_step(st.N, st.lambda, st.M, w, h, a, y, st.Mtry);
+      if (stop) { st.done = 1; st.stop = stop; }
+    }
+  }
+  if (last) {
+    const unsigned long long* in = reinterpret_cast<const unsigned long long*>(M_in) + 9 * (int64_t)pair;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(M_out) + 9 * (int64_t)pair;
+    for (int i = 0; i < 9; i++) out[i] = st.accepted ? (unsigned long long)__double_as_longlong(st.M[i]) : in[i];
+    unsigned long long* o = info + (int64_t)pair * EVH_REFINE_NINFO;
+    o[EVH_REFINE_STATUS] = st.accepted ? EVH_REFINE_REFINED : st.stop ? st.stop : EVH_REFINE_UNCHANGED;
+    o[EVH_REFINE_EVALS] = st.evals; o[EVH_REFINE_ACCEPTED] = st.accepted;
+    o[EVH_REFINE_COVERED_IN] = st.cov_in; o[EVH_REFINE_SSD_IN] = st.ssd_in;
+    o[EVH_REFINE_COVERED_OUT] = st.cov; o[EVH_REFINE_SSD_OUT] = st.ssd; o[EVH_REFINE_N_IN] = st.n_in;
   }
 }
 
@@ -843,6 +1060,65 @@ int launch(evh_ctx* c, const ResidualArgs& A) {
   return launched(c);
 }
 
+// ---- direct alignment: a pair's matrix refined on the pixels ------------------------------------------------------------------------
+struct RefineArgs {
+  const char* who; EvhFrames F; int npairs, frame_step, w, h; const double* M_in; int iters, clip; double* M_out; uint64_t* info;
+  double* normal;
+  bool idle() const { return npairs == 0; }
+};
+int check(evh_ctx* c, const RefineArgs& A) {
+  const std::string W = std::string(A.who) + ": ";
+  if (int rc = need_source(c, W, A.F)) return rc;
+  if (!A.M_in || !A.M_out || !A.info) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (int rc = need_channels(c, W, A.F)) return rc;
+  if (A.frame_step != 1 && A.frame_step != 2) return evh_fail(c, EVH_ERR_INVALID, W + "frame_step must be 1 or 2");
+  if (A.npairs < 0 || A.w < 1 || A.h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or negative npairs");
+  if (A.iters < 0 || A.iters > EVH_REFINE_MAX_ITERS) return evh_fail(c, EVH_ERR_INVALID, W + "iters must lie in 0..64");
+  if (A.clip < 0 || A.clip > 255) return evh_fail(c, EVH_ERR_INVALID, W + "clip must lie in 0..255");
+  // the Jacobian's entries are exact in double up to here; this also keeps w, h below 2^26 and w * h below INT_MAX
+  if (A.w > EVH_REFINE_MAX_SIZE || A.h > EVH_REFINE_MAX_SIZE) return evh_fail(c, EVH_ERR_CAPACITY, W + "w and h stay within 4096");
+  if (A.npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
+  if (int rc = need_source_stride(c, W, A.F, A.w, A.h, true)) return rc;      // a pair takes two frames
+  if (A.npairs == 0) return EVH_SUCCESS;
+  const int64_t nframes = (int64_t)(A.npairs - 1) * A.frame_step + 2;
+  if (A.F.yuv && nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  if (int rc = need_planes(c, A.who, A.F, nframes, A.w, A.h)) return rc;
+  // the outputs apart from each other, from the frames and from d_M_in, which d_M_out may only BE
+  const int64_t np = A.npairs;
+  const Span outs[3] = {{A.M_out, np * 72, "d_M_out"}, {A.info, np * EVH_REFINE_NINFO * 8, "d_info"},
+                        {A.normal, np * EVH_REFINE_NSUMS * 8, "d_normal"}};
+  Span src[3];
+  source_spans(A.F, nframes, A.w, A.h, src);
+  if (int rc = need_apart(c, W, outs, src)) return rc;
+  const Span in{A.M_in, np * 72, "d_M_in"};
+  for (int i = A.M_out == A.M_in ? 1 : 0; i < 3; i++)
+    if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps d_M_in");
+  return EVH_SUCCESS;
+}
+// workgroups per pair: one per 1024 runs, at most 64 -- a function of w and h only (it fixes the order of summation)
+int refine_groups(const Runs& R) { return (int)std::min(64u, std::max(1u, (R.n + 1023u) / 1024u)); }
+// iters + 1 times k_pair_refine_eval and k_pair_refine_step, the first evaluation at d_M_in, the others at the state's trial
+int launch(evh_ctx* c, const RefineArgs& A) {
+  const Runs R = runs_of(A.w, A.h);
+  const int groups = refine_groups(R);
+  const size_t state_bytes = ((size_t)A.npairs * sizeof(RefineState) + 255) & ~(size_t)255;
+  if (int rc = grow(c, &c->d_refine_ws, &c->refine_ws_bytes, state_bytes + (size_t)A.npairs * groups * REFINE_SLOTS * sizeof(double)))
+    return rc;
+  RefineState* state = reinterpret_cast<RefineState*>(c->d_refine_ws);
+  double* part = reinterpret_cast<double*>(c->d_refine_ws + state_bytes);
+  int rc = EVH_SUCCESS;
+  with_source(A.F, [&](auto cn, const auto& S) {
+    for (int k = 0; k <= A.iters && rc == EVH_SUCCESS; k++) {
+      hipLaunchKernelGGL((k_pair_refine_eval<decltype(cn)::value, std::decay_t<decltype(S)>>), dim3(groups, A.npairs), dim3(256), 0,
+                         c->stream, S, A.frame_step, A.w, A.h, k == 0 ? A.M_in : nullptr, state, part, A.clip, R.per_row, R.n);
+      hipLaunchKernelGGL(k_pair_refine_step, dim3(A.npairs), dim3(64), 0, c->stream, state, part, groups, k == 0, k == A.iters, A.w,
+                         A.h, A.M_in, A.M_out, reinterpret_cast<unsigned long long*>(A.info), A.normal);
+      rc = launched(c);
+    }
+  });
+  return rc;
+}
+
 // ---- the trail: the fixed plane with earlier frames dimmed and the frame outlined (stabilization.py:21-97, 129-172) ----------
 struct TrailArgs {
   const char* who; EvhFrames F; int nframes, sw, sh; const double* M; int inverse_map; const int32_t* rect; uint8_t* canvas;
@@ -1046,6 +1322,19 @@ int evh_pair_residual_yuv420(evh_ctx* c, const evh_yuv420* src, int npairs, int 
                              int64_t out_frame_stride) {
   return run(c, ResidualArgs{"evh_pair_residual_yuv420", yuv420_frames(src), npairs, frame_step, w, h, d_M, threshold, d_stats,
                              d_out, kind, out_row_stride, out_frame_stride});
+}
+
+int evh_pair_refine(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int channels, int64_t row_stride,
+                    int64_t frame_stride, const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info,
+                    double* d_normal) {
+  return run(c, RefineArgs{"evh_pair_refine", packed_frames(d_frames, channels, row_stride, frame_stride), npairs, frame_step, w, h,
+                           d_M_in, iters, clip, d_M_out, d_info, d_normal});
+}
+
+int evh_pair_refine_yuv420(evh_ctx* c, const evh_yuv420* src, int npairs, int frame_step, int w, int h, const double* d_M_in,
+                           int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal) {
+  return run(c, RefineArgs{"evh_pair_refine_yuv420", yuv420_frames(src), npairs, frame_step, w, h, d_M_in, iters, clip, d_M_out,
+                           d_info, d_normal});
 }
 
 int evh_trail_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int64_t row_stride,

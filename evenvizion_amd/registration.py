@@ -146,3 +146,153 @@ def residual_frames(capture, superposition_homography_dict, resize_info, thresho
     gray, "mask": 255 where it exceeds threshold (the moving objects), 0 elsewhere and where the pair is not covered."""
     keys, maps, w, h, threshold, chunk = _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, kind)
     return ((no, pic) for no, _, pic in _residuals(capture, keys, maps, w, h, threshold, chunk, ingest, kind, True))
+
+
+# ---- direct alignment: the matrices refined on the pixels ----------------------------------------------------------------------------
+def _whole(value, lo, hi, name):
+    if isinstance(value, bool) or int(value) != value or not lo <= int(value) <= hi:
+        raise ValueError("%s must be an integer in %d..%d" % (name, lo, hi))
+    return int(value)
+
+
+def _refine_arguments(superposition_homography_dict, resize_info, iters, levels, clip, fill_missing, chunk_frames, ingest):
+    """The refusals of refine_pair_maps, before the capture is opened or the device touched"""
+    from ._lib import REFINE_MAX_ITERS, REFINE_MAX_SIZE
+    check_ingest(ingest)
+    iters, levels, clip = _whole(iters, 0, REFINE_MAX_ITERS, "iters"), _whole(levels, 1, 4, "levels"), _whole(clip, 0, 255, "clip")
+    if not isinstance(fill_missing, (bool, np.bool_)):
+        raise ValueError("fill_missing must be True or False")
+    if isinstance(chunk_frames, bool) or int(chunk_frames) != chunk_frames or int(chunk_frames) < 1:
+        raise ValueError("chunk_frames must be an integer of at least 1")
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    if not (1 <= w <= REFINE_MAX_SIZE and 1 <= h <= REFINE_MAX_SIZE):
+        raise ValueError("resize_info must hold a w and h in 1..%d" % REFINE_MAX_SIZE)
+    keys = [k for k in superposition_homography_dict if k != "resize_info"]
+    return keys, pair_maps(superposition_homography_dict), w, h, iters, levels, clip, bool(fill_missing), max(2, int(chunk_frames))
+
+
+def level_map(w, h, lw, lh):
+    """S: pixel of a level of lw x lh -> pixel of the full frame of w x h (pixel centres: f x + (f - 1) / 2, f the true ratio)"""
+    fx, fy = w / lw, h / lh
+    return np.array([[fx, 0, (fx - 1) / 2], [0, fy, (fy - 1) / 2], [0, 0, 1]], np.float64)
+
+
+def _refine_chunk(ctx, pyramid, mats, iters, clip):
+    """pyramid: the chunk's frames coarse to fine, [(frames [n,lh,lw,3], S)], the last being the full size with S = I; mats
+    f64[npairs,3,3] on the host -> (mats refined, info rows int64[npairs,8] of the full size, accepted int64[npairs,levels]).
+    A level hands a map on only where it accepted a step: the bytes of an untouched map survive the way down and up."""
+    import torch
+    from ._lib import REFINE_INFO
+    dev, mats = pyramid[0][0].device, np.array(mats, np.float64).reshape(-1, 3, 3)
+    accepted = np.zeros((len(mats), len(pyramid)), np.int64)
+    for l, (frames, S) in enumerate(pyramid):
+        with np.errstate(all="ignore"):
+            start = np.stack([np.linalg.solve(S, np.dot(M, S)) if np.isfinite(M).all() else M for M in mats]) if S is not None else mats
+        out, info = ctx.pair_refine(frames, torch.from_numpy(start.reshape(-1, 9).copy()).to(dev), iters=iters, clip=clip)
+        ctx.order_torch_after()
+        out, info = out.cpu().numpy().reshape(-1, 3, 3), info.cpu().numpy()
+        accepted[:, l] = info[:, REFINE_INFO.index("accepted")]
+        for p in np.nonzero(accepted[:, l])[0]:
+            T = out[p] if S is None else np.dot(np.dot(S, out[p]), np.linalg.inv(S))
+            mats[p] = T / T[2, 2]
+    return mats, info, accepted
+
+
+def refine_pair_maps(capture, superposition_homography_dict, resize_info, iters=8, levels=1, clip=255, fill_missing=False,
+                     chunk_frames=32, ingest="auto"):
+    """pair_maps' matrices refined on the pixels of the video (evh_pair_refine: damped Gauss-Newton steps on the photometric
+    residual; a matrix is only ever replaced by one that scores better).  Frames are read and laid out as registration_report
+    does.  levels (1..4): coarse to fine, level l on the chunk's frames downsized by 2^l with the area resize, the map taken
+    there and back with level_map's S (M_l = S^-1 M S); iters steps per level; clip: pixels whose residual exceeds it stay out
+    of the normal equations (255: none).  fill_missing: a pair whose map is NaN (matching failed) starts from the previous
+    pair's refined map, the first pair from the identity -- the reference repeats the previous H there -- and keeps what it
+    reaches if that registers anything; without it such a pair stays NaN.
+    -> ({frame_no: f64[3,3] M'}, {frame_no: {status, evals, accepted, covered_in, ssd_in, covered_out, ssd_out, n_in (the
+    full-size level's row of d_info), accepted_by_level (coarse to fine), filled}})."""
+    import torch
+    from ._lib import REFINE_INFO
+    keys, maps, w, h, iters, levels, clip, fill_missing, chunk = _refine_arguments(
+        superposition_homography_dict, resize_info, iters, levels, clip, fill_missing, chunk_frames, ingest)
+    refined, infos = {}, {}
+    if len(keys) < 2:
+        return refined, infos
+    reader = FrameReader(capture, ingest)
+    first = reader.first
+    if not reader.planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
+        raise ValueError("frames must be BGR [h,w,3] or gray [h,w]")
+    ctx = runtime.get_context(64, 64)
+    dev = runtime.device()
+    chunk = max(2, min(chunk, len(keys), runtime.STAGING_BYTES_PER_BUFFER // max(first.nbytes, 1)))
+    ladder = DeviceLadder(dev, chunk, reader.planes, (reader.w0, reader.h0), (w, h), bgr=True, gray3=True)
+    sizes = [(max(1, w >> l), max(1, h >> l)) for l in range(levels - 1, 0, -1)]
+    small = [torch.empty((chunk, lh, lw, 3), dtype=torch.uint8, device=dev) for lw, lh in sizes]
+    last = np.eye(3)                                           # what a missing pair starts from
+    for done, frames in reader.chunks(chunk, 1, len(keys)):
+        n = len(frames)
+        _, src, _ = ladder(ctx, torch.from_numpy(frames).to(dev))
+        src = src.contiguous()
+        pyramid = []
+        for buf, (lw, lh) in zip(small, sizes):
+            ctx.resize_area(src, buf[:n])
+            pyramid.append((buf[:n], level_map(w, h, lw, lh)))
+        pyramid.append((src, None))
+        nos = keys[done + 1:done + n]
+        mats, info, accepted = _refine_chunk(ctx, pyramid, np.stack([maps[k] for k in nos]), iters, clip)
+        for p, no in enumerate(nos):
+            filled = False
+            if fill_missing and not np.isfinite(maps[no]).all():
+                one = [(f[p:p + 2], S) for f, S in pyramid]
+                m1, i1, a1 = _refine_chunk(ctx, one, last[None], iters, clip)
+                if i1[0, REFINE_INFO.index("covered_out")] > 0:
+                    mats[p], info[p], accepted[p], filled = m1[0], i1[0], a1[0], True
+            if np.isfinite(mats[p]).all():
+                last = mats[p]
+            refined[no] = mats[p].copy()
+            infos[no] = dict(zip(REFINE_INFO, (int(v) for v in info[p])), accepted_by_level=[int(v) for v in accepted[p]], filled=filled)
+    return refined, infos
+
+
+def compose_refined(superposition_homography_dict, refined_maps):
+    """The refined maps recomposed into the reference's two dictionaries, float64 on the host: S'_first = the first entry's S
+    (the identity in the reference's dictionaries), S'_k = S'_{k-1} . M'_k / [2][2], H'_k = S'_k . S'_{k-1}^-1 / [2][2]; a
+    pair whose map is not finite gets H = None and keeps the running S', as the reference's superposition does.
+    -> ({frame_no: {"H": 3x3 list or None}}, {frame_no: S' f64[3,3]})"""
+    keys = [k for k in superposition_homography_dict if k != "resize_info"]
+    hd, sup = {}, {}
+    if not keys:
+        return hd, sup
+    S = entry_matrix(superposition_homography_dict[keys[0]])
+    S = S if np.isfinite(S).all() else np.eye(3)
+    sup[keys[0]] = S
+    for no in keys[1:]:
+        M = refined_maps.get(no)
+        H = None
+        if M is not None and np.isfinite(M).all():
+            T = np.dot(S, np.asarray(M, np.float64).reshape(3, 3))
+            T = T / T[2, 2]
+            with np.errstate(all="ignore"):
+                H = np.dot(T, np.linalg.inv(S))
+                H = H / H[2, 2]
+            if np.isfinite(T).all() and np.isfinite(H).all():
+                S = T
+            else:
+                H = None
+        hd[no] = {"H": None if H is None else H.tolist()}
+        sup[no] = S
+    return hd, sup
+
+
+def refined_homography_dict(capture_factory, superposition_homography_dict, resize_info, iters=8, levels=1, clip=255,
+                            fill_missing=False, threshold=16, chunk_frames=32, ingest="auto"):
+    """refine_pair_maps, its maps recomposed (compose_refined) into a dictionary in the reference's format, and the score of
+    both.  capture_factory() opens the video; it is called three times (the refinement and the two reports read it once each).
+    -> {"homography": {frame_no: {"H": ...}}, "superposition": {frame_no: S'}, "info": refine_pair_maps' rows,
+        "report_before": registration_report of the dictionary handed in, "report_after": of the refined one}"""
+    _refine_arguments(superposition_homography_dict, resize_info, iters, levels, clip, fill_missing, chunk_frames, ingest)
+    _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, "abs")
+    maps, info = refine_pair_maps(capture_factory(), superposition_homography_dict, resize_info, iters, levels, clip, fill_missing,
+                                  chunk_frames, ingest)
+    hd, sup = compose_refined(superposition_homography_dict, maps)
+    before = registration_report(capture_factory(), superposition_homography_dict, resize_info, threshold, chunk_frames, ingest)
+    after = registration_report(capture_factory(), sup, resize_info, threshold, chunk_frames, ingest)
+    return {"homography": hd, "superposition": sup, "info": info, "report_before": before, "report_after": after}

@@ -760,6 +760,60 @@ int evh_pair_residual_yuv420(evh_ctx* ctx, const evh_yuv420* src, int npairs, in
                              const double* d_M, int threshold, uint64_t* d_stats,
                              uint8_t* d_out, int kind, int64_t out_row_stride, int64_t out_frame_stride);
 
+/* ---- direct alignment: a pair's matrix refined on the pixels ---------------------------------------------------------------------- */
+/* evh_pair_residual judges a matrix; this entry improves it: inverse-compositional Gauss-Newton with Levenberg damping on the
+ * photometric residual, starting from d_M_in.  Frames, npairs, frame_step, w, h, channels and strides are evh_pair_residual's;
+ * d_M_in f64[npairs,9] (DEVICE) maps pixels of the current frame to pixels of the previous frame.  tests/refine_checks.py restates
+ * all of the following in numpy and is the definition where this text is unclear.
+ * COST of a matrix M: (covered, ssd) = evh_pair_residual's [EVH_RES_COVERED] and [EVH_RES_SSD] for M -- the same coverage, byte
+ *   samples and gray weights, exact integers.  A is BETTER than B iff ssd_A * covered_B < ssd_B * covered_A, compared exactly (the
+ *   products reach 2^78: 128 bits).
+ * NORMAL EQUATIONS at M, over the pixels (x, y) that are covered, interior (1 <= x <= w-2, 1 <= y <= h-2) and have |r| <= clip:
+ *   r = g_cur - g_reg (signed), gx = g_cur(x+1, y) - g_cur(x-1, y), gy = g_cur(x, y+1) - g_cur(x, y-1) (gray values of the current
+ *   frame), X = 2x - (w-1), Y = 2y - (h-1), s = gx*X + gy*Y, J = (gx*X, gx*Y, gx, gy*X, gy*Y, gy, -X*s, -Y*s): exact integers
+ *   below 2^53 for w, h <= 4096.  Each entry is converted to double; each product J_i*J_j (i <= j) and J_i*r is ONE rounded double
+ *   multiplication, accumulated in double.  The EVH_REFINE_NSUMS = 45 sums: [0..35] the upper triangle of J'J row by row ((0,0),
+ *   (0,1) .. (0,7), (1,1) .. (7,7)), [36..43] J'r, [44] the number of pixels n.  The order of summation is fixed by the launch
+ *   geometry (which depends on w and h only): a fixed assignment of pixels to threads, a fixed tree inside a workgroup, the
+ *   workgroups' partial sums added in index order.  No floating-point atomics: the same call twice gives the same bytes.
+ * STEP from the sums (A = J'J, b = J'r) and the damping lambda: d_i = sqrt(A_ii), Ah = A_ij / (d_i d_j) + lambda * I,
+ *   bh = b_i / d_i, Ah y = bh solved by an 8x8 LDL' in double, Delta_i = -4 y_i / d_i (4: doubled coordinates and doubled
+ *   differences).  P = I + [[D0, D1, D2], [D3, D4, D5], [D6, D7, 0]], C = [[2, 0, -(w-1)], [0, 2, -(h-1)], [0, 0, 1]],
+ *   Q = C^-1 P C (C^-1 = [[.5, 0, (w-1)/2], [0, .5, (h-1)/2], [0, 0, 1]], the two products left to right), M_try = M * adj(Q)
+ *   divided by its [2][2] (adj: the adjugate as evh_warp_fixed_plane forms it; the determinant goes with the normalisation).
+ * LOOP: lambda = 1e-3; the first evaluation is at M_in; evaluation k = 1 .. iters is at M_try and is ACCEPTED iff
+ *   covered_try > 0, 10 * covered_try >= 9 * covered_in and it is better than the current matrix: then M, its cost and its sums
+ *   become the trial's and lambda = max(lambda / 10, 1e-9); else lambda = 10 * lambda.  A pair STOPS, and later launches skip
+ *   it, when M_in covers nothing (a NaN, zero, singular-with-tw-0 or otherwise non-finite matrix covers nothing), when n < 64 at
+ *   the current matrix, when a d_i is 0, when Delta or M_try is not finite.
+ * d_M_out f64[npairs,9]: the last accepted matrix; without an accepted step the nine input doubles byte for byte, NaNs
+ *   included.  d_M_out may BE d_M_in (any other overlap is refused).
+ * d_info u64[npairs,EVH_REFINE_NINFO]: [EVH_REFINE_STATUS] EVH_REFINE_REFINED when a step was accepted, else the reason the pair
+ *   stopped (NOTHING_COVERED, TOO_FEW: n < 64, DEGENERATE: a zero d_i or a non-finite step), else EVH_REFINE_UNCHANGED;
+ *   [EVALS] evaluations made, [ACCEPTED] steps accepted, [COVERED_IN], [SSD_IN] the cost of M_in, [COVERED_OUT], [SSD_OUT] the cost of
+ *   d_M_out, [N_IN] n at M_in.
+ * d_normal f64[npairs,45] (may be NULL): the sums at M_in (zeros for a pair that covers nothing).
+ * Launches: iters + 1 evaluations (grid.y = pair, a fixed number of workgroups per pair striding over the runs of 4 pixels), each
+ * followed by one launch of the solving kernel, which adds the partial sums, judges the trial and forms the next one; the last one
+ * only judges and writes the results.  All on the context's stream, no host synchronisation (a first call, or one that needs a
+ * larger workspace than any before, allocates: the workspace belongs to the context and grows on demand).
+ * Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: NULL frames (a NULL plane), d_M_in, d_M_out or d_info,
+ * channels not 1 or 3, frame_step not 1 or 2, w or h < 1, npairs < 0, iters outside 0..64, clip outside 0..255, a frame stride
+ * shorter than its row / frame, an output overlapping the frames, another output or (other than d_M_out == d_M_in) d_M_in;
+ * EVH_ERR_CAPACITY: w or h > 4096, npairs > 65535.  npairs == 0 succeeds and does nothing.  The plane form converts every pixel and
+ * tap as evh_yuv420_to_bgr does: it equals evh_yuv420_to_bgr followed by the BGR form.                                           */
+enum { EVH_REFINE_REFINED = 0, EVH_REFINE_UNCHANGED, EVH_REFINE_NOTHING_COVERED, EVH_REFINE_TOO_FEW, EVH_REFINE_DEGENERATE };
+enum { EVH_REFINE_STATUS = 0, EVH_REFINE_EVALS, EVH_REFINE_ACCEPTED, EVH_REFINE_COVERED_IN, EVH_REFINE_SSD_IN,
+       EVH_REFINE_COVERED_OUT, EVH_REFINE_SSD_OUT, EVH_REFINE_N_IN, EVH_REFINE_NINFO };  /* 8 */
+enum { EVH_REFINE_NSUMS = 45, EVH_REFINE_MIN_PIXELS = 64, EVH_REFINE_MAX_ITERS = 64, EVH_REFINE_MAX_SIZE = 4096 };
+int evh_pair_refine(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int frame_step /* 1 | 2 */, int w, int h,
+                    int channels /* 1 | 3 */, int64_t row_stride, int64_t frame_stride,
+                    const double* d_M_in /* f64[npairs,9] DEVICE */, int iters /* 0..64 */, int clip /* 0..255 */,
+                    double* d_M_out /* f64[npairs,9] DEVICE */, uint64_t* d_info /* u64[npairs,8] DEVICE */,
+                    double* d_normal /* f64[npairs,45] DEVICE, may be NULL */);
+int evh_pair_refine_yuv420(evh_ctx* ctx, const evh_yuv420* src, int npairs, int frame_step, int w, int h,
+                           const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal);
+
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */
 typedef struct evh_stream_seg {

@@ -111,6 +111,8 @@ SIGNATURES = {
     # stabilised output: frames warped into the fixed plane
     "evh_warp_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
+    "evh_warp_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
+    "evh_warp_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
     "evh_trail_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     "evh_trail_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     "evh_plate_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i64,
@@ -622,6 +624,31 @@ class Context:
                 raise ValueError("background must be [dh,dw(,3)] with out's row stride")
         tail = (mats.data_ptr(), int(bool(inverse_map)), mode, bp, op, dw, dh, ors, ofs if lead else 0, int(origin[0]), int(origin[1]))
         self._check(self._form("evh_warp_fixed_plane", planes)(self.h, *head, *tail))
+
+    def warp_ray_surface(self, frames, mats, cols, rows, out, mode, background=None, size=None):
+        """Frames warped onto a canvas of viewing rays (evh_warp_ray_surface[_yuv420], the arithmetic is stated in
+        include/evhip.h).  frames, out, mode, background, size: as for warp_fixed_plane.  mats: CUDA float64, n*9 contiguous
+        elements, ray -> homogeneous frame pixel, used as they are.  cols: CUDA float64 [dw,2], (a, c) per canvas column; rows:
+        CUDA float64 [dh], b per canvas row (surface.surface_tables builds them for a cylinder, a sphere or a plane).  Does
+        not synchronise."""
+        import torch
+        self._enter()
+        mode = WARP_MODES[mode] if isinstance(mode, str) else int(mode)
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        lead = 0 if mode == WARP_MOSAIC else 1
+        op, dw, dh, ors, ofs = self._image_rows(out, cn, lead, "out")
+        if lead and out.shape[0] != n:
+            raise ValueError("out must hold one canvas per frame")
+        self._dev_tensor(cols, torch.float64, (dw, 2), "cols must be a contiguous CUDA float64 tensor [dw,2]")
+        self._dev_tensor(rows, torch.float64, (dh,), "rows must be a contiguous CUDA float64 tensor [dh]")
+        bp = None
+        if background is not None:
+            bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
+            if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
+                raise ValueError("background must be [dh,dw(,3)] with out's row stride")
+        tail = (mats.data_ptr(), cols.data_ptr(), rows.data_ptr(), mode, bp, op, dw, dh, ors, ofs if lead else 0)
+        self._check(self._form("evh_warp_ray_surface", planes)(self.h, *head, *tail))
 
     def trail_fixed_plane(self, frames, mats, canvas, origin, out=None, rects=None, inverse_map=False, size=None):
         """The trail of the stabilised view (evh_trail_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h): per

@@ -145,6 +145,103 @@ __global__ __launch_bounds__(256) void k_warp_fixed_plane(SRC src, int nframes, 
   }
 }
 
+// Fixed surfaces that do not end at a horizon (include/evhip.h states the contract for evh_warp_ray_surface): canvas pixel (x, y)
+// is the viewing ray (a[x], b[y], c[x]) of two caller tables -- cylinder, sphere or plane is the caller's choice of tables, no
+// trigonometry runs here -- and frame k's matrix takes the ray to homogeneous frame pixels as it is.  A ray and its antipode meet
+// the same frame pixel: only tw > 0, the ray in front of the camera, is covered (NaN fails the comparison).
+// The sampling is warp_sample itself, whole: a split of it into position and taps moved instructions in the existing kernels
+// (profiles/surface_warp.txt).  It is handed the point (a, 1) and the map {A0, A1*b, A2*c; ...}: its (a0*X + a1*Y) + a2 is then
+// (A0*a + (A1*b)*1) + A2*c, and a product with 1 is exact, so tx, ty, tw come out as the header states them, with A1*b formed
+// once per frame for the run (RayMap) and A2*c once per pixel.
+struct RayMap { double a[9], b[3]; };
+__device__ __forceinline__ RayMap ray_map(const double* __restrict__ A, double b) {
+  RayMap R = {{A[0], A[1], A[2], A[3], A[4], A[5], A[6], A[7], A[8]}, {0.0, 0.0, 0.0}};
+  R.b[0] = R.a[1] * b; R.b[1] = R.a[4] * b; R.b[2] = R.a[7] * b;
+  return R;
+}
+template <class SRC>
+__device__ __forceinline__ bool ray_sample(const SRC& src, int img, const RayMap& R, double a, double c, int sw, int sh,
+                                           int (&v)[3]) {
+  const WarpMap M = {{R.a[0], R.b[0], R.a[2] * c, R.a[3], R.b[1], R.a[5] * c, R.a[6], R.b[2], R.a[8] * c}};
+  const double tw = (M.a[6] * a + M.a[7]) + M.a[8];
+  if (!(tw > 0.0)) return false;
+  return warp_sample(src, img, M, a, 1.0, sw, sh, v);
+}
+// The modes, the run of WARP_RUN pixels per thread and the stores are k_warp_fixed_plane's.  col: f64[dw,2] = (a, c) per column,
+// the run's four pairs are 64 contiguous bytes (a run cut by the right edge loads only its own columns); row: f64[dh].
+// HISTORY and MOSAIC load them once for all frames, each thread its own; EACH, see below.
+template <int MODE, int CN, class SRC>
+__global__ __launch_bounds__(256) void k_warp_ray_surface(SRC src, int nframes, int sw, int sh, const double* __restrict__ A,
+                                                          const double* __restrict__ col, const double* __restrict__ row,
+                                                          const uint8_t* bg, uint8_t* out, int dw, int64_t out_stride,
+                                                          int64_t out_img_stride, int runs_per_row, unsigned nruns, int vec) {
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = t < nruns;
+  if (MODE != EVH_WARP_EACH && !live) return;
+  const RunPos rp = MODE == EVH_WARP_EACH && !live ? RunPos{0, 0, 0} : run_pos(t, runs_per_row, dw);
+  const int y = rp.y, x0 = rp.x0, n = rp.n;
+  double ra[WARP_RUN], rc[WARP_RUN];
+  if constexpr (MODE == EVH_WARP_EACH) {
+    // One frame per thread: the table loads are not shared among frames, and 64 lanes that each read their own 64 bytes open
+    // 64 pieces of memory per load instruction (profiles/surface_warp.txt).  So a wave loads its 256 pixels lane by lane --
+    // lane i takes pixel p = i & 3 of the run of lane 16 j + i / 4, j = 0 .. 3: neighbouring lanes, neighbouring columns --
+    // and hands them over through LDS.  Every thread of the workgroup comes here, the ones past the last run with n = 0.
+    __shared__ double2 stage[256 * WARP_RUN];
+    const int lane = threadIdx.x & 63, first = (threadIdx.x - lane) * WARP_RUN;
+#pragma unroll
+    for (int j = 0; j < WARP_RUN; j++) {
+      const int s = 64 * j + lane, owner = s >> 2, p = s & 3;
+      const int ox0 = __shfl(x0, owner, 64), on = __shfl(n, owner, 64);
+      double2 ac = {0.0, 0.0};
+      if (p < on) { ac.x = col[2 * ((int64_t)ox0 + p)]; ac.y = col[2 * ((int64_t)ox0 + p) + 1]; }
+      stage[first + s] = ac;
+    }
+    __syncthreads();
+    if (!live) return;
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) { ra[p] = stage[threadIdx.x * WARP_RUN + p].x; rc[p] = stage[threadIdx.x * WARP_RUN + p].y; }
+  } else {
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      ra[p] = p < n ? col[2 * ((int64_t)x0 + p)] : 0.0;
+      rc[p] = p < n ? col[2 * ((int64_t)x0 + p) + 1] : 0.0;
+    }
+  }
+  const bool wide = vec != 0 && n == WARP_RUN;
+  const int64_t at = (int64_t)y * out_stride + (int64_t)x0 * CN;
+  const double b = row[y];
+  int v[WARP_RUN][3];
+#pragma unroll
+  for (int p = 0; p < WARP_RUN; p++) v[p][0] = v[p][1] = v[p][2] = 0;
+  if constexpr (MODE == EVH_WARP_HISTORY) {
+    if (bg) warp_run_load<CN>(bg + at, n, wide, v);
+    for (int k = 0; k < nframes; k++) {
+      const RayMap R = ray_map(A + 9 * (int64_t)k, b);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) if (p < n) ray_sample(src, k, R, ra[p], rc[p], sw, sh, v[p]);
+      warp_run_store<CN>(out + (int64_t)k * out_img_stride + at, n, wide, v);
+    }
+  } else {
+    unsigned open = (1u << n) - 1;                      // pixels of the run no frame has covered yet
+    const int first = MODE == EVH_WARP_EACH ? (int)blockIdx.y : nframes - 1, last = MODE == EVH_WARP_EACH ? first : 0;
+    for (int k = first; k >= last && open; k--) {
+      const RayMap R = ray_map(A + 9 * (int64_t)k, b);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++)
+        if (((open >> p) & 1) && ray_sample(src, k, R, ra[p], rc[p], sw, sh, v[p])) open &= ~(1u << p);
+    }
+    if (open && bg) {
+      int q[WARP_RUN][3];
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) q[p][0] = q[p][1] = q[p][2] = 0;
+      warp_run_load<CN>(bg + at, n, wide, q);
+#pragma unroll
+      for (int p = 0; p < WARP_RUN; p++) if ((open >> p) & 1) { v[p][0] = q[p][0]; v[p][1] = q[p][1]; v[p][2] = q[p][2]; }
+    }
+    warp_run_store<CN>(out + (MODE == EVH_WARP_EACH ? (int64_t)blockIdx.y * out_img_stride : 0) + at, n, wide, v);
+  }
+}
+
 // The motion-compensated residual of a pair (include/evhip.h states the contract for evh_pair_residual): grid.y = pair, previous
 // frame p * frame_step, current frame p * frame_step + 1.  A thread owns WARP_RUN adjacent pixels of a row of the current frame:
 // it loads them and the previous frame's pixels at the same place (as words where vec bit 1 allows; planes are converted pixel by
@@ -1011,6 +1108,37 @@ int launch(evh_ctx* c, const WarpArgs& A) {
   return launched(c);
 }
 
+// ---- fixed surfaces: frames warped onto a canvas of viewing rays ------------------------------------------------------------------
+// W: the plane entry's arguments with M = d_A, inverse_map, ox and oy unused; its refusals hold as they are
+struct RayArgs {
+  WarpArgs W; const double* col; const double* row;
+  bool idle() const { return W.idle(); }
+};
+int check(evh_ctx* c, const RayArgs& A) {
+  if (int rc = need_source(c, std::string(A.W.who) + ": ", A.W.F)) return rc;
+  if (!A.col || !A.row) return evh_fail(c, EVH_ERR_INVALID, std::string(A.W.who) + ": NULL argument");
+  return check(c, A.W);
+}
+// k_warp_ray_surface over the canvas
+int launch(evh_ctx* c, const RayArgs& R) {
+  const WarpArgs& A = R.W;
+  const Runs N = runs_of(A.dw, A.dh);
+  const int vec = words_ok(A.out, A.out_stride, A.out_img_stride, A.many() ? A.nframes : 1) && words_ok(A.bg, A.out_stride, 0, 1);
+  const dim3 grid((N.n + 255) / 256, A.mode == EVH_WARP_EACH ? A.nframes : 1);
+  with_source(A.F, [&](auto cn, const auto& S) {
+    constexpr int CN = decltype(cn)::value;
+    using SRC = std::decay_t<decltype(S)>;
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, S, A.nframes, A.sw, A.sh, A.M, R.col, R.row, A.bg, A.out, A.dw,
+                         A.out_stride, A.out_img_stride, N.per_row, N.n, vec);
+    };
+    if (A.mode == EVH_WARP_EACH) go(k_warp_ray_surface<EVH_WARP_EACH, CN, SRC>);
+    else if (A.mode == EVH_WARP_HISTORY) go(k_warp_ray_surface<EVH_WARP_HISTORY, CN, SRC>);
+    else go(k_warp_ray_surface<EVH_WARP_MOSAIC, CN, SRC>);
+  });
+  return launched(c);
+}
+
 // ---- the score of a homography: the motion-compensated residual of a pair ------------------------------------------------------
 struct ResidualArgs {
   const char* who; EvhFrames F; int npairs, frame_step, w, h; const double* M; int threshold; uint64_t* stats; uint8_t* out;
@@ -1308,6 +1436,20 @@ int evh_warp_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, 
                                 int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy) {
   return run(c, WarpArgs{"evh_warp_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, mode, d_background,
                          d_out, dw, dh, out_row_stride, out_frame_stride, ox, oy});
+}
+
+int evh_warp_ray_surface(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                         int64_t frame_stride, const double* d_A, const double* d_col, const double* d_row, int mode,
+                         const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride) {
+  return run(c, RayArgs{{"evh_warp_ray_surface", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh, d_A,
+                         1, mode, d_background, d_out, dw, dh, out_row_stride, out_frame_stride, 0, 0}, d_col, d_row});
+}
+
+int evh_warp_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                const double* d_col, const double* d_row, int mode, const uint8_t* d_background, uint8_t* d_out,
+                                int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride) {
+  return run(c, RayArgs{{"evh_warp_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, mode, d_background, d_out,
+                         dw, dh, out_row_stride, out_frame_stride, 0, 0}, d_col, d_row});
 }
 
 int evh_pair_residual(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int channels,

@@ -145,20 +145,17 @@ def _check_trail(mode, placement, trail, border):
     return placement == "translate" and border is not False
 
 
-def _chunks(capture, superposition_homography_dict, resize_info, mode, placement, scale, chunk_frames, ingest, max_pixels,
-            trail, border, originals=False):
-    """The loop behind stabilized_frames and comparison_frames: reads and uploads chunk_frames frames at a time and yields
-    (number of the chunk's first frame, n, the canvases of the chunk on the device or None for "mosaic", the chunk's
-    full-size BGR frames on the device when `originals`, the carried canvas).  What it yields is valid until the next step."""
+def _canvas_chunks(capture, mode, chunk_frames, ingest, setup, originals=False):
+    """The loop behind _chunks and surface.surface_frames: reads and uploads chunk_frames frames at a time and yields (number of
+    the chunk's first frame, n, the canvases of the chunk on the device or None for "mosaic", the chunk's full-size BGR frames
+    on the device when `originals`, the carried canvas).  What it yields is valid until the next step.
+    setup(w0, h0) -> (dw, dh, the size the ladder resizes the frames to or None, paint); paint(ctx, number of the frame before the
+    chunk, n, the chunk's source, its size= argument, the chunk's canvases [n,dh,dw,3] or None for "mosaic", the carried canvas)
+    enqueues the chunk's work and leaves torch ordered after it."""
     import torch
-    if mode not in WARP_MODES:
-        raise ValueError("mode must be 'each', 'history' or 'mosaic'")
-    check_ingest(ingest)
-    outline = _check_trail(mode, placement, trail, border)
     reader = FrameReader(capture, ingest)
     w0, h0 = reader.w0, reader.h0
-    ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
-    w, h = int(resize_info["w"]), int(resize_info["h"])
+    dw, dh, resize_to, paint = setup(w0, h0)
     ctx = runtime.get_context(64, 64)             # the entries used here work on caller buffers of any size
     dev = runtime.device()
     per_frame = WARP_MODES[mode] != WARP_MOSAIC
@@ -167,35 +164,56 @@ def _chunks(capture, superposition_homography_dict, resize_info, mode, placement
         chunk = max(1, min(chunk, CHUNK_BYTES // (dw * dh * 3)))
     canvas = torch.zeros((dh, dw, 3), dtype=torch.uint8, device=dev)
     out = torch.empty((chunk, dh, dw, 3), dtype=torch.uint8, device=dev) if per_frame else None
-    ladder = DeviceLadder(dev, chunk, reader.planes, (w0, h0), (w, h) if placement == "translate" else None, bgr=originals)
+    ladder = DeviceLadder(dev, chunk, reader.planes, (w0, h0), resize_to, bgr=originals)
     for frame_no, frames in reader.chunks(chunk, 0):
         n = len(frames)
         full, src, size = ladder(ctx, torch.from_numpy(frames).to(dev))
-        host_mats = np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])
-        mats = torch.from_numpy(host_mats).to(dev)
-        if trail:
-            if frame_no == 0 and placement == "translate":
-                # initialize_background (stabilization.py:245-249): frame 1 at (|min_x|, |min_y|), the plane's origin, undimmed
-                eye = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1], dtype=torch.float64, device=dev)
-                ctx.warp_fixed_plane(src[:1], eye, canvas, "mosaic", (ox, oy), background=canvas, size=size)
-            rects = None
-            if outline:                           # change_frame_location's corners (stabilization.py:76-94)
-                rects = np.tile(np.array([0, 0, -1, -1], np.int32), (n, 1))
-                for k, m in enumerate(host_mats):
-                    if np.isfinite(m[2]) and np.isfinite(m[5]):
-                        rects[k] = frame_outline(-ox, -oy, int(m[2]), int(m[5]), w, h)
-                rects = torch.from_numpy(rects).to(dev)
-            ctx.trail_fixed_plane(src, mats, canvas, (ox, oy), out=out[:n], rects=rects, size=size)
-            ctx.order_torch_after()
-        elif per_frame:
-            ctx.warp_fixed_plane(src, mats, out[:n], mode, (ox, oy), background=canvas if mode == "history" else None, size=size)
-            ctx.order_torch_after()
-            if mode == "history":
-                canvas.copy_(out[n - 1])
-        else:
-            ctx.warp_fixed_plane(src, mats, canvas, mode, (ox, oy), background=canvas, size=size)
-            ctx.order_torch_after()
+        paint(ctx, frame_no, n, src, size, out[:n] if per_frame else None, canvas)
         yield frame_no + 1, n, (out[:n] if per_frame else None), (full if originals else None), canvas
+
+
+def _chunks(capture, superposition_homography_dict, resize_info, mode, placement, scale, chunk_frames, ingest, max_pixels,
+            trail, border, originals=False):
+    """The loop behind stabilized_frames and comparison_frames: _canvas_chunks with the fixed plane's geometry and entries."""
+    import torch
+    if mode not in WARP_MODES:
+        raise ValueError("mode must be 'each', 'history' or 'mosaic'")
+    check_ingest(ingest)
+    outline = _check_trail(mode, placement, trail, border)
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+
+    def setup(w0, h0):
+        ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
+        dev = runtime.device()
+
+        def paint(ctx, frame_no, n, src, size, out, canvas):
+            host_mats = np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])
+            mats = torch.from_numpy(host_mats).to(dev)
+            if trail:
+                if frame_no == 0 and placement == "translate":
+                    # initialize_background (stabilization.py:245-249): frame 1 at (|min_x|, |min_y|), the plane's origin, undimmed
+                    eye = torch.tensor([1, 0, 0, 0, 1, 0, 0, 0, 1], dtype=torch.float64, device=dev)
+                    ctx.warp_fixed_plane(src[:1], eye, canvas, "mosaic", (ox, oy), background=canvas, size=size)
+                rects = None
+                if outline:                           # change_frame_location's corners (stabilization.py:76-94)
+                    rects = np.tile(np.array([0, 0, -1, -1], np.int32), (n, 1))
+                    for k, m in enumerate(host_mats):
+                        if np.isfinite(m[2]) and np.isfinite(m[5]):
+                            rects[k] = frame_outline(-ox, -oy, int(m[2]), int(m[5]), w, h)
+                    rects = torch.from_numpy(rects).to(dev)
+                ctx.trail_fixed_plane(src, mats, canvas, (ox, oy), out=out, rects=rects, size=size)
+                ctx.order_torch_after()
+            elif out is not None:
+                ctx.warp_fixed_plane(src, mats, out, mode, (ox, oy), background=canvas if mode == "history" else None, size=size)
+                ctx.order_torch_after()
+                if mode == "history":
+                    canvas.copy_(out[n - 1])
+            else:
+                ctx.warp_fixed_plane(src, mats, canvas, mode, (ox, oy), background=canvas, size=size)
+                ctx.order_torch_after()
+        return dw, dh, (w, h) if placement == "translate" else None, paint
+
+    yield from _canvas_chunks(capture, mode, chunk_frames, ingest, setup, originals)
 
 
 def frame_outline(abs_min_x, abs_min_y, x_offset, y_offset, w, h):

@@ -1,5 +1,6 @@
 """Command-line driver of the stabilised view, with the arguments of the reference's
-evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison and --plate:
+evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison, --plate
+and --surface:
 
     python -m evenvizion_amd.stabilize --path_to_homography_dict run1/video/dict_with_homography_matrix.json \
            --path_to_video video.mp4 --experiment_name run1 --comparison 1
@@ -17,6 +18,12 @@ evenvizion_amd.stabilization:
                      over the video, where at least --plate_min_cover of them cover the pixel), plate_count.png, how many frames
                      cover each pixel, and with --plate_masks 1 mask_NNNNNN.png per frame taken: white where that frame differs
                      from the plate by more than --plate_threshold gray levels.
+    --surface cylinder | sphere
+                     NNNNNN.ppm per frame (one file for --mode mosaic): the canvas of a fixed cylinder or sphere around the camera
+                     of frame 1 instead of the fixed plane, for a camera that turns by more than the plane can hold (a pan beyond
+                     90 degrees; evenvizion_amd.surface), and surface_report.json: the focal length (--focal F in pixels of the
+                     resized frame, estimated from the matrices without it), the fit residual of the rotation model per pair, the
+                     canvas geometry.  --scale applies; --placement does not.
 
 What is still missing from the reference's picture is its text ("Original", "EvenVizion").  The dimming is the arithmetic
 include/evhip.h states for evh_trail_fixed_plane, not cv2.cvtColor compared byte for byte.
@@ -56,6 +63,11 @@ def parser():
     ap.add_argument("--plate_masks", type=int, choices=(0, 1), default=0,
                     help="plate: 1 writes mask_NNNNNN.png per frame taken, white where the frame differs from the plate")
     ap.add_argument("--plate_threshold", type=int, default=16, help="plate: gray levels a mask pixel must differ by (0..255)")
+    ap.add_argument("--surface", choices=("cylinder", "sphere"), default=None,
+                    help="place the frames on a fixed cylinder or sphere instead of the fixed plane: no horizon, any pan angle; "
+                         "also writes surface_report.json")
+    ap.add_argument("--focal", type=float, default=None,
+                    help="surface: focal length in pixels of the resized frame; estimated from the matrices when not given")
     return ap
 
 
@@ -68,6 +80,12 @@ def main(argv=None):
         ap.error("--plate writes the plate only: not with --trail or --comparison")
     if not (1 <= args.plate_frames <= 255 and 1 <= args.plate_min_cover <= 255 and 0 <= args.plate_threshold <= 255):
         ap.error("--plate_frames and --plate_min_cover lie in 1..255, --plate_threshold in 0..255")
+    if args.surface and (args.trail or args.comparison or args.plate):
+        ap.error("--surface writes the canvases only: not with --trail, --comparison or --plate")
+    if args.focal is not None and not args.surface:
+        ap.error("--focal needs --surface")
+    if args.focal is not None and not args.focal > 0:
+        ap.error("--focal must be positive")
     from .component import open_capture
     from .processing.utils import read_homography_dict, superposition_dict
     from .stabilization import comparison_frames, stabilized_frames, write_ppm
@@ -76,6 +94,16 @@ def main(argv=None):
     os.makedirs(save_folder, exist_ok=True)
     homography_dict, resize_info = read_homography_dict(args.path_to_homography_dict)
     sup = superposition_dict(homography_dict)
+    if args.surface:
+        import json
+        from .surface import surface_frames, surface_model, surface_report
+        model = surface_model(sup, resize_info, surface=args.surface, focal=args.focal, scale=args.scale)
+        with open(os.path.join(save_folder, "surface_report.json"), "w") as f:
+            json.dump(surface_report(model), f, indent=1)
+        for frame_no, picture in surface_frames(cap, sup, resize_info, surface=args.surface, focal=model.focal, mode=args.mode,
+                                                scale=args.scale):
+            write_ppm(os.path.join(save_folder, "%06d.ppm" % frame_no), picture)
+        return save_folder
     if args.plate:
         from .matching_pictures import write_png
         from .stabilization import background_plate

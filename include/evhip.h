@@ -23,6 +23,8 @@
  *   evh_*_yuv420                  capture.read() + imutils.resize + the entry of the same name without the suffix
  *   evh_warp_fixed_plane[_yuv420] stabilize_view / initialize_background: a frame placed on the fixed plane
  *                                 visualization/stabilization.py:129-172, 220-249
+ *   evh_warp_ray_surface[_yuv420] no counterpart: the cylindrical coordinate system the reference's known-issues.md names as the way
+ *                                 past camera rotations above 90 degrees -- frames placed on a cylinder, a sphere or a plane of rays
  *   evh_trail_fixed_plane[_yuv420] stabilize_view with decrease_brightness and change_frame_location: earlier frames dimmed,
  *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
  *   evh_plate_fixed_plane[_yuv420] no counterpart: the "video motion segmentation" the reference's known-issues.md considers --
@@ -476,6 +478,37 @@ int evh_warp_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int
 int evh_warp_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
                                 int inverse_map, int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
                                 int64_t out_row_stride, int64_t out_frame_stride, int ox, int oy);
+
+/* ---- fixed surfaces: frames warped onto a canvas of viewing rays (cylinder, sphere, plane) ----------------------------------- */
+/* evh_warp_fixed_plane's canvas ends at the horizon of a frame's matrix: a camera that turns by 90 degrees runs out of plane.
+ * Here canvas pixel (x, y) stands for a viewing ray, not a plane point, and the ray is separable:
+ *   ray(x, y) = (a[x], b[y], c[x]),  (a, c) = d_col f64[dw,2] (DEVICE), b = d_row f64[dh] (DEVICE).
+ * Rays are projective, so one entry serves every surface the caller tabulates, in double, on the host -- no sin, cos or tan runs
+ * on the device:    cylinder  a = sin t, c = cos t, b = v;    sphere (equirectangular)  a = sin t, c = cos t, b = tan p;
+ * plane  a = X, c = 1, b = Y.  d_A f64[nframes,9] (DEVICE) maps a ray to homogeneous frame pixels and is used as it is (no
+ * adjugate; for a rotating camera A = K . R^T).  Arithmetic, all IEEE float64 with one rounding per operation (no fma), a, c of
+ * the pixel's column and b of its row:
+ *   tx = (A0*a + A1*b) + A2*c,  ty = (A3*a + A4*b) + A5*c,  tw = (A6*a + A7*b) + A8*c;
+ *   U = rint(tx / tw * 32), V = rint(ty / tw * 32), halves to even: the source position in 1/32 pixels.
+ * Frame k COVERS the pixel iff tw > 0 and 0 <= U <= 32*(sw-1) and 0 <= V <= 32*(sh-1), all compared in double: NaN fails, so a
+ * NaN, zero, infinite or all-negative matrix and a NaN table entry cover nothing and read nothing.  tw > 0 is what a closed
+ * surface needs and the plane entry does not have: a ray and its antipode give the same (U, V), and without the sign every
+ * frame would appear twice, 180 degrees apart; with it a frame lies on the half of the surface in front of its camera.  A
+ * covered pixel takes its bytes exactly as in evh_warp_fixed_plane: sx = U >> 5, fx = U & 31, sy = V >> 5, fy = V & 31,
+ *   (p00*(32-fx)*(32-fy) + p01*fx*(32-fy) + p10*(32-fx)*fy + p11*fx*fy + 512) >> 10,  a tap of weight 0 is not read.
+ * With the plane's tables and tw > 0 over the canvas the result is evh_warp_fixed_plane's with inverse_map != 0, byte for byte.
+ * mode (EVH_WARP_EACH, EVH_WARP_HISTORY, EVH_WARP_MOSAIC), d_background (d_background == d_out for EVH_WARP_MOSAIC only), channels,
+ * the plane form, strides, "every byte of every output row inside dw*channels is written, bytes between rows are not", only
+ * caller buffers, and the refusals are evh_warp_fixed_plane's -- EVH_ERR_INVALID also for a NULL d_col or d_row; refused before
+ * anything is launched, outputs untouched.  The tables are not compared with d_out.  nframes == 0 succeeds and does nothing.
+ * Neither entry synchronises.                                                                                                 */
+int evh_warp_ray_surface(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                         int64_t row_stride, int64_t frame_stride, const double* d_A, const double* d_col, const double* d_row,
+                         int mode, const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride,
+                         int64_t out_frame_stride);
+int evh_warp_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                const double* d_col, const double* d_row, int mode, const uint8_t* d_background, uint8_t* d_out,
+                                int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride);
 
 /* ---- the trail: earlier frames fade out behind the current one (stabilization.py:21-97, 129-172) -------------------------- */
 /* What stabilize_view does to its canvas per frame -- paste, white outline on a copy, both through 8-bit BGR -> HSV -> BGR with

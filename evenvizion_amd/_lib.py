@@ -28,6 +28,9 @@ DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
 RESIDUAL_ABS, RESIDUAL_MASK = 0, 1
 RESIDUAL_KINDS = {"abs": RESIDUAL_ABS, "mask": RESIDUAL_MASK}
 RES_COVERED, RES_SAD, RES_SSD, RES_SAD0, RES_SSD0, RES_MOVING, RES_NSTATS = range(7)
+BLEND_FEATHER, BLEND_SEAM = 0, 1
+BLEND_MODES = {"feather": BLEND_FEATHER, "seam": BLEND_SEAM}
+EXPO_NSTATS = 7          # EVH_EXPO_NSTATS: (pixels, sum a per channel x3, sum b per channel x3)
 REFINE_REFINED, REFINE_UNCHANGED, REFINE_NOTHING_COVERED, REFINE_TOO_FEW, REFINE_DEGENERATE = range(5)
 REFINE_INFO = ("status", "evals", "accepted", "covered_in", "ssd_in", "covered_out", "ssd_out", "n_in")
 REFINE_NINFO, REFINE_NSUMS, REFINE_MAX_ITERS, REFINE_MAX_SIZE = 8, 45, 64, 4096
@@ -113,6 +116,13 @@ SIGNATURES = {
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_warp_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
     "evh_warp_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
+    # the blended mosaic and the sums its exposure gains are solved from
+    "evh_blend_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _i]),
+    "evh_blend_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _i]),
+    "evh_blend_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64]),
+    "evh_blend_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64]),
+    "evh_pair_exposure": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "evh_pair_exposure_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "evh_trail_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     "evh_trail_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
     "evh_plate_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i64, _i64,
@@ -246,6 +256,8 @@ class Context:
         self.max_frames = max_frames
         self.max_features = max_features
         self.max_w, self.max_h = max_w, max_h
+
+    _nothing = None          # a few device bytes for calls that take no frames (see _blend)
 
     def close(self):
         if getattr(self, "h", None):
@@ -649,6 +661,97 @@ class Context:
                 raise ValueError("background must be [dh,dw(,3)] with out's row stride")
         tail = (mats.data_ptr(), cols.data_ptr(), rows.data_ptr(), mode, bp, op, dw, dh, ors, ofs if lead else 0)
         self._check(self._form("evh_warp_ray_surface", planes)(self.h, *head, *tail))
+
+    # ---- the blended mosaic ----
+    def _blend(self, name, frames, mats, middle, last, shape, mode, feather, gains, acc, acc_in, out, background, size):
+        """What blend_fixed_plane and blend_ray_surface share.  middle: the arguments between the matrices and `mode`, last:
+        those behind out_row_stride; shape=(dh, dw) or None = out's."""
+        import torch
+        self._enter()
+        mode = BLEND_MODES[mode] if isinstance(mode, str) else int(mode)
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        if out is None and acc is None:
+            raise ValueError("one of out and acc must be given")
+        op, ors = None, 0
+        if out is not None:
+            op, dw, dh, ors, _ = self._image_rows(out, cn, 0, "out")
+            if shape is not None and (int(shape[0]), int(shape[1])) != (dh, dw):
+                raise ValueError("shape does not match out")
+        elif shape is None:
+            raise ValueError("without out the canvas needs shape=(dh, dw)")
+        else:
+            dh, dw = int(shape[0]), int(shape[1])
+        if acc is not None:
+            self._dev_tensor(acc, torch.int64, (dh, dw, cn + 1), "acc must be a contiguous CUDA int64 tensor [dh,dw,%d]", cn + 1)
+        elif acc_in:
+            raise ValueError("acc_in needs acc")
+        if gains is not None:
+            self._dev_tensor(gains, torch.uint16, (n, 3), "gains must be a contiguous CUDA uint16 tensor [n,3]")
+        bp = None
+        if background is not None and out is not None:
+            bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
+            if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
+                raise ValueError("background must be [dh,dw(,3)] with out's row stride")
+        mp = mats.data_ptr()
+        if n == 0:
+            # empty tensors have no address to hand over, and the entry reads neither frames nor matrices: packed frames at
+            # a few bytes of the context's own
+            if self._nothing is None:
+                self._nothing = torch.zeros(16, dtype=torch.uint8, device="cuda:%d" % self.device)
+            planes, head, mp = False, (self._nothing.data_ptr(), 0, sw, sh, cn, sw * cn, sw * sh * cn), self._nothing.data_ptr()
+        tail = (mode, int(feather), _ptr(gains) if n else None, _ptr(acc), int(bool(acc_in)), bp, op, dw, dh, ors)
+        self._check(self._form(name, planes)(self.h, *head, mp, *middle, *tail, *last))
+
+    def blend_fixed_plane(self, frames, mats, origin, out=None, mode="feather", feather=1024, gains=None, acc=None, acc_in=False,
+                          background=None, inverse_map=False, shape=None, size=None):
+        """The blended mosaic on the fixed plane (evh_blend_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h).
+        frames, mats, origin, background, inverse_map, size: as for warp_fixed_plane in mode "mosaic"; out: [dh,dw(,3)] or None
+        (the call then only advances the state; shape=(dh, dw) says how large the canvas is).  mode "feather" or "seam";
+        feather: the feather width in 1/32 pixels, 0..65535; gains: CUDA uint16 [n,3], Q12, or None = 1.0; acc: CUDA int64
+        [dh,dw,channels+1] contiguous, the state (the library's u64 values viewed as int64), read when acc_in, written
+        always, or None.  Does not synchronise."""
+        self._blend("evh_blend_fixed_plane", frames, mats, (int(bool(inverse_map)),), (int(origin[0]), int(origin[1])), shape, mode,
+                    feather, gains, acc, acc_in, out, background, size)
+
+    def blend_ray_surface(self, frames, mats, cols, rows, out=None, mode="feather", feather=1024, gains=None, acc=None,
+                          acc_in=False, background=None, size=None):
+        """The blended mosaic on a canvas of viewing rays (evh_blend_ray_surface[_yuv420]).  frames, mats, cols, rows, size: as
+        for warp_ray_surface (the canvas is [len(rows), len(cols)]); everything else as for blend_fixed_plane."""
+        import torch
+        if cols.dim() != 2 or rows.dim() != 1:
+            raise ValueError("cols must be [dw,2] and rows [dh]")
+        dw, dh = int(cols.shape[0]), int(rows.shape[0])
+        self._dev_tensor(cols, torch.float64, (dw, 2), "cols must be a contiguous CUDA float64 tensor [dw,2]")
+        self._dev_tensor(rows, torch.float64, (dh,), "rows must be a contiguous CUDA float64 tensor [dh]")
+        self._blend("evh_blend_ray_surface", frames, mats, (cols.data_ptr(), rows.data_ptr()), (), (dh, dw), mode, feather, gains,
+                    acc, acc_in, out, background, size)
+
+    # ---- the sums behind exposure gains ----
+    def pair_exposure(self, frames, pairs, mats, step=2, lo=8, hi=247, stats=None, size=None):
+        """The overlap sums of pairs of frames (evh_pair_exposure[_yuv420], stated in include/evhip.h).  frames: as for
+        warp_fixed_plane.  pairs: CUDA int32 [npairs,2] contiguous, (i, j) per pair; an index outside the frames gives seven
+        zeros.  mats: CUDA float64, npairs*9 contiguous, pixel of frame i -> pixel of frame j.  stats: CUDA int64 [npairs,7]
+        contiguous or None = a new tensor; it is returned: (pixels, sum a per channel, sum b per channel).  Does not
+        synchronise."""
+        import torch
+        self._enter()
+        planes, head, n, w, h, cn = self._frame_source(frames, size)
+        if pairs.dim() != 2:
+            raise ValueError("pairs must be a contiguous CUDA int32 tensor [npairs,2]")
+        npairs = int(pairs.shape[0])
+        self._dev_tensor(pairs, torch.int32, (npairs, 2), "pairs must be a contiguous CUDA int32 tensor [npairs,2]")
+        self._dev_tensor(mats, torch.float64, 9 * npairs, "mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        if stats is None:
+            stats = torch.empty((npairs, EXPO_NSTATS), dtype=torch.int64, device="cuda:%d" % self.device)
+        self._dev_tensor(stats, torch.int64, (npairs, EXPO_NSTATS), "stats must be a contiguous CUDA int64 tensor [npairs,%d]", EXPO_NSTATS)
+        if npairs == 0:                      # empty tensors have no address to hand over
+            return stats
+        if n == 0:
+            raise ValueError("pairs need frames")
+        self._check(self._form("evh_pair_exposure", planes)(self.h, *head, pairs.data_ptr(), npairs, mats.data_ptr(), int(step),
+                                                            int(lo), int(hi), stats.data_ptr()))
+        return stats
 
     def trail_fixed_plane(self, frames, mats, canvas, origin, out=None, rects=None, inverse_map=False, size=None):
         """The trail of the stabilised view (evh_trail_fixed_plane[_yuv420], the arithmetic is stated in include/evhip.h): per

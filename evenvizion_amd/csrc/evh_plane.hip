@@ -1,6 +1,7 @@
 // evh_plane.hip -- the products on the fixed plane and the pictures drawn from a batch's results: evh_warp_fixed_plane,
-// evh_pair_residual, evh_pair_refine, evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded
-// 4:2:0 planes), evh_heatmap_render and evh_draw_matches.  Kernels first, then the host side: what the entries share (checks, launch
+// evh_warp_ray_surface, evh_blend_fixed_plane, evh_blend_ray_surface, evh_pair_residual, evh_pair_exposure, evh_pair_refine,
+// evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded 4:2:0 planes), evh_heatmap_render and
+// evh_draw_matches.  Kernels first, then the host side: what the entries share (checks, launch
 // plumbing), then per product its arguments, check() -- every refusal comes before anything is enqueued -- and launch().
 #include "evh_devmath.h"
 #include "evh_internal.h"
@@ -242,6 +243,122 @@ __global__ __launch_bounds__(256) void k_warp_ray_surface(SRC src, int nframes, 
   }
 }
 
+// The blended mosaic (include/evhip.h states the contract for evh_blend_fixed_plane and evh_blend_ray_surface): every covering
+// frame enters a canvas pixel's state u64[CN + 1] -- FEATHER: the sums of w * s * g and of w; SEAM: s * g of the frame with the
+// largest w, and that w -- where w = min(d, F) + 1 and d is the sample's distance to the nearest frame edge in 1/32 pixels.
+// warp_sample does not hand out its position, and taking it apart moves instructions in the existing kernels
+// (profiles/surface_warp.txt), so edge_distance forms the position once more from the same operands in the same order: the two
+// are one computation to the compiler (profiles/blend.txt counts the divisions), and the integers are warp_sample's by
+// construction.  Only called for a covered position: U and V lie inside the frame, every difference is >= 0.
+__device__ __forceinline__ int edge_distance(const WarpMap& A, double X, double Y, int sw, int sh) {
+  const double tx = (A.a[0] * X + A.a[1] * Y) + A.a[2];
+  const double ty = (A.a[3] * X + A.a[4] * Y) + A.a[5];
+  const double tw = (A.a[6] * X + A.a[7] * Y) + A.a[8];
+  const int u = (int)__builtin_rint(tx / tw * 32.0), v = (int)__builtin_rint(ty / tw * 32.0);
+  return min(min(u, 32 * (sw - 1) - u), min(v, 32 * (sh - 1) - v));
+}
+// min(255, num / den) for den > 0, num < 2^63, den < 2^56 (the header's bounds leave room): is the quotient above 255, else its
+// eight bits from the top, a compare and a subtraction each.  The general 64-bit division, which also works out 56 bits nobody
+// needs, is 67 instructions longer per channel (profiles/blend.txt); the result is the same.
+__device__ __forceinline__ int quotient_u8(unsigned long long num, unsigned long long den) {
+  if ((num >> 8) >= den) return 255;                    // num >= den << 8, without the shift that could leave 64 bits
+  int q = 0;
+#pragma unroll
+  for (int b = 7; b >= 0; b--)
+    if (num >= den << b) { num -= den << b; q |= 1 << b; }
+  return q;
+}
+// where the canvas pixels of a blend are: the plane entry's matrices and origin, or the ray entry's tables (col != NULL)
+struct BlendGeo { const double* M; int inverse_map, ox, oy; const double* col; const double* row; };
+// One canvas pixel per thread, its state in registers over all frames, as in k_plate_fixed_plane and unlike the warp kernels: those
+// stop at the first covering frame, this one samples every frame, and a thread that owns a run of WARP_RUN pixels goes through
+// 4 x nframes dependent position-and-tap chains at twice the registers -- 204 us against 124 us for 16 frames of 1280x720
+// (profiles/blend.txt).  vec bit 1: the state moves as 128-bit words (d_acc 16-byte aligned: a pixel's state starts at a multiple
+// of 16 bytes from it, CN + 1 being even).  The picture's bytes go one by one, adjacent lanes to adjacent pixels.  bg may BE out: a
+// pixel no frame has entered (den == 0) reads its bytes before the store; acc is apart from everything.
+template <int MODE, int CN, class SRC, bool RAY>
+__global__ __launch_bounds__(256) void k_blend(SRC src, int nframes, int sw, int sh, BlendGeo G, int feather,
+                                               const uint16_t* __restrict__ gain, unsigned long long* __restrict__ acc,
+                                               int acc_in, const uint8_t* bg, uint8_t* out, int dw, int64_t out_stride,
+                                               unsigned npix, int vec) {
+  constexpr int NS = CN + 1;
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npix) return;
+  const int y = (int)(t / (unsigned)dw), x = (int)t - y * dw;
+  // the plane: (X, Y); the rays: (a, 1) with c beside them
+  double X, Y = 1.0, rc = 0.0, b = 0.0;
+  if constexpr (RAY) {
+    X = G.col[2 * (int64_t)x]; rc = G.col[2 * (int64_t)x + 1]; b = G.row[y];
+  } else {
+    X = (double)((int64_t)x + G.ox); Y = (double)((int64_t)y + G.oy);
+  }
+  unsigned long long st[NS];
+  unsigned long long* const sp = acc ? acc + (int64_t)t * NS : nullptr;
+#pragma unroll
+  for (int c = 0; c < NS; c++) st[c] = 0;
+  if (sp && acc_in) {
+    if (vec & 2) {
+#pragma unroll
+      for (int k = 0; k < NS / 2; k++) {
+        const ulonglong2 q = reinterpret_cast<const ulonglong2*>(sp)[k];
+        st[2 * k] = q.x; st[2 * k + 1] = q.y;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < NS; c++) st[c] = sp[c];
+    }
+  }
+  for (int k = 0; k < nframes; k++) {
+    uint32_t g[CN];
+#pragma unroll
+    for (int c = 0; c < CN; c++) g[c] = gain ? gain[3 * (int64_t)k + c] : 4096u;
+    int s[3] = {0, 0, 0};
+    WarpMap A;
+    if constexpr (RAY) {
+      const RayMap R = ray_map(G.M + 9 * (int64_t)k, b);
+      if (!ray_sample(src, k, R, X, rc, sw, sh, s)) continue;
+      A = {{R.a[0], R.b[0], R.a[2] * rc, R.a[3], R.b[1], R.a[5] * rc, R.a[6], R.b[2], R.a[8] * rc}};         // ray_sample's
+    } else {
+      A = warp_map(G.M + 9 * (int64_t)k, G.inverse_map);
+      if (!warp_sample(src, k, A, X, Y, sw, sh, s)) continue;
+    }
+    const uint32_t w = (uint32_t)min(edge_distance(A, X, Y, sw, sh), feather) + 1u;
+    if constexpr (MODE == EVH_BLEND_FEATHER) {
+#pragma unroll
+      for (int c = 0; c < CN; c++) st[c] += (unsigned long long)w * ((uint32_t)s[c] * g[c]);
+      st[CN] += w;
+    } else if (w > st[CN]) {
+#pragma unroll
+      for (int c = 0; c < CN; c++) st[c] = (uint32_t)s[c] * g[c];
+      st[CN] = w;
+    }
+  }
+  if (sp) {
+    if (vec & 2) {
+#pragma unroll
+      for (int k = 0; k < NS / 2; k++) {
+        ulonglong2 q;
+        q.x = st[2 * k]; q.y = st[2 * k + 1];
+        reinterpret_cast<ulonglong2*>(sp)[k] = q;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < NS; c++) sp[c] = st[c];
+    }
+  }
+  if (!out) return;
+  const int64_t at = (int64_t)y * out_stride + (int64_t)x * CN;
+  const unsigned long long den = st[CN];
+#pragma unroll
+  for (int c = 0; c < CN; c++) {
+    int v;
+    if (den == 0) v = bg ? bg[at + c] : 0;
+    else if constexpr (MODE == EVH_BLEND_FEATHER) v = quotient_u8(st[c] + (den << 11), den << 12);
+    else v = (int)min((st[c] + 2048) >> 12, 255ull);
+    out[at + c] = (uint8_t)v;
+  }
+}
+
 // The motion-compensated residual of a pair (include/evhip.h states the contract for evh_pair_residual): grid.y = pair, previous
 // frame p * frame_step, current frame p * frame_step + 1.  A thread owns WARP_RUN adjacent pixels of a row of the current frame:
 // it loads them and the previous frame's pixels at the same place (as words where vec bit 1 allows; planes are converted pixel by
@@ -311,6 +428,59 @@ __global__ __launch_bounds__(256) void k_pair_residual(SRC src, int frame_step, 
   if (threadIdx.x < EVH_RES_NSTATS) {
     const uint32_t sum = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
     if (sum) atomicAdd(&stats[(int64_t)pair * EVH_RES_NSTATS + threadIdx.x], (unsigned long long)sum);
+  }
+}
+
+// The sums behind exposure gains (include/evhip.h states the contract for evh_pair_exposure): grid.y = pair, the pair's two frame
+// numbers come from device memory and are checked here -- a pair that names a frame outside 0 .. nframes-1 leaves as a whole
+// workgroup, before the barrier, and keeps the zeros of the memset.  The pixels considered are those of the grid x % step == 0,
+// y % step == 0 of frame i, `gw` per row; a thread owns WARP_RUN adjacent ones.  Bounds as in k_pair_residual: a workgroup holds at
+// most 256 * 4 * 255 < 2^32 per sum, a pair at most INT_MAX * 255 < 2^39.
+template <int CN, class SRC>
+__global__ __launch_bounds__(256) void k_pair_exposure(SRC src, int nframes, int w, int h, const int32_t* __restrict__ pairs,
+                                                       const double* __restrict__ M, int step, int lo, int hi,
+                                                       unsigned long long* __restrict__ stats, int gw, int runs_per_row,
+                                                       unsigned nruns) {
+  __shared__ uint32_t part[4][EVH_EXPO_NSTATS];
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int pair = blockIdx.y;
+  const int fi = pairs[2 * (int64_t)pair], fj = pairs[2 * (int64_t)pair + 1];
+  if ((unsigned)fi >= (unsigned)nframes || (unsigned)fj >= (unsigned)nframes) return;
+  uint32_t s[EVH_EXPO_NSTATS];
+#pragma unroll
+  for (int k = 0; k < EVH_EXPO_NSTATS; k++) s[k] = 0;
+  if (t < nruns) {
+    const RunPos rp = run_pos(t, runs_per_row, gw);
+    const int y = rp.y * step;
+    const typename SRC::Row ra = src.row(fi, y);
+    const WarpMap A = warp_map(M + 9 * (int64_t)pair, 1);
+    const double Y = (double)y;
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      const int x = (rp.x0 + p) * step;
+      int a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+      if (p >= rp.n || !warp_sample(src, fj, A, (double)x, Y, w, h, b)) continue;
+      ra.px(x, a);
+      bool in = true;
+#pragma unroll
+      for (int c = 0; c < CN; c++) in = in && a[c] >= lo && a[c] <= hi && b[c] >= lo && b[c] <= hi;
+      if (!in) continue;
+      s[0] += 1;
+#pragma unroll
+      for (int c = 0; c < CN; c++) { s[1 + c] += (uint32_t)a[c]; s[4 + c] += (uint32_t)b[c]; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < EVH_EXPO_NSTATS; k++)
+    for (int m = 32; m > 0; m >>= 1) s[k] += __shfl_xor(s[k], m);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < EVH_EXPO_NSTATS; k++) part[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < EVH_EXPO_NSTATS) {
+    const uint32_t sum = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (sum) atomicAdd(&stats[(int64_t)pair * EVH_EXPO_NSTATS + threadIdx.x], (unsigned long long)sum);
   }
 }
 
@@ -1139,6 +1309,115 @@ int launch(evh_ctx* c, const RayArgs& R) {
   return launched(c);
 }
 
+// ---- the blended mosaic: feathered seams and exposure gains, on the plane or on a surface -------------------------------------------
+// W: the warp entries' arguments with mode = the blend mode and out possibly NULL; col, row: the ray form's tables
+struct BlendArgs {
+  WarpArgs W; bool ray; const double* col; const double* row; int feather; const uint16_t* gain; uint64_t* acc; int acc_in;
+  bool idle() const { return false; }       // no frames: the picture of the incoming state
+};
+int check(evh_ctx* c, const BlendArgs& B) {
+  const WarpArgs& A = B.W;
+  const std::string W = std::string(A.who) + ": ";
+  const int cn = A.F.channels;
+  if (int rc = need_source(c, W, A.F)) return rc;
+  if (!A.M || (B.ray && (!B.col || !B.row))) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (!A.out && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + "d_out and d_acc are both NULL");
+  if (B.acc_in && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + "acc_in without d_acc");
+  if ((uintptr_t)B.acc & 7) return evh_fail(c, EVH_ERR_INVALID, W + "d_acc must be 8-byte aligned");
+  if (int rc = need_channels(c, W, A.F)) return rc;
+  if (A.nframes < 0 || A.sw < 1 || A.sh < 1 || A.dw < 1 || A.dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (A.mode != EVH_BLEND_FEATHER && A.mode != EVH_BLEND_SEAM) return evh_fail(c, EVH_ERR_INVALID, W + "unknown mode");
+  if (B.feather < 0 || B.feather > 65535) return evh_fail(c, EVH_ERR_INVALID, W + "feather must lie in 0..65535");
+  if (int rc = need_below_2_26(c, W, "source", A.sw, A.sh)) return rc;
+  if (int rc = need_area(c, W, "dw * dh", A.dw, A.dh)) return rc;
+  if (A.nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  const int64_t canvas = (int64_t)(A.dh - 1) * A.out_stride + (int64_t)A.dw * cn;
+  if (A.out && A.out_stride < (int64_t)A.dw * cn) return evh_fail(c, EVH_ERR_INVALID, W + "output stride smaller than a row");
+  if (int rc = need_source_stride(c, W, A.F, A.sw, A.sh, A.nframes > 1)) return rc;
+  if (A.out && A.bg && A.bg != A.out && meet({A.bg, canvas, ""}, {A.out, canvas, ""}))
+    return evh_fail(c, EVH_ERR_INVALID, W + "d_background overlaps d_out");
+  if (A.nframes > 0)
+    if (int rc = need_planes(c, A.who, A.F, A.nframes, A.sw, A.sh)) return rc;
+  // the state apart from everything, the picture apart from the frames and the gains
+  Span src[3];
+  source_spans(A.F, A.nframes, A.sw, A.sh, src);
+  const Span gain = {B.gain, (int64_t)A.nframes * 6, "d_gain"};
+  const Span state[1] = {{B.acc, (int64_t)A.dw * A.dh * (cn + 1) * 8, "d_acc"}};
+  const Span others[9] = {{A.out, A.out ? canvas : 0, "d_out"}, {A.out ? A.bg : nullptr, canvas, "d_background"}, gain,
+                          {A.M, (int64_t)A.nframes * 72, B.ray ? "d_A" : "d_M"}, {B.col, (int64_t)A.dw * 16, "d_col"},
+                          {B.row, (int64_t)A.dh * 8, "d_row"}, src[0], src[1], src[2]};
+  if (int rc = need_apart(c, W, state, others)) return rc;
+  const Span picture[1] = {{A.out, A.out ? canvas : 0, "d_out"}};
+  const Span inputs[4] = {gain, src[0], src[1], src[2]};
+  return need_apart(c, W, picture, inputs);
+}
+// k_blend over the canvas; nframes may be 0, and one of out and acc NULL
+int launch(evh_ctx* c, const BlendArgs& B) {
+  const WarpArgs& A = B.W;
+  const unsigned npix = (unsigned)A.dw * (unsigned)A.dh;
+  const int vec = ((uintptr_t)B.acc & 15) == 0 ? 2 : 0;
+  const BlendGeo G = {A.M, A.inverse_map, A.ox, A.oy, B.col, B.row};
+  with_source(A.F, [&](auto cn, const auto& S) {
+    constexpr int CN = decltype(cn)::value;
+    using SRC = std::decay_t<decltype(S)>;
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((npix + 255) / 256), dim3(256), 0, c->stream, S, A.nframes, A.sw, A.sh, G, B.feather, B.gain,
+                         reinterpret_cast<unsigned long long*>(B.acc), B.acc_in, A.out ? A.bg : nullptr, A.out, A.dw,
+                         A.out_stride, npix, vec);
+    };
+    if (B.ray) {
+      if (A.mode == EVH_BLEND_FEATHER) go(k_blend<EVH_BLEND_FEATHER, CN, SRC, true>);
+      else go(k_blend<EVH_BLEND_SEAM, CN, SRC, true>);
+    } else {
+      if (A.mode == EVH_BLEND_FEATHER) go(k_blend<EVH_BLEND_FEATHER, CN, SRC, false>);
+      else go(k_blend<EVH_BLEND_SEAM, CN, SRC, false>);
+    }
+  });
+  return launched(c);
+}
+
+// ---- the sums behind exposure gains: two frames of a batch compared where one maps onto the other ----------------------------------
+struct ExposureArgs {
+  const char* who; EvhFrames F; int nframes, w, h; const int32_t* pairs; int npairs; const double* M; int step, lo, hi;
+  uint64_t* stats;
+  bool idle() const { return npairs == 0; }
+};
+int check(evh_ctx* c, const ExposureArgs& A) {
+  const std::string W = std::string(A.who) + ": ";
+  if (int rc = need_source(c, W, A.F)) return rc;
+  if (!A.pairs || !A.M || !A.stats) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (int rc = need_channels(c, W, A.F)) return rc;
+  if (A.nframes < 0 || A.npairs < 0 || A.w < 1 || A.h < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or negative count");
+  if (A.step < 1 || A.step > 64) return evh_fail(c, EVH_ERR_INVALID, W + "step must lie in 1..64");
+  if (A.lo < 0 || A.hi > 255 || A.lo > A.hi) return evh_fail(c, EVH_ERR_INVALID, W + "lo and hi must satisfy 0 <= lo <= hi <= 255");
+  if (int rc = need_below_2_26(c, W, "frame", A.w, A.h)) return rc;
+  if (int rc = need_area(c, W, "w * h", A.w, A.h)) return rc;
+  if (A.npairs > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 pairs per call");
+  if (A.nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  if (int rc = need_source_stride(c, W, A.F, A.w, A.h, A.nframes > 1)) return rc;
+  if (A.npairs == 0) return EVH_SUCCESS;
+  if (A.nframes > 0)
+    if (int rc = need_planes(c, A.who, A.F, A.nframes, A.w, A.h)) return rc;
+  // the sums apart from everything that is read
+  Span src[3];
+  source_spans(A.F, A.nframes, A.w, A.h, src);
+  const Span outs[1] = {{A.stats, (int64_t)A.npairs * EVH_EXPO_NSTATS * (int64_t)sizeof(uint64_t), "d_stats"}};
+  const Span ins[5] = {{A.pairs, (int64_t)A.npairs * 8, "d_pairs"}, {A.M, (int64_t)A.npairs * 72, "d_M"}, src[0], src[1], src[2]};
+  return need_apart(c, W, outs, ins);
+}
+// d_stats zeroed, then k_pair_exposure over the pairs
+int launch(evh_ctx* c, const ExposureArgs& A) {
+  EVH_HIP(c, hipMemsetAsync(A.stats, 0, (size_t)A.npairs * EVH_EXPO_NSTATS * sizeof(uint64_t), c->stream));
+  const int gw = (A.w + A.step - 1) / A.step, gh = (A.h + A.step - 1) / A.step;
+  const Runs R = runs_of(gw, gh);
+  with_source(A.F, [&](auto cn, const auto& S) {
+    hipLaunchKernelGGL((k_pair_exposure<decltype(cn)::value, std::decay_t<decltype(S)>>), dim3((R.n + 255) / 256, A.npairs),
+                       dim3(256), 0, c->stream, S, A.nframes, A.w, A.h, A.pairs, A.M, A.step, A.lo, A.hi,
+                       reinterpret_cast<unsigned long long*>(A.stats), gw, R.per_row, R.n);
+  });
+  return launched(c);
+}
+
 // ---- the score of a homography: the motion-compensated residual of a pair ------------------------------------------------------
 struct ResidualArgs {
   const char* who; EvhFrames F; int npairs, frame_step, w, h; const double* M; int threshold; uint64_t* stats; uint8_t* out;
@@ -1450,6 +1729,54 @@ int evh_warp_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, 
                                 int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride) {
   return run(c, RayArgs{{"evh_warp_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, mode, d_background, d_out,
                          dw, dh, out_row_stride, out_frame_stride, 0, 0}, d_col, d_row});
+}
+
+int evh_blend_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                          int64_t frame_stride, const double* d_M, int inverse_map, int mode, int feather, const uint16_t* d_gain,
+                          uint64_t* d_acc, int acc_in, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                          int64_t out_row_stride, int ox, int oy) {
+  return run(c, BlendArgs{{"evh_blend_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh, d_M,
+                           inverse_map, mode, d_background, d_out, dw, dh, out_row_stride, 0, ox, oy},
+                          false, nullptr, nullptr, feather, d_gain, d_acc, acc_in});
+}
+
+int evh_blend_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M, int inverse_map,
+                                 int mode, int feather, const uint16_t* d_gain, uint64_t* d_acc, int acc_in,
+                                 const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int ox, int oy) {
+  return run(c, BlendArgs{{"evh_blend_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, mode, d_background,
+                           d_out, dw, dh, out_row_stride, 0, ox, oy},
+                          false, nullptr, nullptr, feather, d_gain, d_acc, acc_in});
+}
+
+int evh_blend_ray_surface(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                          int64_t frame_stride, const double* d_A, const double* d_col, const double* d_row, int mode, int feather,
+                          const uint16_t* d_gain, uint64_t* d_acc, int acc_in, const uint8_t* d_background, uint8_t* d_out, int dw,
+                          int dh, int64_t out_row_stride) {
+  return run(c, BlendArgs{{"evh_blend_ray_surface", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh, d_A,
+                           1, mode, d_background, d_out, dw, dh, out_row_stride, 0, 0, 0},
+                          true, d_col, d_row, feather, d_gain, d_acc, acc_in});
+}
+
+int evh_blend_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                 const double* d_col, const double* d_row, int mode, int feather, const uint16_t* d_gain,
+                                 uint64_t* d_acc, int acc_in, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                 int64_t out_row_stride) {
+  return run(c, BlendArgs{{"evh_blend_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, mode, d_background, d_out, dw,
+                           dh, out_row_stride, 0, 0, 0},
+                          true, d_col, d_row, feather, d_gain, d_acc, acc_in});
+}
+
+int evh_pair_exposure(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels, int64_t row_stride,
+                      int64_t frame_stride, const int32_t* d_pairs, int npairs, const double* d_M, int step, int lo, int hi,
+                      uint64_t* d_stats) {
+  return run(c, ExposureArgs{"evh_pair_exposure", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, w, h, d_pairs,
+                             npairs, d_M, step, lo, hi, d_stats});
+}
+
+int evh_pair_exposure_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int h, const int32_t* d_pairs, int npairs,
+                             const double* d_M, int step, int lo, int hi, uint64_t* d_stats) {
+  return run(c, ExposureArgs{"evh_pair_exposure_yuv420", yuv420_frames(src), nframes, w, h, d_pairs, npairs, d_M, step, lo, hi,
+                             d_stats});
 }
 
 int evh_pair_residual(evh_ctx* c, const uint8_t* d_frames, int npairs, int frame_step, int w, int h, int channels,

@@ -105,8 +105,10 @@ class FrameReader:
 
     def chunks(self, size, overlap, limit=None):
         """Generator of (start, frames): frames = host[:n], valid until the next step, frames[0] being frame `start` (0-based)
-        of the capture.  Consecutive chunks share `overlap` (0 or 1) frames; every chunk has at least one frame no earlier
+        of the capture.  Consecutive chunks share `overlap` (0 .. size - 1) frames; every chunk has at least one frame no earlier
         chunk had and at least overlap + 1 frames.  No more than `limit` frames are consumed (the first one counts)."""
+        if not 0 <= overlap < size:
+            raise ValueError("chunks of %d frames cannot share %d" % (size, overlap))
         host = self.buffer(size)
         start, n = 0, 1
         while True:
@@ -116,7 +118,7 @@ class FrameReader:
                 return
             yield start, host[:n]
             if overlap:
-                host[0] = host[n - 1]
+                host[:overlap] = host[n - overlap:n].copy()
             start, n = start + n - overlap, overlap
 
 

@@ -1,6 +1,6 @@
 """Command-line driver of the stabilised view, with the arguments of the reference's
-evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison, --plate
-and --surface:
+evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison, --plate,
+--surface and --blend:
 
     python -m evenvizion_amd.stabilize --path_to_homography_dict run1/video/dict_with_homography_matrix.json \
            --path_to_video video.mp4 --experiment_name run1 --comparison 1
@@ -24,6 +24,12 @@ evenvizion_amd.stabilization:
                      90 degrees; evenvizion_amd.surface), and surface_report.json: the focal length (--focal F in pixels of the
                      resized frame, estimated from the matrices without it), the fit residual of the rotation model per pair, the
                      canvas geometry.  --scale applies; --placement does not.
+
+    --mode mosaic --blend feather | seam
+                     mosaic_blend.ppm instead of the last-frame-wins mosaic: every covering frame weighted by its distance to
+                     its own border, rising over --feather PX pixels (feather), or per pixel the frame whose border is farthest
+                     away (seam); with --exposure 1 the video is first read once more for the overlap sums, one gain per frame
+                     and channel is solved from them (exposure_gains.json) and applied.  On the plane or with --surface.
 
 What is still missing from the reference's picture is its text ("Original", "EvenVizion").  The dimming is the arithmetic
 include/evhip.h states for evh_trail_fixed_plane, not cv2.cvtColor compared byte for byte.
@@ -68,6 +74,11 @@ def parser():
                          "also writes surface_report.json")
     ap.add_argument("--focal", type=float, default=None,
                     help="surface: focal length in pixels of the resized frame; estimated from the matrices when not given")
+    ap.add_argument("--blend", choices=("feather", "seam"), default=None,
+                    help="mosaic only: blend the covering frames (evenvizion_amd.blend) and write mosaic_blend.ppm")
+    ap.add_argument("--feather", type=float, default=32.0, help="blend: pixels over which a frame's weight rises from its border")
+    ap.add_argument("--exposure", type=int, choices=(0, 1), default=0,
+                    help="blend: 1 solves one gain per frame and channel from the overlaps and writes exposure_gains.json")
     return ap
 
 
@@ -86,6 +97,12 @@ def main(argv=None):
         ap.error("--focal needs --surface")
     if args.focal is not None and not args.focal > 0:
         ap.error("--focal must be positive")
+    if args.blend and (args.mode != "mosaic" or args.trail or args.comparison or args.plate):
+        ap.error("--blend needs --mode mosaic, without --trail, --comparison or --plate")
+    if not args.blend and (args.exposure or args.feather != 32.0):
+        ap.error("--feather and --exposure need --blend")
+    if not 0 <= args.feather <= 2047:
+        ap.error("--feather lies in 0..2047 pixels")
     from .component import open_capture
     from .processing.utils import read_homography_dict, superposition_dict
     from .stabilization import comparison_frames, stabilized_frames, write_ppm
@@ -94,6 +111,28 @@ def main(argv=None):
     os.makedirs(save_folder, exist_ok=True)
     homography_dict, resize_info = read_homography_dict(args.path_to_homography_dict)
     sup = superposition_dict(homography_dict)
+    if args.blend:
+        import json
+        from .blend import blended_mosaic, exposure_pairs, exposure_stats, solve_gains, surface_pair_maps
+        placement = "warp" if args.surface else args.placement
+        gains = None
+        if args.exposure:
+            keys = [k for k in sup if k != "resize_info"]
+            maps = None
+            if args.surface:
+                from .surface import surface_model
+                model = surface_model(sup, resize_info, surface=args.surface, focal=args.focal, scale=args.scale)
+                maps = surface_pair_maps(model, keys, exposure_pairs(len(keys)))
+            pairs, stats = exposure_stats(cap, sup, resize_info, maps=maps)
+            gains = solve_gains(pairs, stats, len(keys))
+            with open(os.path.join(save_folder, "exposure_gains.json"), "w") as f:
+                json.dump({"pairs": len(pairs), "pairs_used": int((stats[:, 0] >= 64).sum()),
+                           "gains": {str(k): [float(v) for v in g] for k, g in zip(keys, gains)}}, f, indent=1)
+            cap, _, _ = open_capture(args.path_to_video)          # the second pass starts from the first frame again
+        picture = blended_mosaic(cap, sup, resize_info, blend=args.blend, feather_px=args.feather, gains=gains, placement=placement,
+                                 scale=args.scale, surface=args.surface, focal=args.focal)
+        write_ppm(os.path.join(save_folder, "mosaic_blend.ppm"), picture)
+        return save_folder
     if args.surface:
         import json
         from .surface import surface_frames, surface_model, surface_report

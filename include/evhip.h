@@ -25,6 +25,9 @@
  *                                 visualization/stabilization.py:129-172, 220-249
  *   evh_warp_ray_surface[_yuv420] no counterpart: the cylindrical coordinate system the reference's known-issues.md names as the way
  *                                 past camera rotations above 90 degrees -- frames placed on a cylinder, a sphere or a plane of rays
+ *   evh_blend_fixed_plane[_yuv420], evh_blend_ray_surface[_yuv420] no counterpart: the mosaic with feathered seams (or the frame
+ *                                 nearest its centre per pixel) and per-frame exposure gains, on the plane or on a surface
+ *   evh_pair_exposure[_yuv420]    no counterpart: the overlap sums from which those gains are solved
  *   evh_trail_fixed_plane[_yuv420] stabilize_view with decrease_brightness and change_frame_location: earlier frames dimmed,
  *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
  *   evh_plate_fixed_plane[_yuv420] no counterpart: the "video motion segmentation" the reference's known-issues.md considers --
@@ -509,6 +512,95 @@ int evh_warp_ray_surface(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int
 int evh_warp_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
                                 const double* d_col, const double* d_row, int mode, const uint8_t* d_background, uint8_t* d_out,
                                 int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride);
+
+/* ---- the blended mosaic: feathered seams and exposure gains, on the plane or on a surface --------------------------------------- */
+/* EVH_WARP_MOSAIC gives a canvas pixel to the last frame that covers it: every frame edge stays as a seam, every change of the
+ * camera's exposure as a step.  These entries reduce the covering frames otherwise.  The frames, d_M / inverse_map / ox / oy
+ * (evh_blend_fixed_plane) or d_A / d_col / d_row (evh_blend_ray_surface), the canvas dw x dh, channels, the strides, the plane
+ * forms and d_background are exactly evh_warp_fixed_plane's and evh_warp_ray_surface's, tw > 0 of the ray form included.
+ *   mode     EVH_BLEND_FEATHER or EVH_BLEND_SEAM;
+ *   feather  F, in 1/32 pixels, 0..65535;
+ *   d_gain   u16[nframes][3] (DEVICE), Q12: 4096 is 1.0.  Column c serves channel c, gray uses column 0.  NULL = all 4096.  Any
+ *            u16 value is valid;
+ *   d_acc    u64[dh][dw][channels + 1] (DEVICE), tight, 8-byte aligned, in and out; may be NULL;
+ *   acc_in   non-zero: the state starts from d_acc; zero: from zeros;
+ *   d_out    dh rows of dw*channels bytes at out_row_stride; may be NULL: the call then only advances the state.
+ * Per canvas pixel the STATE is acc[0 .. cn-1] and acc[cn], unsigned 64-bit.  Frames are taken in order, k = 0 .. nframes-1:
+ *   1. Coverage, the position (U, V) and the sample s_c per channel are exactly the warp entry's: positions in 1/32 pixels rounded
+ *      half to even, the comparisons in double, the four taps with >> 10, a tap of weight 0 not read; a NaN, singular or
+ *      horizon-crossing matrix covers nothing and reads nothing.
+ *   2. The WEIGHT of a covering frame, in int32 from the integers U and V: du = min(U, 32*(sw-1) - U), dv = min(V, 32*(sh-1) - V),
+ *      d = min(du, dv), w = min(d, F) + 1: the distance to the nearest frame edge, cut at the feather width.  w is never 0, and
+ *      F = 0 makes every w equal to 1.
+ *   3. With t_c = s_c * g_c (g = d_gain[k]; at most 255 * 65535 < 2^24):
+ *      EVH_BLEND_FEATHER  acc[c] += w * t_c, acc[cn] += w;
+ *      EVH_BLEND_SEAM     if w > acc[cn]: acc[c] = t_c for every c, acc[cn] = w.  The comparison is strict: among equal weights
+ *                         the earliest frame holds, and the first covering frame always takes the pixel.
+ *   4. After the last frame the state is stored to d_acc, if given, and if d_out is given, with den = acc[cn]:
+ *      den == 0           the pixel takes d_background's bytes, or zeros when that is NULL;
+ *      EVH_BLEND_FEATHER  out_c = min(255, (acc[c] + (den << 11)) / (den << 12)), the division rounding down, in u64;
+ *      EVH_BLEND_SEAM     out_c = min(255, (acc[c] + 2048) >> 12).
+ * BOUNDS, with at most 65535 frames entering one state over all the calls that carry it: w <= 65536 and t_c < 2^24, so acc[c] stays
+ * below 2^56, den below 2^32 and den << 12 below 2^44: nothing wraps.  The formulas hold unwrapped for ANY handed-in state with
+ * acc[c] < 2^62 and den < 2^44 (a state the entry did not write is the caller's to keep inside these).
+ * What follows from the rules: a pixel covered by one frame with gain 4096 holds exactly the warp entry's byte, in both modes and
+ * for any F; frames that all show the same value at a pixel blend to that value; d_gain == NULL equals a table of 4096; calls that
+ * carry d_acc (acc_in != 0 from the second on) equal one call over all their frames, byte for byte and state for state; the ray
+ * form with the plane's tables equals the plane form with inverse_map != 0 wherever tw > 0; the plane forms equal
+ * evh_yuv420_to_bgr followed by the BGR forms.
+ * Every byte of every output row inside dw*channels is written, bytes between rows are not.  d_background == d_out is allowed (a
+ * thread reads only the bytes it writes); d_background is not read when d_out is NULL.  Only caller buffers are used; one launch
+ * on the context's stream, no synchronisation.  nframes == 0 succeeds and writes the picture of the incoming state.
+ * Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: everything the warp entries refuse (d_out may be
+ * NULL here, its stride then is not looked at), an unknown mode, feather outside 0..65535, d_out and d_acc both NULL, acc_in != 0
+ * with d_acc NULL, d_acc not 8-byte aligned, d_acc overlapping any other buffer of the call, d_out overlapping the frames or
+ * d_gain, d_background overlapping d_out other than being it; EVH_ERR_CAPACITY: sw or sh >= 2^26, dw*dh > INT_MAX,
+ * nframes > 65535.  Speed, not results, depends on alignment: d_acc a multiple of 16 lets a thread move its pixel's state as
+ * 128-bit words.                                                                                                                */
+enum { EVH_BLEND_FEATHER = 0, EVH_BLEND_SEAM = 1 };
+int evh_blend_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                          int64_t row_stride, int64_t frame_stride, const double* d_M, int inverse_map, int mode,
+                          int feather /* 0..65535 */, const uint16_t* d_gain /* u16[nframes,3] DEVICE, may be NULL */,
+                          uint64_t* d_acc /* u64[dh,dw,channels+1] DEVICE, may be NULL */, int acc_in,
+                          const uint8_t* d_background, uint8_t* d_out /* may be NULL */, int dw, int dh, int64_t out_row_stride,
+                          int ox, int oy);
+int evh_blend_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                 int inverse_map, int mode, int feather, const uint16_t* d_gain, uint64_t* d_acc, int acc_in,
+                                 const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int ox,
+                                 int oy);
+int evh_blend_ray_surface(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                          int64_t row_stride, int64_t frame_stride, const double* d_A, const double* d_col, const double* d_row,
+                          int mode, int feather, const uint16_t* d_gain, uint64_t* d_acc, int acc_in,
+                          const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride);
+int evh_blend_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                 const double* d_col, const double* d_row, int mode, int feather, const uint16_t* d_gain,
+                                 uint64_t* d_acc, int acc_in, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                 int64_t out_row_stride);
+
+/* ---- the sums behind exposure gains: two frames of a batch compared where one maps onto the other -------------------------------- */
+/* What a gain solve needs (Brown and Lowe's gain compensation: per overlapping pair the number of pixels and the mean of either
+ * frame over them), for arbitrary pairs of the nframes frames of w x h at d_frames; evh_pair_residual is tied to neighbours, gray
+ * and differences.  d_pairs i32[npairs,2] (DEVICE): pair p = (i, j).  d_M f64[npairs,9] (DEVICE): d_M[p] maps pixels of frame i to
+ * pixels of frame j and is used as it is.  Over the pixels (x, y) of frame i with x % step == 0 and y % step == 0:
+ *   a = the pixel's bytes; b = the sample of frame j at d_M[p] . (x, y), coverage and sample exactly evh_warp_fixed_plane's with
+ *   A = d_M[p], sw = w, sh = h (as in evh_pair_residual);
+ *   the pixel COUNTS iff it is covered and every channel of a and of b lies in [lo, hi] -- clipped pixels bias a gain;
+ *   d_stats[p][0] += 1, [1 + c] += a_c, [4 + c] += b_c; gray uses [1] and [4], the others stay 0.
+ * d_stats u64[npairs,EVH_EXPO_NSTATS] (DEVICE): the entry zeroes it itself, stream-ordered.  A pair with an index outside
+ * 0 .. nframes-1 reads nothing and has seven zeros: the indices live on the device, so the kernel checks them.  i == j is allowed.
+ * The sums are exact integers (below 2^39) and do not depend on the order of addition.  Only caller buffers are used; one memset
+ * and one launch on the context's stream, no synchronisation.  Refused before anything is launched, outputs untouched --
+ * EVH_ERR_INVALID: NULL d_frames (a NULL plane), d_pairs, d_M or d_stats, channels not 1 or 3, w or h < 1, nframes or npairs < 0,
+ * step outside 1..64, lo or hi outside 0..255 or lo > hi, a stride shorter than its row / frame, d_stats overlapping the frames,
+ * d_pairs or d_M; EVH_ERR_CAPACITY: w or h >= 2^26, w*h > INT_MAX, npairs > 65535, nframes > 65535.  npairs == 0 succeeds and
+ * does nothing.  The plane form converts every pixel and tap as evh_yuv420_to_bgr does.                                         */
+enum { EVH_EXPO_NSTATS = 7 };
+int evh_pair_exposure(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int w, int h, int channels /* 1 | 3 */,
+                      int64_t row_stride, int64_t frame_stride, const int32_t* d_pairs /* i32[npairs,2] DEVICE */, int npairs,
+                      const double* d_M /* f64[npairs,9] DEVICE */, int step /* 1..64 */, int lo, int hi /* 0..255, lo <= hi */,
+                      uint64_t* d_stats /* u64[npairs,7] DEVICE */);
+int evh_pair_exposure_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, const int32_t* d_pairs, int npairs,
+                             const double* d_M, int step, int lo, int hi, uint64_t* d_stats);
 
 /* ---- the trail: earlier frames fade out behind the current one (stabilization.py:21-97, 129-172) -------------------------- */
 /* What stabilize_view does to its canvas per frame -- paste, white outline on a copy, both through 8-bit BGR -> HSV -> BGR with

@@ -26,6 +26,10 @@ args = ap.parse_args()
 
 sys.path.insert(0, os.path.abspath(args.root))
 from evenvizion_amd import capture, heatmap, moving, registration, stabilization
+try:
+    from evenvizion_amd import blend
+except ImportError:                      # --root names a checkout from before the blended mosaic
+    blend = None
 from evenvizion_amd.processing.utils import superposition_dict
 from evenvizion_amd.processing.video_processing import get_homography_dict
 
@@ -74,6 +78,8 @@ DRIVERS = [
     ("refine_homography_dict", lambda ingest: json.dumps(moving.refine_homography_dict(video(), first, plate, ingest=ingest))),
     ("get_homography_dict_sink", matching),
 ]
+if blend is not None:
+    DRIVERS.append(("blended_mosaic", lambda ingest: blend.blended_mosaic(video(), sup, info, ingest=ingest).tobytes()))
 cases = [(name, ingest, run) for name, run in DRIVERS for ingest in ("bgr", "auto")]
 res = dict(root="this tree" if os.path.abspath(args.root) == HERE else args.root, video=os.path.basename(args.video),
            frames=len(first), repeats=args.repeats, seconds={}, sha1={})

@@ -145,6 +145,8 @@ SIGNATURES = {
     "evh_pair_residual_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i64, _i64]),
     "evh_pair_refine": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     "evh_pair_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "evh_canvas_refine": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "evh_canvas_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -1012,6 +1014,49 @@ class Context:
         """pair_refine on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel and tap converted as
         yuv420_to_bgr converts it (evh_pair_refine_yuv420)."""
         return self._pair_refine(True, planes, mats, iters, clip, out, info, normal, frame_step, size)
+
+    # ---- direct alignment against the mosaic ----
+    def _canvas_refine(self, planes, frames, canvas, mats, count, min_cover, iters, clip, out, info, normal, size):
+        import torch
+        self._enter()
+        planes, head, n, w, h, cn = self._frame_source(frames, size, planes=planes)
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        cp, dw, dh, crs, _ = self._image_rows(canvas, cn, 0, "canvas")
+        kp, krs = None, 0
+        if count is not None:
+            kp, kw, kh, krs, _ = self._image_rows(count, 1, 0, "count")
+            if (kw, kh) != (dw, dh):
+                raise ValueError("count must be [dh,dw] for a canvas [dh,dw(,3)]")
+        dev = "cuda:%d" % self.device
+        if out is None:
+            out = torch.empty((n, 9), dtype=torch.float64, device=dev)
+        if info is None:
+            info = torch.empty((n, REFINE_NINFO), dtype=torch.int64, device=dev)
+        self._dev_tensor(out, torch.float64, 9 * n, "out must be a contiguous CUDA float64 tensor of n*9 elements")
+        self._dev_tensor(info, torch.int64, (n, REFINE_NINFO), "info must be a contiguous CUDA int64 tensor [n,%d]", REFINE_NINFO)
+        if normal is not None:
+            self._dev_tensor(normal, torch.float64, (n, REFINE_NSUMS), "normal must be a contiguous CUDA float64 tensor [n,%d]", REFINE_NSUMS)
+        if n == 0:                           # empty tensors have no address to hand over
+            return out, info
+        tail = (cp, dw, dh, crs, kp, krs, int(min_cover), mats.data_ptr(), int(iters), int(clip), out.data_ptr(), info.data_ptr(),
+                _ptr(normal))
+        self._check(self._form("evh_canvas_refine", planes)(self.h, *head, *tail))
+        return out, info
+
+    def canvas_refine(self, frames, canvas, mats, count=None, min_cover=1, iters=8, clip=255, out=None, info=None, normal=None):
+        """Frames aligned against a canvas (evh_canvas_refine, the contract is stated in include/evhip.h): pair_refine with the
+        previous frame replaced by `canvas`, CUDA uint8 [dh,dw] (gray frames) or [dh,dw,3], rows may be strided.  frames: as in
+        pair_refine, n of them; mats: CUDA float64, n*9 contiguous elements, pixel of frame k -> pixel of the canvas.  count: CUDA
+        uint8 [dh,dw], rows may be strided, or None = every canvas pixel is valid; a pixel counts where count >= min_cover
+        (1..255).  out, info, normal: as in pair_refine, one row per frame; out and info are returned.  iters=0: the score of
+        the frames against the canvas.  Does not synchronise."""
+        return self._canvas_refine(False, frames, canvas, mats, count, min_cover, iters, clip, out, info, normal, None)
+
+    def canvas_refine_yuv420(self, planes, canvas, mats, count=None, min_cover=1, iters=8, clip=255, out=None, info=None, normal=None,
+                             size=None):
+        """canvas_refine on decoded planes (see _yuv420; size=(w, h) for packed I420 frames) against a BGR canvas: every pixel of a
+        frame converted as yuv420_to_bgr converts it (evh_canvas_refine_yuv420)."""
+        return self._canvas_refine(True, planes, canvas, mats, count, min_cover, iters, clip, out, info, normal, size)
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

@@ -200,6 +200,33 @@ def _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, ch
     return on_surface, int(round(float(feather_px) * 32)), gains
 
 
+class CanvasPainter:
+    """A blended canvas that grows group by group, with its coverage: what registration.anchor_superposition aligns frames
+    against.  picture: uint8 [dh,dw,3], the blend of everything painted so far (evh_blend_fixed_plane's d_out, the state d_acc
+    carried from call to call, no gains); cover: uint8 [dh,dw], 255 where a frame has been painted, 0 elsewhere
+    (evh_warp_fixed_plane in mode "mosaic" on frames of 255s with the same matrices over the cover itself: blend and warp share
+    one coverage rule, so cover >= 1 is exactly "the picture holds a blended sample here").  No pixel is touched by torch."""
+
+    def __init__(self, dev, dw, dh, blend="feather", feather=1024):
+        import torch
+        self.blend, self.feather = blend, int(feather)
+        self.acc = torch.zeros((dh, dw, 4), dtype=torch.int64, device=dev)
+        self.picture = torch.zeros((dh, dw, 3), dtype=torch.uint8, device=dev)
+        self.cover = torch.zeros((dh, dw), dtype=torch.uint8, device=dev)
+        self.ones, self.carried = None, False
+
+    def paint(self, ctx, src, mats):
+        """src: CUDA uint8 [n,h,w,3]; mats: CUDA float64 [n,9], frame pixel -> canvas pixel (NaN: the frame is left out)."""
+        import torch
+        n, h, w = src.shape[:3]
+        if self.ones is None or self.ones.shape[0] < n or tuple(self.ones.shape[1:]) != (h, w):
+            self.ones = torch.full((n, h, w), 255, dtype=torch.uint8, device=src.device)
+        ctx.blend_fixed_plane(src, mats, (0, 0), out=self.picture, mode=self.blend, feather=self.feather, acc=self.acc,
+                              acc_in=self.carried)
+        ctx.warp_fixed_plane(self.ones[:n], mats, self.cover, "mosaic", (0, 0), background=self.cover)
+        self.carried = True
+
+
 def blended_mosaic(capture, superposition_homography_dict, resize_info, blend="feather", feather_px=32, gains=None,
                    placement="warp", scale=1.0, surface=None, focal=None, chunk_frames=32, ingest="auto"):
     """uint8 [dh,dw,3]: all frames of `capture` blended into one canvas on the device, the state carried from chunk to chunk.

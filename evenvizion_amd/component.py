@@ -31,6 +31,11 @@ with --reject_moving 1 (extension, default off; --path_to_video and --features O
                                        --moving_min_cover) before the final solve; the first dictionary stays as it is
     moving_rows.json                   {frame_no: {"rows", "moving", "rows_out"}} per pair
     registration_report_refined.json   with --registration_report 1: the refined dictionary scored like the first one.
+with --anchor_mosaic 1 (extension, default off; --path_to_video only) also frame-to-mosaic registration,
+    dict_with_homography_matrix_anchored.json   the dictionary of registration.anchored_homography_dict: every frame (or group of
+                                       --anchor_group frames) aligned against the blended mosaic of the frames before it
+                                       (evh_canvas_refine) and then painted into it; the first dictionary stays as it is
+    anchor_report.json                 the registration report of both dictionaries, the two canvas-score sums and a row per frame.
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
@@ -147,6 +152,13 @@ def parser():
                          "stays as it is (the video is read three times more)")
     ap.add_argument("--refine_levels", type=_int_in(1, 4), default=1, help="--refine_direct: pyramid levels, coarse to fine")
     ap.add_argument("--refine_iters", type=_int_in(0, 64), default=8, help="--refine_direct: steps tried per level")
+    ap.add_argument("--anchor_mosaic", type=int, choices=(0, 1), default=0,
+                    help="1: frame-to-mosaic registration, every frame aligned against the blended picture of the frames before it "
+                         "(extension; --path_to_video only): registration.anchored_homography_dict; writes "
+                         "dict_with_homography_matrix_anchored.json and anchor_report.json beside the first dictionary, which "
+                         "stays as it is (the video is read three times more)")
+    ap.add_argument("--anchor_group", type=_int_in(1, 65535), default=1,
+                    help="--anchor_mosaic: frames aligned and painted together (1: strictly frame by frame)")
     return ap
 
 
@@ -167,6 +179,8 @@ def main(argv=None):
             raise ValueError("--reject_moving takes one video (--path_to_video)")
         if args.refine_direct:
             raise ValueError("--refine_direct takes one video (--path_to_video)")
+        if args.anchor_mosaic:
+            raise ValueError("--anchor_mosaic takes one video (--path_to_video)")
         opened = [open_capture(spec) for spec in args.path_to_videos]
         kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
         results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
@@ -195,7 +209,26 @@ def main(argv=None):
         write_refined(args, save_folder, features)
     if args.refine_direct:
         write_direct(args, save_folder)
+    if args.anchor_mosaic:
+        write_anchored(args, save_folder)
     return save_folder
+
+
+def write_anchored(args, save_folder):
+    """--anchor_mosaic 1: the first pass's matrices anchored on their own mosaic, the anchored dictionary and the score of both
+    beside the first pass's files, which are left as they are.  The capture is opened again for each pass."""
+    from .processing.utils import read_homography_dict, superposition_dict
+    from . import registration
+    spec = args.path_to_video
+    first_pass, resize_info = read_homography_dict(os.path.join(save_folder, "dict_with_homography_matrix.json"))
+    got = registration.anchored_homography_dict(lambda: open_capture(spec)[0], superposition_dict(first_pass), resize_info,
+                                                group=args.anchor_group, ingest=args.ingest)
+    with open(os.path.join(save_folder, "dict_with_homography_matrix_anchored.json"), "w") as json_:
+        json.dump(dict(got["homography"], resize_info=resize_info), json_)
+    with open(os.path.join(save_folder, "anchor_report.json"), "w") as json_:
+        json.dump({"before": got["report_before"], "after": got["report_after"],
+                   "canvas_score_before": got["canvas_score_before"], "canvas_score_after": got["canvas_score_after"],
+                   "info": {str(k): v for k, v in got["info"].items()}}, json_)
 
 
 def write_direct(args, save_folder):

@@ -1,6 +1,6 @@
 // evh_plane.hip -- the products on the fixed plane and the pictures drawn from a batch's results: evh_warp_fixed_plane,
 // evh_warp_ray_surface, evh_blend_fixed_plane, evh_blend_ray_surface, evh_pair_residual, evh_pair_exposure, evh_pair_refine,
-// evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded 4:2:0 planes), evh_heatmap_render and
+// evh_canvas_refine, evh_trail_fixed_plane, evh_plate_fixed_plane, evh_rows_moving_filter (each also on decoded 4:2:0 planes), evh_heatmap_render and
 // evh_draw_matches.  Kernels first, then the host side: what the entries share (checks, launch
 // plumbing), then per product its arguments, check() -- every refusal comes before anything is enqueued -- and launch().
 #include "evh_devmath.h"
@@ -561,6 +561,117 @@ __global__ __launch_bounds__(256) void k_pair_refine_eval(SRC src, int frame_ste
   if (threadIdx.x < REFINE_SLOTS - 1) {
     const int k = threadIdx.x;
     double* o = part + ((int64_t)pair * gridDim.x + blockIdx.x) * REFINE_SLOTS + k;
+    if (k < EVH_REFINE_NSUMS) {
+      *o = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    } else {
+      unsigned long long u = 0;
+      for (int v = 0; v < 4; v++) u += (unsigned long long)__double_as_longlong(wsum[v][k]);
+      *o = __longlong_as_double((long long)u);
+    }
+  }
+}
+// Frame against canvas (include/evhip.h states the contract for evh_canvas_refine): k_pair_refine_eval with the previous frame
+// replaced by a canvas of dw x dh that has holes.  canvas_sample is warp_sample on the canvas -- the same position, coverage test,
+// taps and rounding, written out again because taking warp_sample apart moves instructions in the existing kernels
+// (profiles/surface_warp.txt) -- with the count read beside each tap: a tap of non-zero weight whose count lies below min_cover makes
+// the sample invalid, a tap of weight 0 is neither read nor asked.  count == NULL: every pixel is valid.  No tap leaves the canvas
+// (see warp_sample), so no count read does.
+__device__ __forceinline__ bool canvas_sample(const PackedSrc& canvas, const uint8_t* __restrict__ count, int64_t count_stride,
+                                              int min_cover, const WarpMap& A, double X, double Y, int dw, int dh, int (&v)[3]) {
+  const double tx = (A.a[0] * X + A.a[1] * Y) + A.a[2];
+  const double ty = (A.a[3] * X + A.a[4] * Y) + A.a[5];
+  const double tw = (A.a[6] * X + A.a[7] * Y) + A.a[8];
+  const double U = __builtin_rint(tx / tw * 32.0), V = __builtin_rint(ty / tw * 32.0);
+  if (!(U >= 0.0 && U <= (double)(32 * (dw - 1)) && V >= 0.0 && V <= (double)(32 * (dh - 1)))) return false;
+  const int u = (int)U, w = (int)V;
+  const int sx = u >> 5, fx = u & 31, sy = w >> 5, fy = w & 31;
+  const int cn = canvas.channels();
+  int p00[3] = {0, 0, 0}, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
+  int lowest = 255;                                       // the smallest count under a tap of non-zero weight
+  const uint8_t* c0 = count ? count + (int64_t)sy * count_stride + sx : nullptr;
+  const PackedSrc::Row r0 = canvas.row(0, sy);
+  r0.px(sx, p00);
+  if (count) lowest = c0[0];
+  if (fx) {
+    r0.px(sx + 1, p01);
+    if (count) lowest = min(lowest, (int)c0[1]);
+  }
+  if (fy) {
+    const PackedSrc::Row r1 = canvas.row(0, sy + 1);
+    r1.px(sx, p10);
+    if (count) lowest = min(lowest, (int)c0[count_stride]);
+    if (fx) {
+      r1.px(sx + 1, p11);
+      if (count) lowest = min(lowest, (int)c0[count_stride + 1]);
+    }
+  }
+  if (count && lowest < min_cover) return false;
+  const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+#pragma unroll
+  for (int c = 0; c < 3; c++) if (c < cn) v[c] = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + 512) >> 10;
+  return true;
+}
+// grid.y = frame; the runs, the accumulation, the tree and the partial sums are k_pair_refine_eval's for the same w, h (the frame is
+// the current frame there, the canvas the previous one), so k_pair_refine_step adds and judges them as they are.  The body is written
+// out a second time: folded onto one body templated on the sampler, k_pair_refine_eval's instances compile differently
+// (profiles/canvas_refine.txt).
+template <int CN, class SRC>
+__global__ __launch_bounds__(256) void k_canvas_refine_eval(SRC src, PackedSrc canvas, const uint8_t* __restrict__ count,
+                                                            int64_t count_stride, int min_cover, int w, int h, int dw, int dh,
+                                                            const double* __restrict__ M_in, const RefineState* __restrict__ state,
+                                                            double* __restrict__ part, int clip, int runs_per_row, unsigned nruns) {
+  __shared__ double wsum[4][REFINE_SLOTS];
+  const int cur = blockIdx.y;
+  if (!M_in && state[cur].done) return;                   // the whole workgroup: nobody waits at the barrier below
+  const double* M = M_in ? M_in + 9 * (int64_t)cur : state[cur].Mtry;
+  const WarpMap A = warp_map(M, 1);
+  double acc[EVH_REFINE_NSUMS];
+#pragma unroll
+  for (int k = 0; k < EVH_REFINE_NSUMS; k++) acc[k] = 0.0;
+  unsigned long long cov = 0, ssd = 0;
+  for (unsigned t = blockIdx.x * 256u + threadIdx.x; t < nruns; t += gridDim.x * 256u) {
+    const RunPos rp = run_pos(t, runs_per_row, w);
+    const int y = rp.y, x0 = rp.x0, n = rp.n;
+    const typename SRC::Row rc = src.row(cur, y);
+    const bool yin = y >= 1 && y <= h - 2;
+    const double Y = (double)y, Yc = (double)(2 * y - (h - 1));
+#pragma unroll
+    for (int p = 0; p < WARP_RUN; p++) {
+      int s[3] = {0, 0, 0};
+      const int x = x0 + p;
+      if (p >= n || !canvas_sample(canvas, count, count_stride, min_cover, A, (double)x, Y, dw, dh, s)) continue;
+      const int r = gray_at<CN>(rc, x) - gray_px<CN>(s);
+      cov += 1; ssd += (unsigned)(r * r);
+      if (!yin || x < 1 || x > w - 2 || abs(r) > clip) continue;
+      const int gxi = gray_at<CN>(rc, x + 1) - gray_at<CN>(rc, x - 1);
+      const int gyi = gray_at<CN>(src.row(cur, y + 1), x) - gray_at<CN>(src.row(cur, y - 1), x);
+      const double gx = (double)gxi, gy = (double)gyi, Xc = (double)(2 * x - (w - 1)), rd = (double)r;
+      const double sxy = gx * Xc + gy * Yc;                 // integers below 2^53: every operation here is exact
+      const double J[8] = {gx * Xc, gx * Yc, gx, gy * Xc, gy * Yc, gy, -Xc * sxy, -Yc * sxy};
+      int k = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int j = i; j < 8; j++) acc[k++] += J[i] * J[j];
+#pragma unroll
+      for (int i = 0; i < 8; i++) acc[36 + i] += J[i] * rd;
+      acc[44] += 1.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < EVH_REFINE_NSUMS; k++)
+    for (int m = 32; m > 0; m >>= 1) acc[k] += __shfl_xor(acc[k], m);
+  for (int m = 32; m > 0; m >>= 1) { cov += __shfl_xor(cov, m); ssd += __shfl_xor(ssd, m); }
+  if ((threadIdx.x & 63) == 0) {
+    double* o = wsum[threadIdx.x >> 6];
+#pragma unroll
+    for (int k = 0; k < EVH_REFINE_NSUMS; k++) o[k] = acc[k];
+    o[45] = __longlong_as_double((long long)cov); o[46] = __longlong_as_double((long long)ssd);
+  }
+  __syncthreads();
+  if (threadIdx.x < REFINE_SLOTS - 1) {
+    const int k = threadIdx.x;
+    double* o = part + ((int64_t)cur * gridDim.x + blockIdx.x) * REFINE_SLOTS + k;
     if (k < EVH_REFINE_NSUMS) {
       *o = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
     } else {
@@ -1526,6 +1637,70 @@ int launch(evh_ctx* c, const RefineArgs& A) {
   return rc;
 }
 
+// ---- direct alignment against the mosaic: a frame's matrix refined on a canvas with holes -----------------------------------------
+struct CanvasRefineArgs {
+  const char* who; EvhFrames F; int nframes, w, h; const uint8_t* canvas; int dw, dh; int64_t canvas_stride; const uint8_t* count;
+  int64_t count_stride; int min_cover; const double* M_in; int iters, clip; double* M_out; uint64_t* info; double* normal;
+  bool idle() const { return nframes == 0; }
+};
+int check(evh_ctx* c, const CanvasRefineArgs& A) {
+  const std::string W = std::string(A.who) + ": ";
+  if (int rc = need_source(c, W, A.F)) return rc;
+  if (!A.canvas || !A.M_in || !A.M_out || !A.info) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
+  if (int rc = need_channels(c, W, A.F)) return rc;
+  if (A.nframes < 0 || A.w < 1 || A.h < 1 || A.dw < 1 || A.dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (A.iters < 0 || A.iters > EVH_REFINE_MAX_ITERS) return evh_fail(c, EVH_ERR_INVALID, W + "iters must lie in 0..64");
+  if (A.clip < 0 || A.clip > 255) return evh_fail(c, EVH_ERR_INVALID, W + "clip must lie in 0..255");
+  if (A.count && (A.min_cover < 1 || A.min_cover > 255)) return evh_fail(c, EVH_ERR_INVALID, W + "min_cover must lie in 1..255");
+  // the frame's bounds are evh_pair_refine's (the Jacobian), the canvas's evh_warp_fixed_plane's source bounds (the positions)
+  if (A.w > EVH_REFINE_MAX_SIZE || A.h > EVH_REFINE_MAX_SIZE) return evh_fail(c, EVH_ERR_CAPACITY, W + "w and h stay within 4096");
+  if (int rc = need_below_2_26(c, W, "canvas", A.dw, A.dh)) return rc;
+  if (int rc = need_area(c, W, "dw * dh", A.dw, A.dh)) return rc;
+  if (A.nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  if (int rc = need_source_stride(c, W, A.F, A.w, A.h, A.nframes > 1)) return rc;
+  if (A.canvas_stride < (int64_t)A.dw * A.F.channels) return evh_fail(c, EVH_ERR_INVALID, W + "canvas stride smaller than a row");
+  if (A.count && A.count_stride < A.dw) return evh_fail(c, EVH_ERR_INVALID, W + "count stride smaller than a row");
+  if (A.nframes == 0) return EVH_SUCCESS;
+  if (int rc = need_planes(c, A.who, A.F, A.nframes, A.w, A.h)) return rc;
+  // the outputs apart from each other, from everything that is read and from d_M_in, which d_M_out may only BE
+  const int64_t nf = A.nframes;
+  const Span outs[3] = {{A.M_out, nf * 72, "d_M_out"}, {A.info, nf * EVH_REFINE_NINFO * 8, "d_info"},
+                        {A.normal, nf * EVH_REFINE_NSUMS * 8, "d_normal"}};
+  Span src[3];
+  source_spans(A.F, nf, A.w, A.h, src);
+  const Span ins[5] = {src[0], src[1], src[2],
+                       {A.canvas, (A.dh - 1) * A.canvas_stride + (int64_t)A.dw * A.F.channels, "the canvas"},
+                       {A.count, (A.dh - 1) * A.count_stride + A.dw, "d_count"}};
+  if (int rc = need_apart(c, W, outs, ins)) return rc;
+  const Span in{A.M_in, nf * 72, "d_M_in"};
+  for (int i = A.M_out == A.M_in ? 1 : 0; i < 3; i++)
+    if (meet(outs[i], in)) return evh_fail(c, EVH_ERR_INVALID, W + outs[i].name + " overlaps d_M_in");
+  return EVH_SUCCESS;
+}
+// evh_pair_refine's launches with k_canvas_refine_eval as the evaluation: the same groups for the same w, h, the same workspace
+int launch(evh_ctx* c, const CanvasRefineArgs& A) {
+  const Runs R = runs_of(A.w, A.h);
+  const int groups = refine_groups(R);
+  const size_t state_bytes = ((size_t)A.nframes * sizeof(RefineState) + 255) & ~(size_t)255;
+  if (int rc = grow(c, &c->d_refine_ws, &c->refine_ws_bytes, state_bytes + (size_t)A.nframes * groups * REFINE_SLOTS * sizeof(double)))
+    return rc;
+  RefineState* state = reinterpret_cast<RefineState*>(c->d_refine_ws);
+  double* part = reinterpret_cast<double*>(c->d_refine_ws + state_bytes);
+  const PackedSrc canvas{A.canvas, A.F.channels, A.canvas_stride, 0};
+  int rc = EVH_SUCCESS;
+  with_source(A.F, [&](auto cn, const auto& S) {
+    for (int k = 0; k <= A.iters && rc == EVH_SUCCESS; k++) {
+      hipLaunchKernelGGL((k_canvas_refine_eval<decltype(cn)::value, std::decay_t<decltype(S)>>), dim3(groups, A.nframes), dim3(256), 0,
+                         c->stream, S, canvas, A.count, A.count_stride, A.min_cover, A.w, A.h, A.dw, A.dh,
+                         k == 0 ? A.M_in : nullptr, state, part, A.clip, R.per_row, R.n);
+      hipLaunchKernelGGL(k_pair_refine_step, dim3(A.nframes), dim3(64), 0, c->stream, state, part, groups, k == 0, k == A.iters, A.w,
+                         A.h, A.M_in, A.M_out, reinterpret_cast<unsigned long long*>(A.info), A.normal);
+      rc = launched(c);
+    }
+  });
+  return rc;
+}
+
 // ---- the trail: the fixed plane with earlier frames dimmed and the frame outlined (stabilization.py:21-97, 129-172) ----------
 struct TrailArgs {
   const char* who; EvhFrames F; int nframes, sw, sh; const double* M; int inverse_map; const int32_t* rect; uint8_t* canvas;
@@ -1804,6 +1979,22 @@ int evh_pair_refine_yuv420(evh_ctx* c, const evh_yuv420* src, int npairs, int fr
                            int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal) {
   return run(c, RefineArgs{"evh_pair_refine_yuv420", yuv420_frames(src), npairs, frame_step, w, h, d_M_in, iters, clip, d_M_out,
                            d_info, d_normal});
+}
+
+int evh_canvas_refine(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels, int64_t row_stride,
+                      int64_t frame_stride, const uint8_t* d_canvas, int dw, int dh, int64_t canvas_row_stride, const uint8_t* d_count,
+                      int64_t count_row_stride, int min_cover, const double* d_M_in, int iters, int clip, double* d_M_out,
+                      uint64_t* d_info, double* d_normal) {
+  return run(c, CanvasRefineArgs{"evh_canvas_refine", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, w, h,
+                                 d_canvas, dw, dh, canvas_row_stride, d_count, count_row_stride, min_cover, d_M_in, iters, clip,
+                                 d_M_out, d_info, d_normal});
+}
+
+int evh_canvas_refine_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int w, int h, const uint8_t* d_canvas, int dw, int dh,
+                             int64_t canvas_row_stride, const uint8_t* d_count, int64_t count_row_stride, int min_cover,
+                             const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal) {
+  return run(c, CanvasRefineArgs{"evh_canvas_refine_yuv420", yuv420_frames(src), nframes, w, h, d_canvas, dw, dh, canvas_row_stride,
+                                 d_count, count_row_stride, min_cover, d_M_in, iters, clip, d_M_out, d_info, d_normal});
 }
 
 int evh_trail_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int64_t row_stride,

@@ -9,6 +9,9 @@ transformation fidelity, ITF); the same difference, thresholded, is the moving-o
 `pair_maps` forms the matrix that registers a pair, `registration_report` the per-pair figures and the two means,
 `residual_frames` the difference pictures or masks.  The sampling, differencing and summing is one fused operator,
 evh_pair_residual (include/evhip.h states its arithmetic): no warped frame is ever stored.
+
+`refine_pair_maps` improves each pair's matrix on the pixels (evh_pair_refine); `anchor_superposition` aligns every frame against
+the mosaic of the frames before it (evh_canvas_refine), which is what keeps a long chain of pair matrices from drifting.
 """
 import math
 
@@ -296,3 +299,177 @@ def refined_homography_dict(capture_factory, superposition_homography_dict, resi
     before = registration_report(capture_factory(), superposition_homography_dict, resize_info, threshold, chunk_frames, ingest)
     after = registration_report(capture_factory(), sup, resize_info, threshold, chunk_frames, ingest)
     return {"homography": hd, "superposition": sup, "info": info, "report_before": before, "report_after": after}
+
+
+# ---- frame-to-mosaic registration: every frame aligned against what the plane already holds -----------------------------------------
+def _anchor_arguments(superposition_homography_dict, resize_info, iters, clip, group, blend, feather_px, min_overlap, margin,
+                      chunk_frames, ingest):
+    """The refusals of anchor_superposition, before the capture is opened or the device touched"""
+    from ._lib import BLEND_MODES, REFINE_MAX_ITERS, REFINE_MAX_SIZE
+    from .blend import MAX_FEATHER_PX
+    check_ingest(ingest)
+    iters, clip = _whole(iters, 0, REFINE_MAX_ITERS, "iters"), _whole(clip, 0, 255, "clip")
+    group, margin = _whole(group, 1, 65535, "group"), _whole(margin, 0, 4096, "margin")
+    if blend not in BLEND_MODES:
+        raise ValueError("blend must be 'feather' or 'seam'")
+    if isinstance(feather_px, bool) or not isinstance(feather_px, (int, float)) or not 0 <= feather_px <= MAX_FEATHER_PX:
+        raise ValueError("feather_px must lie in 0..%g" % MAX_FEATHER_PX)
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)) or not 0 <= min_overlap <= 1:
+        raise ValueError("min_overlap must lie in 0..1")
+    if isinstance(chunk_frames, bool) or int(chunk_frames) != chunk_frames or int(chunk_frames) < 1:
+        raise ValueError("chunk_frames must be an integer of at least 1")
+    w, h = int(resize_info["w"]), int(resize_info["h"])
+    if not (1 <= w <= REFINE_MAX_SIZE and 1 <= h <= REFINE_MAX_SIZE):
+        raise ValueError("resize_info must hold a w and h in 1..%d" % REFINE_MAX_SIZE)
+    keys = [k for k in superposition_homography_dict if k != "resize_info"]
+    chunk = max(group, int(chunk_frames) // group * group)              # a group never straddles two chunks
+    return keys, w, h, iters, clip, group, int(round(float(feather_px) * 32)), float(min_overlap), margin, chunk
+
+
+def _normalised(M):
+    with np.errstate(all="ignore"):
+        return M / M[2, 2]
+
+
+def anchor_groups(S, T, w, h, group, min_overlap, refine, paint):
+    """The loop of anchor_superposition on the host, float64.  S: the frames' matrices f64[3,3] in order (NaN = missing), frame
+    pixel -> plane point; T: plane point -> canvas pixel.  refine(first, start f64[n,3,3]) -> (mats f64[n,3,3], info rows
+    int[n,8]) aligns frames first .. first+n-1 against the canvas; paint(first, mats) paints them into it.  D, the running
+    correction, starts as the identity.  Per group of `group` frames: frame k starts at M_k = T D S_k / [2][2]; the first group is
+    taken as it stands; a later frame keeps refine's matrix when its status is REFINED and covered_in >= min_overlap w h, else
+    its start; then D is chosen so that T D S_last = M'_last (the group's last frame with a matrix) and the group is painted.
+    S'_k = T^-1 M'_k / [2][2]; a frame without a matrix repeats the running S'.
+    -> ([S'_k], [info dict: d_info's row by name, used, overlap])"""
+    from ._lib import REFINE_INFO, REFINE_REFINED, REFINE_UNCHANGED
+    T = np.asarray(T, np.float64).reshape(3, 3)
+    Tinv = np.linalg.inv(T)
+    nan = np.full((3, 3), np.nan)
+    D, running = np.eye(3), None
+    out, infos = [], []
+    for first in range(0, len(S), group):
+        Sg = [np.asarray(m, np.float64).reshape(3, 3) for m in S[first:first + group]]
+        ok = [bool(np.isfinite(m).all()) for m in Sg]
+        start = np.stack([_normalised(np.dot(np.dot(T, D), m)) if good else nan for m, good in zip(Sg, ok)])
+        kept = start.copy()
+        rows = np.zeros((len(Sg), len(REFINE_INFO)), np.int64)
+        rows[:, 0] = REFINE_UNCHANGED
+        if first > 0:
+            mats, rows = refine(first, start)
+            mats, rows = np.asarray(mats, np.float64).reshape(-1, 3, 3), np.asarray(rows)
+        for p in range(len(Sg)):
+            info = dict(zip(REFINE_INFO, (int(v) for v in rows[p])))
+            info["used"] = bool(first > 0 and info["status"] == REFINE_REFINED and info["covered_in"] >= min_overlap * w * h
+                                and np.isfinite(mats[p]).all())
+            info["overlap"] = info["covered_in"] / float(w * h)
+            if info["used"]:
+                kept[p] = mats[p]
+            infos.append(info)
+        have = [p for p in range(len(Sg)) if ok[p] and np.isfinite(kept[p]).all()]
+        if have:
+            with np.errstate(all="ignore"):
+                try:
+                    Dn = _normalised(np.dot(np.dot(Tinv, kept[have[-1]]), np.linalg.inv(Sg[have[-1]])))
+                except np.linalg.LinAlgError:
+                    Dn = nan
+            if np.isfinite(Dn).all():
+                D = Dn
+        for p in range(len(Sg)):
+            if ok[p] and np.isfinite(kept[p]).all():
+                running = _normalised(np.dot(Tinv, kept[p]))
+            out.append(nan if running is None else running)
+        paint(first, kept)
+    return out, infos
+
+
+def anchor_superposition(capture, superposition_homography_dict, resize_info, iters=8, clip=255, group=1, blend="feather",
+                         feather_px=32, min_overlap=0.25, margin=32, chunk_frames=32, ingest="auto"):
+    """Frame-to-mosaic registration: every frame aligned against the blended picture of the frames before it
+    (evh_canvas_refine), so that ground the camera comes back to pulls the chain of pair matrices into place again.  The canvas
+    is stabilization.fixed_plane_bounds of the dictionary, `margin` pixels wider on every side; frames are read and taken to the
+    working size as registration_report does; the loop is anchor_groups' (group = 1: strictly frame by frame); a group is painted
+    with evh_blend_fixed_plane (blend, feather_px as in blend.blended_mosaic, no gains) and aligned against that picture where a
+    frame has been painted.  iters = 0 scores the dictionary against its own mosaic and changes nothing.  The i-th frame read
+    goes with the i-th entry of the dictionary; a capture that ends before the dictionary does is a ValueError.
+    -> ({frame_no: S'_k f64[3,3]}, {frame_no: {status, evals, accepted, covered_in, ssd_in, covered_out, ssd_out, n_in, used,
+    overlap = covered_in / (w h)}})."""
+    import torch
+    keys, w, h, iters, clip, group, feather, min_overlap, margin, chunk = _anchor_arguments(
+        superposition_homography_dict, resize_info, iters, clip, group, blend, feather_px, min_overlap, margin, chunk_frames, ingest)
+    if not keys:
+        return {}, {}
+    from .blend import CanvasPainter
+    from .stabilization import fixed_plane_bounds
+    ox, oy, dw, dh = fixed_plane_bounds(superposition_homography_dict, resize_info)
+    ox, oy, dw, dh = ox - margin, oy - margin, dw + 2 * margin, dh + 2 * margin
+    T = np.array([[1, 0, -ox], [0, 1, -oy], [0, 0, 1]], np.float64)
+    S = [entry_matrix(superposition_homography_dict[k]) for k in keys]
+    reader = FrameReader(capture, ingest)
+    first = reader.first
+    if not reader.planes and (first.ndim not in (2, 3) or (first.ndim == 3 and first.shape[2] != 3)):
+        raise ValueError("frames must be BGR [h,w,3] or gray [h,w]")
+    ctx = runtime.get_context(64, 64)
+    dev = runtime.device()
+    chunk = max(group, min(chunk, runtime.STAGING_BYTES_PER_BUFFER // max(first.nbytes, 1)) // group * group)
+    ladder = DeviceLadder(dev, chunk, reader.planes, (reader.w0, reader.h0), (w, h), bgr=True, gray3=True)
+    painter = CanvasPainter(dev, dw, dh, blend, feather)
+    chunks = reader.chunks(chunk, 0, len(keys))
+    held = {"start": 0, "src": None}
+
+    def frames_of(first_no, n):
+        """frames first_no .. first_no+n-1 on the device; groups come in order and never straddle two chunks"""
+        while held["src"] is None or first_no >= held["start"] + held["src"].shape[0]:
+            start, frames = next(chunks)
+            held["start"], held["src"] = start, ladder(ctx, torch.from_numpy(frames).to(dev))[1].contiguous()
+        at = first_no - held["start"]
+        return held["src"][at:at + n]
+
+    def refine(first_no, start):
+        src = frames_of(first_no, len(start))
+        n = src.shape[0]
+        out, info = ctx.canvas_refine(src, painter.picture, torch.from_numpy(start[:n].reshape(-1, 9).copy()).to(dev),
+                                      count=painter.cover, min_cover=1, iters=iters, clip=clip)
+        ctx.order_torch_after()
+        return out.cpu().numpy().reshape(-1, 3, 3), info.cpu().numpy()
+
+    def paint(first_no, mats):
+        src = frames_of(first_no, len(mats))
+        painter.paint(ctx, src, torch.from_numpy(mats[:src.shape[0]].reshape(-1, 9).copy()).to(dev))
+
+    sup, infos = {}, {}
+    try:
+        out, rows = anchor_groups(S, T, w, h, group, min_overlap, refine, paint)
+    except StopIteration:
+        raise ValueError("the capture holds fewer frames than the dictionary")
+    for k, Sk, info in zip(keys, out, rows):
+        sup[k], infos[k] = Sk, info
+    return sup, infos
+
+
+def anchored_homography_dict(capture_factory, superposition_homography_dict, resize_info, iters=8, clip=255, group=1, blend="feather",
+                             feather_px=32, min_overlap=0.25, margin=32, threshold=16, chunk_frames=32, ingest="auto"):
+    """anchor_superposition, its matrices turned into a dictionary in the reference's format, and the score of both.
+    capture_factory() opens the video; it is called three times.  H'_k = S'_k . S'_{k-1}^-1 / [2][2], None where that is not finite.
+    -> {"homography": {frame_no: {"H": ...}} for every entry but the first, "superposition": {frame_no: S'}, "info":
+        anchor_superposition's rows, "report_before" / "report_after": registration_report of the dictionary handed in and of the
+        anchored one, "canvas_score_before" / "canvas_score_after": the sums over the frames of ssd_in / covered_in and of
+        ssd_out / covered_out (frames that cover nothing of the canvas add nothing)}"""
+    _anchor_arguments(superposition_homography_dict, resize_info, iters, clip, group, blend, feather_px, min_overlap, margin, chunk_frames,
+                      ingest)
+    _arguments(superposition_homography_dict, resize_info, threshold, chunk_frames, ingest, "abs")
+    sup, info = anchor_superposition(capture_factory(), superposition_homography_dict, resize_info, iters, clip, group, blend, feather_px,
+                                     min_overlap, margin, chunk_frames, ingest)
+    keys = list(sup)
+    hd = {}
+    for k0, k1 in zip(keys, keys[1:]):
+        H = None
+        with np.errstate(all="ignore"):
+            try:
+                H = _normalised(np.dot(sup[k1], np.linalg.inv(sup[k0])))
+            except np.linalg.LinAlgError:
+                H = None
+        hd[k1] = {"H": H.tolist() if H is not None and np.isfinite(H).all() else None}
+    before = registration_report(capture_factory(), superposition_homography_dict, resize_info, threshold, chunk_frames, ingest)
+    after = registration_report(capture_factory(), sup, resize_info, threshold, chunk_frames, ingest)
+    score = lambda a, b: float(sum(e[a] / e[b] for e in info.values() if e[b] > 0))
+    return {"homography": hd, "superposition": sup, "info": info, "report_before": before, "report_after": after,
+            "canvas_score_before": score("ssd_in", "covered_in"), "canvas_score_after": score("ssd_out", "covered_out")}

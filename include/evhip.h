@@ -42,6 +42,9 @@
  *                                 visualization/processing_visualization.py:22-57
  *   evh_pair_residual[_yuv420]    no counterpart: the measure of a matrix the reference's known-issues.md lacks ("Error",
  *                                 "N/A coordinates"): the motion-compensated residual of a pair of frames
+ *   evh_pair_refine[_yuv420]      no counterpart: that matrix improved on the pixels of the pair (direct alignment)
+ *   evh_canvas_refine[_yuv420]    no counterpart: a frame aligned against the mosaic its predecessors left on the plane, so that
+ *                                 revisited ground pulls the chain of pair matrices back into place
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -938,6 +941,41 @@ int evh_pair_refine(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int frame
                     double* d_normal /* f64[npairs,45] DEVICE, may be NULL */);
 int evh_pair_refine_yuv420(evh_ctx* ctx, const evh_yuv420* src, int npairs, int frame_step, int w, int h,
                            const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal);
+
+/* ---- direct alignment against the mosaic: a frame's matrix refined on a canvas with holes ----------------------------------------- */
+/* evh_pair_refine with the previous frame replaced by a canvas: frame k of nframes frames (w x h, packed or planes exactly as for
+ * evh_pair_refine) is aligned against d_canvas, dh rows of dw * channels bytes at canvas_row_stride -- the frames' channel count;
+ * the plane form takes a BGR canvas -- which need not be valid everywhere.  d_count (may be NULL = every pixel valid): one byte per
+ * canvas pixel, rows of dw at count_row_stride, as evh_plate_fixed_plane writes it; min_cover in 1..255 has evh_rows_moving_filter's
+ * meaning: a canvas pixel counts where d_count >= min_cover.  d_M_in f64[nframes,9] (DEVICE) maps pixels of frame k to pixels of the
+ * canvas (the caller folds the canvas origin in).  tests/canvas_checks.py restates the following in numpy.
+ * SAMPLE for pixel (x, y) of frame k: the position, the coverage test, the taps and the rounding of evh_warp_fixed_plane with
+ *   A = d_M_in[k], inverse_map != 0, sw = dw, sh = dh and the canvas as the source.  A tap of weight 0 is not read.
+ * VALID: every tap of non-zero weight has d_count >= min_cover at its pixel; a count under a tap of weight 0 is not consulted.
+ * COVERED = the warp's coverage AND valid.
+ * COST, NORMAL EQUATIONS, STEP, LOOP, d_M_out, d_info, d_normal: evh_pair_refine's text with "the previous frame" read as "the
+ *   canvas" and "covered" as above: r = g_frame - g_canvas_sample, the gradients and the doubled centred coordinates are the frame's
+ *   (its w, h).  iters == 0 makes the entry the score of a frame against the canvas.
+ * The launch geometry -- the assignment of runs to threads, the tree, the order of workgroups -- is evh_pair_refine's for the same w, h,
+ *   and the solving kernel is the same: with the canvas = the previous frame (dw = w, dh = h) and d_count NULL or valid everywhere,
+ *   d_M_out, d_info and d_normal equal evh_pair_refine's for that pair byte for byte.
+ * Launches: iters + 1 evaluations (grid.y = frame), each followed by evh_pair_refine's solving kernel, on the same context workspace;
+ *   no host synchronisation.
+ * Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: NULL frames (a NULL plane), d_canvas, d_M_in, d_M_out or
+ * d_info, channels not 1 or 3, w, h, dw or dh < 1, nframes < 0, iters outside 0..64, clip outside 0..255, min_cover outside 1..255
+ * (looked at only when d_count is given), a stride shorter than its row / frame (the frame stride when nframes > 1), an output
+ * overlapping the frames, the canvas, d_count, another output or (other than d_M_out == d_M_in) d_M_in; EVH_ERR_CAPACITY: w or
+ * h > 4096, dw or dh >= 2^26, dw*dh > INT_MAX, nframes > 65535.  nframes == 0 succeeds and does nothing.  The plane form converts every
+ * pixel of a frame as evh_yuv420_to_bgr does: it equals evh_yuv420_to_bgr followed by the BGR form.                              */
+int evh_canvas_refine(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int w, int h, int channels /* 1 | 3 */, int64_t row_stride,
+                      int64_t frame_stride, const uint8_t* d_canvas, int dw, int dh, int64_t canvas_row_stride,
+                      const uint8_t* d_count /* may be NULL */, int64_t count_row_stride, int min_cover /* 1..255 */,
+                      const double* d_M_in /* f64[nframes,9] DEVICE */, int iters /* 0..64 */, int clip /* 0..255 */,
+                      double* d_M_out /* f64[nframes,9] DEVICE */, uint64_t* d_info /* u64[nframes,8] DEVICE */,
+                      double* d_normal /* f64[nframes,45] DEVICE, may be NULL */);
+int evh_canvas_refine_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, const uint8_t* d_canvas, int dw, int dh,
+                             int64_t canvas_row_stride, const uint8_t* d_count, int64_t count_row_stride, int min_cover,
+                             const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

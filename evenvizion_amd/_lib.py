@@ -121,6 +121,19 @@ SIGNATURES = {
     "evh_blend_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _i]),
     "evh_blend_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64]),
     "evh_blend_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64]),
+    # multi-band blending under a label mask, and SEAM's labels from the geometry alone
+    "evh_seam_labels_fixed_plane": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "evh_seam_labels_ray_surface": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
+    "evh_bands_state_elems": (_i64, [_i, _i, _i, _i]),
+    "evh_bands_frame_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "evh_blend_bands_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i,
+                                         _i, _i64, _i, _i]),
+    "evh_blend_bands_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i, _i, _i64,
+                                                _i, _i]),
+    "evh_blend_bands_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp,
+                                         _i, _i, _i64]),
+    "evh_blend_bands_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _i, _i,
+                                                _i64]),
     "evh_pair_exposure": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _i, _i, _i, _vp]),
     "evh_pair_exposure_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "evh_trail_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _i]),
@@ -182,6 +195,17 @@ def yuv420_views(packed, w, h):
 
 class EvhError(RuntimeError):
     pass
+
+
+def bands_state_elems(dw, dh, channels, levels):
+    """int64 words of the band blend's state for a canvas (evh_bands_state_elems; host only, -1 for sizes the entries refuse)."""
+    return int(load().evh_bands_state_elems(int(dw), int(dh), int(channels), int(levels)))
+
+
+def bands_frame_ws_bytes(dw, dh, channels, levels):
+    """Workspace bytes one frame's pyramids need (evh_bands_frame_ws_bytes; host only, -1 for sizes the entries refuse).  A
+    call holding g frames at once needs g times this, and 8 * bands_state_elems(...) more where it is given no state."""
+    return int(load().evh_bands_frame_ws_bytes(int(dw), int(dh), int(channels), int(levels)))
 
 
 def build(force=False):
@@ -260,11 +284,13 @@ class Context:
         self.max_w, self.max_h = max_w, max_h
 
     _nothing = None          # a few device bytes for calls that take no frames (see _blend)
+    _bands_ws = None         # the workspace of blend_bands_* calls that bring none (see _blend_bands)
 
     def close(self):
         if getattr(self, "h", None):
             self.lib.evh_destroy(self.h)
             self.h = None
+            self._bands_ws = None
 
     def __del__(self):
         try:
@@ -665,16 +691,9 @@ class Context:
         self._check(self._form("evh_warp_ray_surface", planes)(self.h, *head, *tail))
 
     # ---- the blended mosaic ----
-    def _blend(self, name, frames, mats, middle, last, shape, mode, feather, gains, acc, acc_in, out, background, size):
-        """What blend_fixed_plane and blend_ray_surface share.  middle: the arguments between the matrices and `mode`, last:
-        those behind out_row_stride; shape=(dh, dw) or None = out's."""
-        import torch
-        self._enter()
-        mode = BLEND_MODES[mode] if isinstance(mode, str) else int(mode)
-        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
-        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
-        if out is None and acc is None:
-            raise ValueError("one of out and acc must be given")
+    def _blend_canvas(self, out, shape, cn, background):
+        """The canvas of a blend entry -> (out pointer or None, its row stride, dw, dh, background pointer or None): from out
+        [dh,dw(,3)], or from shape=(dh, dw) where out is None; the background counts only beside a picture."""
         op, ors = None, 0
         if out is not None:
             op, dw, dh, ors, _ = self._image_rows(out, cn, 0, "out")
@@ -684,25 +703,44 @@ class Context:
             raise ValueError("without out the canvas needs shape=(dh, dw)")
         else:
             dh, dw = int(shape[0]), int(shape[1])
-        if acc is not None:
-            self._dev_tensor(acc, torch.int64, (dh, dw, cn + 1), "acc must be a contiguous CUDA int64 tensor [dh,dw,%d]", cn + 1)
-        elif acc_in:
-            raise ValueError("acc_in needs acc")
-        if gains is not None:
-            self._dev_tensor(gains, torch.uint16, (n, 3), "gains must be a contiguous CUDA uint16 tensor [n,3]")
         bp = None
         if background is not None and out is not None:
             bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
             if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
                 raise ValueError("background must be [dh,dw(,3)] with out's row stride")
-        mp = mats.data_ptr()
-        if n == 0:
-            # empty tensors have no address to hand over, and the entry reads neither frames nor matrices: packed frames at
-            # a few bytes of the context's own
-            if self._nothing is None:
-                self._nothing = torch.zeros(16, dtype=torch.uint8, device="cuda:%d" % self.device)
-            planes, head, mp = False, (self._nothing.data_ptr(), 0, sw, sh, cn, sw * cn, sw * sh * cn), self._nothing.data_ptr()
-        tail = (mode, int(feather), _ptr(gains) if n else None, _ptr(acc), int(bool(acc_in)), bp, op, dw, dh, ors)
+        return op, ors, dw, dh, bp
+
+    def _blend_frames(self, planes, head, n, sw, sh, cn, mats, gains):
+        """The matrices and gains of a blend entry checked -> (planes?, head, matrix pointer, gain pointer), with stand-ins
+        for a call without frames."""
+        import torch
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        if gains is not None:
+            self._dev_tensor(gains, torch.uint16, (n, 3), "gains must be a contiguous CUDA uint16 tensor [n,3]")
+        if n:
+            return planes, head, mats.data_ptr(), _ptr(gains)
+        # empty tensors have no address to hand over, and the entry reads neither frames nor matrices: packed frames at a few
+        # bytes of the context's own
+        if self._nothing is None:
+            self._nothing = torch.zeros(16, dtype=torch.uint8, device="cuda:%d" % self.device)
+        return False, (self._nothing.data_ptr(), 0, sw, sh, cn, sw * cn, sw * sh * cn), self._nothing.data_ptr(), None
+
+    def _blend(self, name, frames, mats, middle, last, shape, mode, feather, gains, acc, acc_in, out, background, size):
+        """What blend_fixed_plane and blend_ray_surface share.  middle: the arguments between the matrices and `mode`, last:
+        those behind out_row_stride; shape=(dh, dw) or None = out's."""
+        import torch
+        self._enter()
+        mode = BLEND_MODES[mode] if isinstance(mode, str) else int(mode)
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        if out is None and acc is None:
+            raise ValueError("one of out and acc must be given")
+        op, ors, dw, dh, bp = self._blend_canvas(out, shape, cn, background)
+        if acc is not None:
+            self._dev_tensor(acc, torch.int64, (dh, dw, cn + 1), "acc must be a contiguous CUDA int64 tensor [dh,dw,%d]", cn + 1)
+        elif acc_in:
+            raise ValueError("acc_in needs acc")
+        planes, head, mp, gp = self._blend_frames(planes, head, n, sw, sh, cn, mats, gains)
+        tail = (mode, int(feather), gp, _ptr(acc), int(bool(acc_in)), bp, op, dw, dh, ors)
         self._check(self._form(name, planes)(self.h, *head, mp, *middle, *tail, *last))
 
     def blend_fixed_plane(self, frames, mats, origin, out=None, mode="feather", feather=1024, gains=None, acc=None, acc_in=False,
@@ -728,6 +766,112 @@ class Context:
         self._dev_tensor(rows, torch.float64, (dh,), "rows must be a contiguous CUDA float64 tensor [dh]")
         self._blend("evh_blend_ray_surface", frames, mats, (cols.data_ptr(), rows.data_ptr()), (), (dh, dw), mode, feather, gains,
                     acc, acc_in, out, background, size)
+
+    # ---- multi-band blending ----
+    def _seam_labels(self, name, mats, middle, last, shape, feather, first_label, best, label, state_in, frame_size):
+        import torch
+        self._enter()
+        dh, dw = int(shape[0]), int(shape[1])
+        n = int(mats.numel()) // 9
+        self._dev_tensor(mats, torch.float64, 9 * n, "mats must be a contiguous CUDA float64 tensor of n*9 elements")
+        dev = "cuda:%d" % self.device
+        if state_in and (best is None or label is None):
+            raise ValueError("state_in needs best and label")
+        if best is None:                      # written whole by the entry
+            best = torch.empty((dh, dw), dtype=torch.int32, device=dev)
+        if label is None:
+            label = torch.empty((dh, dw), dtype=torch.uint16, device=dev)
+        self._dev_tensor(best, torch.int32, (dh, dw), "best must be a contiguous CUDA int32 tensor [dh,dw]")
+        self._dev_tensor(label, torch.uint16, (dh, dw), "label must be a contiguous CUDA uint16 tensor [dh,dw]")
+        mp = mats.data_ptr()
+        if n == 0:
+            if self._nothing is None:
+                self._nothing = torch.zeros(16, dtype=torch.uint8, device=dev)
+            mp = self._nothing.data_ptr()
+        self._check(getattr(self.lib, name)(self.h, n, int(frame_size[0]), int(frame_size[1]), mp, *middle, int(feather), dw, dh, *last,
+                                            int(first_label), best.data_ptr(), label.data_ptr(), int(bool(state_in))))
+        return best, label
+
+    def seam_labels_fixed_plane(self, mats, frame_size, origin, shape, feather=1024, first_label=0, best=None, label=None,
+                                state_in=False, inverse_map=False):
+        """SEAM's partition of the canvas from the matrices alone (evh_seam_labels_fixed_plane, stated in include/evhip.h): no
+        frame is read.  mats: CUDA float64, n*9 contiguous; frame_size=(sw, sh); shape=(dh, dw); frame k carries label
+        first_label + k, 65535 is "nobody".  best: CUDA int32 [dh,dw] (the library's u32), label: CUDA uint16 [dh,dw], read when
+        state_in, written always, or None = new tensors.  -> (best, label).  Does not synchronise."""
+        return self._seam_labels("evh_seam_labels_fixed_plane", mats, (int(bool(inverse_map)),), (int(origin[0]), int(origin[1])),
+                                 shape, feather, first_label, best, label, state_in, frame_size)
+
+    def seam_labels_ray_surface(self, mats, frame_size, cols, rows, feather=1024, first_label=0, best=None, label=None,
+                                state_in=False):
+        """evh_seam_labels_ray_surface: as seam_labels_fixed_plane on a canvas of viewing rays, [len(rows), len(cols)]."""
+        import torch
+        if cols.dim() != 2 or rows.dim() != 1:
+            raise ValueError("cols must be [dw,2] and rows [dh]")
+        dw, dh = int(cols.shape[0]), int(rows.shape[0])
+        self._dev_tensor(cols, torch.float64, (dw, 2), "cols must be a contiguous CUDA float64 tensor [dw,2]")
+        self._dev_tensor(rows, torch.float64, (dh,), "rows must be a contiguous CUDA float64 tensor [dh]")
+        return self._seam_labels("evh_seam_labels_ray_surface", mats, (cols.data_ptr(), rows.data_ptr()), (), (dh, dw), feather,
+                                 first_label, best, label, state_in, frame_size)
+
+    def _blend_bands(self, name, frames, mats, middle, last, shape, levels, label, first_label, gains, state, state_in, ws, out,
+                     background, size):
+        """What blend_bands_fixed_plane and blend_bands_ray_surface share; middle, last, shape: as for _blend."""
+        import torch
+        self._enter()
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        if out is None and state is None:
+            raise ValueError("one of out and state must be given")
+        op, ors, dw, dh, bp = self._blend_canvas(out, shape, cn, background)
+        levels = int(levels)
+        elems = bands_state_elems(dw, dh, cn, levels)
+        if elems < 0:
+            raise ValueError("levels must lie in 0..8")
+        if state is not None:
+            self._dev_tensor(state, torch.int64, elems, "state must be a contiguous CUDA int64 tensor of %d elements", elems)
+        elif state_in:
+            raise ValueError("state_in needs state")
+        self._dev_tensor(label, torch.uint16, (dh, dw), "label must be a contiguous CUDA uint16 tensor [dh,dw]")
+        if ws is None:
+            # The context's own workspace, kept from call to call: the launches below are only enqueued, so a tensor dropped on
+            # return could be handed out again by torch while they run.  As many frames as the call has, at most 256 MiB, at
+            # least one.  Before a larger one replaces it, torch is ordered behind what still uses the old one.
+            unit, held = 4 * elems, 0 if state is not None else 8 * elems
+            need = held + unit * max(1, min(max(n, 1), (256 << 20) // unit))
+            if self._bands_ws is None or self._bands_ws.numel() < need:
+                if self._bands_ws is not None:
+                    self.order_torch_after()
+                self._bands_ws = torch.empty(need, dtype=torch.uint8, device="cuda:%d" % self.device)
+            ws = self._bands_ws
+        if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.dim() != 1:
+            raise ValueError("ws must be a contiguous one-dimensional CUDA uint8 tensor")
+        planes, head, mp, gp = self._blend_frames(planes, head, n, sw, sh, cn, mats, gains)
+        tail = (levels, label.data_ptr(), int(first_label), gp, _ptr(state), int(bool(state_in)), ws.data_ptr(),
+                int(ws.numel()), bp, op, dw, dh, ors)
+        self._check(self._form(name, planes)(self.h, *head, mp, *middle, *tail, *last))
+
+    def blend_bands_fixed_plane(self, frames, mats, origin, label, levels=5, out=None, first_label=0, gains=None, state=None,
+                                state_in=False, ws=None, background=None, inverse_map=False, shape=None, size=None):
+        """The multi-band blend on the fixed plane (evh_blend_bands_fixed_plane[_yuv420], stated in include/evhip.h).  frames,
+        mats, origin, out, gains, background, inverse_map, shape, size: as for blend_fixed_plane.  label: CUDA uint16 [dh,dw],
+        which frame owns a pixel (seam_labels_fixed_plane), frame k of the call being first_label + k.  state: CUDA int64,
+        bands_state_elems(dw, dh, channels, levels) contiguous elements, read when state_in, written always, or None.  ws: CUDA
+        uint8 workspace (bands_frame_ws_bytes per frame held at once, plus 8 bytes per state element where state is None), or
+        None = one the context keeps and grows as needed.  Does not synchronise."""
+        self._blend_bands("evh_blend_bands_fixed_plane", frames, mats, (int(bool(inverse_map)),), (int(origin[0]), int(origin[1])),
+                          shape, levels, label, first_label, gains, state, state_in, ws, out, background, size)
+
+    def blend_bands_ray_surface(self, frames, mats, cols, rows, label, levels=5, out=None, first_label=0, gains=None, state=None,
+                                state_in=False, ws=None, background=None, size=None):
+        """The multi-band blend on a canvas of viewing rays (evh_blend_bands_ray_surface[_yuv420]): cols, rows as for
+        blend_ray_surface, everything else as for blend_bands_fixed_plane."""
+        import torch
+        if cols.dim() != 2 or rows.dim() != 1:
+            raise ValueError("cols must be [dw,2] and rows [dh]")
+        dw, dh = int(cols.shape[0]), int(rows.shape[0])
+        self._dev_tensor(cols, torch.float64, (dw, 2), "cols must be a contiguous CUDA float64 tensor [dw,2]")
+        self._dev_tensor(rows, torch.float64, (dh,), "rows must be a contiguous CUDA float64 tensor [dh]")
+        self._blend_bands("evh_blend_bands_ray_surface", frames, mats, (cols.data_ptr(), rows.data_ptr()), (), (dh, dw), levels, label,
+                          first_label, gains, state, state_in, ws, out, background, size)
 
     # ---- the sums behind exposure gains ----
     def pair_exposure(self, frames, pairs, mats, step=2, lo=8, hi=247, stats=None, size=None):

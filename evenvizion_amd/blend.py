@@ -12,7 +12,11 @@ overlapping means should agree, gains should stay near 1), a small linear system
     gains = solve_gains(pairs, stats, n_frames)
     canvas = blended_mosaic(capture_again, sup, resize_info, gains=gains)
 
-Not done here: multi-band blending, seam finding by graph cut, vignetting.
+blend="bands" is multi-band blending (Burt and Adelson; evh_blend_bands_*): seam_labels gives every canvas pixel to the frame
+"seam" would take, from the matrices alone, and the Laplacian pyramids of the frames are blended under the Gaussian pyramids of
+that label mask -- exposure steps fade over a wide zone, detail changes hands over a narrow one.
+
+Not done here: seam finding by graph cut (the label mask is where one would write), vignetting.
 """
 import math
 
@@ -24,6 +28,9 @@ from .frames import DeviceLadder, FrameReader, check_ingest, entry_matrix
 MAX_SOLVE_FRAMES = 4096        # solve_gains forms the normal equations densely: n x n float64
 Q12 = 4096                     # a gain of 1.0 in evh_blend_*'s d_gain
 MAX_FEATHER_PX = 65535 / 32.0
+MAX_BANDS = 8                  # evh_blend_bands_*: levels 0..8
+MAX_LABEL = 65534              # 65535 is "nobody" in a label mask
+LABEL_CHUNK = 1024             # matrices per evh_seam_labels_* call
 
 
 def _whole(value, lo, name):
@@ -171,11 +178,13 @@ def quantise_gains(g):
     return np.clip(np.rint(np.asarray(g, np.float64) * Q12), 1, 65535).astype(np.uint16)
 
 
-def _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, chunk_frames, ingest):
+def _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, chunk_frames, ingest, bands=5):
     from ._lib import BLEND_MODES
     from .stabilization import check_placement
-    if blend not in BLEND_MODES:
-        raise ValueError("blend must be 'feather' or 'seam'")
+    if blend not in BLEND_MODES and blend != "bands":
+        raise ValueError("blend must be 'feather', 'seam' or 'bands'")
+    if isinstance(bands, (bool, np.bool_)) or not isinstance(bands, (int, np.integer)) or not 0 <= int(bands) <= MAX_BANDS:
+        raise ValueError("bands must be an integer in 0..%d" % MAX_BANDS)
     if isinstance(feather_px, bool) or not isinstance(feather_px, (int, float)) or not 0 <= feather_px <= MAX_FEATHER_PX:
         raise ValueError("feather_px must lie in 0..%g" % MAX_FEATHER_PX)
     check_placement(placement)
@@ -198,6 +207,70 @@ def _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, ch
             raise ValueError("gains must be positive finite numbers [n_frames,3]")
         gains = quantise_gains(gains)
     return on_surface, int(round(float(feather_px) * 32)), gains
+
+
+def _geometry(superposition_homography_dict, resize_info, on_surface, surface, focal, placement, scale, w0, h0):
+    """Where the frames of a w0 x h0 video go: (dw, dh, the size the frames are resized to or None, matrix_of(frame_no) -> f64[9],
+    origin (ox, oy) or None, the ray tables (cols, rows) as numpy or None)."""
+    from .stabilization import _placement, MAX_PIXELS
+    if on_surface:
+        from .surface import frame_matrix, surface_model, surface_tables
+        size = (int(resize_info["w"]), int(resize_info["h"]))
+        model = surface_model(superposition_homography_dict, resize_info, surface, focal, scale, MAX_PIXELS)
+        ox, oy, dw, dh, scale_px = model.bounds
+        nan = np.full(9, np.nan)
+
+        def matrix_of(frame_no):
+            R = model.rotations.get(frame_no)
+            return nan if R is None else frame_matrix(R, model.focal, model.centre, (w0, h0), size)
+        return dw, dh, None, matrix_of, None, surface_tables(surface, scale_px, ox, oy, dw, dh)
+    ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, MAX_PIXELS)
+    resize_to = (int(resize_info["w"]), int(resize_info["h"])) if placement == "translate" else None
+    return dw, dh, resize_to, matrix_of, (ox, oy), None
+
+
+def _last_frame(superposition_homography_dict):
+    keys = [int(k) for k in superposition_homography_dict if k != "resize_info"]
+    last = max(keys) if keys else 0
+    if last - 1 > MAX_LABEL:
+        raise ValueError("a label mask names at most %d frames" % (MAX_LABEL + 1))
+    return last
+
+
+def _device_labels(ctx, dev, n_frames, frame_size, dw, dh, matrix_of, origin, tables, feather):
+    """uint16 [dh,dw] on the device: frame number f (from 1) carries label f - 1; the matrices go LABEL_CHUNK at a time, the
+    state carried."""
+    import torch
+    best, label = None, None
+    for first in range(0, max(n_frames, 1), LABEL_CHUNK):
+        n = max(0, min(LABEL_CHUNK, n_frames - first))
+        mats = torch.from_numpy(np.stack([matrix_of(first + 1 + k) for k in range(n)]).reshape(n, 9) if n else np.zeros((0, 9))).to(dev)
+        kw = dict(feather=feather, first_label=first, best=best, label=label, state_in=best is not None)
+        if tables is None:
+            best, label = ctx.seam_labels_fixed_plane(mats, frame_size, origin, (dh, dw), **kw)
+        else:
+            best, label = ctx.seam_labels_ray_surface(mats, frame_size, tables[0], tables[1], **kw)
+        ctx.order_torch_after()        # `mats` is dropped at the next turn: torch may hand its memory out again only behind the call
+    return label
+
+
+def seam_labels(superposition_homography_dict, resize_info, frame_size, feather_px=32, placement="warp", scale=1.0, surface=None,
+                focal=None):
+    """uint16 [dh,dw]: which frame "seam" gives every pixel of blended_mosaic's canvas to, from the matrices alone -- no video is
+    read (evh_seam_labels_*).  The i-th frame read carries label i (from 0), 65535 is a pixel no frame covers.  frame_size: (w, h)
+    of the video's frames; everything else as for blended_mosaic."""
+    import torch
+    on_surface, feather, _ = _check_mosaic("seam", feather_px, None, placement, scale, surface, focal, 1, "auto")
+    w0, h0 = _whole(frame_size[0], 1, "frame_size"), _whole(frame_size[1], 1, "frame_size")
+    n_frames = _last_frame(superposition_homography_dict)
+    dw, dh, resize_to, matrix_of, origin, tables = _geometry(superposition_homography_dict, resize_info, on_surface, surface, focal,
+                                                             placement, scale, w0, h0)
+    ctx = runtime.get_context(64, 64)
+    dev = runtime.device()
+    if tables is not None:
+        tables = tuple(torch.from_numpy(t).to(dev) for t in tables)
+    label = _device_labels(ctx, dev, n_frames, resize_to or (w0, h0), dw, dh, matrix_of, origin, tables, feather)
+    return label.cpu().numpy()
 
 
 class CanvasPainter:
@@ -228,15 +301,18 @@ class CanvasPainter:
 
 
 def blended_mosaic(capture, superposition_homography_dict, resize_info, blend="feather", feather_px=32, gains=None,
-                   placement="warp", scale=1.0, surface=None, focal=None, chunk_frames=32, ingest="auto"):
+                   placement="warp", scale=1.0, surface=None, focal=None, chunk_frames=32, ingest="auto", bands=5):
     """uint8 [dh,dw,3]: all frames of `capture` blended into one canvas on the device, the state carried from chunk to chunk.
     blend "feather": the weighted mean, weights rising over feather_px pixels from a frame's border; "seam": per pixel the frame
-    whose border is farthest away.  gains: float [n_frames,3] (solve_gains), row i for the i-th frame read, or None; frames past
-    its end get 1.  The canvas is the fixed plane's (placement, scale as in stabilization.stabilized_frames) or, with surface
-    "cylinder" / "sphere", surface.surface_model's (focal as there).  Bad arguments are refused before the capture is touched."""
+    whose border is farthest away; "bands": multi-band blending with pyramid levels 0..bands under the label mask of "seam"
+    (seam_labels; first the labels from the matrices, then the frames).  gains: float [n_frames,3] (solve_gains), row i for the
+    i-th frame read, or None; frames past its end get 1.  The canvas is the fixed plane's (placement, scale as in
+    stabilization.stabilized_frames) or, with surface "cylinder" / "sphere", surface.surface_model's (focal as there).  Bad
+    arguments are refused before the capture is touched."""
     import torch
-    from .stabilization import _canvas_chunks, _placement, MAX_PIXELS
-    on_surface, feather, q = _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, chunk_frames, ingest)
+    from .stabilization import _canvas_chunks
+    on_surface, feather, q = _check_mosaic(blend, feather_px, gains, placement, scale, surface, focal, chunk_frames, ingest, bands)
+    n_frames = _last_frame(superposition_homography_dict) if blend == "bands" else 0
     state = {}
 
     def chunk_gains(dev, frame_no, n):
@@ -249,31 +325,40 @@ def blended_mosaic(capture, superposition_homography_dict, resize_info, blend="f
 
     def setup(w0, h0):
         dev = runtime.device()
-        if on_surface:
-            from .surface import frame_matrix, surface_model, surface_tables
-            size = (int(resize_info["w"]), int(resize_info["h"]))
-            model = surface_model(superposition_homography_dict, resize_info, surface, focal, scale, MAX_PIXELS)
-            ox, oy, dw, dh, scale_px = model.bounds
-            cols, rows = (torch.from_numpy(t).to(dev) for t in surface_tables(surface, scale_px, ox, oy, dw, dh))
-            nan = np.full(9, np.nan)
-
-            def matrix_of(frame_no):
-                R = model.rotations.get(frame_no)
-                return nan if R is None else frame_matrix(R, model.focal, model.centre, (w0, h0), size)
-            resize_to = None
+        dw, dh, resize_to, matrix_of, origin, tables = _geometry(superposition_homography_dict, resize_info, on_surface, surface,
+                                                                 focal, placement, scale, w0, h0)
+        if tables is not None:
+            cols, rows = (torch.from_numpy(t).to(dev) for t in tables)
+        if blend == "bands":
+            from ._lib import bands_state_elems
+            ctx = runtime.get_context(64, 64)
+            label = _device_labels(ctx, dev, n_frames, resize_to or (w0, h0), dw, dh, matrix_of, origin,
+                                   None if tables is None else (cols, rows), feather)
+            acc = torch.zeros(bands_state_elems(dw, dh, 3, int(bands)), dtype=torch.int64, device=dev)
         else:
-            ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, MAX_PIXELS)
-            resize_to = (int(resize_info["w"]), int(resize_info["h"])) if placement == "translate" else None
-        acc = torch.zeros((dh, dw, 4), dtype=torch.int64, device=dev)
+            acc = torch.zeros((dh, dw, 4), dtype=torch.int64, device=dev)
 
         def paint(ctx, frame_no, n, src, size, out, canvas):
             mats = torch.from_numpy(np.stack([matrix_of(frame_no + 1 + k) for k in range(n)])).to(dev)
-            common = dict(out=canvas, mode=blend, feather=feather, gains=chunk_gains(dev, frame_no, n), acc=acc,
-                          acc_in=bool(state), size=size)
-            if on_surface:
-                ctx.blend_ray_surface(src, mats, cols, rows, **common)
+            if blend == "bands":
+                # a frame past the last label owns no pixel: it adds nothing, and its label may not be named
+                n = max(0, min(n, MAX_LABEL + 1 - frame_no))
+                if n == 0 and state:
+                    return
+                common = dict(label=label, levels=int(bands), first_label=frame_no, out=canvas, gains=chunk_gains(dev, frame_no, n),
+                              state=acc, state_in=bool(state), size=size)
+                src = tuple(p[:n] for p in src) if isinstance(src, (tuple, list)) else src[:n]
+                if on_surface:
+                    ctx.blend_bands_ray_surface(src, mats[:n], cols, rows, **common)
+                else:
+                    ctx.blend_bands_fixed_plane(src, mats[:n], origin, **common)
             else:
-                ctx.blend_fixed_plane(src, mats, (ox, oy), **common)
+                common = dict(out=canvas, mode=blend, feather=feather, gains=chunk_gains(dev, frame_no, n), acc=acc,
+                              acc_in=bool(state), size=size)
+                if on_surface:
+                    ctx.blend_ray_surface(src, mats, cols, rows, **common)
+                else:
+                    ctx.blend_fixed_plane(src, mats, origin, **common)
             ctx.order_torch_after()
             state["carried"] = True
         return dw, dh, resize_to, paint

@@ -1426,15 +1426,18 @@ struct BlendArgs {
   WarpArgs W; bool ray; const double* col; const double* row; int feather; const uint16_t* gain; uint64_t* acc; int acc_in;
   bool idle() const { return false; }       // no frames: the picture of the incoming state
 };
-int check(evh_ctx* c, const BlendArgs& B) {
+// The refusals of a blend whose state is called `sname` (d_acc, or the band blend's d_state) and in_name (acc_in, state_in) and
+// holds state_elems(dw, dh, channels) 64-bit words -- asked for only once the sizes have passed.
+template <class Elems>
+int check_blend(evh_ctx* c, const BlendArgs& B, const char* sname, const char* in_name, Elems state_elems) {
   const WarpArgs& A = B.W;
   const std::string W = std::string(A.who) + ": ";
   const int cn = A.F.channels;
   if (int rc = need_source(c, W, A.F)) return rc;
   if (!A.M || (B.ray && (!B.col || !B.row))) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
-  if (!A.out && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + "d_out and d_acc are both NULL");
-  if (B.acc_in && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + "acc_in without d_acc");
-  if ((uintptr_t)B.acc & 7) return evh_fail(c, EVH_ERR_INVALID, W + "d_acc must be 8-byte aligned");
+  if (!A.out && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + "d_out and " + sname + " are both NULL");
+  if (B.acc_in && !B.acc) return evh_fail(c, EVH_ERR_INVALID, W + in_name + " without " + sname);
+  if ((uintptr_t)B.acc & 7) return evh_fail(c, EVH_ERR_INVALID, W + sname + " must be 8-byte aligned");
   if (int rc = need_channels(c, W, A.F)) return rc;
   if (A.nframes < 0 || A.sw < 1 || A.sh < 1 || A.dw < 1 || A.dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
   if (A.mode != EVH_BLEND_FEATHER && A.mode != EVH_BLEND_SEAM) return evh_fail(c, EVH_ERR_INVALID, W + "unknown mode");
@@ -1453,7 +1456,7 @@ int check(evh_ctx* c, const BlendArgs& B) {
   Span src[3];
   source_spans(A.F, A.nframes, A.sw, A.sh, src);
   const Span gain = {B.gain, (int64_t)A.nframes * 6, "d_gain"};
-  const Span state[1] = {{B.acc, (int64_t)A.dw * A.dh * (cn + 1) * 8, "d_acc"}};
+  const Span state[1] = {{B.acc, state_elems(A.dw, A.dh, cn) * 8, sname}};
   const Span others[9] = {{A.out, A.out ? canvas : 0, "d_out"}, {A.out ? A.bg : nullptr, canvas, "d_background"}, gain,
                           {A.M, (int64_t)A.nframes * 72, B.ray ? "d_A" : "d_M"}, {B.col, (int64_t)A.dw * 16, "d_col"},
                           {B.row, (int64_t)A.dh * 8, "d_row"}, src[0], src[1], src[2]};
@@ -1461,6 +1464,9 @@ int check(evh_ctx* c, const BlendArgs& B) {
   const Span picture[1] = {{A.out, A.out ? canvas : 0, "d_out"}};
   const Span inputs[4] = {gain, src[0], src[1], src[2]};
   return need_apart(c, W, picture, inputs);
+}
+int check(evh_ctx* c, const BlendArgs& B) {
+  return check_blend(c, B, "d_acc", "acc_in", [](int dw, int dh, int cn) { return (int64_t)dw * dh * (cn + 1); });
 }
 // k_blend over the canvas; nframes may be 0, and one of out and acc NULL
 int launch(evh_ctx* c, const BlendArgs& B) {
@@ -1486,6 +1492,8 @@ int launch(evh_ctx* c, const BlendArgs& B) {
   });
   return launched(c);
 }
+
+#include "evh_plane_bands.h"       // the multi-band blend and the seam labels: kernels, check() and launch()
 
 // ---- the sums behind exposure gains: two frames of a batch compared where one maps onto the other ----------------------------------
 struct ExposureArgs {
@@ -1939,6 +1947,69 @@ int evh_blend_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes,
   return run(c, BlendArgs{{"evh_blend_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, mode, d_background, d_out, dw,
                            dh, out_row_stride, 0, 0, 0},
                           true, d_col, d_row, feather, d_gain, d_acc, acc_in});
+}
+
+int evh_seam_labels_fixed_plane(evh_ctx* c, int nframes, int sw, int sh, const double* d_M, int inverse_map, int feather, int dw, int dh,
+                                int ox, int oy, int first_label, uint32_t* d_best, uint16_t* d_label, int state_in) {
+  return run(c, LabelArgs{"evh_seam_labels_fixed_plane", nframes, sw, sh, d_M, inverse_map, false, nullptr, nullptr, feather, dw, dh, ox,
+                          oy, first_label, d_best, d_label, state_in});
+}
+
+int evh_seam_labels_ray_surface(evh_ctx* c, int nframes, int sw, int sh, const double* d_A, const double* d_col, const double* d_row,
+                                int feather, int dw, int dh, int first_label, uint32_t* d_best, uint16_t* d_label, int state_in) {
+  return run(c, LabelArgs{"evh_seam_labels_ray_surface", nframes, sw, sh, d_A, 1, true, d_col, d_row, feather, dw, dh, 0, 0, first_label,
+                          d_best, d_label, state_in});
+}
+
+int64_t evh_bands_state_elems(int dw, int dh, int channels, int levels) {
+  if (dw < 1 || dh < 1 || (channels != 1 && channels != 3) || levels < 0 || levels > 8) return -1;
+  return bands_state_elems(dw, dh, channels, levels);
+}
+
+int64_t evh_bands_frame_ws_bytes(int dw, int dh, int channels, int levels) {
+  const int64_t elems = evh_bands_state_elems(dw, dh, channels, levels);
+  return elems < 0 ? -1 : elems * 4;
+}
+
+int evh_blend_bands_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                                int64_t frame_stride, const double* d_M, int inverse_map, int levels, const uint16_t* d_label,
+                                int first_label, const uint16_t* d_gain, int64_t* d_state, int state_in, void* d_ws, int64_t ws_bytes,
+                                const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int ox, int oy) {
+  return run(c, BandsArgs{{{"evh_blend_bands_fixed_plane", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
+                            d_M, inverse_map, EVH_BLEND_SEAM, d_background, d_out, dw, dh, out_row_stride, 0, ox, oy},
+                           false, nullptr, nullptr, 0, d_gain, reinterpret_cast<uint64_t*>(d_state), state_in},
+                          levels, d_label, first_label, d_ws, ws_bytes});
+}
+
+int evh_blend_bands_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M, int inverse_map,
+                                       int levels, const uint16_t* d_label, int first_label, const uint16_t* d_gain, int64_t* d_state,
+                                       int state_in, void* d_ws, int64_t ws_bytes, const uint8_t* d_background, uint8_t* d_out, int dw,
+                                       int dh, int64_t out_row_stride, int ox, int oy) {
+  return run(c, BandsArgs{{{"evh_blend_bands_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, EVH_BLEND_SEAM,
+                            d_background, d_out, dw, dh, out_row_stride, 0, ox, oy},
+                           false, nullptr, nullptr, 0, d_gain, reinterpret_cast<uint64_t*>(d_state), state_in},
+                          levels, d_label, first_label, d_ws, ws_bytes});
+}
+
+int evh_blend_bands_ray_surface(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                                int64_t frame_stride, const double* d_A, const double* d_col, const double* d_row, int levels,
+                                const uint16_t* d_label, int first_label, const uint16_t* d_gain, int64_t* d_state, int state_in,
+                                void* d_ws, int64_t ws_bytes, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                int64_t out_row_stride) {
+  return run(c, BandsArgs{{{"evh_blend_bands_ray_surface", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh,
+                            d_A, 1, EVH_BLEND_SEAM, d_background, d_out, dw, dh, out_row_stride, 0, 0, 0},
+                           true, d_col, d_row, 0, d_gain, reinterpret_cast<uint64_t*>(d_state), state_in},
+                          levels, d_label, first_label, d_ws, ws_bytes});
+}
+
+int evh_blend_bands_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                       const double* d_col, const double* d_row, int levels, const uint16_t* d_label, int first_label,
+                                       const uint16_t* d_gain, int64_t* d_state, int state_in, void* d_ws, int64_t ws_bytes,
+                                       const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride) {
+  return run(c, BandsArgs{{{"evh_blend_bands_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, EVH_BLEND_SEAM,
+                            d_background, d_out, dw, dh, out_row_stride, 0, 0, 0},
+                           true, d_col, d_row, 0, d_gain, reinterpret_cast<uint64_t*>(d_state), state_in},
+                          levels, d_label, first_label, d_ws, ws_bytes});
 }
 
 int evh_pair_exposure(evh_ctx* c, const uint8_t* d_frames, int nframes, int w, int h, int channels, int64_t row_stride,

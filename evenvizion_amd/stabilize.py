@@ -74,8 +74,10 @@ def parser():
                          "also writes surface_report.json")
     ap.add_argument("--focal", type=float, default=None,
                     help="surface: focal length in pixels of the resized frame; estimated from the matrices when not given")
-    ap.add_argument("--blend", choices=("feather", "seam"), default=None,
-                    help="mosaic only: blend the covering frames (evenvizion_amd.blend) and write mosaic_blend.ppm")
+    ap.add_argument("--blend", choices=("feather", "seam", "bands"), default=None,
+                    help="mosaic only: blend the covering frames (evenvizion_amd.blend) and write mosaic_blend.ppm; bands: "
+                         "multi-band blending under the label mask of seam")
+    ap.add_argument("--bands", type=int, default=None, help="blend bands: the pyramid has levels 0..N (0..8, default 5)")
     ap.add_argument("--feather", type=float, default=32.0, help="blend: pixels over which a frame's weight rises from its border")
     ap.add_argument("--exposure", type=int, choices=(0, 1), default=0,
                     help="blend: 1 solves one gain per frame and channel from the overlaps and writes exposure_gains.json")
@@ -103,6 +105,11 @@ def main(argv=None):
         ap.error("--feather and --exposure need --blend")
     if not 0 <= args.feather <= 2047:
         ap.error("--feather lies in 0..2047 pixels")
+    if args.blend != "bands" and args.bands is not None:
+        ap.error("--bands needs --blend bands")
+    bands = 5 if args.bands is None else args.bands
+    if not 0 <= bands <= 8:
+        ap.error("--bands lies in 0..8")
     from .component import open_capture
     from .processing.utils import read_homography_dict, superposition_dict
     from .stabilization import comparison_frames, stabilized_frames, write_ppm
@@ -130,7 +137,7 @@ def main(argv=None):
                            "gains": {str(k): [float(v) for v in g] for k, g in zip(keys, gains)}}, f, indent=1)
             cap, _, _ = open_capture(args.path_to_video)          # the second pass starts from the first frame again
         picture = blended_mosaic(cap, sup, resize_info, blend=args.blend, feather_px=args.feather, gains=gains, placement=placement,
-                                 scale=args.scale, surface=args.surface, focal=args.focal)
+                                 scale=args.scale, surface=args.surface, focal=args.focal, bands=bands)
         write_ppm(os.path.join(save_folder, "mosaic_blend.ppm"), picture)
         return save_folder
     if args.surface:

@@ -27,6 +27,7 @@
  *                                 past camera rotations above 90 degrees -- frames placed on a cylinder, a sphere or a plane of rays
  *   evh_blend_fixed_plane[_yuv420], evh_blend_ray_surface[_yuv420] no counterpart: the mosaic with feathered seams (or the frame
  *                                 nearest its centre per pixel) and per-frame exposure gains, on the plane or on a surface
+ *   evh_seam_labels_*, evh_blend_bands_*[_yuv420] no counterpart: multi-band blending of that mosaic under a label mask
  *   evh_pair_exposure[_yuv420]    no counterpart: the overlap sums from which those gains are solved
  *   evh_trail_fixed_plane[_yuv420] stabilize_view with decrease_brightness and change_frame_location: earlier frames dimmed,
  *                                 the frame outlined            visualization/stabilization.py:21-97, 129-172
@@ -579,6 +580,99 @@ int evh_blend_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframe
                                  const double* d_col, const double* d_row, int mode, int feather, const uint16_t* d_gain,
                                  uint64_t* d_acc, int acc_in, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
                                  int64_t out_row_stride);
+
+/* ---- multi-band blending of the mosaic: Laplacian pyramids blended under the pyramids of a label mask ----------------------------- */
+/* FEATHER smooths exposure steps and every detail on which two frames disagree; SEAM keeps the detail and every step.  The band
+ * blend (Burt and Adelson) blends low frequencies over a wide zone and high frequencies over a narrow one, in integers throughout.
+ *
+ * LABELS.  evh_seam_labels_fixed_plane / evh_seam_labels_ray_surface write SEAM's partition of the canvas from the geometry alone;
+ * they read no frame.  nframes, sw, sh, d_M / inverse_map / ox / oy or d_A / d_col / d_row, feather, dw, dh are the blend entries'.
+ *   first_label  frame k of the call carries label first_label + k; all labels lie in 0..65534, 65535 means "nobody";
+ *   d_best       u32[dh][dw] (DEVICE), tight, in and out: the largest w so far, 0 = nobody;
+ *   d_label      u16[dh][dw] (DEVICE), tight, in and out;
+ *   state_in     zero: start from best = 0, label = 65535; non-zero: from the two buffers.
+ * Frames in order: coverage and w = min(d, F) + 1 are steps 1-2 of the blend entries' contract (tw > 0 of the ray form included);
+ * if w > best: best = w, label = first_label + k.  The comparison is strict: the earliest frame holds among equal weights, as in
+ * SEAM.  Calls that carry the two buffers equal one call.  One launch, caller buffers only, nframes == 0 writes the start state.
+ * Refused before the launch, outputs untouched -- EVH_ERR_INVALID: a NULL argument, d_best not 4-byte or d_label not 2-byte aligned,
+ * nframes < 0, an empty frame or canvas, feather outside 0..65535, a label outside 0..65534, d_best or d_label overlapping each
+ * other, the matrices or the tables; EVH_ERR_CAPACITY: sw or sh >= 2^26, dw*dh > INT_MAX, nframes > 65535.
+ *
+ * THE BAND BLEND.  evh_blend_bands_* take the four forms of evh_blend_*: the same frames, geometry, d_gain, d_background, d_out,
+ * strides and plane forms, and instead of mode, feather and d_acc:
+ *   levels       n in 0..8: the pyramid has levels 0..n.  dw_0 = dw, dw_{l+1} = (dw_l + 1) >> 1, dh alike;
+ *   d_label      u16[dh][dw] (DEVICE), tight, read only: which frame owns a pixel;
+ *   first_label  frame k of the call is the one d_label calls first_label + k;
+ *   d_state      i64 (DEVICE), 8-byte aligned, in and out, may be NULL: per level l an array [dh_l][dw_l][cn + 1], levels 0..n one
+ *                after the other; words 0..cn-1 of a pixel hold A_c, word cn holds D.  evh_bands_state_elems gives the word count;
+ *   state_in     non-zero: the state starts from d_state; zero: from zeros;
+ *   d_ws, ws_bytes  caller workspace (DEVICE), 8-byte aligned.  evh_bands_frame_ws_bytes is what one frame's pyramids need; the
+ *                entry takes the frames in groups of as many as fit.  With d_state == NULL the state is kept at the head of d_ws,
+ *                which must then hold 8 * evh_bands_state_elems bytes more.  The result does not depend on ws_bytes.
+ * Per frame k, in any order (the state is a sum of integers):
+ *   1. EXTENDED SAMPLE.  (U, V) is the warp entry's position, the same operations in the same order.  It is VALID if neither is NaN
+ *      (ray form: and tw > 0).  U' = min(max(U, 0), 32*(sw-1)) in double, V' alike; the taps and the >> 10 at (U', V') are the warp
+ *      entry's: the frame continued past its border by its edge pixels, no tap leaves the frame.  An invalid position gives
+ *      s_c = 0.  G0_c(p) = s_c * g_c (below 2^24) at EVERY canvas pixel p: a frame's border is no step inside its own pyramid.
+ *   2. MASK.  W0(p) = 65536 if d_label[p] == first_label + k, else 0.
+ *   3. REDUCE.  K = (1,4,6,4,1) in both directions, indices clamped to the level:
+ *      G{l+1}(x,y) = (sum_ij K_i K_j Gl(2x+i-2, 2y+j-2) + 128) >> 8 (the sum fits u32); W{l+1} the same with + 255: it rounds up,
+ *      a weight with any support stays positive, and a full mask stays 65536 at every level.
+ *   4. EXPAND E(G{l+1}) to the size of level l.  Along an axis, with j = i >> 1 and clamped indices: even i gives
+ *      g[j-1] + 6 g[j] + g[j+1], odd i gives 4 g[j] + 4 g[j+1].  Rows, then columns, then (. + 32) >> 6 once (>> rounds down, also
+ *      below zero).  Ll = Gl - E(G{l+1}) for l < n, Ln = Gn.
+ *   5. ACCUMULATE.  Al_c += Wl * Ll_c, Dl += Wl, in i64.
+ * The PICTURE, written when d_out is given, is a function of the state alone.  With ql_c = floor((2 A + D) / (2 D)) where D > 0,
+ * else 0: Rn = qn, Rl = ql + E(R{l+1}) top-down; out_c = clamp((R0_c + 2048) >> 12, 0, 255) where D0 > 0; elsewhere the pixel takes
+ * d_background's bytes, or zeros.  nframes == 0 writes the picture of the incoming state.
+ * BOUNDS.  The labels partition the canvas, so over all frames sum_k W_k^l <= 65536 + (frames whose masks reach the pixel);
+ * |L| < 2^25, so |A| < 2^42 + small for any number of frames; |q| < 2^26, |R| < 9 * 2^26.  The formulas hold unwrapped for ANY
+ * handed-in state with 0 <= D < 2^25 and |A_c| <= 2^26 * D (a state the entry did not write is the caller's to keep inside these).
+ * What follows from the rules:
+ *   (a) if every covered pixel is labelled with the one frame that entered, the picture holds min(255, (s*g + 2048) >> 12) at every
+ *       labelled pixel, at any `levels`: the warp entry's byte for gain 4096 (the round-up of W makes this hold to the border);
+ *   (b) levels = 0 with labels from evh_seam_labels_* equals evh_blend_* in mode SEAM with the same feather and gains, byte for byte;
+ *   (c) frames that show one constant value s*g everywhere give R0 exactly equal to it, for any labels that give every pixel to
+ *       one of them (a level with D = 0 somewhere has q = 0 there, and an expansion beside such a hole mixes that 0 in);
+ *   (d) calls that carry d_state equal one call, state word for state word; so do any frame order and any ws_bytes;
+ *   (e) the plane forms equal evh_yuv420_to_bgr followed by the BGR forms; the ray form with the plane's tables equals the plane
+ *       form with inverse_map != 0 wherever tw > 0 holds on the whole canvas.
+ * Only caller buffers are used; the launches go to the context's stream, no synchronisation.  d_background == d_out is allowed.
+ * Refused before anything is launched, outputs untouched -- everything evh_blend_* refuses (with d_state for d_acc), and
+ * EVH_ERR_INVALID: levels outside 0..8, d_label NULL or not 2-byte aligned, a label outside 0..65534, d_out and d_state both NULL,
+ * state_in with d_state NULL, d_ws NULL or not 8-byte aligned, ws_bytes below one frame's pyramids (plus the state where d_state
+ * is NULL), d_ws overlapping any other buffer, d_state or d_out overlapping d_label.
+ * The sizing helpers run on the host alone and touch no device; they return -1 for sizes the entries refuse.  What to allocate
+ * for d_ws: g * evh_bands_frame_ws_bytes(...) for groups of g >= 1 frames, plus 8 * evh_bands_state_elems(...) when d_state is NULL. */
+int evh_seam_labels_fixed_plane(evh_ctx* ctx, int nframes, int sw, int sh, const double* d_M, int inverse_map,
+                                int feather /* 0..65535 */, int dw, int dh, int ox, int oy, int first_label,
+                                uint32_t* d_best /* u32[dh,dw] DEVICE */, uint16_t* d_label /* u16[dh,dw] DEVICE */, int state_in);
+int evh_seam_labels_ray_surface(evh_ctx* ctx, int nframes, int sw, int sh, const double* d_A, const double* d_col,
+                                const double* d_row, int feather, int dw, int dh, int first_label, uint32_t* d_best,
+                                uint16_t* d_label, int state_in);
+int64_t evh_bands_state_elems(int dw, int dh, int channels, int levels);
+int64_t evh_bands_frame_ws_bytes(int dw, int dh, int channels, int levels);
+int evh_blend_bands_fixed_plane(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                                int64_t row_stride, int64_t frame_stride, const double* d_M, int inverse_map, int levels /* 0..8 */,
+                                const uint16_t* d_label, int first_label, const uint16_t* d_gain /* may be NULL */,
+                                int64_t* d_state /* may be NULL */, int state_in, void* d_ws, int64_t ws_bytes,
+                                const uint8_t* d_background, uint8_t* d_out /* may be NULL */, int dw, int dh,
+                                int64_t out_row_stride, int ox, int oy);
+int evh_blend_bands_fixed_plane_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_M,
+                                       int inverse_map, int levels, const uint16_t* d_label, int first_label,
+                                       const uint16_t* d_gain, int64_t* d_state, int state_in, void* d_ws, int64_t ws_bytes,
+                                       const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int ox,
+                                       int oy);
+int evh_blend_bands_ray_surface(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                                int64_t row_stride, int64_t frame_stride, const double* d_A, const double* d_col,
+                                const double* d_row, int levels, const uint16_t* d_label, int first_label, const uint16_t* d_gain,
+                                int64_t* d_state, int state_in, void* d_ws, int64_t ws_bytes, const uint8_t* d_background,
+                                uint8_t* d_out, int dw, int dh, int64_t out_row_stride);
+int evh_blend_bands_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
+                                       const double* d_col, const double* d_row, int levels, const uint16_t* d_label,
+                                       int first_label, const uint16_t* d_gain, int64_t* d_state, int state_in, void* d_ws,
+                                       int64_t ws_bytes, const uint8_t* d_background, uint8_t* d_out, int dw, int dh,
+                                       int64_t out_row_stride);
 
 /* ---- the sums behind exposure gains: two frames of a batch compared where one maps onto the other -------------------------------- */
 /* What a gain solve needs (Brown and Lowe's gain compensation: per overlapping pair the number of pixels and the mean of either

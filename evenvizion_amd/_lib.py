@@ -23,6 +23,7 @@ MODE_INDEPENDENT_PAIRS, MODE_STREAM = 0, 1
 WARP_EACH, WARP_HISTORY, WARP_MOSAIC = 0, 1, 2
 WARP_MODES = {"each": WARP_EACH, "history": WARP_HISTORY, "mosaic": WARP_MOSAIC}
 PLATE_MAX_FRAMES = 255   # EVH_PLATE_MAX_FRAMES (include/evhip.h): frames one plate_fixed_plane call takes
+COMPONENTS_TILE = (32, 16)   # EVH_COMPONENTS_TILE_W, _H (include/evhip.h): the tile of mask_components' first pass
 DRAW_REFERENCE, DRAW_OWN_FRAME = 0, 1
 DRAW_POINTS = {"reference": DRAW_REFERENCE, "own_frame": DRAW_OWN_FRAME}
 RESIDUAL_ABS, RESIDUAL_MASK = 0, 1
@@ -147,6 +148,9 @@ SIGNATURES = {
                                     _d, _d, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "evh_rows_moving_filter_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i,
                                            _d, _d, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # the masks' connected components: labels, and a table of boxes, areas and centre sums
+    "evh_mask_components_work_bytes": (C.c_size_t, [_i, _i, _i]),
+    "evh_mask_components": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i64, _i64, _vp, _i, _vp, _vp, C.c_size_t]),
     # heat-map pictures: colour index, table, blend over the frame
     "evh_heatmap_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _i64, _vp, _d, _d, _i, _vp, _i64, _i64]),
     # matching pictures: the rows a batch handed to its final solve, and the two frames side by side with a line per row
@@ -206,6 +210,22 @@ def bands_frame_ws_bytes(dw, dh, channels, levels):
     """Workspace bytes one frame's pyramids need (evh_bands_frame_ws_bytes; host only, -1 for sizes the entries refuse).  A
     call holding g frames at once needs g times this, and 8 * bands_state_elems(...) more where it is given no state."""
     return int(load().evh_bands_frame_ws_bytes(int(dw), int(dh), int(channels), int(levels)))
+
+
+def component_dtype():
+    """evh_component (include/evhip.h) as a structured numpy dtype: 40 bytes."""
+    import numpy as np
+    return np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("area", "<i4"), ("first", "<i4"),
+                     ("sx", "<i8"), ("sy", "<i8")])
+
+
+def mask_components_work_bytes(dw, dh, nmasks):
+    """Bytes of scratch mask_components needs (evh_mask_components_work_bytes; host only, 0 for arguments the entry refuses):
+    at most 8 * dw * dh * nmasks."""
+    args = [int(dw), int(dh), int(nmasks)]
+    if any(abs(a) > 0x7fffffff for a in args):
+        return 0
+    return int(load().evh_mask_components_work_bytes(*args))
 
 
 def build(force=False):
@@ -285,12 +305,14 @@ class Context:
 
     _nothing = None          # a few device bytes for calls that take no frames (see _blend)
     _bands_ws = None         # the workspace of blend_bands_* calls that bring none (see _blend_bands)
+    _components_work = None  # the scratch of mask_components calls that bring none: kept, the launches outlive the call
 
     def close(self):
         if getattr(self, "h", None):
             self.lib.evh_destroy(self.h)
             self.h = None
             self._bands_ws = None
+            self._components_work = None
 
     def __del__(self):
         try:
@@ -954,6 +976,57 @@ class Context:
         tail = (mats.data_ptr(), int(bool(inverse_map)), int(min_cover), bp, pp, prs, cp, crs, mp, int(threshold), mrs, mfs, dw, dh,
                 int(origin[0]), int(origin[1]))
         self._check(self._form("evh_plate_fixed_plane", planes)(self.h, *head, *tail))
+
+    def mask_components(self, masks, labels, connectivity=8, open_radius=0, min_area=1, objects=None, nobjects=None, work=None):
+        """The connected components of masks (evh_mask_components, the contract is stated in include/evhip.h).  masks: CUDA
+        uint8 [n,dh,dw] as plate_fixed_plane writes them, non-zero = set; rows and masks may be strided.  labels: CUDA int32
+        [n,dh,dw], rows and sheets may be strided: 0, or the number 1..K of the pixel's component, numbered by first pixel in
+        raster order among the components of at least min_area pixels, after an opening by a (2*open_radius+1)^2 square.
+        objects: None, or a contiguous CUDA tensor of n*max_objects*40 bytes (int64 [n,max_objects,5] has the alignment): the
+        table of evh_component, read with components_table().  nobjects: CUDA int32 [n] or None (one is made).  work: a
+        contiguous CUDA tensor of at least mask_components_work_bytes(dw, dh, n) bytes, or None (the context keeps one).  Returns
+        nobjects.  Does not synchronise."""
+        import torch
+        self._enter()
+        mp, dw, dh, mrs, mfs = self._image_rows(masks, 1, 1, "masks")
+        n = int(masks.shape[0])
+        if labels.dtype != torch.int32 or not labels.is_cuda or labels.device.index != self.device or labels.dim() != 3:
+            raise ValueError("labels must be an int32 tensor [n,dh,dw] on the context's device (cuda:%d)" % self.device)
+        if tuple(labels.shape) != (n, dh, dw) or (dw > 1 and labels.stride(2) != 1):
+            raise ValueError("labels must be [n,dh,dw] for masks [n,dh,dw], with packed rows")
+        lrs = labels.stride(1) if dh > 1 else dw
+        max_objects = 0
+        if objects is not None:
+            nbytes = objects.numel() * objects.element_size()
+            if not objects.is_cuda or objects.device.index != self.device or not objects.is_contiguous() or \
+                    nbytes % (40 * max(n, 1)):
+                raise ValueError("objects must be a contiguous CUDA tensor of n*max_objects*40 bytes")
+            max_objects = nbytes // (40 * max(n, 1))
+        if nobjects is None:
+            nobjects = torch.zeros(n, dtype=torch.int32, device=labels.device)
+        self._dev_tensor(nobjects, torch.int32, n, "nobjects must be a contiguous CUDA int32 tensor of n elements")
+        need = mask_components_work_bytes(dw, dh, n)
+        if work is None:
+            if self._components_work is None or self._components_work.numel() * 4 < need:
+                if self._components_work is not None:
+                    self.order_torch_after()         # before a larger one replaces it: torch behind what still uses the old one
+                self._components_work = torch.empty(max(need, 4) // 4, dtype=torch.int32, device=labels.device)
+            work = self._components_work
+        if not work.is_cuda or work.device.index != self.device or not work.is_contiguous():
+            raise ValueError("work must be a contiguous CUDA tensor")
+        if n == 0:                           # empty tensors have no address to hand over
+            return nobjects
+        self._check(self.lib.evh_mask_components(self.h, mp, n, dw, dh, mrs, mfs, int(connectivity), int(open_radius), int(min_area),
+                                                 labels.data_ptr(), lrs, labels.stride(0),
+                                                 objects.data_ptr() if max_objects else None, max_objects, nobjects.data_ptr(),
+                                                 work.data_ptr(), work.numel() * work.element_size()))
+        return nobjects
+
+    @staticmethod
+    def components_table(objects):
+        """The table mask_components filled, downloaded: a numpy array [n,max_objects] of component_dtype()."""
+        n = objects.shape[0]
+        return objects.cpu().contiguous().view(-1).numpy().view("u1").reshape(-1).view(component_dtype()).reshape(n, -1)
 
     def rows_moving_filter(self, frames, mats, plate, count, origin, rows, counts, status1, out_rows, out_counts, moving=None,
                            flags=None, *, threshold=16, min_cover=1, radius=1, min_hits=1, row_scale=(1.0, 1.0), frame_step=1,

@@ -1882,6 +1882,8 @@ int launch(evh_ctx* c, const MovingArgs& A) {
   return launched(c);
 }
 
+#include "evh_plane_components.h"  // the connected components of the masks: kernels, check() and launch()
+
 }  // namespace
 
 extern "C" {
@@ -2099,6 +2101,17 @@ int evh_plate_fixed_plane_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes,
   return run(c, PlateArgs{"evh_plate_fixed_plane_yuv420", yuv420_frames(src), nframes, sw, sh, d_M, inverse_map, min_cover,
                           d_background, d_plate, plate_row_stride, d_count, count_row_stride, d_mask, threshold, mask_row_stride,
                           mask_frame_stride, dw, dh, ox, oy});
+}
+
+size_t evh_mask_components_work_bytes(int dw, int dh, int nmasks) { return components_work_bytes(dw, dh, nmasks); }
+
+int evh_mask_components(evh_ctx* c, const uint8_t* d_mask, int nmasks, int dw, int dh, int64_t mask_row_stride, int64_t mask_frame_stride,
+                        int connectivity, int open_radius, int min_area, int32_t* d_labels, int64_t label_row_stride,
+                        int64_t label_frame_stride, evh_component* d_objects, int max_objects, int32_t* d_nobjects, void* d_work,
+                        size_t work_bytes) {
+  return run(c, ComponentsArgs{"evh_mask_components", d_mask, nmasks, dw, dh, mask_row_stride, mask_frame_stride, connectivity,
+                               open_radius, min_area, d_labels, label_row_stride, label_frame_stride, d_objects, max_objects,
+                               d_nobjects, d_work, work_bytes});
 }
 
 int evh_rows_moving_filter(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,

@@ -150,3 +150,131 @@ def refine_homography_dict(capture, homography_dict, plate, placement="warp", sc
         _pairs_into(refined, frame_no, Hs.cpu().numpy().reshape(-1, 3, 3), sts_h, none_H_processing)
     refined["resize_info"] = {"h": h, "w": w}
     return refined, stats
+
+
+# ---- the masks as objects: connected components on the device, tracks on the host ----------------------------------------------------
+def _objects_arguments(placement, scale, max_frames, min_cover, threshold, connectivity, open_radius, min_area, max_objects, ingest):
+    """The refusals of moving_objects, before the capture is touched."""
+    from .stabilization import check_plate_arguments
+    for name, value in (("max_frames", max_frames), ("min_cover", min_cover), ("threshold", threshold)):
+        _integer(name, value, 0)
+    check_plate_arguments(max_frames, min_cover, threshold, placement, ingest)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or scale <= 0:
+        raise ValueError("scale must be a finite positive number")
+    if placement == "translate" and float(scale) != 1.0:
+        raise ValueError("placement='translate' is the reference's paste: scale must be 1")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    _integer("open_radius", open_radius, 0, 3)
+    _integer("min_area", min_area, 1)
+    _integer("max_objects", max_objects, 1, 65535)
+
+
+def _iou(a, b):
+    """Intersection over union of two inclusive boxes (x0, y0, x1, y1); edges count as one unit, as pixels do."""
+    w = min(a[2], b[2]) - max(a[0], b[0]) + 1
+    h = min(a[3], b[3]) - max(a[1], b[1]) + 1
+    if w <= 0 or h <= 0:
+        return 0.0
+    inter = w * h
+    return inter / ((a[2] - a[0] + 1) * (a[3] - a[1] + 1) + (b[2] - b[0] + 1) * (b[3] - b[1] + 1) - inter)
+
+
+def link_objects(objects_by_frame, min_iou=0.1):
+    """Objects linked into tracks by the overlap of their boxes -> a list of tracks, each a list of (frame_no, object index), in
+    the order the tracks were opened.  objects_by_frame: {frame_no: [object, ...]}, an object a dict with "box_plane" = (x0, y0,
+    x1, y1) inclusive, in plane coordinates.
+
+    Frames are taken in ascending order.  Every pair (open track, object of the frame) whose intersection over union -- the
+    track's last box against the object's -- is at least min_iou (and above 0) is a candidate; candidates are taken greedily in
+    order of descending IoU, ties to the lower track, then to the lower object index; a track and an object are matched at most
+    once.  A track that finds no match in a frame closes (an empty frame closes every track), an object without a match opens
+    a new track."""
+    if isinstance(min_iou, bool) or not isinstance(min_iou, (int, float, np.integer, np.floating)) or not 0 <= min_iou <= 1:
+        raise ValueError("min_iou must lie in 0..1")
+    tracks, open_tracks = [], []                   # open_tracks: indices into tracks
+    for frame_no in sorted(objects_by_frame):
+        objects = objects_by_frame[frame_no]
+        boxes = [tuple(o["box_plane"]) for o in objects]
+        candidates = []
+        for t in open_tracks:
+            last_frame, last_index = tracks[t][-1]
+            last = tuple(objects_by_frame[last_frame][last_index]["box_plane"])
+            for k, box in enumerate(boxes):
+                v = _iou(last, box)
+                if v > 0 and v >= min_iou:
+                    candidates.append((-v, t, k))
+        candidates.sort()
+        taken_tracks, taken_objects = set(), set()
+        for _, t, k in candidates:
+            if t in taken_tracks or k in taken_objects:
+                continue
+            taken_tracks.add(t)
+            taken_objects.add(k)
+            tracks[t].append((frame_no, k))
+        still_open = [t for t in open_tracks if t in taken_tracks]
+        for k in range(len(objects)):
+            if k not in taken_objects:
+                tracks.append([(frame_no, k)])
+                still_open.append(len(tracks) - 1)
+        open_tracks = sorted(still_open)
+    return tracks
+
+
+def moving_objects(capture, homography_dict, resize_info, placement="warp", scale=1.0, max_frames=64, min_cover=2, threshold=16,
+                   connectivity=8, open_radius=1, min_area=25, max_objects=256, ingest="auto", max_pixels=None, max_bytes=2 << 30,
+                   min_iou=0.1, labels=False):
+    """The moving objects of a video -> a dict {"frames": {frame_no: {"count": K, "truncated": bool, "objects": [...]}},
+    "tracks": [[(frame_no, object index), ...], ...], "origin": (ox, oy), "size": (dw, dh), "frame_nos": [...]} and, with
+    labels=True, "labels": i32[n,dh,dw] (else the labels never leave the device).
+
+    homography_dict: the SUPERPOSED dictionary, as background_plate takes it.  The reader, the frame ladder, the canvas and the
+    frames kept (placement, scale, max_frames, max_pixels, ingest) are background_plate's; the plate with its masks
+    (min_cover, threshold) and their labelling (connectivity, open_radius, min_area: Context.mask_components) are one sequence on
+    the device, and only the counts and the tables of max_objects rows per frame are downloaded.  An object is a dict:
+    "number" (its label), "area", "box_canvas" (x0, y0, x1, y1 inclusive canvas pixels), "box_plane" and "centre_plane"
+    ((canvas + origin) / scale, the centre being sum / area), "box_frame" and "centre_frame": the plane points taken to the
+    object's own original frame through from_fix_to_original (two decimals, as there).  "truncated": K > max_objects, the
+    objects past max_objects are missing from the list (the labels still hold them).  Tracks: link_objects(., min_iou)."""
+    import torch
+    from .processing.fixed_coordinate_system import from_fix_to_original
+    from .stabilization import MAX_PIXELS, _matrix, _plate_on_device
+    _objects_arguments(placement, scale, max_frames, min_cover, threshold, connectivity, open_radius, min_area, max_objects, ingest)
+    if isinstance(min_iou, bool) or not isinstance(min_iou, (int, float, np.integer, np.floating)) or not 0 <= min_iou <= 1:
+        raise ValueError("min_iou must lie in 0..1")
+    plate = _plate_on_device(capture, homography_dict, resize_info, placement, scale, max_frames, min_cover, True, threshold, ingest,
+                             MAX_PIXELS if max_pixels is None else max_pixels, max_bytes, extra_bytes_per_mask_pixel=12)
+    ctx, masks, (ox, oy), frame_nos = plate.ctx, plate.masks, plate.origin, plate.frame_nos
+    n, dh, dw = masks.shape
+    sheets = torch.empty((n, dh, dw), dtype=torch.int32, device=masks.device)
+    table = torch.zeros((n, int(max_objects), 5), dtype=torch.int64, device=masks.device)
+    counts = ctx.mask_components(masks, sheets, int(connectivity), int(open_radius), int(min_area), objects=table)
+    ctx.order_torch_after()
+    counts_h, table_h = counts.cpu().numpy(), ctx.components_table(table)
+    s = float(scale)
+    frames, points = {}, {}
+    for i, frame_no in enumerate(frame_nos):
+        found = []
+        for k in range(min(int(counts_h[i]), int(max_objects))):
+            o = table_h[i, k]
+            x0, y0, x1, y1, area = (int(o[f]) for f in ("x0", "y0", "x1", "y1", "area"))
+            cx, cy = int(o["sx"]) / area, int(o["sy"]) / area
+            found.append({"number": k + 1, "area": area, "box_canvas": (x0, y0, x1, y1),
+                          "box_plane": ((x0 + ox) / s, (y0 + oy) / s, (x1 + ox) / s, (y1 + oy) / s),
+                          "centre_plane": ((cx + ox) / s, (cy + oy) / s)})
+        frames[frame_no] = {"count": int(counts_h[i]), "truncated": int(counts_h[i]) > int(max_objects), "objects": found}
+        points[frame_no] = [{"x1": p[0], "y1": p[1]} for o in found
+                            for p in (o["box_plane"][:2], o["box_plane"][2:], o["centre_plane"])]
+    w0, h0 = plate.frame_size
+    mats = {k: _matrix(homography_dict.get(k)) for k in frame_nos if points[k]}
+    back = from_fix_to_original(points, mats, (h0, w0), (int(resize_info["h"]), int(resize_info["w"])))
+    for frame_no in frame_nos:
+        for j, o in enumerate(frames[frame_no]["objects"]):
+            a, b, c = (back[frame_no][3 * j + t] for t in range(3))
+            o["box_frame"] = (float(a["x1"]), float(a["y1"]), float(b["x1"]), float(b["y1"]))
+            o["centre_frame"] = (float(c["x1"]), float(c["y1"]))
+    out = {"frames": frames, "tracks": link_objects({k: v["objects"] for k, v in frames.items()}, min_iou), "origin": (ox, oy),
+           "size": (int(dw), int(dh)), "frame_nos": list(frame_nos)}
+    if labels:
+        out["labels"] = sheets.cpu().numpy()
+    return out

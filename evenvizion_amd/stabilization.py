@@ -323,7 +323,18 @@ def background_plate(capture, superposition_homography_dict, resize_info, placem
     by more than threshold (0..255) -- what moves, in fixed-plane coordinates.  A kept frame without a usable matrix covers
     nothing; frame_nos lists the frames that were kept (fewer when the capture ends early).  ValueError when frames, plate, count
     and masks together would take more than max_bytes on the device."""
-    import torch
+    dev = _plate_on_device(capture, superposition_homography_dict, resize_info, placement, scale, max_frames, min_cover, masks,
+                           threshold, ingest, max_pixels, max_bytes)
+    dev.ctx.order_torch_after()
+    return BackgroundPlate(dev.plate.cpu().numpy(), dev.count.cpu().numpy(), dev.origin, dev.frame_nos,
+                           dev.masks.cpu().numpy() if masks else None)
+
+
+DevicePlate = collections.namedtuple("DevicePlate", "ctx plate count masks origin frame_nos frame_size inputs")
+
+
+def check_plate_arguments(max_frames, min_cover, threshold, placement, ingest):
+    """The refusals background_plate and moving.moving_objects share, before the capture is touched."""
     if not 1 <= int(max_frames) <= PLATE_MAX_FRAMES:
         raise ValueError("max_frames must lie in 1..%d" % PLATE_MAX_FRAMES)
     if not 1 <= int(min_cover) <= 255:
@@ -332,6 +343,17 @@ def background_plate(capture, superposition_homography_dict, resize_info, placem
         raise ValueError("threshold must lie in 0..255")
     check_placement(placement)
     check_ingest(ingest)
+
+
+def _plate_on_device(capture, superposition_homography_dict, resize_info, placement, scale, max_frames, min_cover, masks, threshold,
+                     ingest, max_pixels, max_bytes, extra_bytes_per_mask_pixel=0):
+    """background_plate up to its launch: the reader, the ladder, _placement and evh_plate_fixed_plane, with plate, count and masks
+    left on the device -> DevicePlate (frame_size: the original (w0, h0)).  Nothing is synchronised: whatever follows on the
+    context's stream is ordered behind the plate.  inputs holds the tensors the launch reads: the caller keeps the DevicePlate
+    until it has ordered or synchronised, so that their memory is not handed out again while the launch runs.  extra_bytes_per_mask_pixel: what the caller will add per mask pixel, counted
+    against max_bytes."""
+    import torch
+    check_plate_arguments(max_frames, min_cover, threshold, placement, ingest)
     reader = FrameReader(capture, ingest)
     planes, w0, h0 = reader.planes, reader.w0, reader.h0
     ox, oy, dw, dh, matrix_of = _placement(superposition_homography_dict, resize_info, placement, scale, w0, h0, max_pixels)
@@ -340,7 +362,7 @@ def background_plate(capture, superposition_homography_dict, resize_info, placem
     n = len(frame_nos)
     resize = placement == "translate" and (w, h) != (w0, h0)
     device_bytes = n * reader.first.size + (n * h0 * w0 * 3 if planes and resize else 0) + (n * h * w * 3 if resize else 0) \
-        + dw * dh * (4 + (n if masks else 0))
+        + dw * dh * (4 + (n if masks else 0) + n * int(extra_bytes_per_mask_pixel))
     if device_bytes > int(max_bytes):
         raise ValueError("%d frames, plate, count and masks take %d bytes on the device, more than max_bytes = %d"
                          % (n, device_bytes, int(max_bytes)))
@@ -360,9 +382,7 @@ def background_plate(capture, superposition_homography_dict, resize_info, placem
     pictures = torch.empty((n, dh, dw), dtype=torch.uint8, device=dev) if masks else None
     ctx.plate_fixed_plane(src, mats, plate, (ox, oy), count=count, masks=pictures, threshold=int(threshold),
                           min_cover=int(min_cover), size=size)
-    ctx.order_torch_after()
-    return BackgroundPlate(plate.cpu().numpy(), count.cpu().numpy(), (ox, oy), frame_nos,
-                           pictures.cpu().numpy() if masks else None)
+    return DevicePlate(ctx, plate, count, pictures, (ox, oy), frame_nos, (w0, h0), (ladder, src, mats))
 
 
 def write_ppm(path, image):

@@ -17,7 +17,11 @@ evenvizion_amd.stabilization:
     --plate 1        plate.ppm, the scene without its moving objects (the per-pixel median of up to --plate_frames frames spread
                      over the video, where at least --plate_min_cover of them cover the pixel), plate_count.png, how many frames
                      cover each pixel, and with --plate_masks 1 mask_NNNNNN.png per frame taken: white where that frame differs
-                     from the plate by more than --plate_threshold gray levels.
+                     from the plate by more than --plate_threshold gray levels.  With --plate_objects 1 also
+                     moving_objects.json: per frame taken the connected components of its mask after an opening (--object_open R,
+                     --object_connectivity 4 | 8, --object_min_area N, at most --object_max N per frame) with box, centre and area
+                     on the plane and in the frame, linked into tracks by box overlap (evenvizion_amd.moving.moving_objects); with
+                     --plate_masks 1 then labels_NNNNNN.png too: gray ((label - 1) mod 255) + 1, background 0.
     --surface cylinder | sphere
                      NNNNNN.ppm per frame (one file for --mode mosaic): the canvas of a fixed cylinder or sphere around the camera
                      of frame 1 instead of the fixed plane, for a camera that turns by more than the plane can hold (a pan beyond
@@ -69,6 +73,12 @@ def parser():
     ap.add_argument("--plate_masks", type=int, choices=(0, 1), default=0,
                     help="plate: 1 writes mask_NNNNNN.png per frame taken, white where the frame differs from the plate")
     ap.add_argument("--plate_threshold", type=int, default=16, help="plate: gray levels a mask pixel must differ by (0..255)")
+    ap.add_argument("--plate_objects", type=int, choices=(0, 1), default=0,
+                    help="plate: 1 labels the masks on the device and writes moving_objects.json (frames, objects, tracks, parameters)")
+    ap.add_argument("--object_connectivity", type=int, choices=(4, 8), default=None, help="objects: 4 or 8 neighbours (default 8)")
+    ap.add_argument("--object_open", type=int, default=None, help="objects: radius of the opening before labelling (0..3, default 1)")
+    ap.add_argument("--object_min_area", type=int, default=None, help="objects: pixels an object must have (default 25)")
+    ap.add_argument("--object_max", type=int, default=None, help="objects: table rows per frame (1..65535, default 256)")
     ap.add_argument("--surface", choices=("cylinder", "sphere"), default=None,
                     help="place the frames on a fixed cylinder or sphere instead of the fixed plane: no horizon, any pan angle; "
                          "also writes surface_report.json")
@@ -93,6 +103,17 @@ def main(argv=None):
         ap.error("--plate writes the plate only: not with --trail or --comparison")
     if not (1 <= args.plate_frames <= 255 and 1 <= args.plate_min_cover <= 255 and 0 <= args.plate_threshold <= 255):
         ap.error("--plate_frames and --plate_min_cover lie in 1..255, --plate_threshold in 0..255")
+    given = [n for n in ("object_connectivity", "object_open", "object_min_area", "object_max") if getattr(args, n) is not None]
+    if args.plate_objects and not args.plate:
+        ap.error("--plate_objects needs --plate 1")
+    if given and not args.plate_objects:
+        ap.error("--%s needs --plate_objects 1" % given[0])
+    objects = dict(connectivity=8 if args.object_connectivity is None else args.object_connectivity,
+                   open_radius=1 if args.object_open is None else args.object_open,
+                   min_area=25 if args.object_min_area is None else args.object_min_area,
+                   max_objects=256 if args.object_max is None else args.object_max)
+    if not (0 <= objects["open_radius"] <= 3 and objects["min_area"] >= 1 and 1 <= objects["max_objects"] <= 65535):
+        ap.error("--object_open lies in 0..3, --object_min_area is at least 1, --object_max lies in 1..65535")
     if args.surface and (args.trail or args.comparison or args.plate):
         ap.error("--surface writes the canvases only: not with --trail, --comparison or --plate")
     if args.focal is not None and not args.surface:
@@ -159,6 +180,8 @@ def main(argv=None):
         write_png(os.path.join(save_folder, "plate_count.png"), got.count, gray=True)
         for k, frame_no in enumerate(got.frame_nos if args.plate_masks else ()):
             write_png(os.path.join(save_folder, "mask_%06d.png" % frame_no), got.masks[k], gray=True)
+        if args.plate_objects:
+            write_moving_objects(save_folder, open_capture(args.path_to_video)[0], sup, resize_info, args, objects)
         return save_folder
     if args.comparison:
         from .matching_pictures import write_png
@@ -169,6 +192,27 @@ def main(argv=None):
                                                scale=args.scale, trail=bool(args.trail)):
         write_ppm(os.path.join(save_folder, "%06d.ppm" % frame_no), picture)
     return save_folder
+
+
+def write_moving_objects(save_folder, cap, sup, resize_info, args, objects):
+    """moving_objects.json, and labels_NNNNNN.png with --plate_masks 1: the video is read once more, from its first frame."""
+    import json
+
+    import numpy as np
+
+    from .matching_pictures import write_png
+    from .moving import moving_objects
+    params = dict(placement=args.placement, scale=args.scale, max_frames=args.plate_frames, min_cover=args.plate_min_cover,
+                  threshold=args.plate_threshold, **objects)
+    got = moving_objects(cap, sup, resize_info, labels=bool(args.plate_masks), **params)
+    report = {"parameters": params, "origin": list(got["origin"]), "size": list(got["size"]), "frame_nos": got["frame_nos"],
+              "frames": {str(k): v for k, v in got["frames"].items()}, "tracks": [[list(step) for step in t] for t in got["tracks"]]}
+    with open(os.path.join(save_folder, "moving_objects.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    for k, frame_no in enumerate(got["frame_nos"] if args.plate_masks else ()):
+        sheet = got["labels"][k]
+        write_png(os.path.join(save_folder, "labels_%06d.png" % frame_no), np.where(sheet > 0, (sheet - 1) % 255 + 1, 0).astype(np.uint8),
+                  gray=True)
 
 
 if __name__ == "__main__":

@@ -35,6 +35,7 @@
  *                                 the temporal median of the registered frames (a background plate) and a moving-object mask per frame
  *   evh_rows_moving_filter[_yuv420] no counterpart: match rows whose points differ from that plate are dropped before the final
  *                                 solve (known-issues.md: key points cling to what moves)
+ *   evh_mask_components           no counterpart: the connected components of those masks, with box, area and centre sums
  *   evh_heatmap_render            heatmap_frame_processing without part_line: colour index, table, blend
  *                                 visualization/processing_visualization.py:336-344
  *   evh_batch_static_info         the length of the static point lists that reach draw_matches   video_processing.py:69
@@ -842,6 +843,51 @@ int evh_rows_moving_filter_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nfram
                                   int min_hits, double row_sx, double row_sy, const float* d_rows, int row_cap,
                                   const int32_t* d_counts, const int32_t* d_status1, int npairs, int frame_step, int min_keep,
                                   float* d_out_rows, int32_t* d_out_counts, int32_t* d_moving, uint8_t* d_flags);
+/* The masks turned into objects: connected-component labelling of nmasks masks of dw x dh bytes, with each object's box, area and
+ * centre sums in a compact table, so that only a few kilobytes leave the device.  Mask m is dh rows of dw bytes at
+ * mask_row_stride, at d_mask + m*mask_frame_stride: exactly what evh_plate_fixed_plane writes into d_mask.  For each mask m,
+ * independently:
+ *   1. Foreground.  A pixel is set iff its byte is non-zero.
+ *   2. Opening, when open_radius = r > 0 (0..3).  E[y][x] is set iff every (x+i, y+j) with |i|, |j| <= r lies inside the canvas
+ *      and is set; O[y][x] is set iff some (x+i, y+j) with |i|, |j| <= r lies inside the canvas and has E set.  Outside the canvas
+ *      counts as background.  With r = 0, O is the foreground itself.
+ *   3. Components of O under connectivity 4 (the pixels left, right, above and below) or 8 (the diagonals too).  A component's
+ *      area is its number of pixels, its `first` the raster index y*dw + x of its first pixel in raster order.  A component is KEPT
+ *      iff area >= min_area (>= 1).  Kept components are numbered 1..K in ascending order of `first`.
+ *   4. Labels.  d_labels[m][y][x] (i32, rows of dw elements at label_row_stride ELEMENTS, sheet m at m*label_frame_stride
+ *      elements) is the number of the pixel's component if that component is kept, else 0.  Every element inside dw of every row
+ *      is written; elements between rows are not.
+ *   5. Objects.  d_nobjects[m] = K, whatever max_objects is.  d_objects[m*max_objects + k-1] holds component k for
+ *      k <= min(K, max_objects): its inclusive box x0 <= x <= x1, y0 <= y <= y1 in canvas pixels, area, first, and sx, sy, the sums
+ *      of x and of y over its pixels (the centre is sx/area, sy/area).  Entries past that are untouched.  max_objects never
+ *      changes a label.
+ * The result is a pure function of the mask: every sum is an integer, nothing depends on the order in which workgroups arrive.
+ * Only caller buffers are used.  d_work is scratch of at least evh_mask_components_work_bytes(dw, dh, nmasks) bytes, 4-byte
+ * aligned: one i32 of area and one of scanned ordinal per pixel (8*dw*dh bytes per mask) for as many masks as are labelled at
+ * once -- all of them up to 256 MiB, beyond that the entry loops over groups of masks, and a larger buffer means larger groups.
+ * d_labels serves as the parent array while the call runs.  The call is a fixed sequence of launches on the context's stream
+ * (eight per group of masks, six when the canvas is one tile; each kernel ends on its own: every link of the union-find points to a smaller raster index, and no
+ * workgroup waits for another); it does not synchronise and leaves the record of the last batch alone.  Refused before anything
+ * is launched, outputs untouched -- EVH_ERR_INVALID: a NULL d_mask, d_labels, d_nobjects or d_work, d_objects NULL while
+ * max_objects > 0, connectivity not 4 or 8, open_radius outside 0..3, min_area < 1, max_objects < 0, dw or dh < 1, nmasks < 0, a
+ * stride shorter than its row / frame (frame strides count when nmasks > 1), d_labels, d_nobjects or d_work not 4-byte aligned,
+ * d_objects not 8-byte aligned, work_bytes too small, any output or the work buffer overlapping the mask or another output;
+ * EVH_ERR_CAPACITY: dw*dh > INT_MAX, nmasks > 65535.  nmasks == 0 succeeds and does nothing.  The tile of the first pass is
+ * EVH_COMPONENTS_TILE_W x EVH_COMPONENTS_TILE_H pixels; results do not depend on it.                                         */
+enum { EVH_COMPONENTS_TILE_W = 32, EVH_COMPONENTS_TILE_H = 16 };
+typedef struct evh_component {        /* 40 bytes, 8-byte aligned */
+  int32_t x0, y0, x1, y1;             /* bounding box in canvas pixels, inclusive */
+  int32_t area;                       /* pixels */
+  int32_t first;                      /* y*dw + x of the first pixel in raster order */
+  int64_t sx, sy;                     /* sum of x, sum of y over the pixels: centre = sx/area, sy/area */
+} evh_component;
+/* host only; 0 for arguments the entry would refuse (and for nmasks == 0); at most 8*dw*dh*nmasks bytes */
+size_t evh_mask_components_work_bytes(int dw, int dh, int nmasks);
+int evh_mask_components(evh_ctx* ctx, const uint8_t* d_mask, int nmasks, int dw, int dh, int64_t mask_row_stride,
+                        int64_t mask_frame_stride, int connectivity /* 4 | 8 */, int open_radius /* 0..3 */,
+                        int min_area /* >= 1 */, int32_t* d_labels, int64_t label_row_stride /* in elements */,
+                        int64_t label_frame_stride, evh_component* d_objects /* may be NULL iff max_objects == 0 */,
+                        int max_objects /* >= 0 */, int32_t* d_nobjects /* i32[nmasks] */, void* d_work, size_t work_bytes);
 
 /* ---- heat-map pictures: the colouring of heatmap_frame_processing (processing_visualization.py:336-344) ------------------------ */
 /* What heatmap_frame_processing does with the field of evh_fixed_plane_field and the resized frame, without part_line's grid,

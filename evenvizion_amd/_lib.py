@@ -35,6 +35,8 @@ EXPO_NSTATS = 7          # EVH_EXPO_NSTATS: (pixels, sum a per channel x3, sum b
 REFINE_REFINED, REFINE_UNCHANGED, REFINE_NOTHING_COVERED, REFINE_TOO_FEW, REFINE_DEGENERATE = range(5)
 REFINE_INFO = ("status", "evals", "accepted", "covered_in", "ssd_in", "covered_out", "ssd_out", "n_in")
 REFINE_NINFO, REFINE_NSUMS, REFINE_MAX_ITERS, REFINE_MAX_SIZE = 8, 45, 64, 4096
+GRAPH_NSUMS, GRAPH_BAD_INDEX, GRAPH_BAD_STATUS = 154, 1, 2   # EVH_GRAPH_* (include/evhip.h)
+GRAPH_INFO = ("used", "gated", "behind", "flags")
 
 # every symbol include/evhip.h declares, with its ctypes signature
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -164,6 +166,8 @@ SIGNATURES = {
     "evh_pair_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "evh_canvas_refine": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "evh_canvas_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    # global alignment: the normal equations over all superposed matrices, from the match rows of any frame pairs
+    "evh_graph_normal": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _d, _vp, _vp]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
     "evh_streams_homography_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
     "evh_streams_homography_batch_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _d, _i, _d, _i, _vp, _vp, _vp, _vp]),
@@ -1274,6 +1278,36 @@ class Context:
         """canvas_refine on decoded planes (see _yuv420; size=(w, h) for packed I420 frames) against a BGR canvas: every pixel of a
         frame converted as yuv420_to_bgr converts it (evh_canvas_refine_yuv420)."""
         return self._canvas_refine(True, planes, canvas, mats, count, min_cover, iters, clip, out, info, normal, size)
+
+    # ---- global alignment ----
+    def graph_normal(self, S, edges, rows, counts, status=None, H_edge=None, inlier_thr=3.0, huber_delta=0.0, sums=None, info=None):
+        """The normal equations of the joint problem over all superposed matrices (evh_graph_normal, the arithmetic is stated in
+        include/evhip.h).  All CUDA, contiguous: S float64 with nframes*9 elements; edges int32 [nedges,2] = (i, j); rows float32
+        [nedges,cap,4] as batch_static_rows lays them out (a in frame i, b in frame j); counts int32 [nedges]; status int32
+        [nedges] or None; H_edge float64 with nedges*9 elements (the pair matrices, a onto b: rows beyond inlier_thr are gated) or
+        None.  -> (sums float64 [nedges,154], info int32 [nedges,4] = used, gated, behind, flags); the two may be handed in.  Does
+        not synchronise."""
+        import torch
+        nedges = edges.shape[0] if edges.dim() == 2 else -1
+        dev = "cuda:%d" % self.device
+        if sums is None:
+            sums = torch.empty((max(nedges, 0), GRAPH_NSUMS), dtype=torch.float64, device=dev)
+        if info is None:
+            info = torch.empty((max(nedges, 0), 4), dtype=torch.int32, device=dev)
+        if edges.dim() != 2 or edges.shape[1] != 2 or rows.dim() != 3 or rows.shape[2] != 4 or rows.shape[0] < nedges or S.numel() % 9:
+            raise ValueError("graph_normal: S holds nframes*9 elements, edges is [nedges,2], rows [nedges,cap,4]")
+        for t, dt, numel, what in ((S, torch.float64, 9, "S"), (edges, torch.int32, 2 * nedges, "edges"), (rows, torch.float32, 0, "rows"),
+                                   (counts, torch.int32, nedges, "counts"), (status, torch.int32, nedges, "status"),
+                                   (H_edge, torch.float64, 9 * nedges, "H_edge"), (sums, torch.float64, GRAPH_NSUMS * nedges, "sums"),
+                                   (info, torch.int32, 4 * nedges, "info")):
+            if t is not None and (t.dtype != dt or not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or
+                                  t.numel() < numel):
+                raise ValueError("graph_normal: %s must be a contiguous CUDA %s tensor of at least %d elements" % (what, dt, numel))
+        self._enter()
+        self._check(self.lib.evh_graph_normal(self.h, S.data_ptr(), S.numel() // 9, edges.data_ptr(), nedges, rows.data_ptr(),
+                                              rows.shape[1], counts.data_ptr(), _ptr(status), _ptr(H_edge), float(inlier_thr),
+                                              float(huber_delta), sums.data_ptr(), info.data_ptr()))
+        return sums, info
 
     def orb_detect_batch_yuv420(self, planes, size=None, nfeatures=500, resize_to=None):
         """orb_detect_batch on decoded planes (see _yuv420), level 0 straight from them."""

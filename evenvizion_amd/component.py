@@ -36,6 +36,13 @@ with --anchor_mosaic 1 (extension, default off; --path_to_video only) also frame
                                        --anchor_group frames) aligned against the blended mosaic of the frames before it
                                        (evh_canvas_refine) and then painted into it; the first dictionary stays as it is
     anchor_report.json                 the registration report of both dictionaries, the two canvas-score sums and a row per frame.
+with --global_align 1 (extension, default off; --path_to_video only) also the whole chain aligned at once,
+    dict_with_homography_matrix_aligned.json    the dictionary of graph.aligned_homography_dict: consecutive frames and frames that see
+                                       the same ground again (--graph_gap, --graph_partners, --graph_min_inliers) matched, the rows of all those pairs in
+                                       one least-squares problem over every frame's matrix (evh_graph_normal), solved for
+                                       --graph_model; the first dictionary stays as it is
+    graph_report.json                  the edges tried and kept, the loop edges per frame, the cost before and after, the steps
+                                       and the registration report of both dictionaries.
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
@@ -159,6 +166,18 @@ def parser():
                          "stays as it is (the video is read three times more)")
     ap.add_argument("--anchor_group", type=_int_in(1, 65535), default=1,
                     help="--anchor_mosaic: frames aligned and painted together (1: strictly frame by frame)")
+    ap.add_argument("--global_align", type=int, choices=(0, 1), default=0,
+                    help="1: the whole chain aligned at once (extension; --path_to_video only): graph.aligned_homography_dict; "
+                         "writes dict_with_homography_matrix_aligned.json and graph_report.json beside the first dictionary, "
+                         "which stays as it is (the video is read three times more)")
+    ap.add_argument("--graph_model", type=str, default="homography", choices=("translation", "similarity", "affine", "homography"),
+                    help="--global_align: the correction every frame's matrix may take")
+    ap.add_argument("--graph_partners", type=_int_in(0, 64), default=4, help="--global_align: loop edges per frame at the most")
+    ap.add_argument("--graph_min_inliers", type=_int_in(1, 65535), default=20,
+                    help="--global_align: rows of a pair that must lie within 3 px of the pair's own matrix for its edge to be kept; "
+                         "a consecutive pair below it breaks the chain and the alignment refuses, naming the pair")
+    ap.add_argument("--graph_gap", type=_int_in(1, 65535), default=8,
+                    help="--global_align: frames a loop partner lies back at the least, and two partners of a frame apart")
     return ap
 
 
@@ -181,6 +200,8 @@ def main(argv=None):
             raise ValueError("--refine_direct takes one video (--path_to_video)")
         if args.anchor_mosaic:
             raise ValueError("--anchor_mosaic takes one video (--path_to_video)")
+        if args.global_align:
+            raise ValueError("--global_align takes one video (--path_to_video)")
         opened = [open_capture(spec) for spec in args.path_to_videos]
         kw = {k: v for k, v in (("max_streams", args.max_streams), ("decode_threads", args.decode_threads)) if v is not None}
         results = get_homography_dicts([cap for cap, _, _ in opened], resize_width=args.resize_width,
@@ -211,7 +232,28 @@ def main(argv=None):
         write_direct(args, save_folder)
     if args.anchor_mosaic:
         write_anchored(args, save_folder)
+    if args.global_align:
+        write_aligned(args, save_folder)
     return save_folder
+
+
+def write_aligned(args, save_folder):
+    """--global_align 1: the first pass's matrices aligned all at once, the aligned dictionary and its report beside the first
+    pass's files, which are left as they are.  The capture is opened again for each pass."""
+    from .processing.utils import read_homography_dict, superposition_dict
+    from . import graph
+    spec = args.path_to_video
+    first_pass, resize_info = read_homography_dict(os.path.join(save_folder, "dict_with_homography_matrix.json"))
+    got = graph.aligned_homography_dict(lambda: open_capture(spec)[0], superposition_dict(first_pass), resize_info, ingest=args.ingest,
+                                        model=args.graph_model, max_partners=args.graph_partners, min_gap=args.graph_gap,
+                                        min_inliers=args.graph_min_inliers)
+    with open(os.path.join(save_folder, "dict_with_homography_matrix_aligned.json"), "w") as json_:
+        json.dump(dict(got["homography"], resize_info=resize_info), json_)
+    report = dict(got["report"])
+    report["loop_edges"] = {str(k): v for k, v in report["loop_edges"].items()}
+    report["loop_edges_kept"] = {str(k): v for k, v in report.get("loop_edges_kept", {}).items()}
+    with open(os.path.join(save_folder, "graph_report.json"), "w") as json_:
+        json.dump(report, json_)
 
 
 def write_anchored(args, save_folder):

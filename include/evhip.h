@@ -47,6 +47,8 @@
  *   evh_pair_refine[_yuv420]      no counterpart: that matrix improved on the pixels of the pair (direct alignment)
  *   evh_canvas_refine[_yuv420]    no counterpart: a frame aligned against the mosaic its predecessors left on the plane, so that
  *                                 revisited ground pulls the chain of pair matrices back into place
+ *   evh_graph_normal              no counterpart: the normal equations of ONE least-squares problem over all superposed matrices, from
+ *                                 the match rows of any frame pairs, so that a loop's closing error is spread over the whole chain
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -1154,6 +1156,63 @@ int evh_streams_homography_batch_yuv420(evh_ctx* ctx, const evh_yuv420* src, int
                                         int nstreams, double ransac_thr, int ransac_max_iters, double ransac_conf,
                                         int force_max_iters, const double* d_state_in, double* d_state_out, double* d_H,
                                         int32_t* d_status);
+
+/* ---- global alignment: the normal equations of one joint least-squares problem over all superposed matrices --------------------- */
+/* Every coordinate the library hands out goes through S_k, a product of k pair matrices.  This entry turns the match rows of
+ * ARBITRARY frame pairs ("edges": consecutive frames and frames that see the same ground again) into the normal equations of one
+ * problem over all S_k; the solve is the host's (evenvizion_amd/graph.py).  tests/graph_checks.py restates all of the following in
+ * numpy float64 and is the definition where this text is unclear.  All buffers are DEVICE buffers.
+ * d_S f64[nframes][9]: S_k takes pixels of frame k to the plane.  d_edges i32[nedges][2] = (i, j).  d_rows f32[nedges][row_cap][4]:
+ * rows (ax, ay, bx, by) in the layout of evh_batch_static_rows, a = the point in frame i (the CURRENT frame of a pair slot),
+ * b = the point in frame j (the PREVIOUS frame).  Edge e reads rows r < n = min(max(d_counts[e], 0), row_cap): a count above
+ * row_cap is taken as row_cap, a negative one as 0, as in evh_draw_matches.  d_status (may be NULL): i32[nedges].  d_H_edge (may be
+ * NULL): f64[nedges][9], the matrix of the pair, which maps a onto b -- the direction of compute_homography(pts_a, pts_b), whose
+ * residual is H.a - b (evh_compute_homography, evh_pair_homography_batch: what EVH_MODE_INDEPENDENT_PAIRS returns for the slot
+ * (frame j, frame i) = (prev, cur)).
+ * Per row, IEEE float64 with one rounding per operation (the library is built with -ffp-contract=off), after ax, ay, bx, by have
+ * been converted to double:
+ *   1. Plane points.  (tx, ty, tw) = (fma(s0, ax, s1*ay) + s2, fma(s3, ax, s4*ay) + s5, fma(s6, ax, s7*ay) + s8) with s = S_i, and
+ *      (sx, sy, sw) alike from S_j and (bx, by): the order of evh_transform_points, so U, V below equal its output bit for bit.
+ *   2. Validity.  If tw or sw is not finite or is <= 0 the row is skipped and counted in `behind`.
+ *   3. Gate, only with d_H_edge: (hx, hy, hw) from H_e and (ax, ay) as in 1; gx = hx / hw - bx, gy = hy / hw - by; the row is used
+ *      iff gx*gx + gy*gy <= inlier_thr*inlier_thr (both products rounded, then the sum), otherwise it is counted in `gated` (a NaN
+ *      compares false: gated).  No validity rule applies to hw.
+ *   4. U = tx / tw, V = ty / tw (P_i); X = sx / sw, Y = sy / sw (P_j).  Residual ru = U - X, rv = V - Y, in plane units.
+ *   5. Weight.  q = ru*ru + rv*rv.  With huber_delta <= 0, or q <= d*d (d = huber_delta): w = 1, rho = q.  Else s = sqrt(q),
+ *      w = d / s, rho = (2*d)*s - d*d.
+ * Steps 1 to 5 fix used, gated, behind and the atoms U, V, X, Y, ru, rv, q, w, rho of every used row bit for bit.
+ * The unknown of frame k is a correction D_k = I + Delta_k composed on the left, S'_k = D_k . S_k, Delta_k = (d0 d1 d2; d3 d4 d5;
+ * d6 d7 0).  At Delta = 0 the derivatives of a plane point P = (U, V) are Ju(P) = (U, V, 1, 0, 0, 0, -U*U, -U*V) and
+ * Jv(P) = (0, 0, 0, U, V, 1, -U*V, -V*V); J_i = J(P_i), J_j = -J(P_j).
+ * d_sums f64[nedges][EVH_GRAPH_NSUMS], over the used rows of the edge:
+ *   [0..35]    the upper triangle, row-major, of A_ii = sum w (Ju_i^T Ju_i + Jv_i^T Jv_i)
+ *   [36..71]   the same of A_jj
+ *   [72..135]  A_ij = sum w (Ju_i^T Ju_j + Jv_i^T Jv_j), the full 8 x 8 block, row = parameter of frame i
+ *   [136..143] g_i = sum w (Ju_i ru + Jv_i rv)        [144..151] g_j
+ *   [152]      sum rho                                  [153] sum q
+ * Every entry is, up to one sign, a sum of TERMS, a term being w (for the gradients w*ru or w*rv) times a product of up to four of
+ * U, V, X, Y: one term per row for most entries, two (the u and the v part) for rows and columns 6 and 7 among themselves and for
+ * g[6], g[7]; entries that are structurally zero hold +0.0.  The device forms a term with at most four roundings and adds the
+ * terms in an order fixed by the row index alone (row r belongs to lane r mod 256; lanes, then the four waves, are added in a fixed
+ * tree; no atomics), so an edge's sums are a pure function of that edge's rows, counts, matrices and the two parameters, wherever
+ * the edge sits in the list; each lies within (n + 8) * 2^-53 * sum |term| of the exact sum of the exact terms, n = used.  With
+ * huber_delta <= 0, [152] and [153] are the same bytes.
+ * d_info i32[nedges][4] = {used, gated, behind, flags}.  flags: EVH_GRAPH_BAD_INDEX: i or j outside [0, nframes), or i == j;
+ * EVH_GRAPH_BAD_STATUS: d_status given and d_status[e] != EVH_PAIR_OK.  A flagged edge reads no row and no matrix, has all 154
+ * sums +0.0 and the three counters 0.  An edge without a used row has +0.0 everywhere too.
+ * One launch of nedges workgroups on the context's stream; does not synchronise; only caller buffers are used.  Refused with
+ * EVH_ERR_INVALID before anything is enqueued, outputs untouched: a NULL d_S, d_edges, d_rows, d_counts, d_sums or d_info; nframes,
+ * nedges or row_cap < 1; nedges > 4 194 304 (2^22 workgroups of 256 threads: a grid of 2^30 threads); a NaN inlier_thr or
+ * huber_delta; d_H_edge given with inlier_thr < 0; d_rows not 16-byte aligned (a row is loaded as one vector) or another buffer not
+ * aligned to its element.                                                                                                        */
+enum { EVH_GRAPH_NSUMS = 154 };
+enum { EVH_GRAPH_BAD_INDEX = 1, EVH_GRAPH_BAD_STATUS = 2 };
+int evh_graph_normal(evh_ctx* ctx, const double* d_S /* f64[nframes][9] */, int nframes,
+                     const int32_t* d_edges /* i32[nedges][2] = (i, j) */, int nedges,
+                     const float* d_rows /* f32[nedges][row_cap][4] */, int row_cap, const int32_t* d_counts,
+                     const int32_t* d_status /* may be NULL */, const double* d_H_edge /* f64[nedges][9], may be NULL */,
+                     double inlier_thr, double huber_delta,
+                     double* d_sums /* f64[nedges][EVH_GRAPH_NSUMS] */, int32_t* d_info /* i32[nedges][4] */);
 
 #ifdef __cplusplus
 }

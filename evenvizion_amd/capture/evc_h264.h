@@ -11,6 +11,11 @@
 //   multiple reference frames with list modification and MMCO, in-loop deblocking, frame cropping, POC types 0 and 2.
 // Anything else (CAVLC, interlace/MBAFF, FMO/ASO, 4:2:2/4:4:4, >8 bit, SP/SI, data partitioning) is rejected with an
 // explicit error, never decoded approximately.
+// Parameter sets: one that repeats the stored set changes nothing.  One that differs from a set the current coded video
+// sequence uses takes effect at the next IDR picture (7.4.1.2.1) and is an error when a non-IDR slice refers to it first, or
+// when it arrives in the middle of a picture.  The decoder itself follows a change of picture size at an IDR picture; the
+// capture source on top of it (evcap_api.cpp) delivers one geometry per handle, the one evcap_info reports, and answers
+// the first picture of another one with an explicit error.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -128,6 +133,7 @@ struct SliceHeader {
 // deblocking filter read after the picture is finished.
 struct Picture {
     int mb_w = 0, mb_h = 0, stride = 0, cstride = 0;  // planes cover the coded size (mb_w*16 x mb_h*16)
+    int width = 0, height = 0, crop_l = 0, crop_t = 0;  // the cropping window of the sequence parameter set it was decoded with
     std::vector<uint8_t> Y, Cb, Cr;
     std::vector<int16_t> mv[2];       // [list][(y4*w4 + x4)*2 + c]
     std::vector<int8_t> ref[2];       // [list][y4*w4 + x4]; -1 = list not used, -2 = intra
@@ -193,6 +199,9 @@ class Decoder {
     void decode_nal(const uint8_t* data, size_t size);
     // Marks the end of the stream: everything still waiting for output is released.
     void flush();
+    // After decode_nal() has thrown: gives up the picture that was being decoded and releases, like flush(), every picture
+    // that had been decoded completely before.  Does not throw.
+    void abandon();
     // Pictures in output (POC) order that have become available.
     std::vector<PicPtr> take_output();
     const SPS* active_sps() const;

@@ -3,6 +3,7 @@
 // modification (8.2.4), reference picture marking (8.2.5) and output in picture-order-count order (C.4.5.3 "bumping").
 #include <algorithm>
 #include <cstdlib>
+#include <map>
 
 #include "evc_h264_int.h"
 
@@ -16,6 +17,11 @@ void parse_slice_header(BitReader& b, const SPS* spss, const PPS* ppss, int nal_
 struct DecoderImpl {
     SPS sps[32];
     PPS pps[256];
+    std::vector<uint8_t> sps_raw[32], pps_raw[256];  // the RBSP each set was parsed from: tells a repetition from a replacement
+    // replacements of sets the current coded video sequence uses; they take effect at the next IDR picture
+    std::map<int, std::pair<SPS, std::vector<uint8_t>>> sps_next;
+    std::map<int, std::pair<PPS, std::vector<uint8_t>>> pps_next;
+    bool pps_used[256] = {};  // by a picture since the last IDR picture (inclusive)
     const SPS* asps = nullptr;
     std::vector<PicPtr> dpb;      // pictures marked "used for reference"
     std::vector<PicPtr> pending;  // decoded, waiting for output
@@ -31,6 +37,7 @@ struct DecoderImpl {
     int prev_poc_msb = 0, prev_poc_lsb = 0, prev_frame_num = 0, prev_frame_num_offset = 0, prev_ref_frame_num = 0;
     int next_id = 0, idr_epoch = 0;
     bool cur_mmco5 = false;
+    bool cur_finishing = false;  // finish_picture() has begun to change cur (deblocking, marking)
     Stats stats;
 
     int max_frame_num() const { return 1 << asps->log2_max_frame_num; }
@@ -62,6 +69,7 @@ struct DecoderImpl {
             bump(true);
             dpb.clear();
             ++idr_epoch;
+            std::memset(pps_used, 0, sizeof pps_used);
         } else if (dpb.empty() && next_id == 0) {
             fail("the stream does not start with an IDR picture");
         }
@@ -70,6 +78,12 @@ struct DecoderImpl {
             fail("gap in frame_num (%d after %d): frames are missing from the stream", h.frame_num, prev_ref_frame_num);
         cur = std::make_shared<Picture>();
         cur->alloc(s.mb_w, s.mb_h);
+        cur->width = s.width();
+        cur->height = s.height();
+        cur->crop_l = s.crop_l;
+        cur->crop_t = s.crop_t;
+        cur_finishing = false;
+        pps_used[h.pps_id] = true;
         cur->id = next_id++;
         cur->idr_epoch = idr_epoch;
         cur->frame_num = h.frame_num;
@@ -116,6 +130,7 @@ struct DecoderImpl {
         const SPS& s = *asps;
         if (mbs_decoded != s.mb_w * s.mb_h)
             fail("picture %d (frame_num %d): %d of %d macroblocks were present in its slices", cur->id, cur->frame_num, mbs_decoded, s.mb_w * s.mb_h);
+        cur_finishing = true;
         deblock_picture(*cur, mbi, *cur_pps);
         const SliceHeader& h = cur_sh;
         // 8.2.5
@@ -156,7 +171,71 @@ struct DecoderImpl {
         }
         pending.push_back(cur);
         cur.reset();
+        cur_finishing = false;
         bump(false);
+    }
+
+    bool cur_complete() const { return cur && asps && mbs_decoded == asps->mb_w * asps->mb_h; }
+
+    void abandon() {
+        if (cur_complete() && !cur_finishing) {
+            try {
+                finish_picture();
+            } catch (const std::exception&) {
+            }
+        }
+        cur.reset();
+        cur_finishing = false;
+        bump(true);
+    }
+
+    // ---------------------------------------------------------------------------------------------- parameter sets
+    // 7.4.1.2.1: the content of a parameter set in use may change only where the set is activated anew -- for a sequence
+    // parameter set that is an IDR picture.  This decoder holds picture parameter sets to the same rule: every picture in
+    // the buffer keeps the geometry, frame_num range and reference counts it was decoded with, so a set that changed under
+    // them would have motion compensation, co-located motion data and deblocking work on two layouts at once.
+    void store_sps(int id, const SPS& s, std::vector<uint8_t>& raw) {
+        if (sps[id].valid && raw == sps_raw[id]) {
+            sps_next.erase(id);
+            return;
+        }
+        if (asps != &sps[id]) {
+            sps[id] = s;
+            sps_raw[id].swap(raw);
+            return;
+        }
+        if (cur && !cur_complete()) fail("sequence parameter set %d is replaced in the middle of a picture", id);
+        finish_picture();
+        sps_next[id] = std::make_pair(s, raw);
+    }
+
+    void store_pps(int id, const PPS& p, std::vector<uint8_t>& raw) {
+        if (pps[id].valid && raw == pps_raw[id]) {
+            pps_next.erase(id);
+            return;
+        }
+        if (!pps_used[id]) {
+            pps[id] = p;
+            pps_raw[id].swap(raw);
+            return;
+        }
+        if (cur && !cur_complete() && cur_pps == &pps[id]) fail("picture parameter set %d is replaced in the middle of a picture", id);
+        if (cur_pps == &pps[id]) finish_picture();
+        pps_next[id] = std::make_pair(p, raw);
+    }
+
+    void activate_replacements() {
+        finish_picture();
+        for (auto& e : sps_next) {
+            sps[e.first] = e.second.first;
+            sps_raw[e.first].swap(e.second.second);
+        }
+        for (auto& e : pps_next) {
+            pps[e.first] = e.second.first;
+            pps_raw[e.first].swap(e.second.second);
+        }
+        sps_next.clear();
+        pps_next.clear();
     }
 
     void unmark(Picture* p) {
@@ -366,8 +445,15 @@ struct DecoderImpl {
         std::vector<uint8_t> rbsp = nal_to_rbsp(nal + 1, size - 1);
         BitReader b(rbsp.data(), rbsp.size());
         SliceHeader h;
+        if (type == 5 && (!sps_next.empty() || !pps_next.empty())) activate_replacements();
         parse_slice_header(b, sps, pps, ref_idc, type, h);
         const PPS& p = pps[h.pps_id];
+        if (pps_next.count(h.pps_id))
+            fail("picture parameter set %d was re-sent with other content, which takes effect at an IDR picture only, and a non-IDR slice refers to it",
+                 h.pps_id);
+        if (sps_next.count(p.sps_id))
+            fail("sequence parameter set %d was re-sent with other content, which takes effect at an IDR picture only, and a non-IDR slice refers to it",
+                 p.sps_id);
         bool new_pic = !cur;
         if (cur) {
             const SliceHeader& f = cur_sh;
@@ -426,8 +512,7 @@ struct DecoderImpl {
                 SPS s;
                 int id;
                 parse_sps(r.data(), r.size(), s, id);
-                if (cur && asps == &sps[id]) finish_picture();
-                sps[id] = s;
+                store_sps(id, s, r);
                 break;
             }
             case 8: {
@@ -435,8 +520,7 @@ struct DecoderImpl {
                 PPS p;
                 int id;
                 parse_pps(r.data(), r.size(), p, id);
-                if (cur && cur_pps == &pps[id]) finish_picture();
-                pps[id] = p;
+                store_pps(id, p, r);
                 break;
             }
             case 9:   // access unit delimiter
@@ -457,6 +541,7 @@ void Decoder::flush() {
     d->finish_picture();
     d->bump(true);
 }
+void Decoder::abandon() { d->abandon(); }
 std::vector<PicPtr> Decoder::take_output() {
     std::vector<PicPtr> o;
     o.swap(d->out);

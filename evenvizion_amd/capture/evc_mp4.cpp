@@ -49,6 +49,14 @@ std::vector<Box> children(const Rd& r, uint64_t o, uint64_t e) {
     return out;
 }
 
+// A table of n entries of `entry` bytes behind `head` bytes of payload must lie inside its box: the counts are read from the
+// file, and a count the box cannot hold would walk into whatever follows it.
+void check_table(const Box& b, uint64_t head, uint64_t n, uint64_t entry, const char* name) {
+    if (b.end - b.body < head || n > (b.end - b.body - head) / entry)
+        fail("mp4: %s announces %llu entries, more than its box of %llu bytes holds", name, (unsigned long long)n,
+             (unsigned long long)(b.end - b.body));
+}
+
 const Box* find(const std::vector<Box>& v, uint32_t tp) {
     for (auto& b : v)
         if (b.type == tp) return &b;
@@ -96,6 +104,7 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
                 int ver = (int)r.u(elst->body, 1);
                 uint32_t n = (uint32_t)r.u(elst->body + 4, 4);
                 uint64_t o = elst->body + 8;
+                check_table(*elst, 8, n, ver == 1 ? 20 : 12, "elst");
                 for (uint32_t i = 0; i < n; ++i) {
                     Mp4Track::Edit e;
                     if (ver == 1) {
@@ -128,6 +137,7 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
             if (etp != fourcc("avc1") && etp != fourcc("avc3"))
                 fail("mp4: video sample entry '%c%c%c%c' is not AVC (only H.264 is decoded)", etp >> 24, (etp >> 16) & 255,
                      (etp >> 8) & 255, etp & 255);
+            if (stsd->end - stsd->body < 16 || esz < 86 || esz > stsd->end - o) fail("mp4: the sample entry of %llu bytes does not fit stsd", (unsigned long long)esz);
             t.width = (int)r.u(o + 32, 2);
             t.height = (int)r.u(o + 34, 2);
             auto sub = children(r, o + 86, o + esz);
@@ -160,6 +170,11 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
         uint32_t fixed = (uint32_t)r.u(stsz->body + 4, 4);
         uint32_t count = (uint32_t)r.u(stsz->body + 8, 4);
         if (count > (1u << 24)) fail("mp4: implausible sample count %u", count);
+        if (fixed) {
+            if (count > r.n / fixed) fail("mp4: stsz announces %u samples of %u bytes, more than the file holds", count, fixed);
+        } else {
+            check_table(*stsz, 12, count, 4, "stsz");
+        }
         t.samples.resize(count);
         for (uint32_t i = 0; i < count; ++i) t.samples[i].size = fixed ? fixed : (uint32_t)r.u(stsz->body + 12 + 4ull * i, 4);
 
@@ -167,9 +182,11 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
         std::vector<uint64_t> chunk_off;
         if (const Box* stco = find(st, fourcc("stco"))) {
             uint32_t n = (uint32_t)r.u(stco->body + 4, 4);
+            check_table(*stco, 8, n, 4, "stco");
             for (uint32_t i = 0; i < n; ++i) chunk_off.push_back(r.u(stco->body + 8 + 4ull * i, 4));
         } else if (const Box* co64 = find(st, fourcc("co64"))) {
             uint32_t n = (uint32_t)r.u(co64->body + 4, 4);
+            check_table(*co64, 8, n, 8, "co64");
             for (uint32_t i = 0; i < n; ++i) chunk_off.push_back(r.u(co64->body + 8 + 8ull * i, 8));
         } else {
             fail("mp4: no stco/co64");
@@ -178,6 +195,7 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
         if (!stsc) fail("mp4: no stsc");
         {
             uint32_t n = (uint32_t)r.u(stsc->body + 4, 4);
+            check_table(*stsc, 8, n, 12, "stsc");
             struct E {
                 uint32_t first, per, desc;
             };
@@ -202,11 +220,12 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
             if (s != count) fail("mp4: sample tables cover %u of %u samples", s, count);
         }
         for (auto& s : t.samples)
-            if (s.offset + s.size > r.n) fail("mp4: a sample lies outside the file");
+            if (s.size > r.n || s.offset > r.n - s.size) fail("mp4: a sample lies outside the file");
 
         // ---- timing
         if (const Box* stts = find(st, fourcc("stts"))) {
             uint32_t n = (uint32_t)r.u(stts->body + 4, 4);
+            check_table(*stts, 8, n, 8, "stts");
             int64_t dts = 0;
             uint32_t s = 0;
             for (uint32_t i = 0; i < n; ++i) {
@@ -221,6 +240,7 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
         if (const Box* ctts = find(st, fourcc("ctts"))) {
             int ver = (int)r.u(ctts->body, 1);
             uint32_t n = (uint32_t)r.u(ctts->body + 4, 4);
+            check_table(*ctts, 8, n, 8, "ctts");
             uint32_t s = 0;
             for (uint32_t i = 0; i < n; ++i) {
                 uint32_t cnt = (uint32_t)r.u(ctts->body + 8 + 8ull * i, 4);
@@ -231,6 +251,7 @@ Mp4Track mp4_parse(const std::vector<uint8_t>& data) {
         }
         if (const Box* stss = find(st, fourcc("stss"))) {
             uint32_t n = (uint32_t)r.u(stss->body + 4, 4);
+            check_table(*stss, 8, n, 4, "stss");
             for (uint32_t i = 0; i < n; ++i) {
                 uint32_t k = (uint32_t)r.u(stss->body + 8 + 4ull * i, 4);
                 if (k >= 1 && k <= count) t.samples[k - 1].sync = true;

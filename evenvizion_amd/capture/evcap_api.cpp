@@ -26,6 +26,7 @@ struct evcap {
     int64_t win_start = 0, win_end = 0;
     int dropped_by_edit = 0;
     bool started = false;
+    bool failed = false;  // the decoder gave up (err says why); reported once the pictures before the failure are delivered
     std::string err;
 };
 
@@ -52,15 +53,23 @@ void feed_nals(evcap* c, const uint8_t* d, size_t n) {
     }
 }
 
-// decodes until at least one picture is ready or the stream ends
+// Decodes until at least one picture is ready or the stream ends.  A stream the decoder cannot follow ends there: the
+// pictures decoded completely before the failure are still delivered, in output order, then `failed` is reported.
 void pump(evcap* c) {
     while (c->ready.empty() && !c->flushed) {
-        if (c->next_sample < c->track.samples.size()) {
-            const Mp4Sample& s = c->track.samples[c->next_sample++];
-            feed_nals(c, c->file.data() + s.offset, s.size);
-        } else {
-            c->dec.flush();
+        try {
+            if (c->next_sample < c->track.samples.size()) {
+                const Mp4Sample& s = c->track.samples[c->next_sample++];
+                feed_nals(c, c->file.data() + s.offset, s.size);
+            } else {
+                c->flushed = true;
+                c->dec.flush();
+            }
+        } catch (const std::exception& e) {
+            c->err = e.what();
+            c->failed = true;
             c->flushed = true;
+            c->dec.abandon();
         }
         for (auto& p : c->dec.take_output()) c->ready.push_back(p);
     }
@@ -87,12 +96,22 @@ int open_common(evcap* c, evcap** out) {
         for (auto& p : c->track.pps) c->dec.decode_nal(p.data(), p.size());
         // decode ahead to the first picture so that the geometry is known (in-band parameter sets may override avcC)
         pump(c);
-        const SPS* sps = c->dec.active_sps();
-        if (!sps) fail("mp4: the video track holds no decodable picture");
-        c->width = sps->width();
-        c->height = sps->height();
-        c->crop_l = sps->crop_l;
-        c->crop_t = sps->crop_t;
+        if (c->ready.empty() && c->failed) throw Error(c->err);
+        if (!c->ready.empty()) {
+            // the geometry of the handle is the first picture's: the parameter set active by now may belong to a later IDR
+            const Picture& p = *c->ready.front();
+            c->width = p.width;
+            c->height = p.height;
+            c->crop_l = p.crop_l;
+            c->crop_t = p.crop_t;
+        } else {
+            const SPS* sps = c->dec.active_sps();
+            if (!sps) fail("mp4: the video track holds no decodable picture");
+            c->width = sps->width();
+            c->height = sps->height();
+            c->crop_l = sps->crop_l;
+            c->crop_t = sps->crop_t;
+        }
     } catch (const std::exception& e) {
         std::lock_guard<std::mutex> g(g_open_mutex);
         g_open_error = e.what();
@@ -220,16 +239,24 @@ int evcap_set_bgr_mode(evcap* c, int mode) {
 
 static int next_picture(evcap* c, PicPtr& p) {
     for (;;) {
-        try {
-            pump(c);
-        } catch (const std::exception& e) {
-            c->err = e.what();
+        pump(c);
+        if (c->ready.empty()) return c->failed ? classify(c->err) : EVCAP_EOF;
+        p = c->ready.front();
+        // One handle, one geometry: callers size their buffers from evcap_info once, and the readers below index every
+        // picture with the opened width, height and crop offsets.  A later IDR picture may activate a parameter set of
+        // another size (concatenated recordings); it is refused here, not delivered through the wrong window.
+        if (p->width != c->width || p->height != c->height || p->crop_l != c->crop_l || p->crop_t != c->crop_t) {
+            char msg[256];
+            std::snprintf(msg, sizeof msg,
+                          "the picture geometry changed at picture %d: %dx%d at crop offset (%d,%d) after %dx%d at (%d,%d); one handle "
+                          "delivers one geometry",
+                          p->id, p->width, p->height, p->crop_l, p->crop_t, c->width, c->height, c->crop_l, c->crop_t);
+            c->err = msg;
+            c->failed = true;
             c->flushed = true;
             c->ready.clear();
-            return classify(c->err);
+            return EVCAP_ERR_STREAM;
         }
-        if (c->ready.empty()) return EVCAP_EOF;
-        p = c->ready.front();
         c->ready.pop_front();
         // one picture per sample: Picture::id counts pictures in decoding order = sample index
         if (c->honour_edits && c->have_window && (size_t)p->id < c->track.samples.size()) {

@@ -54,7 +54,10 @@ int evcap_set_bgr_mode(evcap* c, int mode);
 int evcap_set_honour_edit_list(evcap* c, int on);
 
 /* capture.read() -- video_processing.py:58,70.  Writes the next frame in presentation order as 8-bit BGR, rows of
- * width*3 bytes at `stride`.  Returns EVCAP_OK, EVCAP_EOF or an error. */
+ * width*3 bytes at `stride`.  Returns EVCAP_OK, EVCAP_EOF or an error.  When the stream cannot be followed, the pictures
+ * decoded completely before that point are still delivered, then the error is returned (and again on every later call).
+ * One handle delivers one geometry, the one evcap_info reports: a later IDR picture of another size or crop offset is
+ * answered with EVCAP_ERR_STREAM ("the picture geometry changed"), never read through the first window. */
 int evcap_read_bgr(evcap* c, uint8_t* dst, int64_t stride);
 /* The same frame as planar 4:2:0 (Y width x height, Cb/Cr ((width+1)/2) x ((height+1)/2)), written straight into the
  * caller's planes: the source of libevhip's evh_*_yuv420 entries.  EVCAP_ERR_INVALID, before a picture is taken from the

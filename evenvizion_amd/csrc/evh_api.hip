@@ -399,16 +399,13 @@ int evh_create(int device, int max_w, int max_h, int max_features, int max_frame
   A_(dalloc(c, &c->d_fast_thr, F * EVH_NLEVELS));
   A_(dalloc(c, &c->d_fast_hist, F * EVH_NLEVELS * 256));
   A_(dalloc(c, &c->d_fast_redo, F * EVH_NLEVELS + 1));
-  {
-    int64_t mw = 0;
-    for (int l = 0; l < EVH_NLEVELS; l++) mw += (int64_t)((gmax.lv[l].w + 31) / 32) * gmax.lv[l].h;
-    c->cv_mask_frame_words = mw + 64;
-  }
+  c->cv_band_frame_entries = EVH_NLEVELS;   // a base per band of FAST tiles (tiles_y grows with the frame's height), then the level totals
+  for (int l = 0; l < EVH_NLEVELS; l++) c->cv_band_frame_entries += gmax.lv[l].tiles_y;
   A_(dalloc(c, &c->d_cv_seq, F * (size_t)gmax.cand_frame_entries));
   A_(dalloc(c, &c->d_cv_seq32, F * (size_t)gmax.cand_frame_entries));
   A_(dalloc(c, &c->d_cv_lpos, F * (size_t)gmax.cand_frame_entries));
   A_(dalloc(c, &c->d_cv_rpos, F * (size_t)gmax.cand_frame_entries));
-  A_(dalloc(c, &c->d_cv_mask, F * 2 * (size_t)c->cv_mask_frame_words));
+  A_(dalloc(c, &c->d_cv_band, F * (size_t)c->cv_band_frame_entries));
   A_(dalloc(c, &c->d_cv_tdesc, F * 8 * (size_t)gmax.total_tiles + 64));
   A_(dalloc(c, &c->d_fast_hint, 16 + 8 * 256 + 8));
   if (hipMemset(c->d_fast_hint, 0, sizeof(int) * (16 + 8 * 256 + 8)) != hipSuccess) {

@@ -134,14 +134,22 @@ int evh_launch_select(evh_ctx* c, int nframes) {
   if (c->order_mode == EVH_ORDER_OPENCV) {
     SelCvArgs B;
     B.s = A;
-    B.seq = c->d_cv_seq; B.seq32 = c->d_cv_seq32; B.lpos = c->d_cv_lpos; B.rpos = c->d_cv_rpos; B.mask = c->d_cv_mask;
-    B.mask_frame_words = c->cv_mask_frame_words;
-    int mo = 0;
-    for (int l = 0; l < EVH_NLEVELS; l++) { B.mask_off[l] = mo; mo += ((A.lv[l].w + 31) / 32) * A.lv[l].h; }
-    if (mo > c->cv_mask_frame_words) return evh_fail(c, EVH_ERR_CAPACITY, "evh_launch_select: row-major table scratch larger than the context's");
+    B.seq = c->d_cv_seq; B.seq32 = c->d_cv_seq32; B.lpos = c->d_cv_lpos; B.rpos = c->d_cv_rpos;
+    B.band = c->d_cv_band; B.band_frame_entries = c->cv_band_frame_entries;
+    B.nbands = 0;
+    for (int l = 0; l < EVH_NLEVELS; l++) {
+      B.band_start[l] = B.nbands; B.nbands += A.lv[l].tiles_y;
+      if (A.lv[l].tiles_x > CVP_MAX_TX || A.lv[l].tiles_y > CVP_MAX_BANDS)
+        return evh_fail(c, EVH_ERR_CAPACITY, "evh_launch_select: a level has more FAST tiles per row or per column than the row-major placement takes");
+    }
+    if (B.nbands + EVH_NLEVELS > c->cv_band_frame_entries) return evh_fail(c, EVH_ERR_CAPACITY, "evh_launch_select: band bases larger than the context's");
     B.heap_cap = 2 * q0 + 2;
     B.tdesc = c->d_cv_tdesc; B.total_tiles = c->g.total_tiles;
     { const char* e = getenv("EVH_CV_PHASE"); B.phase_limit = e ? atoi(e) : 0; }
+    // the row-major sequence of every level: band bases (one workgroup per level), then one wave per band of FAST tiles
+    hipLaunchKernelGGL(k_cv_band_base, xcd_grid(EVH_NLEVELS, nframes), dim3(256), 0, c->stream, B);
+    hipLaunchKernelGGL(k_cv_place, xcd_grid(B.nbands, nframes), dim3(CVP_NT), 0, c->stream, B);
+    EVH_HIP(c, hipGetLastError());
     // 256 threads on every level (1024 on the large levels was measured at 10.6 ms against 6.4 ms: a barrier over 16 waves
     // costs more than the partition steps it saves)
     const size_t heap_bytes = sizeof(unsigned long long) * (size_t)B.heap_cap;

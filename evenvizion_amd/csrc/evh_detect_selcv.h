@@ -16,8 +16,8 @@ namespace {
 //     the right that is not "after" it while the former lies left of the latter; the pairs are independent, so the two
 //     stopper lists are built by ranking, the number of pairs by a search, the swaps in parallel; the cut follows from the
 //     first unpaired stoppers.  std::partition is the same with a predicate.
-//   * the row-major sequence comes from one pass over the level's list: a candidate's x and y name its tile and row, small
-//     tables built from the FAST tile descriptors turn them into its place (cv_build_tables / cv_place).
+//   * the row-major sequence is made before k_select_cv starts, by two launches of their own (k_cv_band_base, k_cv_place at
+//     the end of this file): pure data movement, shaped for the memory system and not for the selection's one workgroup per level.
 // What stays sequential is what libstdc++ does per round in O(1): the median-of-three pivot and the final insertion sort.
 // The kernel is bound by dependent memory round trips and barriers, not by bytes or arithmetic, so every pass is shaped to
 // have few of them: loads that do not depend on one another, one exchange between the waves per partition pass (cv_partition),
@@ -28,11 +28,12 @@ struct SelCvArgs {
   uint32_t* seq32;           // [nframes][cand_frame_entries]  stage 1: the candidates themselves (key = FAST score = top byte)
   uint32_t* lpos;            // [nframes][cand_frame_entries]  left-stopper positions, ascending
   uint32_t* rpos;            // [nframes][cand_frame_entries]  right-stopper positions, ascending
-  uint32_t* mask;            // [nframes][2 * mask_frame_words] scratch of the row-major tables that do not fit LDS (E | RB)
-  int64_t mask_frame_words;
-  int mask_off[EVH_NLEVELS];
   const uint32_t* tdesc;     // [nframes][total_tiles][8] tile burst descriptors written by k_fast
   int total_tiles;
+  int* band;                 // [nframes][band_frame_entries] k_cv_band_base: corners before each band of its level, then the 8 level totals
+  int band_frame_entries;
+  int band_start[EVH_NLEVELS];   // first band of a level among the frame's bands (a band = one row of FAST tiles)
+  int nbands;                // bands of a frame, all levels
   int heap_cap;              // entries of the dynamic LDS heap (>= 2 * largest quota + 1)
   int phase_limit;           // profiling aid: 1 = stop after the row-major sequence, 2 = after the first retainBest, 0 = all
 };
@@ -267,15 +268,25 @@ __device__ __forceinline__ void cv_heap_select(EP a, int first, int middle, int 
   __syncthreads();
 }
 
-// a range of at most CV_SMALL elements is worked on in LDS: a round then costs LDS latencies instead of a chain of
-// dependent global accesses (pivot, cut, lists), which is what the small pyramid levels and the last rounds of the large
-// ones consist of
-#define CV_SMALL 2048
+// a range that fits the LDS block is worked on in LDS: a round then costs LDS latencies instead of a chain of dependent
+// global accesses (pivot, cut, lists), which is what the small pyramid levels and the last rounds of the large ones consist
+// of.  The block serves the two retainBest stages one after the other, so its range is counted in bytes: CV_CAP32 32-bit
+// elements (first stage) or CV_CAP64 64-bit ones (second stage).  A stopper list can take as many entries as the range has
+// elements: with every key equal to the pivot each element is a left and a right stopper, and cv_partition stores up to
+// min(cntL, cntR) + 1 of them before it knows how many pair.  2048 / 1024 elements: 16 KB + the heap, eight workgroups per CU
+// (measured against 2048 / 2048 at six, 2048 / 1024 at seven and 4096 / 2048 at four: profiles/select_place_ab.txt).
+#define CV_CAP32 2048
+#define CV_CAP64 1024
+#define CV_WAVES_PER_EU 8
+#define CV_SMALL_BYTES (CV_CAP32 * 4 > CV_CAP64 * 8 ? CV_CAP32 * 4 : CV_CAP64 * 8)
+#define CV_LIST_CAP (CV_CAP32 > CV_CAP64 ? CV_CAP32 : CV_CAP64)
+static_assert(CV_LIST_CAP <= 65536, "16-bit positions");
 struct CvSmall {
-  unsigned long long a[CV_SMALL];
-  uint16_t l[CV_SMALL], r[CV_SMALL];
+  unsigned long long a[CV_SMALL_BYTES / 8];
+  uint16_t l[CV_LIST_CAP], r[CV_LIST_CAP];
 };
-#define CV_TAB_BYTES ((int)sizeof(CvSmall))   // what the row-major tables of a level may take of it
+template <class E>
+__device__ __forceinline__ constexpr int cv_small_cap() { return sizeof(E) == 4 ? CV_CAP32 : CV_CAP64; }
 
 // libstdc++ __introselect on a[first, last) with `depth` rounds left; false = the heap of the depth-limit fall-back does
 // not fit the LDS array (cannot happen for nth <= 2 * quota: the launcher sizes it so)
@@ -285,7 +296,7 @@ __device__ __forceinline__ bool cv_introselect_loop(EP a, int first, int nth, in
   typedef typename std::remove_pointer<EP>::type E;
   E* hp = reinterpret_cast<E*>(hp_raw);
   while (last - first > 3) {
-    if constexpr (std::is_same<LP, uint32_t*>::value) if (sm && last - first <= CV_SMALL) {   // (the LDS instantiation never stages)
+    if constexpr (std::is_same<LP, uint32_t*>::value) if (sm && last - first <= cv_small_cap<E>()) {   // (the LDS instantiation never stages)
       const int len = last - first;
       E* la = reinterpret_cast<E*>(sm->a);
       for (int i = threadIdx.x; i < len; i += (int)blockDim.x) la[i] = a[first + i];
@@ -344,19 +355,16 @@ __device__ __forceinline__ bool cv_introselect_loop(EP a, int first, int nth, in
 
 // KeyPointsFilter::retainBest on a[0, n): std::nth_element(a, a + npoints, a + n), then std::partition of the tail by
 // "response >= a[npoints - 1].response".  Returns the new size, -1 when the fall-back heap does not fit.
-// staged: the sequence already lies in sm->a and not in a (n > npoints and n <= CV_SMALL then; the survivors go to a)
 template <class E>
 __device__ __forceinline__ int cv_retain_best(E* a, int n, int npoints, uint32_t* lpos, uint32_t* rpos, CvLds& S,
-                              unsigned long long* hp, int hp_cap, CvSmall* sm, bool staged = false) {
+                              unsigned long long* hp, int hp_cap, CvSmall* sm) {
   if (npoints < 0 || n <= npoints) return n;
   if (npoints == 0) return 0;
   const int depth = 2 * (31 - __clz(n));
-  if (n <= CV_SMALL) {                       // everything in LDS, the survivors copied back
+  if (n <= cv_small_cap<E>()) {              // everything in LDS, the survivors copied back
     E* la = reinterpret_cast<E*>(sm->a);
-    if (!staged) {
-      for (int i = threadIdx.x; i < n; i += (int)blockDim.x) la[i] = a[i];
-      __syncthreads();
-    }
+    for (int i = threadIdx.x; i < n; i += (int)blockDim.x) la[i] = a[i];
+    __syncthreads();
     if (!cv_introselect_loop<E*, uint16_t*>(la, 0, npoints, n, depth, sm->l, sm->r, S, hp, hp_cap, nullptr)) return -1;
     const uint32_t amb = cv_key(la[npoints - 1]);
     const int k = cv_partition<1>(la, npoints, n, amb, sm->l, sm->r, S);
@@ -370,64 +378,171 @@ __device__ __forceinline__ int cv_retain_best(E* a, int n, int npoints, uint32_t
 }
 
 // ---- the corners of a level in row-major order (as cv::FAST hands them over).  Every FAST tile left its corners as one
-// row-major burst in the level's list, with a descriptor (offset of the burst, corners per tile row).  The place of a corner is
+// row-major burst in the level's list, with a descriptor (word 0 = offset of the burst, words 1..7 = corners per tile row, a
+// byte each).  The place of a corner is
 //     (corners in earlier rows of the level) + (corners of its row in tiles to the left) + (its rank in its tile's row),
 // and its rank in its tile's row is (its index in the list) - (offset of the burst) - (corners in earlier rows of the tile).
-// A candidate word carries x and y, hence its tile and row, so with
-//     RB[row]          = corners in earlier rows of the level                               (row = tile row * FT_H + row in the tile)
-//     E[row][tile col] = corners of the row in tiles to the left - corners in earlier rows of the tile   (16 bits: |E| < 4096)
-// the place of candidate i is RB[row] + E[row][tx] - D[tile].offset + i: one pass over the list with independent, coalesced
-// loads, three table reads each.  D, RB and E lie in LDS where they fit (CvSmall is idle until the sequence exists), else in
-// the per-frame global scratch; the pass is the same.  D: descriptors (8 words per tile).  Returns the corners the descriptors count.
-template <class TD, class TR, class TE>
-__device__ __forceinline__ int cv_build_tables(TD D, TR RB, TE E, int TX, int TY, CvLds& S) {
-  const int tid = threadIdx.x, NT = (int)blockDim.x, NR = TY * FT_H;
-  auto corners = [&](int t, int r) { return (int)((D[t * 8 + 1 + (r >> 2)] >> (8 * (r & 3))) & 0xFFu); };
-  // rows of the level, `per` consecutive ones per thread: E = corners to the left in the row, RB by a scan of the row totals
-  const int per = (NR + NT - 1) / NT, r0 = min(NR, tid * per), r1 = min(NR, r0 + per);
-  int sum = 0;
-  for (int row = r0; row < r1; row++) {
-    const int ty = row / FT_H, r = row - ty * FT_H;
-    int in = 0;
-    for (int tx = 0; tx < TX; tx++) { E[row * TX + tx] = (int16_t)in; in += corners(ty * TX + tx, r); }
-    RB[row] = in;
-    sum += in;
-  }
-  int ex, d0, tot, d1;
-  cv_scan2(S, sum, 0, ex, d0, tot, d1);
-  for (int row = r0; row < r1; row++) { const int c = RB[row]; RB[row] = ex; ex += c; }
+// The work is split by BAND, one row of FAST tiles (FT_H level rows by tiles_x tiles): with
+//     base             = corners in earlier bands of the level                              (k_cv_band_base, a prefix of band totals)
+//     E[row][tile col] = corners in earlier rows of the band + corners of the row in tiles to the left
+//                        - corners in earlier rows of the tile                              (row = row in the band, 0 .. FT_H - 1)
+// the place of candidate i of tile column tx is base + E[row][tx] - D[tx].offset + i.  A band's table is 28 x 32 entries at
+// the most and its destination is one contiguous range of the sequence, so a band is a small unit that needs nothing but
+// its own tiles_x descriptors and its base: a 720p frame has 105 of them, a launch some hundred thousand.
+// The index arithmetic is __host__ __device__ and checked on the host against a sort by (y, x): tools/cv_place_host_check.hip.
+#define CVP_MAX_TX 32        // tiles per band: widths below 4096 (evh_create) give at most 32
+#define CVP_MAX_BANDS 160    // bands per level: heights below 4096 give at most 145
+#define CVP_NT 64            // k_cv_place: one wave per band (2, 4 and 8 bands per workgroup measured the same)
+#define CVP_TILE_CHUNKS 16   // chunks of CVP_NT corners per tile: k_fast_main's list of a tile holds 1024
+#define CVP_EPT 16           // chunks per step: sixteen loads in flight per lane (4: +0.13 ms, 8: +0.06 ms per launch of 2048 720p frames)
+
+__host__ __device__ __forceinline__ int cvp_word_sum(uint32_t w) {   // the four bytes of a descriptor word added up
+  const uint32_t p = (w & 0x00FF00FFu) + ((w >> 8) & 0x00FF00FFu);
+  return (int)((p & 0xFFFFu) + (p >> 16));
+}
+// corners of tile row r (0 .. FT_H - 1) of the tile whose descriptor is d[0..8)
+__host__ __device__ __forceinline__ int cvp_corners(const uint32_t* d, int r) { return (int)((d[1 + (r >> 2)] >> (8 * (r & 3))) & 0xFFu); }
+__host__ __device__ __forceinline__ int cvp_tile_total(const uint32_t* d) {
+  int s = 0;
+  for (int w = 1; w < 8; w++) s += cvp_word_sum(d[w]);
+  return s;
+}
+// E[row][tx] from: rows_before = corners in earlier rows of the band, left = corners of the row in tiles to the left,
+// tile_before = corners in earlier rows of the tile
+__host__ __device__ __forceinline__ int cvp_entry(int rows_before, int left, int tile_before) { return rows_before + left - tile_before; }
+// row in band ty of the level that a candidate's y names (clamped: a candidate always lies in the band of its tile)
+__host__ __device__ __forceinline__ int cvp_band_row(uint32_t c, int ty) {
+  const int r = (int)((c >> 12) & 0xFFFu) - EVH_FAST_OY - ty * FT_H;
+  return r < 0 ? 0 : (r > FT_H - 1 ? FT_H - 1 : r);
+}
+// a burst is taken in chunks of CVP_NT corners: the list entry of chunk q of tile column tx, and the chunk's first corner
+__host__ __device__ __forceinline__ uint16_t cvp_chunk(int tx, int q) { return (uint16_t)(tx | (q << 8)); }
+__host__ __device__ __forceinline__ int cvp_chunk_first(int w) { return (w >> 8) * CVP_NT; }
+// place of candidate i of a tile whose burst starts at off: base = the band's, e = E[row][tx]
+__host__ __device__ __forceinline__ int cvp_place(int base, int e, int off, int i) { return base + e - off + i; }
+
+// the level of band b of a frame and b's index inside the level
+__device__ __forceinline__ int cvp_level_of_band(const SelCvArgs& B, int& b) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < EVH_NLEVELS; i++)
+    if (b >= B.band_start[i]) l = i;
+  b -= B.band_start[l];
+  return l;
+}
+
+// Pre-pass, one workgroup per (level, frame): the level's descriptors are read once, the corners of each band added up and
+// their exclusive prefix written to B.band (the band bases), the level's total behind the frame's bands.
+__global__ __launch_bounds__(256) void k_cv_band_base(SelCvArgs B) {
+  const SelectArgs& A = B.s;
+  __shared__ int bs[CVP_MAX_BANDS];
+  int l, f;
+  xcd_order(l, f);
+  if (f >= A.nframes || l >= EVH_NLEVELS) return;
+  const int tid = threadIdx.x, NT = (int)blockDim.x;
+  const EvhLevel L = A.lv[l];
+  const int n = min(A.cand_count[f * EVH_NLEVELS + l], L.cand_cap);
+  if (n <= 0 || L.quota <= 0) return;          // no placement, and k_select_cv does not ask for the total
+  const int TX = L.tiles_x, TY = min(L.tiles_y, CVP_MAX_BANDS);
+  const uint4* td = reinterpret_cast<const uint4*>(B.tdesc + ((int64_t)f * B.total_tiles + L.tile_start) * 8);
+  for (int b = tid; b < TY; b += NT) bs[b] = 0;
   __syncthreads();
-  // tiles: take the corners in earlier rows of the tile off E
   for (int t = tid; t < TX * TY; t += NT) {
-    const int ty = t / TX, tx = t - ty * TX;
-    int before = 0;
-#pragma unroll 4
-    for (int r = 0; r < FT_H; r++) {
-      E[(ty * FT_H + r) * TX + tx] -= (int16_t)before;
-      before += corners(t, r);
+    const uint4 lo = td[2 * t], hi = td[2 * t + 1];
+    const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const int c = cvp_tile_total(d);
+    if (c) atomicAdd(&bs[t / TX], c);
+  }
+  __syncthreads();
+  if (tid < 64) {                              // exclusive prefix over the bands, 64 at a step
+    int* out = B.band + (int64_t)f * B.band_frame_entries;
+    int carry = 0;
+    for (int b0 = 0; b0 < TY; b0 += 64) {
+      const int b = b0 + tid, v = b < TY ? bs[b] : 0;
+      const int incl = wave_scan_incl(v);
+      if (b < TY) out[B.band_start[l] + b] = carry + incl - v;
+      carry += __builtin_amdgcn_readlane(incl, 63);
+    }
+    if (tid == 0) out[B.nbands + l] = carry;
+  }
+}
+
+struct CvpLds {
+  int E[FT_H * CVP_MAX_TX];
+  uint16_t W[CVP_MAX_TX * CVP_TILE_CHUNKS];
+};
+
+// Placement, one wave per band.  Lane tx holds the descriptor of tile column tx in registers; row by row a scan over the
+// lanes gives the corners to the left, two running sums the corners in earlier rows of the band and of the tile: E goes to
+// LDS with no load behind it.  Then the bursts, 64 corners (a chunk) at a time; offset and corners of a chunk's tile are
+// the wave's, read off lane tx; a lane takes one corner of the chunk: one coalesced load, one table entry, one store.
+// Candidates whose place or whose index falls outside [0, n) are dropped (never: descriptors and list come from the same tiles).
+__global__ __launch_bounds__(CVP_NT) void k_cv_place(SelCvArgs B) {
+  const SelectArgs& A = B.s;
+  __shared__ CvpLds S;
+  static_assert(CVP_NT == 64 && CVP_MAX_TX <= 64, "one wave, a lane per tile column");
+  int ty, f;
+  xcd_order(ty, f);
+  if (f >= A.nframes || ty >= B.nbands) return;
+  const int band = ty;
+  const int l = cvp_level_of_band(B, ty);
+  const int lane = threadIdx.x;
+  const EvhLevel L = A.lv[l];
+  const int n = min(A.cand_count[f * EVH_NLEVELS + l], L.cand_cap);
+  if (n <= 0 || L.quota <= 0 || ty >= CVP_MAX_BANDS) return;
+  const int TX = min(L.tiles_x, CVP_MAX_TX);
+  const uint4* td = reinterpret_cast<const uint4*>(B.tdesc + ((int64_t)f * B.total_tiles + L.tile_start + ty * L.tiles_x) * 8);
+  const int base = B.band[(int64_t)f * B.band_frame_entries + band];
+  uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+  if (lane < TX) { lo = td[2 * lane]; hi = td[2 * lane + 1]; }
+  const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  int tile_before = 0, rows_before = 0;
+#pragma unroll
+  for (int r = 0; r < FT_H; r++) {
+    const int c = cvp_corners(d, r);            // 0 in the lanes past TX
+    const int incl = wave_scan_incl(c);
+    if (lane < TX) S.E[r * TX + lane] = cvp_entry(rows_before, incl - c, tile_before);
+    rows_before += __builtin_amdgcn_readlane(incl, 63);
+    tile_before += c;
+  }
+  // the band's chunks, tile by tile: lane tx lists those of its tile
+  const int nch = min((tile_before + CVP_NT - 1) / CVP_NT, CVP_TILE_CHUNKS);   // 0 in the lanes past TX
+  const int incl_ch = wave_scan_incl(nch);
+  const int nchunks = __builtin_amdgcn_readlane(incl_ch, 63);
+  for (int q = 0; q < nch; q++) S.W[incl_ch - nch + q] = cvp_chunk(lane, q);
+  __syncthreads();
+  const uint32_t* cand = A.cand + (int64_t)f * A.cand_frame_entries + L.cand_off;
+  uint32_t* out = B.seq32 + (int64_t)f * A.cand_frame_entries + L.cand_off;
+  // the bursts in chunks of 64 corners, CVP_EPT chunks a step: the loads of a step are issued together (chunk by chunk a wave
+  // would wait for memory once per chunk, some twenty times for a level-0 band of a 720p frame)
+  for (int k0 = 0; k0 < nchunks; k0 += CVP_EPT) {
+    uint32_t c[CVP_EPT];
+    int tx[CVP_EPT], off[CVP_EPT], idx[CVP_EPT];
+#pragma unroll
+    for (int s = 0; s < CVP_EPT; s++) {
+      const int w = __builtin_amdgcn_readfirstlane((int)S.W[min(k0 + s, nchunks - 1)]);
+      tx[s] = w & 0xFF;
+      off[s] = __builtin_amdgcn_readlane((int)d[0], tx[s]);
+      const int j = cvp_chunk_first(w) + lane, cnt = __builtin_amdgcn_readlane(tile_before, tx[s]);
+      idx[s] = (int)((uint32_t)off[s] + (uint32_t)j);
+      if (k0 + s >= nchunks || j >= cnt || (unsigned)idx[s] >= (unsigned)n) idx[s] = -1;
+      c[s] = cand[max(idx[s], 0)];
+    }
+#pragma unroll
+    for (int s = 0; s < CVP_EPT; s++) {
+      if (idx[s] < 0) continue;
+      const int e = S.E[cvp_band_row(c[s], ty) * TX + tx[s]];
+      const int pos = cvp_place(base, e, off[s], idx[s]);
+      if ((unsigned)pos < (unsigned)n) out[pos] = c[s];
     }
   }
-  __syncthreads();
-  return tot;
 }
 
-// cand[0, n) -> out[place]; candidates the tables cannot place (never: descriptors and list come from the same tiles) are dropped
-template <class TD, class TR, class TE, class TO>
-__device__ __forceinline__ void cv_place(const uint32_t* cand, int n, TD D, TR RB, TE E, int TX, int TY, TO out) {
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n; i += (int)blockDim.x) {
-    const uint32_t c = cand[i];
-    const int tx = min(max(cand_x(c) - EVH_FAST_OX, 0) / FT_W, TX - 1);
-    const int row = min(max(cand_y(c) - EVH_FAST_OY, 0), TY * FT_H - 1);
-    const int pos = RB[row] + (int)E[row * TX + tx] - (int)D[((row / FT_H) * TX + tx) * 8] + i;
-    if ((unsigned)pos < (unsigned)n) out[pos] = c;
-  }
-}
-
-// One workgroup of 256 threads per (level, frame).  65 VGPRs, no scratch, 24.2 KB static LDS + the heap: six workgroups per CU.
-// The bounds ask for that occupancy outright; under looser ones the compiler spends 128 VGPRs, and every device function has to
-// be inlined (left as a call, its callee-saved registers go to scratch).
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k_select_cv(SelCvArgs B) {
+// One workgroup of 256 threads per (level, frame), started when the row-major sequence of every level lies in seq32.
+// 63 VGPRs, no scratch, 16.2 KB static LDS + the heap: eight workgroups per CU.  The bounds ask for that occupancy outright:
+// under looser ones the compiler spends 128 VGPRs, and every device function has to be inlined (left as a call, its
+// callee-saved registers go to scratch).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CV_WAVES_PER_EU))) void k_select_cv(SelCvArgs B) {
   const SelectArgs& A = B.s;
   __shared__ CvLds S;
   __shared__ CvSmall SM;
@@ -437,7 +552,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
   if (f >= A.nframes || l >= EVH_NLEVELS) return;
   const int tid = threadIdx.x, NT = (int)blockDim.x;
   const EvhLevel L = A.lv[l];
-  const uint32_t* cand = A.cand + (int64_t)f * A.cand_frame_entries + L.cand_off;
   const int n_raw = A.cand_count[f * EVH_NLEVELS + l];
   bool overflow = n_raw > L.cand_cap;
   const int n = min(n_raw, L.cand_cap);
@@ -449,37 +563,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
   int k2 = 0;
   bool unsupported = false;
   if (n > 0 && q > 0) {
-    // ---- the row-major sequence (cv_build_tables).  Where the tables lie:
-    //   * in CvSmall when D + RB + E fit its CV_TAB_BYTES (720p level 0, 10 x 24 tiles: 23.8 KB; 1080p level 0 and 4K levels
-    //     0..2 do not fit) -- and behind the first CV_SMALL words of it when the sequence itself fits those and retainBest is
-    //     going to work on it in LDS: the pass then writes it there, with no global copy in between;
-    //   * else in the frame's global scratch (B.mask: E in the level's slice of the first half, RB of the second), D read in place.
-    const int TX = L.tiles_x, TY = L.tiles_y, NR = TY * FT_H;
-    const int tab_bytes = TX * TY * 32 + NR * 4 + NR * TX * 2;
-    const bool staged = n > 2 * q && n <= CV_SMALL && tab_bytes <= CV_TAB_BYTES - CV_SMALL * 4;
-    const uint32_t* td = B.tdesc + ((int64_t)f * B.total_tiles + L.tile_start) * 8;
-    int tot;
-    if (staged || tab_bytes <= CV_TAB_BYTES) {
-      uint32_t* D = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(&SM) + (staged ? CV_SMALL * 4 : 0));
-      int* RB = reinterpret_cast<int*>(D + TX * TY * 8);
-      int16_t* E = reinterpret_cast<int16_t*>(RB + NR);
-      for (int i = tid; i < TX * TY * 8; i += NT) D[i] = td[i];
-      __syncthreads();
-      tot = cv_build_tables(D, RB, E, TX, TY, S);
-      if (staged) cv_place(cand, n, D, RB, E, TX, TY, reinterpret_cast<uint32_t*>(SM.a));
-      else cv_place(cand, n, D, RB, E, TX, TY, a32);
-    } else {
-      uint32_t* P = B.mask + (int64_t)f * 2 * B.mask_frame_words + B.mask_off[l];
-      int* RB = reinterpret_cast<int*>(P + B.mask_frame_words);
-      int16_t* E = reinterpret_cast<int16_t*>(P);
-      tot = cv_build_tables(td, RB, E, TX, TY, S);
-      cv_place(cand, n, td, RB, E, TX, TY, a32);
-    }
-    if (tot != n) overflow = true;    // cannot happen: the descriptors and the list come from the same tiles
-    __syncthreads();
+    // the corners the level's descriptors count (k_cv_band_base)
+    if (B.band[(int64_t)f * B.band_frame_entries + B.nbands + l] != n) overflow = true;    // cannot happen: the descriptors and the list come from the same tiles
     if (B.phase_limit == 1) { if (tid == 0) A.lvl_count[f * EVH_NLEVELS + l] = 0; return; }   // (no key points: nothing downstream reads what was not written)
     // ---- retainBest(2 * quota) by FAST score
-    int k1 = cv_retain_best(a32, n, 2 * q, lpos, rpos, S, cv_heap, B.heap_cap, &SM, staged);
+    int k1 = cv_retain_best(a32, n, 2 * q, lpos, rpos, S, cv_heap, B.heap_cap, &SM);
     if (k1 < 0) { unsupported = true; k1 = 0; }
     if (B.phase_limit == 2) { if (tid == 0) A.lvl_count[f * EVH_NLEVELS + l] = 0; return; }   // (no key points: nothing downstream reads what was not written)
     // ---- Harris response of the survivors, in place

@@ -170,9 +170,9 @@ struct evh_ctx {
   uint32_t* d_cv_seq32 = nullptr; // [max_frames][cand_frame_entries] the first retainBest works on the candidates themselves
   uint32_t* d_cv_lpos = nullptr;  // [max_frames][cand_frame_entries] stopper positions of the partition passes
   uint32_t* d_cv_rpos = nullptr;
-  uint32_t* d_cv_mask = nullptr;  // [max_frames][2][cv_mask_frame_words] row-major tables of the levels that do not fit LDS (E | RB, evh_detect_selcv.h)
+  int* d_cv_band = nullptr;       // [max_frames][cv_band_frame_entries] corners before each band of FAST tiles, then the level totals (evh_detect_selcv.h)
   uint32_t* d_cv_tdesc = nullptr; // [max_frames][total_tiles][8] FAST tile burst descriptors
-  int64_t cv_mask_frame_words = 0;
+  int cv_band_frame_entries = 0;
   bool fast_lift = true;
   bool fast_share = true;         // evh_set_fast_share
   bool fast_hint = true;          // evh_set_fast_hint

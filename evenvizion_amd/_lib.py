@@ -35,6 +35,8 @@ EXPO_NSTATS = 7          # EVH_EXPO_NSTATS: (pixels, sum a per channel x3, sum b
 REFINE_REFINED, REFINE_UNCHANGED, REFINE_NOTHING_COVERED, REFINE_TOO_FEW, REFINE_DEGENERATE = range(5)
 REFINE_INFO = ("status", "evals", "accepted", "covered_in", "ssd_in", "covered_out", "ssd_out", "n_in")
 REFINE_NINFO, REFINE_NSUMS, REFINE_MAX_ITERS, REFINE_MAX_SIZE = 8, 45, 64, 4096
+TRACK_FLAGS = ("tracked", "bad_point", "no_window", "left_frame", "flat", "high_error", "fb_failed")   # EVH_TRACK_* in order
+TRACK_TRACKED, TRACK_NO_ERR = 0, 0xFFFFFFFF
 GRAPH_NSUMS, GRAPH_BAD_INDEX, GRAPH_BAD_STATUS = 154, 1, 2   # EVH_GRAPH_* (include/evhip.h)
 GRAPH_INFO = ("used", "gated", "behind", "flags")
 
@@ -166,6 +168,11 @@ SIGNATURES = {
     "evh_pair_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "evh_canvas_refine": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "evh_canvas_refine_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i64, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    # points followed between frames, and the points worth following
+    "evh_track_points": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i, _vp, _i, _i, _i, _d, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "evh_track_points_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _d, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "evh_track_seeds": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _d, _vp, _i, _vp]),
+    "evh_track_seeds_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _vp]),
     # global alignment: the normal equations over all superposed matrices, from the match rows of any frame pairs
     "evh_graph_normal": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _d, _vp, _vp]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
@@ -1235,6 +1242,100 @@ class Context:
         """pair_refine on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel and tap converted as
         yuv420_to_bgr converts it (evh_pair_refine_yuv420)."""
         return self._pair_refine(True, planes, mats, iters, clip, out, info, normal, frame_step, size)
+
+    # ---- points followed between frames ----
+    def _track_points(self, planes, frames, pts, npts, mats, levels, radius, iters, min_eig, fb_max, max_err, rows, counts, flags, err,
+                      frame_step, size):
+        import torch
+        self._enter()
+        frame_step = int(frame_step)
+        if frame_step not in (1, 2):
+            raise ValueError("frame_step must be 1 or 2")
+        planes, head, n, w, h, _ = self._frame_source(frames, size, planes=planes)
+        if pts.dim() != 3 or pts.shape[2] != 2:
+            raise ValueError("pts must be [npairs,pt_cap,2]")
+        npairs, pt_cap = int(pts.shape[0]), int(pts.shape[1])
+        self._dev_tensor(pts, torch.float32, npairs * pt_cap * 2, "pts must be a contiguous CUDA float32 tensor [npairs,pt_cap,2]")
+        self._dev_tensor(npts, torch.int32, npairs, "npts must be a contiguous CUDA int32 tensor of npairs elements")
+        if mats is not None:
+            self._dev_tensor(mats, torch.float64, 9 * npairs, "mats must be a contiguous CUDA float64 tensor of npairs*9 elements")
+        if npairs and n < (npairs - 1) * frame_step + 2:
+            raise ValueError("frames holds fewer frames than the pairs take")
+        dev = "cuda:%d" % self.device
+        if rows is None:
+            rows = torch.empty((npairs, pt_cap, 4), dtype=torch.float32, device=dev)
+        if counts is None:
+            counts = torch.empty(npairs, dtype=torch.int32, device=dev)
+        if rows.dim() != 3 or rows.shape[0] != npairs or rows.shape[2] != 4:
+            raise ValueError("rows must be [npairs,row_cap,4]")
+        row_cap = int(rows.shape[1])
+        self._dev_tensor(rows, torch.float32, npairs * row_cap * 4, "rows must be a contiguous CUDA float32 tensor [npairs,row_cap,4]")
+        self._dev_tensor(counts, torch.int32, npairs, "counts must be a contiguous CUDA int32 tensor of npairs elements")
+        if flags is not None:
+            self._dev_tensor(flags, torch.uint8, (npairs, pt_cap), "flags must be a contiguous CUDA uint8 tensor [npairs,pt_cap]")
+        if err is not None:
+            self._dev_tensor(err, torch.int32, (npairs, pt_cap), "err must be a contiguous CUDA int32 tensor [npairs,pt_cap]")
+        if npairs == 0 or pt_cap == 0:       # empty tensors have no address to hand over
+            if npairs:
+                counts.zero_()
+            return rows, counts
+        fb = -1 if fb_max is None else int(round(32.0 * float(fb_max)))
+        tail = (pts.data_ptr(), npts.data_ptr(), pt_cap, _ptr(mats), int(levels), int(radius), int(iters), float(min_eig), fb,
+                -1 if max_err is None else int(max_err), rows.data_ptr(), row_cap, counts.data_ptr(), _ptr(flags), _ptr(err))
+        self._check(self._form("evh_track_points", planes)(self.h, head[0], npairs, frame_step, w, h, *head[4:], *tail))
+        return rows, counts
+
+    def track_points(self, frames, pts, npts, mats=None, levels=3, radius=7, iters=20, min_eig=0.0, fb_max=None, max_err=None,
+                     rows=None, counts=None, flags=None, err=None, frame_step=1):
+        """Points of the current frame of every pair followed into its previous frame (evh_track_points, the arithmetic is stated
+        in include/evhip.h).  frames and frame_step as in pair_residual.  pts: CUDA float32 [npairs,pt_cap,2], (x, y) on the current
+        frame; npts: CUDA int32 [npairs]; mats: CUDA float64 npairs*9, current pixel -> previous pixel, the first guess, or None.
+        fb_max: the forward-backward bar in pixels (taken to 1/32 pixel) or None = no backward pass; max_err: 0..255 gray levels of
+        mean absolute difference or None.  rows: CUDA float32 [npairs,row_cap >= pt_cap,4] or None = a new tensor, counts: CUDA
+        int32 [npairs] or None; both are returned: rows (ax, ay, bx, by) of the kept points in input order, the layout of
+        batch_static_rows.  flags: CUDA uint8 [npairs,pt_cap] or None (TRACK_FLAGS names the codes); err: CUDA int32
+        [npairs,pt_cap] or None (the library's u32 values; -1 = TRACK_NO_ERR).  Does not synchronise."""
+        return self._track_points(False, frames, pts, npts, mats, levels, radius, iters, min_eig, fb_max, max_err, rows, counts, flags,
+                                  err, frame_step, None)
+
+    def track_points_yuv420(self, planes, pts, npts, mats=None, levels=3, radius=7, iters=20, min_eig=0.0, fb_max=None, max_err=None,
+                            rows=None, counts=None, flags=None, err=None, frame_step=1, size=None):
+        """track_points on decoded planes (see _yuv420; size=(w, h) for packed I420 frames): every pixel converted as yuv420_to_bgr
+        converts it (evh_track_points_yuv420)."""
+        return self._track_points(True, planes, pts, npts, mats, levels, radius, iters, min_eig, fb_max, max_err, rows, counts, flags,
+                                  err, frame_step, size)
+
+    def _track_seeds(self, planes, frames, radius, cell, border, min_eig, pts, npts, pt_cap, size):
+        import torch
+        self._enter()
+        planes, head, n, w, h, _ = self._frame_source(frames, size, planes=planes)
+        dev = "cuda:%d" % self.device
+        if pts is None:
+            pts = torch.empty((n, int(pt_cap), 2), dtype=torch.float32, device=dev)
+        if npts is None:
+            npts = torch.empty(n, dtype=torch.int32, device=dev)
+        if pts.dim() != 3 or pts.shape[0] != n or pts.shape[2] != 2:
+            raise ValueError("pts must be [n,pt_cap,2]")
+        pt_cap = int(pts.shape[1])
+        self._dev_tensor(pts, torch.float32, n * pt_cap * 2, "pts must be a contiguous CUDA float32 tensor [n,pt_cap,2]")
+        self._dev_tensor(npts, torch.int32, n, "npts must be a contiguous CUDA int32 tensor of n elements")
+        if n == 0:                           # empty tensors have no address to hand over
+            return pts, npts
+        border = int(radius) + 1 if border is None else int(border)
+        tail = (int(radius), int(cell), border, float(min_eig), pts.data_ptr(), pt_cap, npts.data_ptr())
+        self._check(self._form("evh_track_seeds", planes)(self.h, *head, *tail))
+        return pts, npts
+
+    def track_seeds(self, frames, radius=2, cell=16, border=None, min_eig=0.0, pts=None, npts=None, pt_cap=1024):
+        """The best-conditioned pixel of every cell of every frame (evh_track_seeds, stated in include/evhip.h).  frames: CUDA uint8
+        [n,h,w] or [n,h,w,3], rows and frames may be strided.  border: None = radius + 1.  pts: CUDA float32 [n,pt_cap,2] or None =
+        a new tensor of pt_cap slots per frame; npts: CUDA int32 [n] or None; both are returned: the seeds (x, y) in cell raster
+        order and their full count (it may exceed pt_cap; only pt_cap are written).  Does not synchronise."""
+        return self._track_seeds(False, frames, radius, cell, border, min_eig, pts, npts, pt_cap, None)
+
+    def track_seeds_yuv420(self, planes, radius=2, cell=16, border=None, min_eig=0.0, pts=None, npts=None, pt_cap=1024, size=None):
+        """track_seeds on decoded planes (see _yuv420; size=(w, h) for packed I420 frames) (evh_track_seeds_yuv420)."""
+        return self._track_seeds(True, planes, radius, cell, border, min_eig, pts, npts, pt_cap, size)
 
     # ---- direct alignment against the mosaic ----
     def _canvas_refine(self, planes, frames, canvas, mats, count, min_cover, iters, clip, out, info, normal, size):

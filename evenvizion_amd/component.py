@@ -43,6 +43,12 @@ with --global_align 1 (extension, default off; --path_to_video only) also the wh
                                        --graph_model; the first dictionary stays as it is
     graph_report.json                  the edges tried and kept, the loop edges per frame, the cost before and after, the steps
                                        and the registration report of both dictionaries.
+with --recover_tracking 1 (extension, default off; --path_to_video and --features ORB only) also a second pass for the pairs whose matching failed,
+    dict_with_homography_matrix_recovered.json  the dictionary of tracking.recover_homography_dict: such a pair's rows come from points
+                                       followed on the pixels (evh_track_seeds, evh_track_points: --track_levels, --track_radius,
+                                       --track_cell, --track_fb, --track_min_eig); the first dictionary stays as it is.  Where the
+                                       first pass cannot finish (no matrix for the first pair) only these two files are written
+    tracking_report.json               {frame_no: {"first_status", "seeds", "tracked", "flags", "final_status"}} per tracked pair.
 --path_to_video takes what the reference's script takes for H.264 video in an MP4/MOV container: the file is opened by
 evenvizion_amd.capture.VideoCapture (libevcap.so: this repository's own demultiplexer + H.264 decoder, standing in for
 cv2.VideoCapture at evenvizion_component.py:132), e.g. the reference's own evenvizion/examples/test_video/test_video.mp4.
@@ -159,6 +165,19 @@ def parser():
                          "stays as it is (the video is read three times more)")
     ap.add_argument("--refine_levels", type=_int_in(1, 4), default=1, help="--refine_direct: pyramid levels, coarse to fine")
     ap.add_argument("--refine_iters", type=_int_in(0, 64), default=8, help="--refine_direct: steps tried per level")
+    ap.add_argument("--recover_tracking", type=int, choices=(0, 1), default=0,
+                    help="1: a second pass that gives the pairs whose matching failed rows from points followed on the pixels "
+                         "(extension; --path_to_video and --features ORB only): tracking.recover_homography_dict; writes "
+                         "dict_with_homography_matrix_recovered.json and tracking_report.json beside the first dictionary, which "
+                         "stays as it is (the video is read once more)")
+    ap.add_argument("--track_levels", type=_int_in(1, 4), default=3, help="--recover_tracking: pyramid levels")
+    ap.add_argument("--track_radius", type=_int_in(1, 10), default=7, help="--recover_tracking: the window is (2*radius + 1)^2 pixels")
+    ap.add_argument("--track_cell", type=_int_in(8, 64), default=16, help="--recover_tracking: one seed per cell of this many pixels")
+    ap.add_argument("--track_fb", type=float, default=0.5,
+                    help="--recover_tracking: pixels a point may miss its start by when followed back; negative: no backward pass")
+    ap.add_argument("--track_min_eig", type=float, default=None,
+                    help="--recover_tracking: the smaller eigenvalue of the mean structure tensor a seed and a window must reach "
+                         "(default: tracking.MIN_EIG)")
     ap.add_argument("--anchor_mosaic", type=int, choices=(0, 1), default=0,
                     help="1: frame-to-mosaic registration, every frame aligned against the blended picture of the frames before it "
                          "(extension; --path_to_video only): registration.anchored_homography_dict; writes "
@@ -191,7 +210,11 @@ def main(argv=None):
     features = [f for f in args.features.split(",") if f]
     if args.reject_moving and features != ["ORB"]:
         raise ValueError("--reject_moving takes --features ORB: the second pass is built on the fused ORB path only")
+    if args.recover_tracking and features != ["ORB"]:
+        raise ValueError("--recover_tracking takes --features ORB: the second pass is built on the fused ORB path only")
     if args.path_to_videos:
+        if args.recover_tracking:
+            raise ValueError("--recover_tracking takes one video (--path_to_video)")
         if _bool(args.matching_pictures):
             raise ValueError("--matching_pictures takes one video (--path_to_video)")
         if args.reject_moving:
@@ -222,10 +245,22 @@ def main(argv=None):
 
         def sink(frame_no, picture):
             write_png(os.path.join(pictures, "matching_vis_{}.png".format(frame_no)), picture)
-    result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
-                                 none_H_processing=_bool(args.none_H_processing),
-                                 features_type_list=features, ingest=args.ingest, matching_sink=sink)
+    try:
+        result = get_homography_dict(cap, resize_width=args.resize_width, matching_path=None,
+                                     none_H_processing=_bool(args.none_H_processing),
+                                     features_type_list=features, ingest=args.ingest, matching_sink=sink)
+    except AttributeError as error:         # the reference's end of a video whose first pair has no matrix, and nothing else
+        if not args.recover_tracking or "no homography for frame" not in str(error):
+            raise
+        from .processing.video_processing import resized_shape
+        w, h = resized_shape(original_shape, args.resize_width)
+        save_folder = output_folder(args, stem)
+        os.makedirs(save_folder, exist_ok=True)
+        write_recovered(args, save_folder, {"resize_info": {"h": h, "w": w}})
+        return save_folder
     save_folder = write_outputs(args, result, original_shape, stem, args.path_to_video)
+    if args.recover_tracking:
+        write_recovered(args, save_folder)
     if args.reject_moving:
         write_refined(args, save_folder, features)
     if args.refine_direct:
@@ -235,6 +270,25 @@ def main(argv=None):
     if args.global_align:
         write_aligned(args, save_folder)
     return save_folder
+
+
+def write_recovered(args, save_folder, first_pass=None):
+    """--recover_tracking 1: the pairs the first pass lost solved from tracked points, the recovered dictionary and its report beside
+    the first pass's files, which are left as they are.  first_pass: None = the dictionary in save_folder."""
+    from .processing.utils import read_homography_dict
+    from . import tracking
+    if first_pass is None:
+        matrices, resize_info = read_homography_dict(os.path.join(save_folder, "dict_with_homography_matrix.json"))
+        first_pass = dict(matrices, resize_info=resize_info)
+    recovered, report = tracking.recover_homography_dict(
+        open_capture(args.path_to_video)[0], first_pass, levels=args.track_levels, radius=args.track_radius, cell=args.track_cell,
+        fb_max=args.track_fb if args.track_fb >= 0 else None,
+        min_eig=tracking.MIN_EIG if args.track_min_eig is None else args.track_min_eig, ingest=args.ingest,
+        none_H_processing=_bool(args.none_H_processing))
+    with open(os.path.join(save_folder, "dict_with_homography_matrix_recovered.json"), "w") as json_:
+        json.dump(recovered, json_)
+    with open(os.path.join(save_folder, "tracking_report.json"), "w") as json_:
+        json.dump({str(k): v for k, v in report.items()}, json_)
 
 
 def write_aligned(args, save_folder):

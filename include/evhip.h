@@ -47,6 +47,9 @@
  *   evh_pair_refine[_yuv420]      no counterpart: that matrix improved on the pixels of the pair (direct alignment)
  *   evh_canvas_refine[_yuv420]    no counterpart: a frame aligned against the mosaic its predecessors left on the plane, so that
  *                                 revisited ground pulls the chain of pair matrices back into place
+ *   evh_track_points[_yuv420], evh_track_seeds[_yuv420] no counterpart: the second source of correspondences the reference's
+ *                                 known-issues.md lacks ("H=None": the 4 points can't be found) -- well-conditioned points of a frame
+ *                                 followed into the previous one by pyramidal Lucas-Kanade, as (ax, ay, bx, by) rows
  *   evh_graph_normal              no counterpart: the normal equations of ONE least-squares problem over all superposed matrices, from
  *                                 the match rows of any frame pairs, so that a loop's closing error is spread over the whole chain
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
@@ -1118,6 +1121,89 @@ int evh_canvas_refine(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int w,
 int evh_canvas_refine_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, const uint8_t* d_canvas, int dw, int dh,
                              int64_t canvas_row_stride, const uint8_t* d_count, int64_t count_row_stride, int min_cover,
                              const double* d_M_in, int iters, int clip, double* d_M_out, uint64_t* d_info, double* d_normal);
+
+/* ---- points followed between frames: sparse pyramidal Lucas-Kanade in integers ------------------------------------------------------ */
+/* Where descriptors find nothing to match -- defocus, blur, fog, low contrast: gradients but no corners -- points of the current
+ * frame are followed into the previous one on the pixels.  Frames, npairs, frame_step, w, h, channels and strides are
+ * evh_pair_residual's: pair p has the previous frame p*frame_step and the current frame p*frame_step + 1.  d_pts f32[npairs][pt_cap][2]
+ * holds points (x, y) of the CURRENT frame, d_npts i32[npairs] how many (above pt_cap: pt_cap, negative: 0); d_M f64[npairs,9] (may be
+ * NULL = identity) maps pixels of the current frame to pixels of the previous one and is only the first guess.  The result is a PURE
+ * FUNCTION of the inputs -- integer sums, one rounded double operation at a time in the 2x2 solve, no atomics -- and
+ * tests/track_checks.py restates all of the following in numpy, for equality; it is the definition where this text is unclear.
+ * GRAY: (b*1868 + g*9617 + r*4899 + 8192) >> 14, with one channel the byte.  LEVEL l (l < levels) is level l-1 reduced by 2x2 means,
+ *   (a + b + c + d + 2) >> 2, of size (w_{l-1} >> 1, h_{l-1} >> 1): an odd last column or row is dropped.  A level with a side < 2 does
+ *   not exist, nor do the levels above it.
+ * POSITIONS are integers in 1/32 pixel.  A0 = (rint(32 x), rint(32 y)) in double, halves to even; the point is EVH_TRACK_BAD_POINT
+ *   unless 0 <= A0 <= (32 (w-1), 32 (h-1)) (NaN and +-inf fail).  B0 = evh_warp_fixed_plane's (U, V) for A = d_M[p], inverse_map != 0,
+ *   at (X, Y) = A0 / 32; B0 = A0 without d_M, or when |U| or |V| is not <= EVH_TRACK_GUESS_MAX (a NaN, zero or huge matrix).
+ *   One level down: P_l = (P_{l-1} - 16) >> 1, arithmetic shift (the centre of a 2x2 mean lies at +0.5); one level up: P_{l-1} =
+ *   2 P_l + 16.  A_l always comes from A0; B is taken down to the top level once and then carried up.
+ * SAMPLE S(img, X, Y) = p00 (32-fx)(32-fy) + p01 fx (32-fy) + p10 (32-fx) fy + p11 fx fy with x = X >> 5, fx = X & 31 (rows alike):
+ *   evh_warp_fixed_plane's bilinear sum before its shift.  A tap of weight 0 is not read.  It is defined iff 0 <= X <= 32 (w_l - 1) and
+ *   0 <= Y <= 32 (h_l - 1).
+ * A LEVEL, radius r, n = (2r+1)^2 window offsets (i, j): T(i, j) = S(cur_l, A_l + 32 (i, j)) for |i|, |j| <= r + 1; gx = T(i+1, j) -
+ *   T(i-1, j), gy = T(i, j+1) - T(i, j-1); Gxx, Gxy, Gyy = the sums of gx gx, gx gy, gy gy over the window, exact integers below 2^48,
+ *   converted to double; det = Gxx Gyy - Gxy Gxy.  Then, k = 0, 1, ...: d = S(prev_l, B_l + 32 (i, j)) - T(i, j), err = sum |d|,
+ *   bx = sum d gx, by = sum d gy (exact integers, converted); after `iters` steps the level ends; else dx = (Gyy bx - Gxy by) / det,
+ *   dy = (Gxx by - Gxy bx) / det, step = (rint(-64 dx), rint(-64 dy)), each component clamped to +-32 r (64: the differences are doubled,
+ *   positions are 1/32 pixel); a step (0, 0) ends the level, any other is added to B_l.
+ * FAILURES.  A level fails when the template (|i|, |j| <= r + 1 around A_l) is not defined everywhere, when det is not > 0, or when
+ *   the search window (|i|, |j| <= r around B_l) is not defined at some k.  Above level 0 such a level is skipped: B_l stays what it was
+ *   when the level began.  At level 0 the point is dropped: EVH_TRACK_NO_WINDOW, EVH_TRACK_FLAT or EVH_TRACK_LEFT_FRAME, in this order
+ *   of the checks; EVH_TRACK_FLAT also when lambda = ((Gxx + Gyy) - sqrt((Gxx - Gyy)^2 + 4 Gxy^2)) * 0.5 < (min_eig * n) * 2^22 --
+ *   min_eig is the smaller eigenvalue of the mean structure tensor, in gray levels squared per pixel squared.
+ * d_err: err at the final B of level 0.  max_err >= 0: a point with err > max_err * n * 1024 is dropped (EVH_TRACK_HIGH_ERROR).
+ * FORWARD-BACKWARD (fb_max32 >= 0): the same procedure with the frames exchanged -- the template around the found B in the previous
+ *   frame, the search in the current frame starting at A0, giving A'.  The point is dropped (EVH_TRACK_FB_FAILED) when the backward pass
+ *   fails at level 0 or max(|A'x - A0x|, |A'y - A0y|) > fb_max32.
+ * OUTPUTS.  d_out_rows f32[npairs][row_cap][4]: a kept point's row (A0x/32, A0y/32, Bx/32, By/32) = (ax, ay, bx, by) -- a on the current
+ *   frame, b on the previous one, the layout of evh_batch_static_rows; exact in float32 --, compacted IN INPUT ORDER; rows past the
+ *   count are untouched.  d_out_counts i32[npairs].  d_flags u8[npairs][pt_cap] (may be NULL): the code of every point below the count;
+ *   d_err u32[npairs][pt_cap] (may be NULL): its err, EVH_TRACK_NO_ERR for a point that failed before level 0 was solved.  Entries of points
+ *   at or past the count are untouched.  row_cap >= pt_cap.
+ * Launches: the gray pyramids of every frame of the call (level 0 fused with the ingest, planes converted as evh_yuv420_to_bgr does),
+ * one wave per point with levels, iterations and the backward pass inside the kernel, one workgroup per pair for the compaction;
+ * all on the context's stream, no host synchronisation (the workspace belongs to the context and grows on demand).
+ * Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: NULL frames (a NULL plane), d_pts, d_npts, d_out_rows or
+ * d_out_counts, channels not 1 or 3, frame_step not 1 or 2, w or h < 1, npairs < 0, pt_cap < 1, row_cap < pt_cap, levels outside 1..4,
+ * radius outside 1..10, iters outside 1..64, min_eig negative or not finite, max_err outside -1..255, a frame stride shorter than its
+ * row / frame, an output overlapping another output, the frames, d_pts, d_npts or d_M; EVH_ERR_CAPACITY: w or h > 4096, npairs > 65535,
+ * pt_cap > 65535.  npairs == 0 succeeds and does nothing.                                                                          */
+enum { EVH_TRACK_TRACKED = 0, EVH_TRACK_BAD_POINT, EVH_TRACK_NO_WINDOW, EVH_TRACK_LEFT_FRAME, EVH_TRACK_FLAT, EVH_TRACK_HIGH_ERROR,
+       EVH_TRACK_FB_FAILED, EVH_TRACK_NFLAGS };  /* 7 */
+enum { EVH_TRACK_MAX_LEVELS = 4, EVH_TRACK_MAX_RADIUS = 10, EVH_TRACK_MAX_ITERS = 64, EVH_TRACK_MAX_SIZE = 4096,
+       EVH_TRACK_GUESS_MAX = 1 << 24 };
+#define EVH_TRACK_NO_ERR 0xFFFFFFFFu
+int evh_track_points(evh_ctx* ctx, const uint8_t* d_frames, int npairs, int frame_step /* 1 | 2 */, int w, int h,
+                     int channels /* 1 | 3 */, int64_t row_stride, int64_t frame_stride,
+                     const float* d_pts /* f32[npairs,pt_cap,2] DEVICE */, const int32_t* d_npts /* i32[npairs] DEVICE */, int pt_cap,
+                     const double* d_M /* f64[npairs,9] DEVICE, may be NULL */, int levels /* 1..4 */, int radius /* 1..10 */,
+                     int iters /* 1..64 */, double min_eig, int fb_max32 /* < 0: off */, int max_err /* -1 | 0..255 */,
+                     float* d_out_rows /* f32[npairs,row_cap,4] DEVICE */, int row_cap, int32_t* d_out_counts /* i32[npairs] DEVICE */,
+                     uint8_t* d_flags /* u8[npairs,pt_cap] DEVICE, may be NULL */, uint32_t* d_err /* u32[npairs,pt_cap] DEVICE, may be NULL */);
+int evh_track_points_yuv420(evh_ctx* ctx, const evh_yuv420* src, int npairs, int frame_step, int w, int h, const float* d_pts,
+                            const int32_t* d_npts, int pt_cap, const double* d_M, int levels, int radius, int iters, double min_eig,
+                            int fb_max32, int max_err, float* d_out_rows, int row_cap, int32_t* d_out_counts, uint8_t* d_flags,
+                            uint32_t* d_err);
+
+/* Points worth following on frames where FAST finds none.  Per frame of nframes frames (packed or planes as above), on the gray values
+ * of level 0: gx = g(x+1, y) - g(x-1, y), gy = g(x, y+1) - g(x, y-1); Gxx, Gxy, Gyy summed over the (2 radius + 1)^2 window around a
+ * pixel (exact integers), lambda from them as above.  The rectangle [border, w-1-border] x [border, h-1-border] is tiled from its
+ * top-left corner by cells of cell x cell pixels (partial cells at the right and at the bottom count).  Per cell the pixel of largest
+ * lambda is taken, ties to the smallest (y, x); it is a seed iff lambda >= (min_eig * n) * 4, n = (2 radius + 1)^2 -- min_eig in
+ * evh_track_points's unit.  d_pts f32[nframes][pt_cap][2] receives the seeds (x, y) in cell raster order, d_npts i32[nframes] their
+ * full count, also where it exceeds pt_cap (only pt_cap are written; slots past the seeds are untouched).  A border above
+ * (w - 1) / 2 or (h - 1) / 2, up to INT_MAX, leaves an empty rectangle, which gives 0 seeds.  tests/track_checks.py restates it, for equality.  Two launches (cells, compaction) on the context's stream, no host
+ * synchronisation.  Refused before anything is launched, outputs untouched -- EVH_ERR_INVALID: NULL frames (a NULL plane), d_pts or
+ * d_npts, channels not 1 or 3, w or h < 1, nframes < 0, pt_cap < 1, radius outside 1..3, cell outside 8..64, border < radius + 1,
+ * min_eig negative or not finite, a frame stride shorter than its row / frame (the frame stride when nframes > 1), an output
+ * overlapping the other or the frames; EVH_ERR_CAPACITY: w or h > 4096, nframes > 65535, pt_cap > 65535.  nframes == 0 succeeds and
+ * does nothing.                                                                                                                    */
+int evh_track_seeds(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int w, int h, int channels /* 1 | 3 */, int64_t row_stride,
+                    int64_t frame_stride, int radius /* 1..3 */, int cell /* 8..64 */, int border /* >= radius + 1 */, double min_eig,
+                    float* d_pts /* f32[nframes,pt_cap,2] DEVICE */, int pt_cap, int32_t* d_npts /* i32[nframes] DEVICE */);
+int evh_track_seeds_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, int radius, int cell, int border,
+                           double min_eig, float* d_pts, int pt_cap, int32_t* d_npts);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

@@ -37,6 +37,8 @@ REFINE_INFO = ("status", "evals", "accepted", "covered_in", "ssd_in", "covered_o
 REFINE_NINFO, REFINE_NSUMS, REFINE_MAX_ITERS, REFINE_MAX_SIZE = 8, 45, 64, 4096
 TRACK_FLAGS = ("tracked", "bad_point", "no_window", "left_frame", "flat", "high_error", "fb_failed")   # EVH_TRACK_* in order
 TRACK_TRACKED, TRACK_NO_ERR = 0, 0xFFFFFFFF
+JPEG_444, JPEG_420 = 0, 1   # EVH_JPEG_* (include/evhip.h)
+JPEG_SUBSAMPLINGS = {"444": JPEG_444, "420": JPEG_420}
 GRAPH_NSUMS, GRAPH_BAD_INDEX, GRAPH_BAD_STATUS = 154, 1, 2   # EVH_GRAPH_* (include/evhip.h)
 GRAPH_INFO = ("used", "gated", "behind", "flags")
 
@@ -173,6 +175,10 @@ SIGNATURES = {
     "evh_track_points_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _d, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "evh_track_seeds": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _d, _vp, _i, _vp]),
     "evh_track_seeds_yuv420": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _i, _vp]),
+    # pictures encoded on the device: baseline JPEG files (bound and header are host functions without a context)
+    "evh_jpeg_bound": (_i64, [_i, _i, _i, _i]),
+    "evh_jpeg_header": (_i, [_i, _i, _i, _i, _vp, _vp, _i]),
+    "evh_jpeg_encode": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _i, _i, _vp, _vp, _i64, _i64, _vp]),
     # global alignment: the normal equations over all superposed matrices, from the match rows of any frame pairs
     "evh_graph_normal": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _d, _d, _vp, _vp]),
     # ragged batches of several streams (h_types, then h_segs: an array of StreamSeg)
@@ -237,6 +243,30 @@ def mask_components_work_bytes(dw, dh, nmasks):
     if any(abs(a) > 0x7fffffff for a in args):
         return 0
     return int(load().evh_mask_components_work_bytes(*args))
+
+
+def _jpeg_tables(qtabs):
+    """Both quantisation tables as a contiguous uint16 [2, 64] array (natural order), as the jpeg entries take them."""
+    q = np.ascontiguousarray(np.asarray(qtabs).reshape(2, 64).astype(np.uint16))
+    if not np.array_equal(q, np.asarray(qtabs).reshape(2, 64)):
+        raise ValueError("qtabs holds values a uint16 cannot")
+    return q
+
+
+def jpeg_bound(w, h, channels, subsampling="420"):
+    """The largest file evh_jpeg_encode can write for such a picture (evh_jpeg_bound; host only, -1 for what the entry refuses)."""
+    sub = JPEG_SUBSAMPLINGS[subsampling] if isinstance(subsampling, str) else int(subsampling)
+    return int(load().evh_jpeg_bound(int(w), int(h), int(channels), sub))
+
+
+def jpeg_header(w, h, channels, qtabs, subsampling="420"):
+    """SOI .. SOS of the files evh_jpeg_encode writes, as bytes (evh_jpeg_header; host only)."""
+    sub = JPEG_SUBSAMPLINGS[subsampling] if isinstance(subsampling, str) else int(subsampling)
+    q, out = _jpeg_tables(qtabs), np.zeros(1024, np.uint8)
+    n = load().evh_jpeg_header(int(w), int(h), int(channels), sub, _hp(q), _hp(out), out.size)
+    if n < 0:
+        raise EvhError("evh_jpeg_header refuses these arguments (%d)" % n)
+    return out[:n].tobytes()
 
 
 def build(force=False):
@@ -1158,6 +1188,41 @@ class Context:
             raise ValueError("color is (b, g, r) with bytes")
         self._check(self.lib.evh_draw_matches(self.h, fp, npairs, int(frame_step), w, h, frs, ffs, rows.data_ptr(), rows.shape[1],
                                               counts.data_ptr(), _ptr(status), points, b | g << 8 | r << 16, op, ors, ofs))
+
+    # ---- pictures encoded on the device ----
+    def jpeg_encode(self, pictures, qtabs, subsampling="420", out=None):
+        """Baseline JPEG files of pictures that lie on the device (evh_jpeg_encode, the arithmetic is stated in include/evhip.h)
+        -> a list of bytes, one file per picture.  pictures: uint8 [n,h,w] gray or [n,h,w,3] BGR, rows and pictures may be
+        strided (a view cut out of a larger canvas); qtabs: [2,64] in natural order, each 1..255 (pictures.quant_tables).  The
+        files are written into `out` (uint8 [n, cap] on the device; without it a quarter of the raw size per picture); if a
+        picture reports more than cap the call is repeated once with the largest length reported.  Synchronises: the lengths
+        and the files come to the host."""
+        import torch
+        sub = JPEG_SUBSAMPLINGS[subsampling] if isinstance(subsampling, str) else int(subsampling)
+        cn = 1 if pictures.dim() == 3 else 3
+        pp, w, h, prs, pps = self._image_rows(pictures, cn, 1, "pictures")
+        n = pictures.shape[0]
+        q = _jpeg_tables(qtabs)
+        if out is not None:
+            self._dev_tensor(out, torch.uint8, out.numel(), "out must be a contiguous CUDA uint8 tensor [n, cap]")
+            if out.dim() != 2 or out.shape[0] < n:
+                raise ValueError("out must be [n, cap]")
+        else:
+            out = torch.empty((max(n, 1), max(1024, w * h * cn // 4)), dtype=torch.uint8, device=pictures.device)
+        if n == 0:
+            return []
+        sizes = torch.zeros(max(n, 1), dtype=torch.int64, device=pictures.device)
+        for _ in range(2):
+            self._enter()
+            self._check(self.lib.evh_jpeg_encode(self.h, pp, n, w, h, prs, pps, cn, sub, _hp(q), out.data_ptr(), out.shape[1],
+                                                 out.shape[1], sizes.data_ptr()))
+            self.order_torch_after()
+            lengths = sizes[:n].cpu().numpy()
+            if n == 0 or int(lengths.max()) <= out.shape[1]:
+                break
+            out = torch.empty((n, int(lengths.max())), dtype=torch.uint8, device=pictures.device)
+        host = out[:n, :int(lengths.max())].cpu().numpy()       # the files and no more: the slots are far longer than they are
+        return [host[p, :int(lengths[p])].tobytes() for p in range(n)]
 
     # ---- the score of a homography ----
     def _pair_residual(self, planes, frames, mats, stats, out, threshold, kind, frame_step, size):

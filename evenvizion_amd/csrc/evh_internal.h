@@ -162,6 +162,7 @@ struct evh_ctx {
   uint8_t* d_yuv_bgr = nullptr; size_t yuv_bgr_bytes = 0;   // BGR frames of evh_stream_homography_batch_types_yuv420's chunk
   char* d_refine_ws = nullptr; size_t refine_ws_bytes = 0;  // evh_pair_refine: per-pair state, then the workgroups' partial sums
   char* d_track_ws = nullptr; size_t track_ws_bytes = 0;    // evh_track_points: the gray pyramids, then a record per point; evh_track_seeds: a word per cell
+  char* d_jpeg_ws = nullptr; size_t jpeg_ws_bytes = 0;      // evh_jpeg_encode: tables and head, coefficients, code lengths, the rows' bit buffers
   bool trail_tab_ready = false;   // evh_trail_fixed_plane's colour tables are on the device (uploaded by its first launch)
   int* d_fast_redo = nullptr;     // [1 + max_frames*8] redo work list (count first)
   // key-point order of the reference (EVH_ORDER_OPENCV): work arrays of k_select_cv

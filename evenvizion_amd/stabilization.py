@@ -250,6 +250,19 @@ def stabilized_frames(capture, superposition_homography_dict, resize_info, mode=
         yield frame_no, canvas.cpu().numpy()
 
 
+def stabilized_jpegs(capture, superposition_homography_dict, resize_info, mode="history", placement="warp", scale=1.0,
+                     chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS, trail=False, border="auto", quality=90,
+                     subsampling="420"):
+    """Generator of (frame_no, bytes): the pictures of stabilized_frames -- same arguments, same canvases -- as baseline JPEG
+    files (quality 1..100, subsampling "420" or "444"), encoded on the device where the chunk's canvases lie
+    (evh_jpeg_encode, include/evhip.h): no canvas is downloaded, only the files.  A file is a pure function of its canvas:
+    tests/jpeg_checks.py restates it."""
+    from .pictures import check_format, jpegs_of_chunks
+    check_format(quality, subsampling)
+    return jpegs_of_chunks(_chunks(capture, superposition_homography_dict, resize_info, mode, placement, scale, chunk_frames, ingest,
+                                   max_pixels, trail, border), mode == "mosaic", quality, subsampling)
+
+
 def comparison_size(w0, h0, dw, dh, height=300):
     """((width of the original, width of the fixed plane), height) of the two halves of a comparison picture:
     imutils.resize(image, height=height) gives (int(w * (height / float(h))), height)."""

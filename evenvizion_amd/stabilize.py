@@ -35,6 +35,14 @@ evenvizion_amd.stabilization:
                      away (seam); with --exposure 1 the video is first read once more for the overlap sums, one gain per frame
                      and channel is solved from them (exposure_gains.json) and applied.  On the plane or with --surface.
 
+    --format jpeg | mjpeg
+                     the pictures leave the device compressed (evenvizion_amd.pictures, evh_jpeg_encode): jpeg writes NNNNNN.jpg in
+                     place of NNNNNN.ppm, mjpeg one stabilized.avi (Motion-JPEG, --fps) a player opens; --quality 1..100,
+                     --subsampling 420 | 444.  For the canvases per frame, --trail 1 and --surface; the one picture of --mode
+                     mosaic, of --blend (mosaic_blend.jpg) and of --plate (plate.jpg) is encoded too -- a single picture is
+                     written as .jpg under either format, --mode mosaic excepted, whose stabilized.avi has one frame.  Not with
+                     --comparison.  The default, ppm, writes every file as before.
+
 What is still missing from the reference's picture is its text ("Original", "EvenVizion").  The dimming is the arithmetic
 include/evhip.h states for evh_trail_fixed_plane, not cv2.cvtColor compared byte for byte.
 """
@@ -91,7 +99,36 @@ def parser():
     ap.add_argument("--feather", type=float, default=32.0, help="blend: pixels over which a frame's weight rises from its border")
     ap.add_argument("--exposure", type=int, choices=(0, 1), default=0,
                     help="blend: 1 solves one gain per frame and channel from the overlaps and writes exposure_gains.json")
+    ap.add_argument("--format", choices=("ppm", "jpeg", "mjpeg"), default="ppm",
+                    help="ppm: binary P6 per picture; jpeg: NNNNNN.jpg encoded on the device; mjpeg: stabilized.avi of those files")
+    ap.add_argument("--quality", type=int, default=90, help="jpeg, mjpeg: 1..100, the usual scaling of the Annex K tables")
+    ap.add_argument("--subsampling", choices=("420", "444"), default="420", help="jpeg, mjpeg: chroma sub-sampling")
+    ap.add_argument("--fps", type=float, default=25.0, help="mjpeg: frames per second written into the AVI headers")
     return ap
+
+
+def write_pictures(save_folder, args, files):
+    """--format jpeg | mjpeg: the (frame_no, bytes) of a generator of files as NNNNNN.jpg, or as the frames of stabilized.avi."""
+    from .pictures import MjpegAviWriter, write_jpeg
+    writer = None
+    for frame_no, data in files:
+        if args.format == "jpeg":
+            write_jpeg(os.path.join(save_folder, "%06d.jpg" % frame_no), data)
+            continue
+        if writer is None:
+            h, w = jpeg_size(data)
+            writer = MjpegAviWriter(os.path.join(save_folder, "stabilized.avi"), w, h, args.fps)
+        writer.write(data)
+    if writer is not None:
+        writer.close()
+
+
+def jpeg_size(data):
+    """(h, w) of a JPEG file, from its SOF0 segment (the segments are walked: a table may hold the marker's two bytes)."""
+    at = 2
+    while data[at + 1] != 0xC0:
+        at += 2 + (data[at + 2] << 8 | data[at + 3])
+    return data[at + 5] << 8 | data[at + 6], data[at + 7] << 8 | data[at + 8]
 
 
 def main(argv=None):
@@ -128,6 +165,13 @@ def main(argv=None):
         ap.error("--feather lies in 0..2047 pixels")
     if args.blend != "bands" and args.bands is not None:
         ap.error("--bands needs --blend bands")
+    if args.format == "ppm" and (args.quality != 90 or args.subsampling != "420" or args.fps != 25.0):
+        ap.error("--quality, --subsampling and --fps need --format jpeg or mjpeg")
+    if args.format != "ppm" and args.comparison:
+        ap.error("--comparison writes PNG: not with --format jpeg or mjpeg")
+    if not 1 <= args.quality <= 100 or not args.fps > 0:
+        ap.error("--quality lies in 1..100, --fps is positive")
+    coded = dict(quality=args.quality, subsampling=args.subsampling)
     bands = 5 if args.bands is None else args.bands
     if not 0 <= bands <= 8:
         ap.error("--bands lies in 0..8")
@@ -159,7 +203,11 @@ def main(argv=None):
             cap, _, _ = open_capture(args.path_to_video)          # the second pass starts from the first frame again
         picture = blended_mosaic(cap, sup, resize_info, blend=args.blend, feather_px=args.feather, gains=gains, placement=placement,
                                  scale=args.scale, surface=args.surface, focal=args.focal, bands=bands)
-        write_ppm(os.path.join(save_folder, "mosaic_blend.ppm"), picture)
+        if args.format == "ppm":
+            write_ppm(os.path.join(save_folder, "mosaic_blend.ppm"), picture)
+        else:
+            from .pictures import encode_jpeg, write_jpeg
+            write_jpeg(os.path.join(save_folder, "mosaic_blend.jpg"), encode_jpeg(picture, **coded)[0])
         return save_folder
     if args.surface:
         import json
@@ -167,6 +215,11 @@ def main(argv=None):
         model = surface_model(sup, resize_info, surface=args.surface, focal=args.focal, scale=args.scale)
         with open(os.path.join(save_folder, "surface_report.json"), "w") as f:
             json.dump(surface_report(model), f, indent=1)
+        if args.format != "ppm":
+            from .surface import surface_jpegs
+            write_pictures(save_folder, args, surface_jpegs(cap, sup, resize_info, surface=args.surface, focal=model.focal,
+                                                            mode=args.mode, scale=args.scale, **coded))
+            return save_folder
         for frame_no, picture in surface_frames(cap, sup, resize_info, surface=args.surface, focal=model.focal, mode=args.mode,
                                                 scale=args.scale):
             write_ppm(os.path.join(save_folder, "%06d.ppm" % frame_no), picture)
@@ -176,7 +229,11 @@ def main(argv=None):
         from .stabilization import background_plate
         got = background_plate(cap, sup, resize_info, placement=args.placement, scale=args.scale, max_frames=args.plate_frames,
                                min_cover=args.plate_min_cover, masks=bool(args.plate_masks), threshold=args.plate_threshold)
-        write_ppm(os.path.join(save_folder, "plate.ppm"), got.plate)
+        if args.format == "ppm":
+            write_ppm(os.path.join(save_folder, "plate.ppm"), got.plate)
+        else:
+            from .pictures import encode_jpeg, write_jpeg
+            write_jpeg(os.path.join(save_folder, "plate.jpg"), encode_jpeg(got.plate, **coded)[0])
         write_png(os.path.join(save_folder, "plate_count.png"), got.count, gray=True)
         for k, frame_no in enumerate(got.frame_nos if args.plate_masks else ()):
             write_png(os.path.join(save_folder, "mask_%06d.png" % frame_no), got.masks[k], gray=True)
@@ -187,6 +244,11 @@ def main(argv=None):
         from .matching_pictures import write_png
         for frame_no, picture in comparison_frames(cap, sup, resize_info, placement=args.placement, scale=args.scale):
             write_png(os.path.join(save_folder, "%06d.png" % frame_no), picture)
+        return save_folder
+    if args.format != "ppm":
+        from .stabilization import stabilized_jpegs
+        write_pictures(save_folder, args, stabilized_jpegs(cap, sup, resize_info, mode=args.mode, placement=args.placement,
+                                                           scale=args.scale, trail=bool(args.trail), **coded))
         return save_folder
     for frame_no, picture in stabilized_frames(cap, sup, resize_info, mode=args.mode, placement=args.placement,
                                                scale=args.scale, trail=bool(args.trail)):

@@ -330,8 +330,21 @@ def surface_frames(capture, superposition_homography_dict, resize_info, surface=
                            max_pixels, none_processing)
 
 
-def _surface_frames(capture, superposition_homography_dict, resize_info, surface, focal, mode, scale, chunk_frames, ingest,
+def surface_jpegs(capture, superposition_homography_dict, resize_info, surface="cylinder", focal=None, mode="history", scale=1.0,
+                  chunk_frames=32, ingest="auto", max_pixels=MAX_PIXELS, none_processing=True, quality=90, subsampling="420"):
+    """Generator of (frame_no, bytes): the pictures of surface_frames -- same arguments, same canvases -- as baseline JPEG files
+    (quality 1..100, subsampling "420" or "444") encoded on the device where the chunk's canvases lie (evh_jpeg_encode): no
+    canvas is downloaded, only the files."""
+    from .pictures import check_format, jpegs_of_chunks
+    _check_surface_arguments(surface, focal, mode, scale, ingest)
+    check_format(quality, subsampling)
+    return jpegs_of_chunks(_surface_chunks(capture, superposition_homography_dict, resize_info, surface, focal, mode, scale,
+                                           chunk_frames, ingest, max_pixels, none_processing), mode == "mosaic", quality, subsampling)
+
+
+def _surface_chunks(capture, superposition_homography_dict, resize_info, surface, focal, mode, scale, chunk_frames, ingest,
                     max_pixels, none_processing):
+    """The chunks behind surface_frames and surface_jpegs: _canvas_chunks with the surface's geometry and entry."""
     import torch
     model = surface_model(superposition_homography_dict, resize_info, surface, focal, scale, max_pixels, none_processing)
     ox, oy, dw, dh, scale_px = model.bounds
@@ -356,8 +369,14 @@ def _surface_frames(capture, superposition_homography_dict, resize_info, surface
                 canvas.copy_(out[n - 1])
         return dw, dh, None, paint
 
+    return _canvas_chunks(capture, mode, chunk_frames, ingest, setup)
+
+
+def _surface_frames(capture, superposition_homography_dict, resize_info, surface, focal, mode, scale, chunk_frames, ingest,
+                    max_pixels, none_processing):
     frame_no = 0
-    for first, n, pictures, _, canvas in _canvas_chunks(capture, mode, chunk_frames, ingest, setup):
+    for first, n, pictures, _, canvas in _surface_chunks(capture, superposition_homography_dict, resize_info, surface, focal, mode,
+                                                         scale, chunk_frames, ingest, max_pixels, none_processing):
         frame_no = first + n - 1
         if pictures is not None:
             pictures = pictures.cpu().numpy()

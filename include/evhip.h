@@ -52,6 +52,9 @@
  *                                 followed into the previous one by pyramidal Lucas-Kanade, as (ax, ay, bx, by) rows
  *   evh_graph_normal              no counterpart: the normal equations of ONE least-squares problem over all superposed matrices, from
  *                                 the match rows of any frame pairs, so that a loop's closing error is spread over the whole chain
+ *   evh_jpeg_encode, evh_jpeg_header, evh_jpeg_bound   cv2.imwrite of every picture the reference writes: baseline JPEG files of
+ *                                 the canvases, encoded where they lie, so that only compressed bytes leave the device
+ *                                 visualization/stabilization.py:286
  *   evh_pair_homography_batch     the per-pair body of get_homography_dict video_processing.py:67-105
  *                                 (FrameProcessing.concatenate_all_features_types frame_processing.py:73-108
  *                                  + compute_homography utils.py:328-363 + matrix_superposition utils.py:118-145)
@@ -1204,6 +1207,61 @@ int evh_track_seeds(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int w, i
                     float* d_pts /* f32[nframes,pt_cap,2] DEVICE */, int pt_cap, int32_t* d_npts /* i32[nframes] DEVICE */);
 int evh_track_seeds_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int w, int h, int radius, int cell, int border,
                            double min_eig, float* d_pts, int pt_cap, int32_t* d_npts);
+
+/* ---- pictures encoded on the device: baseline JPEG -------------------------------------------------------------------------
+ * evh_jpeg_encode writes, for each of n pictures (gray, or BGR as every canvas here is), a complete baseline JFIF file to
+ * d_out + p * out_stride; only the compressed bytes have to cross the host link.  Every step is stated in integers, so a file is
+ * a PURE FUNCTION of the pixels, the two tables and the layout; tests/jpeg_checks.py restates all of it in numpy, for equality
+ * of the bytes, and is the definition where this text is unclear.
+ * FILE: SOI | APP0 (JFIF 1.01, no units, 1:1, no thumbnail) | DQT table 0 (8-bit, zig-zag order) | with three channels DQT
+ *   table 1 | SOF0 (8 bits, h, w; component ids 1 2 3; Y samples 1x1, with EVH_JPEG_420 2x2; Y uses table 0, Cb Cr table 1) |
+ *   DHT DC 0 | DHT AC 0 | DHT DC 1 | DHT AC 1 -- the four tables of T.81 Annex K.3, always, each a segment of its own | DRI |
+ *   SOS (Y: tables 0/0, Cb Cr: 1/1; 0, 63, 0) | the scan | EOI.  That head is 550 bytes with one channel, 629 with three.
+ * COLOUR (three channels): Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) +
+ *   32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16 (arithmetic shifts; the rows sum to 65536, 0, 0, so
+ *   every value lies in 0..255 unclamped).  One channel: Y is the byte.
+ * GEOMETRY: an MCU is 8 x 8 pixels, with EVH_JPEG_420 16 x 16 (blocks Y0 Y1 / Y2 Y3, then Cb, Cr); otherwise its blocks are Y
+ *   [, Cb, Cr].  A pixel past the right or bottom edge is the last pixel of its row / column.  A 4:2:0 chroma sample is
+ *   (a + b + c + d + 2) >> 2 of the 2 x 2 converted values, taken after that padding.  Every sample s has 128 subtracted.
+ * TRANSFORM: T[u][x] = rint(8192 * c(u) / 2 * cos((2 x + 1) u pi / 16)), c(0) = 1 / sqrt 2, c(u > 0) = 1; the rows are
+ *   u = 0:  2896  2896  2896  2896  2896  2896  2896  2896      u = 4:  2896 -2896 -2896  2896  2896 -2896 -2896  2896
+ *   u = 1:  4017  3406  2276   799  -799 -2276 -3406 -4017      u = 5:  2276 -4017   799  3406 -3406  -799  4017 -2276
+ *   u = 2:  3784  1567 -1567 -3784 -3784 -1567  1567  3784      u = 6:  1567 -3784  3784 -1567 -1567  3784 -3784  1567
+ *   u = 3:  3406  -799 -4017 -2276  2276  4017   799 -3406      u = 7:   799 -2276  3406 -4017  4017 -3406  2276  -799
+ *   Rows first: A[y][u] = (sum_x T[u][x] s[y][x] + 128) >> 8 (five fraction bits stay); then columns:
+ *   F[v][u] = (sum_y T[v][y] A[y][u] + (1 << 17)) >> 18.  Both sums fit 32 bits (|A| <= 11585, second sum below 2^29); F lies within
+ *   1 of the float64 orthonormal DCT-II (measured: tests/test_jpeg_host.py).
+ * QUANTISATION: q = sign(F) * ((|F| + (Q >> 1)) / Q), Q = qtab[0][8 v + u] for Y, qtab[1][8 v + u] for Cb and Cr.
+ * SCAN: baseline Huffman with the Annex K.3 tables; the coefficients of a block in zig-zag order; DC as the difference to the
+ *   previous block of the same component, category = bit length of |d|, a negative d sent as d - 1 in that many bits; AC as
+ *   (run, size) with ZRL (0xF0) for each 16 zeros of a run and EOB (0x00) unless coefficient 63 is non-zero.  The restart interval is
+ *   ONE MCU ROW, always: DRI = ceil(w / mcu_w).  Each interval is padded to a byte with 1-bits, the DC prediction starts at 0
+ *   in each, RSTm with m = row mod 8 stands between intervals (none after the last), and a 0xFF data byte is followed by 0x00.
+ *   An MCU row's bytes are thus a function of its own pixels.
+ * BOUND: a block has at most 20 bits of DC (a 9-bit code, 11 bits) and 63 * 26 of AC (a 16-bit code, 10 bits) = 1658 bits
+ *   (an 8-bit sample cannot reach an AC magnitude of 1024: sum |basis| * 128 <= 1024 is not met with equality by samples in
+ *   -128..127).  A row of B blocks has at most ceil(1658 B / 8) bytes before stuffing, at most twice that after, and 2 of a
+ *   marker: evh_jpeg_bound = head + rows * (2 * ceil(1658 B / 8) + 2) + 2, or -1 for arguments evh_jpeg_encode refuses.
+ * evh_jpeg_header writes the head (SOI..SOS) to `out` and returns its length, or EVH_ERR_INVALID for the arguments
+ * evh_jpeg_encode refuses, a NULL pointer, or cap below that length (nothing is written then).  Both are host functions and need
+ * no context.
+ * evh_jpeg_encode: d_pictures u8, picture p at d_pictures + p * picture_stride, its rows row_stride bytes apart, pixels packed
+ * (B, G, R with three channels); qtab is a HOST array u16[2][64] in natural (row-major) order, every entry in 1..255 (both tables
+ * are checked, also with one channel).  d_out_bytes[p] receives the file's length, ALSO where it exceeds out_cap: then the first
+ * out_cap bytes of the file are written, nothing at or past d_out + p * out_stride + out_cap, and the other pictures are not
+ * affected.  Bytes of a slot past the file's end are untouched.  The context keeps a workspace that grows on demand (128 bytes of
+ * coefficients and 8 of lengths per block, the rows' bit buffers at the bound above); six launches and one clearing of the bit
+ * buffers on the context's stream, no host synchronisation.  Refused before anything is launched, outputs untouched --
+ * EVH_ERR_INVALID: a NULL context, d_pictures, qtab, d_out or d_out_bytes, n < 0, w or h outside 1..65535, channels not 1 or 3,
+ * a subsampling other than the two or EVH_JPEG_420 with one channel, a table entry outside 1..255, row_stride < w * channels,
+ * out_cap < 0, out_stride < out_cap.  n == 0 succeeds and does nothing.                                                      */
+enum { EVH_JPEG_444 = 0, EVH_JPEG_420 = 1 };
+int64_t evh_jpeg_bound(int w, int h, int channels, int subsampling);
+int evh_jpeg_header(int w, int h, int channels, int subsampling, const uint16_t* qtab /* HOST u16[2][64] */, uint8_t* out, int cap);
+int evh_jpeg_encode(evh_ctx* ctx, const uint8_t* d_pictures, int n, int w, int h, int64_t row_stride, int64_t picture_stride,
+                    int channels /* 1 gray | 3 BGR */, int subsampling /* EVH_JPEG_444 | EVH_JPEG_420 */,
+                    const uint16_t* qtab /* HOST u16[2][64], natural order, each 1..255 */, uint8_t* d_out /* DEVICE */,
+                    int64_t out_stride, int64_t out_cap, int64_t* d_out_bytes /* i64[n] DEVICE */);
 
 /* ---- ragged batches of several streams: many videos or cameras in one call ----------------------------------------------- */
 /* One stream's share of a batch: nframes consecutive frames starting at frame first_frame of the batch's one frame buffer.  */

@@ -29,6 +29,18 @@ int need_area(evh_ctx* c, const std::string& W, const char* what, int w, int h) 
   if ((int64_t)w * h > INT_MAX) return evh_fail(c, EVH_ERR_CAPACITY, W + what + " above INT_MAX");
   return EVH_SUCCESS;
 }
+// nframes frames of sw x sh onto a canvas of dw x dh: nothing empty
+int need_frame_and_canvas(evh_ctx* c, const std::string& W, int nframes, int sw, int sh, int dw, int dh) {
+  if (nframes < 0 || sw < 1 || sh < 1 || dw < 1 || dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  return EVH_SUCCESS;
+}
+// ... and nothing too large, for the entries that ask these three in this order (the warps, the blends, the seam labels, the trail)
+int need_canvas_bounds(evh_ctx* c, const std::string& W, int nframes, int sw, int sh, int dw, int dh) {
+  if (int rc = need_below_2_26(c, W, "source", sw, sh)) return rc;
+  if (int rc = need_area(c, W, "dw * dh", dw, dh)) return rc;
+  if (nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  return EVH_SUCCESS;
+}
 // packed frames only; `apart`: the frame stride is used (more than one frame, or pairs of frames)
 int need_source_stride(evh_ctx* c, const std::string& W, const EvhFrames& F, int w, int h, bool apart) {
   const int64_t row = (int64_t)w * F.channels;

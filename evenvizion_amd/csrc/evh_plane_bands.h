@@ -1,11 +1,9 @@
 // evh_plane_bands.h -- multi-band blending of the mosaic and the seam labels it blends under (include/evhip.h states the contract
 // for evh_seam_labels_* and evh_blend_bands_*).  Included by evh_plane.hip inside its unnamed namespace, after the blend entries:
-// it uses their geometry (BlendGeo, warp_map), their checks and the launch plumbing, and adds kernels of its own only -- no
-// existing device function is touched (profiles/bands.txt records the instruction comparison).
+// it uses their geometry (BlendGeo, warp_map), their checks and the launch plumbing.
 //
-// The extended sampler is written out beside warp_sample, as canvas_sample was: it needs the position before the coverage test,
-// and taking warp_sample apart moves instructions in the existing kernels.  The position is formed from the same operands in the
-// same order, one IEEE operation at a time, so a covered position gives warp_sample's integers.
+// Level 0 continues a frame past its border, so it takes the sampler of evh_plane_sample.h by its pieces: the position before the
+// coverage test, clamped here, then the taps.  A covered position gives warp_sample's integers.
 //
 // Per group of frames that the workspace holds:   k_bands_level0     G^0 = s * g and W^0 = 65536 [label == frame], frames on grid.z
 //                                                 k_bands_reduce     G^{l+1}, W^{l+1} from G^l, W^l, one launch per level for the group
@@ -31,23 +29,16 @@ BandsGeo bands_geo(int dw, int dh, int levels) {
   return P;
 }
 
-// the position of a canvas pixel in frame k, in 1/32 pixels before any test: the header's tx, ty, tw
-struct BandsPos { double U, V, tw; };
+// the position of a canvas pixel in frame k, in 1/32 pixels before any test: the plane's through its map, a ray's from the
+// header's tx, ty, tw, whose third term is a product
 template <bool RAY>
-__device__ __forceinline__ BandsPos bands_position(const BlendGeo& G, int k, double X, double Y, double rc) {
-  double tx, ty, tw;
+__device__ __forceinline__ SamplePos bands_position(const BlendGeo& G, int k, double X, double Y, double rc) {
   if constexpr (RAY) {
     const double* A = G.M + 9 * (int64_t)k;
-    tx = (A[0] * X + A[1] * Y) + A[2] * rc;
-    ty = (A[3] * X + A[4] * Y) + A[5] * rc;
-    tw = (A[6] * X + A[7] * Y) + A[8] * rc;
+    return sample_position(MapRows{(A[0] * X + A[1] * Y) + A[2] * rc, (A[3] * X + A[4] * Y) + A[5] * rc, (A[6] * X + A[7] * Y) + A[8] * rc});
   } else {
-    const WarpMap A = warp_map(G.M + 9 * (int64_t)k, G.inverse_map);
-    tx = (A.a[0] * X + A.a[1] * Y) + A.a[2];
-    ty = (A.a[3] * X + A.a[4] * Y) + A.a[5];
-    tw = (A.a[6] * X + A.a[7] * Y) + A.a[8];
+    return sample_position(warp_map(G.M + 9 * (int64_t)k, G.inverse_map), X, Y);
   }
-  return {__builtin_rint(tx / tw * 32.0), __builtin_rint(ty / tw * 32.0), tw};
 }
 // canvas pixel (x, y) as the position takes it: the plane point, or the ray (a, b, c)
 template <bool RAY>
@@ -71,13 +62,11 @@ __global__ __launch_bounds__(256) void k_seam_labels(int nframes, int sw, int sh
   bands_pixel<RAY>(G, x, y, X, Y, rc);
   uint32_t b = state_in ? best[t] : 0u;
   uint32_t lab = state_in ? label[t] : 65535u;
-  const double umax = (double)(32 * (sw - 1)), vmax = (double)(32 * (sh - 1));
   for (int k = 0; k < nframes; k++) {
-    const BandsPos P = bands_position<RAY>(G, k, X, Y, rc);
+    const SamplePos P = bands_position<RAY>(G, k, X, Y, rc);
     if (RAY && !(P.tw > 0.0)) continue;
-    if (!(P.U >= 0.0 && P.U <= umax && P.V >= 0.0 && P.V <= vmax)) continue;
-    const int u = (int)P.U, v = (int)P.V;
-    const uint32_t w = (uint32_t)min(min(min(u, 32 * (sw - 1) - u), min(v, 32 * (sh - 1) - v)), feather) + 1u;
+    if (!sample_covered(P, sw, sh)) continue;
+    const uint32_t w = (uint32_t)min(edge_distance(P, sw, sh), feather) + 1u;
     if (w > b) { b = w; lab = (uint32_t)(first_label + k); }
   }
   best[t] = b;
@@ -85,8 +74,7 @@ __global__ __launch_bounds__(256) void k_seam_labels(int nframes, int sw, int sh
 }
 
 // Level 0 of frame f0 + blockIdx.z: the frame continued past its border by its edge pixels, times its gain, at every canvas pixel,
-// and the frame's mask.  A clamped position has 0 <= sx <= sw - 1, and sx + 1 is read only with fx != 0, i.e. sx <= sw - 2 (rows
-// alike): no tap leaves the frame.
+// and the frame's mask.  A clamped position lies in 0 .. 32 (sw - 1), 0 .. 32 (sh - 1): no tap leaves the frame (sample_taps).
 template <int CN, class SRC, bool RAY>
 __global__ __launch_bounds__(256) void k_bands_level0(SRC src, int f0, int sw, int sh, BlendGeo G, const uint16_t* __restrict__ gain,
                                                       const uint16_t* __restrict__ label, int first_label, uint32_t* __restrict__ ws,
@@ -97,25 +85,12 @@ __global__ __launch_bounds__(256) void k_bands_level0(SRC src, int f0, int sw, i
   const int y = (int)(t / (unsigned)dw), x = (int)t - y * dw;
   double X, Y, rc;
   bands_pixel<RAY>(G, x, y, X, Y, rc);
-  const BandsPos P = bands_position<RAY>(G, k, X, Y, rc);
+  const SamplePos P = bands_position<RAY>(G, k, X, Y, rc);
   int s[3] = {0, 0, 0};
   if (P.U == P.U && P.V == P.V && (!RAY || P.tw > 0.0)) {
     const double umax = (double)(32 * (sw - 1)), vmax = (double)(32 * (sh - 1));
     const double Uc = P.U < 0.0 ? 0.0 : (P.U > umax ? umax : P.U), Vc = P.V < 0.0 ? 0.0 : (P.V > vmax ? vmax : P.V);
-    const int u = (int)Uc, w = (int)Vc;
-    const int sx = u >> 5, fx = u & 31, sy = w >> 5, fy = w & 31;
-    int p00[3] = {0, 0, 0}, p01[3] = {0, 0, 0}, p10[3] = {0, 0, 0}, p11[3] = {0, 0, 0};
-    const typename SRC::Row r0 = src.row(k, sy);
-    r0.px(sx, p00);
-    if (fx) r0.px(sx + 1, p01);
-    if (fy) {
-      const typename SRC::Row r1 = src.row(k, sy + 1);
-      r1.px(sx, p10);
-      if (fx) r1.px(sx + 1, p11);
-    }
-    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
-#pragma unroll
-    for (int c = 0; c < CN; c++) s[c] = (p00[c] * w00 + p01[c] * w01 + p10[c] * w10 + p11[c] * w11 + 512) >> 10;
+    sample_taps(src, k, (int)Uc, (int)Vc, s);
   }
   uint32_t* o = ws + (int64_t)blockIdx.z * frame_elems;
 #pragma unroll
@@ -287,11 +262,9 @@ int check(evh_ctx* c, const LabelArgs& A) {
   if (!A.M || (A.ray && (!A.col || !A.row)) || !A.best || !A.label) return evh_fail(c, EVH_ERR_INVALID, W + "NULL argument");
   if (((uintptr_t)A.best & 3) || ((uintptr_t)A.label & 1))
     return evh_fail(c, EVH_ERR_INVALID, W + "d_best must be 4-byte and d_label 2-byte aligned");
-  if (A.nframes < 0 || A.sw < 1 || A.sh < 1 || A.dw < 1 || A.dh < 1) return evh_fail(c, EVH_ERR_INVALID, W + "empty frame or canvas");
+  if (int rc = need_frame_and_canvas(c, W, A.nframes, A.sw, A.sh, A.dw, A.dh)) return rc;
   if (A.feather < 0 || A.feather > 65535) return evh_fail(c, EVH_ERR_INVALID, W + "feather must lie in 0..65535");
-  if (int rc = need_below_2_26(c, W, "source", A.sw, A.sh)) return rc;
-  if (int rc = need_area(c, W, "dw * dh", A.dw, A.dh)) return rc;
-  if (A.nframes > 65535) return evh_fail(c, EVH_ERR_CAPACITY, W + "at most 65535 frames per call");
+  if (int rc = need_canvas_bounds(c, W, A.nframes, A.sw, A.sh, A.dw, A.dh)) return rc;
   if (int rc = need_labels(c, W, A.first_label, A.nframes)) return rc;
   const int64_t npix = (int64_t)A.dw * A.dh;
   const Span outs[2] = {{A.best, npix * 4, "d_best"}, {A.label, npix * 2, "d_label"}};

@@ -2,6 +2,9 @@
 // Replaces cv2.DescriptorMatcher_create("BruteForce").knnMatch(q, t, 2) (matching.py:102-108) and the glue
 // lowes_ratio_test / filter_corresponding_points (matching.py:166-239) / remove_double_matching (utils.py:41-68).
 // Distances are exact integers: D = |q|^2 + |t|^2 - 2 q.t with v_dot4_u32_u8 on LDS-staged train tiles.
+// Written once and shared: dup_scan_tile (remove_double_matching's search: k_filter<false>, k_filter_dup, k_merge_dup),
+// emit_kept (the kept survivors in order: k_filter<false>, k_filter_out), block_ordered_slot (every ordered compaction),
+// KF_TOP2_INSERT (k_knn2_f32's two insertions) and launched (the launchers' tail).
 #include "evh_internal.h"
 #include "evh_match.h"
 #include <cfloat>
@@ -308,6 +311,13 @@ __global__ __launch_bounds__(256) void k_knn2_f32(EvhKnnF32Args A) {
   for (int k = 0; k < R4; k++) { const float4 v = Q[k]; q[2 * k] = v2f{v.x, v.y}; q[2 * k + 1] = v2f{v.z, v.w}; }
   float b0 = FLT_MAX, b1 = FLT_MAX;
   int i0 = -1, i1 = -1;
+  // the strict insertion of (ds_, j_), known to lie before the second best: equal distances keep the earlier row.  A macro
+  // like the tile loads below: as a function or a lambda taking the four by reference the compiler kept i0 / i1 in scratch
+#define KF_TOP2_INSERT(ds_, j_)                                 \
+  {                                                             \
+    if (b0 > (ds_)) { b1 = b0; i1 = i0; b0 = (ds_); i0 = (j_); } \
+    else { b1 = (ds_); i1 = (j_); }                             \
+  }
   const int per = (nt + 3) >> 2, j0 = wave * per, j1 = min(nt, j0 + per);
   const int ntile = j1 > j0 ? (j1 - j0 + KF_TILE - 1) / KF_TILE : 0;
   const float4* T4 = reinterpret_cast<const float4*>(Tb);
@@ -356,10 +366,7 @@ __global__ __launch_bounds__(256) void k_knn2_f32(EvhKnnF32Args A) {
       const float u0 = d0a.x + d1a.x, u1 = d0a.y + d1a.y, u2 = d0b.x + d1b.x, u3 = d0b.y + d1b.y;
       const float ds = sqrtf(u0 + u1 + u2 + u3);
       const int j = jb + r;
-      if (ds < b1) {
-        if (b0 > ds) { b1 = b0; i1 = i0; b0 = ds; i0 = j; }
-        else { b1 = ds; i1 = j; }
-      }
+      if (ds < b1) KF_TOP2_INSERT(ds, j)
     }
   }
 #undef KF_LOAD_TILE
@@ -374,11 +381,9 @@ __global__ __launch_bounds__(256) void k_knn2_f32(EvhKnnF32Args A) {
       for (int e = 0; e < 2; e++) {
         const float ds = s_b[w][e][lane];
         const int j = s_i[w][e][lane];
-        if (j >= 0 && ds < b1) {
-          if (b0 > ds) { b1 = b0; i1 = i0; b0 = ds; i0 = j; }
-          else { b1 = ds; i1 = j; }
-        }
+        if (j >= 0 && ds < b1) KF_TOP2_INSERT(ds, j)
       }
+#undef KF_TOP2_INSERT
     if (act) {
       oidx[2 * qi] = i0; oidx[2 * qi + 1] = i1;
       odist[2 * qi] = b0; odist[2 * qi + 1] = b1;
@@ -400,6 +405,43 @@ __device__ __forceinline__ int block_ordered_slot(bool flag, int* wave_tot /*[4]
   int slot = base + off + in_wave;
   base += tot;
   return slot;
+}
+
+// remove_double_matching's search for row i against the rows t0 .. t0 + tn - 1, whose keys (or the half of them worth
+// staging) lie in the LDS tile: clears `first` if an equal row lies before i and raises `last` to the last equal row.
+// same(staged, g) says whether row g, staged as `staged`, has row i's key.  Eight rows are read before any is compared.
+template <class K, class Same>
+__device__ __forceinline__ void dup_scan_tile(const K* tile, int t0, int tn, int i, const Same& same, int& first, int& last) {
+  int j = 0;
+  for (; j + 8 <= tn; j += 8) {
+    K b[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) b[u] = tile[j + u];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 8; u++)
+      if (same(b[u], t0 + j + u)) { if (t0 + j + u < i) first = 0; last = max(last, t0 + j + u); }
+  }
+  for (; j < tn; j++)
+    if (same(tile[j], t0 + j)) { if (t0 + j < i) first = 0; last = max(last, t0 + j); }
+}
+
+// the kept ones of a pair's m survivors in order -> its matched rows (a of mq[i], b of mt[lastj[i]]), then count and status
+__device__ __forceinline__ void emit_kept(const EvhFilterArgs& A, int p, int m, const int* mq, const int* mt, const int* keep,
+                                          const int* lastj, const float* xyq, const float* xyt, int* wave_tot) {
+  float* out = A.pts + (int64_t)p * A.pts_stride * 4;
+  int u = 0;
+  for (int c0 = 0; c0 < m; c0 += 256) {
+    int i = c0 + threadIdx.x;
+    bool f = i < m && keep[i];
+    int slot = block_ordered_slot(f, wave_tot, u);
+    if (f) {
+      int tq = mq[i], tt = mt[lastj[i]];
+      out[4 * slot] = xyq[2 * tq]; out[4 * slot + 1] = xyq[2 * tq + 1];
+      out[4 * slot + 2] = xyt[2 * tt]; out[4 * slot + 3] = xyt[2 * tt + 1];
+    }
+  }
+  if (threadIdx.x == 0) { A.npts[p] = u; A.status[p] = EVH_PAIR_OK; }
 }
 
 // ratio test + one-to-one filter + duplicate-coordinate filter; one workgroup per pair.
@@ -426,7 +468,6 @@ __global__ __launch_bounds__(256) void k_filter(EvhFilterArgs A) {
   const uint32_t* d2 = A.d2 + (int64_t)p * A.knn_stride * 2;
   const float* xyq = A.xy_q + (int64_t)qs * A.xy_slot_floats;
   const float* xyt = A.xy_t + (int64_t)ts * A.xy_slot_floats;
-  float* out = A.pts + (int64_t)p * A.pts_stride * 4;
   if constexpr (GLOBAL) { if (tid == 0) claims[5 * A.kcap + 1] = 0; }     // hdr[1]: no second stage unless the survivors get that far
   if ((A.flags_arr && (A.flags_arr[qs] | A.flags_arr[ts])) != 0) {
     if (tid == 0) { A.npts[p] = 0; A.status[p] = EVH_PAIR_CAPACITY; }
@@ -479,33 +520,11 @@ __global__ __launch_bounds__(256) void k_filter(EvhFilterArgs A) {
   for (int i = tid; i < m; i += 256) {
     const float ax = sx[i], ay = xyq[2 * mq[i] + 1];
     int first = 1, last = i;
-    int j = 0;
-    for (; j + 8 <= m; j += 8) {
-      float bx[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) bx[u] = sx[j + u];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (bx[u] == ax && xyq[2 * mq[j + u] + 1] == ay) { if (j + u < i) first = 0; if (j + u > last) last = j + u; }
-    }
-    for (; j < m; j++)
-      if (sx[j] == ax && xyq[2 * mq[j] + 1] == ay) { if (j < i) first = 0; if (j > last) last = j; }
+    dup_scan_tile(sx, 0, m, i, [&](float bx, int g) { return bx == ax && xyq[2 * mq[g] + 1] == ay; }, first, last);
     keep[i] = first; lastj[i] = last;
   }
   __syncthreads();
-  int u = 0;
-  for (int c0 = 0; c0 < m; c0 += 256) {
-    int i = c0 + tid;
-    bool f = i < m && keep[i];
-    int slot = block_ordered_slot(f, wave_tot, u);
-    if (f) {
-      int tq = mq[i], tt = mt[lastj[i]];
-      out[4 * slot] = xyq[2 * tq]; out[4 * slot + 1] = xyq[2 * tq + 1];
-      out[4 * slot + 2] = xyt[2 * tt]; out[4 * slot + 3] = xyt[2 * tt + 1];
-    }
-  }
-  if (tid == 0) { A.npts[p] = u; A.status[p] = EVH_PAIR_OK; }
+  emit_kept(A, p, m, mq, mt, keep, lastj, xyq, xyt, wave_tot);
 }
 
 
@@ -559,20 +578,7 @@ __global__ __launch_bounds__(256) void k_filter_dup(EvhFilterArgs A) {
     __syncthreads();
     for (int k = tid; k < tn; k += 256) s_x[k] = xyq[2 * mq[t0 + k]];
     __syncthreads();
-    if (act) {
-      int j = 0;
-      for (; j + 8 <= tn; j += 8) {
-        float bx[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) bx[u] = s_x[j + u];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 8; u++)
-          if (bx[u] == ax && xyq[2 * mq[t0 + j + u] + 1] == ay) { if (t0 + j + u < i) first = 0; if (t0 + j + u > last) last = t0 + j + u; }
-      }
-      for (; j < tn; j++)
-        if (s_x[j] == ax && xyq[2 * mq[t0 + j] + 1] == ay) { if (t0 + j < i) first = 0; if (t0 + j > last) last = t0 + j; }
-    }
+    if (act) dup_scan_tile(s_x, t0, tn, i, [&](float bx, int g) { return bx == ax && xyq[2 * mq[g] + 1] == ay; }, first, last);
   }
   if (act) { keep[i] = first; lastj[i] = last; }
 }
@@ -580,7 +586,7 @@ __global__ __launch_bounds__(256) void k_filter_dup(EvhFilterArgs A) {
 // third stage: the kept survivors in order -> the matched rows of the pair
 __global__ __launch_bounds__(256) void k_filter_out(EvhFilterArgs A) {
   __shared__ int wave_tot[4];
-  const int p = blockIdx.x, tid = threadIdx.x;
+  const int p = blockIdx.x;
   const int* w = A.work + (int64_t)p * (5 * A.kcap + 2);
   const int* hdr = w + 5 * A.kcap;
   if (!hdr[1]) return;                               // the first stage has already written the pair's status
@@ -589,19 +595,7 @@ __global__ __launch_bounds__(256) void k_filter_out(EvhFilterArgs A) {
   const int qs = A.q_slot0 + p * A.q_slot_step, ts = A.t_slot0 + p * A.t_slot_step;
   const float* xyq = A.xy_q + (int64_t)qs * A.xy_slot_floats;
   const float* xyt = A.xy_t + (int64_t)ts * A.xy_slot_floats;
-  float* out = A.pts + (int64_t)p * A.pts_stride * 4;
-  int u = 0;
-  for (int c0 = 0; c0 < m; c0 += 256) {
-    int i = c0 + tid;
-    bool f = i < m && keep[i];
-    int slot = block_ordered_slot(f, wave_tot, u);
-    if (f) {
-      int tq = mq[i], tt = mt[lastj[i]];
-      out[4 * slot] = xyq[2 * tq]; out[4 * slot + 1] = xyq[2 * tq + 1];
-      out[4 * slot + 2] = xyt[2 * tt]; out[4 * slot + 3] = xyt[2 * tt + 1];
-    }
-  }
-  if (tid == 0) { A.npts[p] = u; A.status[p] = EVH_PAIR_OK; }
+  emit_kept(A, p, m, mq, mt, keep, lastj, xyq, xyt, wave_tot);
 }
 
 // frame_processing.py:102-104: remove_double_matching over the concatenated rows of all feature types (utils.py:60-68):
@@ -619,31 +613,16 @@ __global__ __launch_bounds__(256) void k_merge_dup(EvhMergeArgs A) {
   int* W = A.work + (int64_t)p * A.acc_stride * 2;
   const int i = blockIdx.x * 256 + tid;
   const bool act = i < m;
-  bool first = true; int last = i;
+  int first = 1, last = i;
   const float ax = act ? R[i].x : 0.f, ay = act ? R[i].y : 0.f;
   for (int t0 = 0; t0 < m; t0 += 1024) {
     const int tn = min(1024, m - t0);
     __syncthreads();
     for (int k = tid; k < tn; k += 256) { const float4 o = R[t0 + k]; s_xy[k] = make_float2(o.x, o.y); }
     __syncthreads();
-    if (act) {
-      int j = 0;
-      for (; j + 8 <= tn; j += 8) {
-        float2 o[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) o[q] = s_xy[j + q];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-          if (o[q].x == ax && o[q].y == ay) { if (t0 + j + q < i) first = false; if (t0 + j + q > last) last = t0 + j + q; }
-      }
-      for (; j < tn; j++) {
-        const float2 o = s_xy[j];
-        if (o.x == ax && o.y == ay) { if (t0 + j < i) first = false; if (t0 + j > last) last = t0 + j; }
-      }
-    }
+    if (act) dup_scan_tile(s_xy, t0, tn, i, [&](float2 o, int) { return o.x == ax && o.y == ay; }, first, last);
   }
-  if (act) { W[2 * i] = first ? 1 : 0; W[2 * i + 1] = last; }
+  if (act) { W[2 * i] = first; W[2 * i + 1] = last; }
 }
 
 // stage 2 (one workgroup per pair): the first rows in order, each with the b of its key's last row
@@ -669,6 +648,8 @@ __global__ __launch_bounds__(256) void k_merge(EvhMergeArgs A) {
   if (tid == 0) { A.nout[p] = u; A.status[p] = 0; }
 }
 
+int launched(evh_ctx* c) { EVH_HIP(c, hipGetLastError()); return EVH_SUCCESS; }
+
 }  // namespace
 
 int evh_launch_knn2(evh_ctx* c, const EvhKnnArgs& A, int npairs) {
@@ -679,8 +660,7 @@ int evh_launch_knn2(evh_ctx* c, const EvhKnnArgs& A, int npairs) {
   if (A.desc_bytes == 128)
     hipLaunchKernelGGL(k_knn2_mfma128, dim3(npairs, std::max(1, std::min((nq_max + KM_GQ - 1) / KM_GQ, 256))), dim3(256), 0, c->stream, A);
   else hipLaunchKernelGGL(k_knn2, dim3(npairs, chunks), dim3(256), 0, c->stream, A);
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launched(c);
 }
 
 int evh_launch_knn2_f32(evh_ctx* c, const EvhKnnF32Args& A, int npairs) {
@@ -690,15 +670,13 @@ int evh_launch_knn2_f32(evh_ctx* c, const EvhKnnF32Args& A, int npairs) {
   if (A.dim == 128) hipLaunchKernelGGL(k_knn2_f32<128>, grid, dim3(256), 0, c->stream, A);
   else if (A.dim == 64) hipLaunchKernelGGL(k_knn2_f32<64>, grid, dim3(256), 0, c->stream, A);
   else return evh_fail(c, EVH_ERR_UNSUPPORTED, "float descriptors: 64 or 128 elements per row (SURF / SIFT)");
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launched(c);
 }
 
 int evh_launch_accumulate(evh_ctx* c, const EvhAccArgs& A, int npairs) {
   if (npairs <= 0) return EVH_SUCCESS;
   hipLaunchKernelGGL(k_accumulate, dim3(npairs), dim3(256), 0, c->stream, A);
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launched(c);
 }
 
 int evh_launch_merge(evh_ctx* c, const EvhMergeArgs& A_, int npairs) {
@@ -709,8 +687,7 @@ int evh_launch_merge(evh_ctx* c, const EvhMergeArgs& A_, int npairs) {
   A.work = c->d_merge_ws;
   hipLaunchKernelGGL(k_merge_dup, dim3((unsigned)((A.acc_stride + 255) / 256), npairs), dim3(256), 0, c->stream, A);
   hipLaunchKernelGGL(k_merge, dim3(npairs), dim3(256), 0, c->stream, A);
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launched(c);
 }
 
 int evh_launch_filter(evh_ctx* c, const EvhFilterArgs& A_, int npairs) {
@@ -724,13 +701,11 @@ int evh_launch_filter(evh_ctx* c, const EvhFilterArgs& A_, int npairs) {
     hipLaunchKernelGGL(k_filter<true>, dim3(npairs), dim3(256), 0, c->stream, A);
     hipLaunchKernelGGL(k_filter_dup, dim3((A.kcap + 255) / 256, npairs), dim3(256), 0, c->stream, A);
     hipLaunchKernelGGL(k_filter_out, dim3(npairs), dim3(256), 0, c->stream, A);
-    EVH_HIP(c, hipGetLastError());
-    return EVH_SUCCESS;
+    return launched(c);
   }
   if (lds > 48 * 1024)   // large key-point budgets (N = 4000 -> ~105 KB): opt in to more dynamic LDS than the default
     EVH_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_filter<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
   hipLaunchKernelGGL(k_filter<false>, dim3(npairs), dim3(256), lds, c->stream, A);
-  EVH_HIP(c, hipGetLastError());
-  return EVH_SUCCESS;
+  return launched(c);
 }

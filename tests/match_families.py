@@ -454,6 +454,25 @@ def f4_case():
     return c, pad
 
 
+def f4_case_three_tiles():
+    """F4, a second logical input: 4203 survivors -- three 2048-row tiles of k_filter_dup, the last of 107 rows (13 x 8 + 3:
+    the remainder loop) -- among 4353 queries, claims on trains below 4300; two keys of dup_keys(4203) have occurrences in
+    all three tiles (rows 3 .. 4200, 50 of them, and rows 5 and 4202), so `first` and `last` are carried across tiles.
+    Presented at kcap 7680 (the last LDS size) and 7681 (the first global-scratch size) by the same padding.
+    -> (case with nt = 4300, pad(nt) -> xy_t of that size)"""
+    c = filter_case(np.random.default_rng(5606), 4203, nt=4300, doubles=10, big_claim=60, fails=70, dup=True)
+
+    def pad(nt):
+        xy = np.empty((nt, 2), np.float32)
+        xy[:4300] = c["xy_t"]
+        xy[4300:] = _coords(nt - 4300, 123.0) + np.float32(20000)
+        return xy
+    return c, pad
+
+
+F4_THREE_TILES_KCAPS = (7680, 7681)
+
+
 # ---- D1: remove_double_matching over concatenated rows -----------------------------------------------------------------
 D1_N = (0, 1, 255, 256, 257, 1023, 1024, 1025, 15000)
 

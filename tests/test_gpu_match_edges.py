@@ -155,7 +155,16 @@ def test_f3_duplicate_coordinates_among_survivors(ctx):
 
 def test_f4_every_form_returns_the_same_rows(ctx):
     """kcap 2457 (default dynamic LDS), 2458 (opt-in above 48 KB), 7680 (last LDS size), 7681 and 65535 (k_filter<true> +
-    k_filter_dup + k_filter_out in a global scratch); 65536 is refused and the context stays usable"""
+    k_filter_dup + k_filter_out in a global scratch); 65536 is refused and the context stays usable.  A second input with
+    4203 survivors (three tiles of k_filter_dup) at kcap 7680 and 7681"""
+    c3, pad3 = F.f4_case_three_tiles()
+    first3 = None
+    for kcap in F.F4_THREE_TILES_KCAPS:
+        st, rows = check_filter(ctx, dict(c3, xy_t=pad3(kcap)), 4, "f4_three_tiles_kcap%d" % kcap)
+        assert st == F.OK
+        if first3 is None:
+            first3 = rows
+        assert same_rows(rows, first3), kcap
     c, pad = F.f4_case()
     first = None
     for kcap in F.F4_KCAPS:

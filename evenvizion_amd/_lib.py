@@ -121,6 +121,9 @@ SIGNATURES = {
     # stabilised output: frames warped into the fixed plane
     "evh_warp_fixed_plane": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
     "evh_warp_fixed_plane_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _i, _i]),
+    "evh_steady_frames": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _vp, _i64,
+                               _i64, _vp]),
+    "evh_steady_frames_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _i64, _vp]),
     "evh_warp_ray_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
     "evh_warp_ray_surface_yuv420": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i64]),
     # the blended mosaic and the sums its exposure gains are solved from
@@ -727,6 +730,42 @@ class Context:
                 raise ValueError("background must be [dh,dw(,3)] with out's row stride")
         tail = (mats.data_ptr(), int(bool(inverse_map)), mode, bp, op, dw, dh, ors, ofs if lead else 0, int(origin[0]), int(origin[1]))
         self._check(self._form("evh_warp_fixed_plane", planes)(self.h, *head, *tail))
+
+    def steady_frames(self, frames, tap_frame, tap_M, out, feather=0, background=None, tap_of=None, counts=None, size=None):
+        """The steady view (evh_steady_frames[_yuv420], the arithmetic is stated in include/evhip.h): output picture j from its own
+        ordered list of sources.  frames, size: as for warp_fixed_plane.  tap_frame: CUDA int32 [nout,ntaps] contiguous, an index
+        into frames per tap, anything outside 0..n-1 = no tap.  tap_M: CUDA float64, nout*ntaps*9 contiguous elements, output
+        pixel -> frame pixel.  out: [nout,dh,dw(,3)], rows and pictures may be strided.  feather: in 1/32 pixels.  background:
+        [dh,dw(,3)] with out's row stride, or None = zeros.  tap_of: CUDA uint8 [nout,dh,dw] (may be strided) or None; counts: CUDA
+        int32 or uint32 [nout,ntaps+1] contiguous, or None.  Does not synchronise."""
+        import torch
+        self._enter()
+        planes, head, n, sw, sh, cn = self._frame_source(frames, size)
+        if tap_frame.dim() != 2:
+            raise ValueError("tap_frame must be [nout,ntaps]")
+        nout, ntaps = (int(v) for v in tap_frame.shape)
+        self._dev_tensor(tap_frame, torch.int32, (nout, ntaps), "tap_frame must be a contiguous CUDA int32 tensor [nout,ntaps]")
+        self._dev_tensor(tap_M, torch.float64, 9 * nout * ntaps, "tap_M must be a contiguous CUDA float64 tensor of nout*ntaps*9 elements")
+        op, dw, dh, ors, ofs = self._image_rows(out, cn, 1, "out")
+        if out.shape[0] != nout:
+            raise ValueError("out must hold one picture per row of tap_frame")
+        bp = None
+        if background is not None:
+            bp, bw, bh, brs, _ = self._image_rows(background, cn, 0, "background")
+            if (bw, bh) != (dw, dh) or (dh > 1 and brs != ors):
+                raise ValueError("background must be [dh,dw(,3)] with out's row stride")
+        tp, trs, tfs = None, 0, 0
+        if tap_of is not None:
+            tp, tw, th, trs, tfs = self._image_rows(tap_of, 1, 1, "tap_of")
+            if (tap_of.shape[0], tw, th) != (nout, dw, dh):
+                raise ValueError("tap_of must be [nout,dh,dw]")
+        if counts is not None:
+            if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError("counts must be an int32 or uint32 tensor")
+            self._dev_tensor(counts, counts.dtype, (nout, ntaps + 1), "counts must be a contiguous CUDA tensor [nout,ntaps+1]")
+        tail = (tap_frame.data_ptr(), tap_M.data_ptr(), nout, ntaps, int(feather), bp, op, dw, dh, ors, ofs, tp, trs, tfs,
+                None if counts is None else counts.data_ptr())
+        self._check(self._form("evh_steady_frames", planes)(self.h, *head, *tail))
 
     def warp_ray_surface(self, frames, mats, cols, rows, out, mode, background=None, size=None):
         """Frames warped onto a canvas of viewing rays (evh_warp_ray_surface[_yuv420], the arithmetic is stated in

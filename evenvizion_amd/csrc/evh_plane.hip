@@ -3,6 +3,7 @@
 // struct, check() -- every refusal comes before anything is enqueued -- and launch(), included inside the unnamed namespace:
 //   evh_plane_sample.h      the run of pixels per thread, the canvas -> frame maps, the sampler, the blends' geometry
 //   evh_plane_warp.h        evh_warp_fixed_plane, evh_warp_ray_surface
+//   evh_plane_steady.h      evh_steady_frames
 //   evh_plane_blend.h       evh_blend_fixed_plane, evh_blend_ray_surface
 //   evh_plane_bands.h       evh_seam_labels_*, evh_blend_bands_*
 //   evh_plane_align.h       evh_pair_exposure, evh_pair_residual, evh_pair_refine, evh_canvas_refine
@@ -49,6 +50,7 @@ int run(evh_ctx* c, const Args& A) {
 }
 
 #include "evh_plane_warp.h"
+#include "evh_plane_steady.h"
 #include "evh_plane_blend.h"
 #include "evh_plane_bands.h"
 #include "evh_plane_align.h"
@@ -86,6 +88,24 @@ int evh_warp_ray_surface_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, 
                                 int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride) {
   return run(c, RayArgs{{"evh_warp_ray_surface_yuv420", yuv420_frames(src), nframes, sw, sh, d_A, 1, mode, d_background, d_out,
                          dw, dh, out_row_stride, out_frame_stride, 0, 0}, d_col, d_row});
+}
+
+int evh_steady_frames(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,
+                      int64_t frame_stride, const int32_t* d_tap_frame, const double* d_tap_M, int nout, int ntaps, int feather,
+                      const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride,
+                      uint8_t* d_tap_of, int64_t tap_of_row_stride, int64_t tap_of_frame_stride, uint32_t* d_counts) {
+  return run(c, SteadyArgs{"evh_steady_frames", packed_frames(d_frames, channels, row_stride, frame_stride), nframes, sw, sh, d_tap_frame,
+                           d_tap_M, nout, ntaps, feather, d_background, d_out, dw, dh, out_row_stride, out_frame_stride, d_tap_of,
+                           tap_of_row_stride, tap_of_frame_stride, d_counts});
+}
+
+int evh_steady_frames_yuv420(evh_ctx* c, const evh_yuv420* src, int nframes, int sw, int sh, const int32_t* d_tap_frame,
+                             const double* d_tap_M, int nout, int ntaps, int feather, const uint8_t* d_background, uint8_t* d_out,
+                             int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride, uint8_t* d_tap_of,
+                             int64_t tap_of_row_stride, int64_t tap_of_frame_stride, uint32_t* d_counts) {
+  return run(c, SteadyArgs{"evh_steady_frames_yuv420", yuv420_frames(src), nframes, sw, sh, d_tap_frame, d_tap_M, nout, ntaps, feather,
+                           d_background, d_out, dw, dh, out_row_stride, out_frame_stride, d_tap_of, tap_of_row_stride,
+                           tap_of_frame_stride, d_counts});
 }
 
 int evh_blend_fixed_plane(evh_ctx* c, const uint8_t* d_frames, int nframes, int sw, int sh, int channels, int64_t row_stride,

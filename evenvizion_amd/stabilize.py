@@ -1,6 +1,6 @@
 """Command-line driver of the stabilised view, with the arguments of the reference's
 evenvizion/examples/compare_evenvizion_with_original_video.py plus --mode, --placement, --scale, --trail, --comparison, --plate,
---surface and --blend:
+--surface, --blend and --steady:
 
     python -m evenvizion_amd.stabilize --path_to_homography_dict run1/video/dict_with_homography_matrix.json \
            --path_to_video video.mp4 --experiment_name run1 --comparison 1
@@ -34,6 +34,15 @@ evenvizion_amd.stabilization:
                      its own border, rising over --feather PX pixels (feather), or per pixel the frame whose border is farthest
                      away (seam); with --exposure 1 the video is first read once more for the overlap sums, one gain per frame
                      and channel is solved from them (exposure_gains.json) and applied.  On the plane or with --surface.
+
+    --steady 1       steady_NNNNNN.ppm per frame: the video itself, at its own size (times --scale), on a smoothed camera path
+                     (evenvizion_amd.steady): every frame's corners follow the Gaussian mean of their neighbours' over
+                     --steady_radius R frames on each side (--steady_sigma S, default R / 2), the picture is enlarged by
+                     --steady_zoom Z (auto: the least zoom, up to 1.25, that keeps every picture inside its frame), and what a
+                     frame still leaves uncovered is filled from the --steady_fill F frames before and after it, feathered over
+                     --steady_feather PX pixels.  Always writes steady_report.json: the zoom, the jitter of the path before and
+                     after, per frame the shares its own frame and its neighbours gave.  With --format jpeg steady_NNNNNN.jpg,
+                     with mjpeg one steady.avi.  Not with --trail, --comparison, --plate, --surface or --blend.
 
     --format jpeg | mjpeg
                      the pictures leave the device compressed (evenvizion_amd.pictures, evh_jpeg_encode): jpeg writes NNNNNN.jpg in
@@ -99,6 +108,14 @@ def parser():
     ap.add_argument("--feather", type=float, default=32.0, help="blend: pixels over which a frame's weight rises from its border")
     ap.add_argument("--exposure", type=int, choices=(0, 1), default=0,
                     help="blend: 1 solves one gain per frame and channel from the overlaps and writes exposure_gains.json")
+    ap.add_argument("--steady", type=int, choices=(0, 1), default=0,
+                    help="1: the video itself on a smoothed camera path, borders filled from neighbouring frames: "
+                         "steady_NNNNNN.ppm (or .jpg, or steady.avi) and steady_report.json")
+    ap.add_argument("--steady_radius", type=int, default=None, help="steady: frames on each side the path is averaged over (default 15)")
+    ap.add_argument("--steady_sigma", type=float, default=None, help="steady: the Gaussian's sigma in frames (default radius / 2)")
+    ap.add_argument("--steady_zoom", default=None, help="steady: a zoom factor, or auto (the default)")
+    ap.add_argument("--steady_fill", type=int, default=None, help="steady: neighbours on each side that fill the borders (0..7, default 2)")
+    ap.add_argument("--steady_feather", type=float, default=None, help="steady: pixels the fill is feathered over (0..255, default 8)")
     ap.add_argument("--format", choices=("ppm", "jpeg", "mjpeg"), default="ppm",
                     help="ppm: binary P6 per picture; jpeg: NNNNNN.jpg encoded on the device; mjpeg: stabilized.avi of those files")
     ap.add_argument("--quality", type=int, default=90, help="jpeg, mjpeg: 1..100, the usual scaling of the Annex K tables")
@@ -107,17 +124,17 @@ def parser():
     return ap
 
 
-def write_pictures(save_folder, args, files):
+def write_pictures(save_folder, args, files, name="%06d.jpg", video="stabilized.avi"):
     """--format jpeg | mjpeg: the (frame_no, bytes) of a generator of files as NNNNNN.jpg, or as the frames of stabilized.avi."""
     from .pictures import MjpegAviWriter, write_jpeg
     writer = None
     for frame_no, data in files:
         if args.format == "jpeg":
-            write_jpeg(os.path.join(save_folder, "%06d.jpg" % frame_no), data)
+            write_jpeg(os.path.join(save_folder, name % frame_no), data)
             continue
         if writer is None:
             h, w = jpeg_size(data)
-            writer = MjpegAviWriter(os.path.join(save_folder, "stabilized.avi"), w, h, args.fps)
+            writer = MjpegAviWriter(os.path.join(save_folder, video), w, h, args.fps)
         writer.write(data)
     if writer is not None:
         writer.close()
@@ -172,6 +189,7 @@ def main(argv=None):
     if not 1 <= args.quality <= 100 or not args.fps > 0:
         ap.error("--quality lies in 1..100, --fps is positive")
     coded = dict(quality=args.quality, subsampling=args.subsampling)
+    steady = steady_arguments(ap, args)
     bands = 5 if args.bands is None else args.bands
     if not 0 <= bands <= 8:
         ap.error("--bands lies in 0..8")
@@ -183,6 +201,19 @@ def main(argv=None):
     os.makedirs(save_folder, exist_ok=True)
     homography_dict, resize_info = read_homography_dict(args.path_to_homography_dict)
     sup = superposition_dict(homography_dict)
+    if args.steady:
+        import json
+        from .steady import steady_frames, steady_jpegs, steady_report
+        report = {}
+        if args.format != "ppm":
+            write_pictures(save_folder, args, steady_jpegs(cap, sup, resize_info, scale=args.scale, report=report, **steady, **coded),
+                           "steady_%06d.jpg", "steady.avi")
+        else:
+            for frame_no, picture in steady_frames(cap, sup, resize_info, scale=args.scale, report=report, **steady):
+                write_ppm(os.path.join(save_folder, "steady_%06d.ppm" % frame_no), picture)
+        with open(os.path.join(save_folder, "steady_report.json"), "w") as f:
+            json.dump(steady_report(report), f, indent=1)
+        return save_folder
     if args.blend:
         import json
         from .blend import blended_mosaic, exposure_pairs, exposure_stats, solve_gains, surface_pair_maps
@@ -254,6 +285,32 @@ def main(argv=None):
                                                scale=args.scale, trail=bool(args.trail)):
         write_ppm(os.path.join(save_folder, "%06d.ppm" % frame_no), picture)
     return save_folder
+
+
+def steady_arguments(ap, args):
+    """The refusals of --steady and its options -> the keyword arguments of steady.steady_frames."""
+    given = [n for n in ("steady_radius", "steady_sigma", "steady_zoom", "steady_fill", "steady_feather") if getattr(args, n) is not None]
+    if given and not args.steady:
+        ap.error("--%s needs --steady 1" % given[0])
+    if not args.steady:
+        return None
+    for flag in ("trail", "comparison", "plate", "surface", "blend"):
+        if getattr(args, flag):
+            ap.error("--steady writes the steady view only: not with --%s" % flag)
+    zoom = "auto" if args.steady_zoom in (None, "auto") else None
+    if zoom is None:
+        try:
+            zoom = float(args.steady_zoom)
+        except ValueError:
+            ap.error("--steady_zoom is a number or auto")
+    got = dict(radius=15 if args.steady_radius is None else args.steady_radius, sigma=args.steady_sigma, zoom=zoom,
+               fill=2 if args.steady_fill is None else args.steady_fill, feather_px=8.0 if args.steady_feather is None else args.steady_feather)
+    from .steady import check_steady_arguments
+    try:
+        check_steady_arguments(got["radius"], got["sigma"], got["zoom"], 1.25, got["fill"], got["feather_px"], args.scale, 32, "auto")
+    except ValueError as e:
+        ap.error("--steady: %s" % e)
+    return got
 
 
 def write_moving_objects(save_folder, cap, sup, resize_info, args, objects):

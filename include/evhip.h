@@ -25,6 +25,8 @@
  *                                 visualization/stabilization.py:129-172, 220-249
  *   evh_warp_ray_surface[_yuv420] no counterpart: the cylindrical coordinate system the reference's known-issues.md names as the way
  *                                 past camera rotations above 90 degrees -- frames placed on a cylinder, a sphere or a plane of rays
+ *   evh_steady_frames[_yuv420]    no counterpart (create_video_comparison shows a frame sliding over a canvas): the video itself on a
+ *                                 smoothed camera path, every output picture from its frame and, at the borders, its neighbours
  *   evh_blend_fixed_plane[_yuv420], evh_blend_ray_surface[_yuv420] no counterpart: the mosaic with feathered seams (or the frame
  *                                 nearest its centre per pixel) and per-frame exposure gains, on the plane or on a surface
  *   evh_seam_labels_*, evh_blend_bands_*[_yuv420] no counterpart: multi-band blending of that mosaic under a label mask
@@ -525,6 +527,61 @@ int evh_warp_ray_surface(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int
 int evh_warp_ray_surface_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const double* d_A,
                                 const double* d_col, const double* d_row, int mode, const uint8_t* d_background, uint8_t* d_out,
                                 int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride);
+
+/* ---- the steady view: every output picture from its own ordered list of frames and maps ---------------------------------------- */
+/* The products above live on one fixed plane or surface.  A stabilised VIDEO is the input at its own size on a smoother camera
+ * path: output picture j is frame k seen through a map of its own, and the wedges that frame leaves uncovered at the borders are
+ * filled from its neighbours in time, each through its own map.  So every output picture has its own ordered list of sources:
+ *   the frames   nframes frames of sw x sh, gray, BGR or decoded planes, with strides as in evh_warp_fixed_plane;
+ *   nout         output pictures of dw x dh pixels of the source's channels (the plane form: BGR);
+ *   ntaps        1..16 candidate sources ("taps") per output picture;
+ *   d_tap_frame  i32[nout, ntaps] (DEVICE): the tap's frame, an index into the frames of the call;
+ *   d_tap_M      f64[nout, ntaps, 9] (DEVICE): the tap's map from output pixel to frame pixel, used as it is (no adjugate, no origin);
+ *   feather      F, in 1/32 pixels, 0..8160 (255 pixels);
+ *   d_background dh rows of dw*channels bytes at out_row_stride, or NULL = zeros;
+ *   d_out        nout pictures at out_frame_stride, dh rows of dw*channels bytes at out_row_stride;
+ *   d_tap_of     u8[nout, dh, dw] at tap_of_row_stride / tap_of_frame_stride, or NULL: which tap gave the pixel;
+ *   d_counts     u32[nout, ntaps + 1] (DEVICE), or NULL.
+ * Arithmetic, all IEEE float64 with one rounding per operation (no fma).  For output picture j, pixel (x, y), tap t with
+ * a = d_tap_M[j, t]:  X = (double)x, Y = (double)y, and tx, ty, tw, U, V exactly as evh_warp_fixed_plane forms them with
+ * inverse_map != 0:  tx = (a0*X + a1*Y) + a2, ty = (a3*X + a4*Y) + a5, tw = (a6*X + a7*Y) + a8, U = rint(tx / tw * 32),
+ * V = rint(ty / tw * 32), halves to even.
+ *   1. Tap t is LIVE iff 0 <= d_tap_frame[j, t] < nframes.  Any other value is defined: the tap covers nothing and reads nothing
+ *      (its matrix is not looked at either).
+ *   2. A live tap COVERS the pixel iff 0 <= U <= 32*(sw-1) and 0 <= V <= 32*(sh-1), compared in double: a NaN, zero or singular
+ *      matrix and pixels on or beyond the horizon cover nothing and read nothing.
+ *   3. first = the smallest covering t.  None: the pixel takes d_background's bytes, or zeros when that is NULL, and
+ *      d_tap_of = 0.  Otherwise the pixel takes v, the bilinear value of frame d_tap_frame[j, first] at (U, V) exactly as in
+ *      evh_warp_fixed_plane ((p00*(32-fx)*(32-fy) + ... + 512) >> 10, a tap of weight 0 is not read), and d_tap_of = first + 1.
+ *   4. FEATHER, for tap 0 only: when F > 0, first == 0 and d < F, where d = min(U, 32*(sw-1) - U, V, 32*(sh-1) - V) of tap 0 in
+ *      int32, its distance to the nearest frame edge in 1/32 pixels.  Let second be the smallest covering t >= 1 and v1 its
+ *      bilinear value.  If it exists every channel becomes (v*d + v1*(F - d) + (F >> 1)) / F in unsigned 32-bit integers, the
+ *      division rounding down (at most 255 * 8160 + 4080: nothing wraps).  At d = 0 that is v1: the picture is continuous with the
+ *      pixel just outside tap 0's frame, which `second` gives as its first tap.  If no second tap covers, the pixel stays v:
+ *      nothing is feathered into the background.  d_tap_of stays 1.
+ *   5. d_counts[j, 0] = the pixels of picture j no tap covered, d_counts[j, 1 + t] = those first covered by tap t: exact
+ *      integers that sum to dw*dh.  The entry zeroes them itself, on its stream, before the launch (d_counts[j, 1] is formed
+ *      last, as what the other buckets leave of dw*dh: nearly every pixel of a steady view falls there).
+ * What follows: ntaps = 1, d_tap_frame[j] = j, F = 0 is evh_warp_fixed_plane, EVH_WARP_EACH, inverse_map != 0, origin (0, 0), byte
+ * for byte; an identity tap copies the frame; taps behind the first covering one matter only inside tap 0's feather band.
+ * Every byte of every output row inside dw*channels (d_tap_of: dw) is written, bytes between rows are not.  Only caller buffers are
+ * used; on the context's stream, no synchronisation.  The plane form converts every tap as
+ * evh_yuv420_to_bgr does and then interpolates: it equals evh_yuv420_to_bgr followed by the BGR form.  Speed, not results,
+ * depends on alignment: d_out, d_background and the output strides (d_tap_of and its strides) multiples of 4 let a thread store
+ * its four pixels as a word.
+ * Refused before anything is launched or zeroed, outputs untouched -- EVH_ERR_INVALID: a NULL source, d_tap_frame, d_tap_M or d_out,
+ * channels not 1 or 3, sw, sh, dw or dh < 1, nframes or nout < 0, ntaps outside 1..16, feather outside 0..8160, a stride shorter
+ * than its row / frame / picture, d_background, d_tap_of or d_counts overlapping d_out (or one another); EVH_ERR_CAPACITY: sw or
+ * sh >= 2^26, dw*dh > INT_MAX, nout > 65535.  nout == 0 succeeds and does nothing.                                              */
+int evh_steady_frames(evh_ctx* ctx, const uint8_t* d_frames, int nframes, int sw, int sh, int channels /* 1 | 3 */,
+                      int64_t row_stride, int64_t frame_stride, const int32_t* d_tap_frame, const double* d_tap_M, int nout,
+                      int ntaps, int feather, const uint8_t* d_background, uint8_t* d_out, int dw, int dh, int64_t out_row_stride,
+                      int64_t out_frame_stride, uint8_t* d_tap_of, int64_t tap_of_row_stride, int64_t tap_of_frame_stride,
+                      uint32_t* d_counts);
+int evh_steady_frames_yuv420(evh_ctx* ctx, const evh_yuv420* src, int nframes, int sw, int sh, const int32_t* d_tap_frame,
+                             const double* d_tap_M, int nout, int ntaps, int feather, const uint8_t* d_background, uint8_t* d_out,
+                             int dw, int dh, int64_t out_row_stride, int64_t out_frame_stride, uint8_t* d_tap_of,
+                             int64_t tap_of_row_stride, int64_t tap_of_frame_stride, uint32_t* d_counts);
 
 /* ---- the blended mosaic: feathered seams and exposure gains, on the plane or on a surface --------------------------------------- */
 /* EVH_WARP_MOSAIC gives a canvas pixel to the last frame that covers it: every frame edge stays as a seam, every change of the
